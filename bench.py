@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — training-step throughput of the AC-VAE hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,8 @@ global-norm clip -> Adam, on BASELINE.json configs[1]: B=32 clips per GPU, T=100
 22-token captions, vocab 5000, E=H=512, fp32, synthetic seeded data, random-init weights.  Weak scaling:
 every rank processes its own 32-clip batch; gradients are averaged over RCCL.  Every step's 8.2 MB feature batch is uploaded
 from page-locked host memory inside the timed region (prefetched during the previous step).  Rank 0 prints ONE JSON line.
+--dump-outputs DIR: rank 0 also writes what the last timed step handed its caller as DIR/<name>.npy (dump_outputs); the
+inputs and weights are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -52,6 +54,45 @@ def synthetic(seed):
     caps[:, 1:-1] = torch.randint(4, V, (B, L - 2), generator=g).float()
     import numpy as np
     return feats, caps, np.full(B, T, dtype=np.int64), np.full(B, L, dtype=np.int64)
+
+
+DUMP_MAX_ELEMS = 1 << 17          # per array; a larger tensor is written as a sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, model, parts):
+    """Write what TrainStep.step handed its caller in the last timed step to `path`/<name>.npy: the loss terms and the
+    gradient norm it returned (loss, ce, kl, mse, grad_norm: float64 scalars), every entry of the model's state dict after
+    the step (state.<key>: parameters after Adam, BatchNorm running statistics) and every parameter's gradient
+    (grad.<key>).  Floating-point tensors stay float32, integer ones become float64.  A tensor of more than DUMP_MAX_ELEMS
+    elements is written as the elements at DUMP_MAX_ELEMS fixed indices (sorted, drawn by a generator seeded with its key),
+    so the files of two runs line up element for element.  Call it after a device synchronise."""
+    import zlib
+
+    import numpy as np
+    import torch
+
+    def host(key, t):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(zlib.crc32(key.encode())).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu().numpy()
+        return a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+
+    arrays = {k: np.asarray(float(v), dtype=np.float64) for k, v in parts.items() if v is not None}
+    for k, v in model.state_dict().items():
+        arrays["state." + k] = host(k, v)
+    for k, p in model.named_parameters():
+        if p.grad is not None:
+            arrays["grad." + k] = host(k, p.grad)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def host_cores():
@@ -119,7 +160,14 @@ def main():
                          "(conv stack on the bf16 MFMA pipe, activations stored in bf16; text side, loss, parameters fp32)")
     ap.add_argument("--lib", default=None, help="dev: time another build of the library (tools/ab_build.py) instead of the "
                                                 "product's; recorded in config.lib")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss terms, gradient norm, state dict, gradients; large "
+                         "tensors as a fixed seeded sample) as DIR/<name>.npy, at most 64 MB (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks as CHILD processes (one per GPU, torch.distributed.run
@@ -138,6 +186,8 @@ def main():
         cmd += ["--dtype", args.dtype]
         if args.lib:
             cmd += ["--lib", args.lib]
+        if args.dump_outputs:
+            cmd += ["--dump-outputs", args.dump_outputs]
         raise SystemExit(subprocess.call(cmd))
 
     import torch
@@ -218,6 +268,8 @@ def main():
     _lib.lib().acvae_prof_enable(0)
     loss = float(parts["loss"])
     ts.synchronize()                                  # raises if a persistent launch of the run gave up
+    if args.dump_outputs and rank == 0:               # before the extra steps below change the parameters again
+        dump_outputs(args.dump_outputs, model, parts)
     # Beside it: the same loop on ONE resident tensor (no upload at all), and with the upload queued in front of each step on
     # the compute stream (no prefetch: what `feats.to(device)` inside the step costs when nothing hides it).
     EXTRA = 8
