@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "common.h"
+#include "job_table.h"
 
 struct DropoutSpec {
   float p;              // drop probability; 0 disables
@@ -36,12 +37,9 @@ bool conv3x3_wino_ok(int H, int W, int Cin, int Cout);
 long conv3x3_wino_weight_floats(int Cin, int Cout);
 int conv_wino_partials_rows(int N, int H, int W);
 int conv3x3_wino_weights(const float* W_oihw, float* U, int Cout, int Cin, bool dgrad, hipStream_t st);
-// several images in one launch (fill W, U, Cout, Cin, dgrad and n; start is computed)
-struct WinoWeightsBatch {
-  static constexpr int MAXL = 32;
-  const float* W[MAXL]; float* U[MAXL]; int Cout[MAXL], Cin[MAXL], dgrad[MAXL]; long start[MAXL + 1]; int n = 0;
-  void add(const float* w, float* u, int cout, int cin, bool dg) { W[n] = w; U[n] = u; Cout[n] = cout; Cin[n] = cin; dgrad[n] = dg ? 1 : 0; ++n; }
-};
+// several images in one launch (the launcher seals the table)
+struct WinoWeightsJob { const float* W; float* U; int Cout, Cin, dgrad; };
+using WinoWeightsBatch = RangeTable<WinoWeightsJob, 32>;
 int conv3x3_wino_weights_batch(WinoWeightsBatch& b, hipStream_t st);
 // red (data gradient only; partials = [conv_wino_partials_rows][2][Cout] then receives bn_bwd_reduce_kernel's sums): the launch's
 // output is the upstream gradient of the BatchNorm + ReLU that normalised red->Y (same shape as the output)
@@ -56,11 +54,8 @@ int conv3x3_wino_wgrad(const float* dY, const float* X, const float* scale, cons
 template <class T>
 int repack_weights(const float* W_oihw, T* Wf, T* Wd, int Cout, int Cin, hipStream_t st);
 // several repacks (implicit-GEMM weight layouts: forward [cout][tap][cin], data gradient [cin][8 - tap][cout]) in one launch
-struct RepackBatch {
-  static constexpr int MAXL = 32;
-  const float* W[MAXL]; void* dst[MAXL]; int Cout[MAXL], Cin[MAXL], dgrad[MAXL]; long start[MAXL + 1]; int n = 0;
-  void add(const float* w, void* d, int cout, int cin, bool dg) { W[n] = w; dst[n] = d; Cout[n] = cout; Cin[n] = cin; dgrad[n] = dg ? 1 : 0; ++n; }
-};
+struct RepackJob { const float* W; void* dst; int Cout, Cin, dgrad; };
+using RepackBatch = RangeTable<RepackJob, 32>;
 template <class T>
 int repack_weights_batch(RepackBatch& b, hipStream_t st);
 // storage-type overloads so that the encoder driver is one template
@@ -93,14 +88,9 @@ int colsum2(const float* x, int P, int width, double* dpart, float* out, float* 
 // text side); job j: out[i] (and out_b[i], if given: the two LSTM biases share a gradient) = sum_p x[p][i].  Each job keeps the
 // row groups and the order of additions of its own colsum2 launch (bit-identical); they share the tickets and the scratch of
 // one dpart: falls back to separate launches when those do not hold them all.
-struct ColsumBatch {
-  static constexpr int MAXJ = 6;
-  const float* x[MAXJ]; int P[MAXJ], width[MAXJ], R[MAXJ], blk0[MAXJ + 1]; long d0[MAXJ]; float* out[MAXJ]; float* out_b[MAXJ]; int n = 0;
-  void add(const float* xs, int p, int w, float* o, float* ob = nullptr) {       // n > MAXJ: too many jobs (colsum_batch refuses)
-    if (n < MAXJ) { x[n] = xs; P[n] = p; width[n] = w; out[n] = o; out_b[n] = ob; }
-    ++n;
-  }
-};
+// Ranges: column blocks of 64.  R (row groups) and d0 (offset of the group sums in dpart) are filled by the launcher.
+struct ColsumJob { const float* x; int P, width; float* out; float* out_b; int R; long d0; };
+using ColsumBatch = RangeTable<ColsumJob, 6, int>;
 int colsum_batch(ColsumBatch& b, double* dpart, long dpart_doubles, hipStream_t st);
 int conv1_first_blocks(int N, int T);
 template <class TY>
@@ -146,4 +136,8 @@ int acvae_gemm_tn_fused(const float* A, int64_t lda, const float* B, int64_t ldb
 long acvae_skinny_ws_floats();
 long acvae_skinny_ticket_words();       // words at the head of a skinny workspace that a composite call zeroes once
 int acvae_skinny_ws_reset(float* ws, hipStream_t st);
-#include "transpose_batch.h"
+// several transposes in ONE launch (out[c][r] = in[r][c]): the decode backward needs nine transposed weight matrices per step.
+// Ranges: 32 x 32 tiles.
+struct TransposeJob { const float* in; long ld_in; float* out; long ld_out; int rows, cols; };
+using TransposeBatch = acvae::RangeTable<TransposeJob, 12, int>;
+int acvae_transpose_batch(TransposeBatch& b, hipStream_t st);

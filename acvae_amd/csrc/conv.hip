@@ -583,13 +583,13 @@ template <class T>
 __global__ void repack_batch_kernel(acvae::RepackBatch b) {
   const long total = b.start[b.n];
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l + 1 < b.n && i >= b.start[l + 1]) ++l;
+    const int l = b.find(i);
+    const acvae::RepackJob& job = b.job[l];
     const long k = i - b.start[l];
-    const int Cout = b.Cout[l], Cin = b.Cin[l];
-    const float* W = b.W[l];
-    T* out = reinterpret_cast<T*>(b.dst[l]);
-    if (!b.dgrad[l]) {
+    const int Cout = job.Cout, Cin = job.Cin;
+    const float* W = job.W;
+    T* out = reinterpret_cast<T*>(job.dst);
+    if (!job.dgrad) {
       const int co = (int)(k / (9 * Cin)), rem = (int)(k % (9 * Cin));
       const int tap = rem / Cin, ci = rem % Cin;
       out[k] = (T)W[((long)co * Cin + ci) * 9 + tap];
@@ -746,16 +746,16 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ p
 __global__ __launch_bounds__(256) void colsum_batch_kernel(acvae::ColsumBatch b, double* __restrict__ dpart) {
   __shared__ double red[4][64];
   __shared__ int s_last;
-  int j = 0;
-  while (j + 1 < b.n && (int)blockIdx.x >= b.blk0[j + 1]) ++j;
-  const int R = b.R[j];
+  const int j = b.find((int)blockIdx.x);
+  const acvae::ColsumJob& job = b.job[j];
+  const int R = job.R;
   if ((int)blockIdx.y >= R) return;
-  const float* __restrict__ partials = b.x[j];
-  const int P = b.P[j], width = b.width[j];
+  const float* __restrict__ partials = job.x;
+  const int P = job.P, width = job.width;
   unsigned* tickets = reinterpret_cast<unsigned*>(dpart);
-  double* dsum = dpart + CS_TICKETS / 2 + b.d0[j];
+  double* dsum = dpart + CS_TICKETS / 2 + job.d0;
   const int il = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int i = ((int)blockIdx.x - b.blk0[j]) * 64 + il;
+  const int i = ((int)blockIdx.x - b.start[j]) * 64 + il;
   double a = 0.0;
   if (i < width)
     for (int p = blockIdx.y + g * R; p < P; p += 4 * R) a += (double)partials[(long)p * width + i];
@@ -773,8 +773,8 @@ __global__ __launch_bounds__(256) void colsum_batch_kernel(acvae::ColsumBatch b,
     for (int u = 0; u < 8; ++u)
       if (r0 + u < R) t += v[u];
   }
-  b.out[j][i] = (float)t;
-  if (b.out_b[j]) b.out_b[j][i] = (float)t;
+  job.out[i] = (float)t;
+  if (job.out_b) job.out_b[i] = (float)t;
 }
 
 // evaluation mode: scale / shift from the running statistics (no batch statistics, nothing to reduce)
@@ -1548,13 +1548,11 @@ template int repack_weights<float>(const float*, float*, float*, int, int, hipSt
 template int repack_weights<bf16_t>(const float*, bf16_t*, bf16_t*, int, int, hipStream_t);
 template <class T>
 int repack_weights_batch(RepackBatch& b, hipStream_t st) {
+  if (!b.ok()) return ACVAE_EINVAL;
   if (b.n <= 0) return ACVAE_OK;
-  b.start[0] = 0;
-  for (int l = 0; l < b.n; ++l) {
-    if (!b.W[l] || !b.dst[l]) return ACVAE_EINVAL;
-    b.start[l + 1] = b.start[l] + (long)b.Cout[l] * b.Cin[l] * 9;
-  }
-  const long total = b.start[b.n];
+  for (int l = 0; l < b.n; ++l)
+    if (!b.job[l].W || !b.job[l].dst) return ACVAE_EINVAL;
+  const long total = b.seal([](const RepackJob& j) { return (long)j.Cout * j.Cin * 9; });
   hipLaunchKernelGGL(repack_batch_kernel<T>, dim3(cdiv(total, 256) > 8192 ? 8192 : cdiv(total, 256)), dim3(256), 0, st, b);
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
@@ -1583,22 +1581,23 @@ int colsum2(const float* partials, int P, int width, double* dpart, float* out, 
   return ACVAE_OK;
 }
 int colsum_batch(ColsumBatch& b, double* dpart, long dpart_doubles, hipStream_t st) {
+  if (!b.ok()) return ACVAE_EINVAL;
   if (b.n <= 0) return ACVAE_OK;
-  if (b.n > ColsumBatch::MAXJ) return ACVAE_EINVAL;
   long d = 0;
-  int blocks = 0, maxr = 1;
+  int maxr = 1;
   for (int j = 0; j < b.n; ++j) {
-    b.R[j] = cs_groups(b.P[j]);
-    b.blk0[j] = blocks; b.d0[j] = d;
-    blocks += cdiv(b.width[j], 64);
-    d += (long)b.R[j] * b.width[j];
-    if (b.R[j] > maxr) maxr = b.R[j];
+    ColsumJob& c = b.job[j];
+    c.R = cs_groups(c.P);
+    c.d0 = d;
+    d += (long)c.R * c.width;
+    if (c.R > maxr) maxr = c.R;
   }
-  b.blk0[b.n] = blocks;
+  const int blocks = b.seal([](const ColsumJob& c) { return cdiv(c.width, 64); });
   if (b.n == 1 || blocks > CS_TICKETS || CS_TICKETS / 2 + d > dpart_doubles) {         // one launch each, as before
     for (int j = 0; j < b.n; ++j) {
-      ACVAE_TRY(colsum2(b.x[j], b.P[j], b.width[j], dpart, b.out[j], nullptr, 0, st));
-      if (b.out_b[j]) ACVAE_TRY(colsum2(b.x[j], b.P[j], b.width[j], dpart, b.out_b[j], nullptr, 0, st));
+      const ColsumJob& c = b.job[j];
+      ACVAE_TRY(colsum2(c.x, c.P, c.width, dpart, c.out, nullptr, 0, st));
+      if (c.out_b) ACVAE_TRY(colsum2(c.x, c.P, c.width, dpart, c.out_b, nullptr, 0, st));
     }
     return ACVAE_OK;
   }

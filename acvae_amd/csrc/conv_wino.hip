@@ -687,9 +687,9 @@ __global__ void wino_weights_kernel(const float* __restrict__ Wt, float4* __rest
 __global__ void wino_weights_batch_kernel(acvae::WinoWeightsBatch b) {
   const long total = b.start[b.n];
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l + 1 < b.n && idx >= b.start[l + 1]) ++l;
-    wino_weights_item(b.W[l], reinterpret_cast<float4*>(b.U[l]), b.Cout[l], b.Cin[l], b.dgrad[l], idx - b.start[l]);
+    const int l = b.find(idx);
+    const acvae::WinoWeightsJob& j = b.job[l];
+    wino_weights_item(j.W, reinterpret_cast<float4*>(j.U), j.Cout, j.Cin, j.dgrad, idx - b.start[l]);
   }
 }
 
@@ -717,15 +717,16 @@ int conv3x3_wino_weights(const float* W_oihw, float* U, int Cout, int Cin, bool 
 }
 
 int conv3x3_wino_weights_batch(WinoWeightsBatch& b, hipStream_t st) {
+  if (!b.ok()) return ACVAE_EINVAL;
   if (b.n <= 0) return ACVAE_OK;
-  b.start[0] = 0;
   for (int l = 0; l < b.n; ++l) {
-    if (!b.W[l] || !b.U[l]) return ACVAE_EINVAL;
-    const int K = b.dgrad[l] ? b.Cout[l] : b.Cin[l], NO = b.dgrad[l] ? b.Cin[l] : b.Cout[l];
+    const WinoWeightsJob& j = b.job[l];
+    if (!j.W || !j.U) return ACVAE_EINVAL;
+    const int K = j.dgrad ? j.Cout : j.Cin, NO = j.dgrad ? j.Cin : j.Cout;
     if (K % 16 != 0 || NO % WN_TN != 0) return ACVAE_EUNSUPPORTED;
-    b.start[l + 1] = b.start[l] + (long)NO * (K / 4);
   }
-  const long total = b.start[b.n];
+  // an image is NO * (K / 4) float4 items, which is Cout * Cin / 4 either way (K % 16 == 0)
+  const long total = b.seal([](const WinoWeightsJob& j) { return (long)j.Cout * j.Cin / 4; });
   hipLaunchKernelGGL(wino_weights_batch_kernel, dim3(cdiv(total, 256) > 8192 ? 8192 : cdiv(total, 256)), dim3(256), 0, st, b);
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;

@@ -31,6 +31,7 @@
 #include "common.h"
 #include "../../include/acvae_hip.h"
 #include "decode_persist.h"
+#include "job_table.h"
 #include <atomic>
 #include <mutex>
 
@@ -1314,15 +1315,15 @@ struct PersistSlot {
 };
 PersistSlot g_slot[PERSIST_MAX_DEV];
 
-struct PoisonList { float* p[8]; long n[8]; int count; };
-inline void poison_add(PoisonList& l, float* p, long n) {
-  if (p && n > 0 && l.count < 8) { l.p[l.count] = p; l.n[l.count] = n; ++l.count; }
-}
+struct PoisonRegion { float* p; long floats; };
+struct PoisonList : acvae::JobTable<PoisonRegion, 8> {
+  void add(float* p, long floats) { if (p && floats > 0) JobTable::add({p, floats}); }
+};
 __global__ void persist_tail_kernel(const unsigned* abort_word, unsigned* status, int kind, PoisonList list) {
   if (__hip_atomic_load(abort_word, PD_RLX_AGENT) == 0u) return;
   const float qnan = __uint_as_float(0x7fc00000u);
-  for (int k = 0; k < list.count; ++k)
-    for (long i = threadIdx.x; i < list.n[k]; i += blockDim.x) list.p[k][i] = qnan;
+  for (int k = 0; k < list.n; ++k)
+    for (long i = threadIdx.x; i < list.job[k].floats; i += blockDim.x) list.job[k].p[i] = qnan;
   if (status && threadIdx.x == 0) {
     __hip_atomic_store(status + kind, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(status + PK_COUNT, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1366,6 +1367,7 @@ bool persist_fits(K kernel, int kid, int grid, size_t shm) {
 template <class K, class P>
 int persist_launch(K kernel, int kid, const P& p, int grid, size_t shm, long counter_words, const PoisonList& poison, hipStream_t st,
                    bool zeroed = false) {
+  if (!poison.ok()) return ACVAE_EINVAL;
   int dev = 0;
   ACVAE_TRY(persist_device(dev));
   PersistSlot& sl = g_slot[dev];
@@ -1448,9 +1450,9 @@ int decode_persist_fwd(PdParams p, hipStream_t st, int flags) {
   p.abort_word = p.cnt + (long)PD_C_COUNT * p.Tc;
   persist_test_stall(flags, grid, p.spin_limit);
   const long R = (long)p.N * p.Tc;
-  PoisonList poison{};
-  poison_add(poison, p.outputs, R * p.H); poison_add(poison, p.p_means, R * p.E); poison_add(poison, p.p_logs, R * p.E);
-  poison_add(poison, p.p_z, R * p.E); poison_add(poison, p.attn_w, R * p.S);
+  PoisonList poison;
+  poison.add(p.outputs, R * p.H); poison.add(p.p_means, R * p.E); poison.add(p.p_logs, R * p.E);
+  poison.add(p.p_z, R * p.E); poison.add(p.attn_w, R * p.S);
   return persist_launch(decode_persist_kernel, PK_DECODE_FWD, p, grid, shm, words, poison, st, (flags & ACVAE_FLAG_INT_CNT_ZEROED) != 0);
 }
 
@@ -1491,10 +1493,10 @@ int decode_persist_bwd(PbParams p, hipStream_t st, int flags) {
   int grid = p.n_ra + p.n_rb + p.N * p.rc_splits + p.n_pa + p.n_pb;
   persist_test_stall(flags, grid, p.spin_limit);
   const long R = (long)p.N * p.Tc;
-  PoisonList poison{};
-  poison_add(poison, p.dgi, R * 3 * p.H); poison_add(poison, p.dgh, R * 3 * p.H); poison_add(poison, p.dgates, R * 4 * p.E);
-  poison_add(poison, p.dml_all, R * 2 * p.E); poison_add(poison, p.dctx, R * p.E); poison_add(poison, p.dqd, R * p.A);
-  poison_add(poison, p.dencproj, (long)p.N * p.S * p.A);
+  PoisonList poison;
+  poison.add(p.dgi, R * 3 * p.H); poison.add(p.dgh, R * 3 * p.H); poison.add(p.dgates, R * 4 * p.E);
+  poison.add(p.dml_all, R * 2 * p.E); poison.add(p.dctx, R * p.E); poison.add(p.dqd, R * p.A);
+  poison.add(p.dencproj, (long)p.N * p.S * p.A);
   ACVAE_TRY(persist_launch(decode_persist_bwd_kernel, PK_DECODE_BWD, p, grid, decode_bwd_shm(p.S, p.A), words, poison, st,
                            (flags & ACVAE_FLAG_INT_CNT_ZEROED) != 0));
   // (dctx poisoned = NaN in dmem: attn_dmem_kernel forms it from dctx behind the tail)
@@ -1517,8 +1519,8 @@ int posterior_persist_fwd(PqParams p, hipStream_t st, int flags) {
   p.abort_word = p.cnt + 2L * p.Tc;
   int grid = 2 * (p.Hq / 32);
   persist_test_stall(flags, grid, p.spin_limit);
-  PoisonList poison{};
-  poison_add(poison, p.hid, (long)p.N * p.Tc * 2 * p.Hq);
+  PoisonList poison;
+  poison.add(p.hid, (long)p.N * p.Tc * 2 * p.Hq);
   return persist_launch(posterior_persist_fwd_kernel, PK_POST_FWD, p, grid, sizeof(PqSmem), posterior_persist_counter_words(p.Tc),
                         poison, st, (flags & ACVAE_FLAG_INT_CNT_ZEROED) != 0);
 }
@@ -1527,10 +1529,10 @@ int posterior_persist_bwd(PqbParams p, hipStream_t st, int flags) {
   p.abort_word = p.cnt + 2L * p.Tc;
   int grid = 2 * (p.Hq / 32);
   persist_test_stall(flags, grid, p.spin_limit);
-  PoisonList poison{};
+  PoisonList poison;
   for (int dir = 0; dir < 2; ++dir) {
-    poison_add(poison, p.dgi[dir], (long)p.N * p.Tc * 3 * p.Hq);
-    poison_add(poison, p.dgh[dir], (long)p.N * p.Tc * 3 * p.Hq);
+    poison.add(p.dgi[dir], (long)p.N * p.Tc * 3 * p.Hq);
+    poison.add(p.dgh[dir], (long)p.N * p.Tc * 3 * p.Hq);
   }
   return persist_launch(posterior_persist_bwd_kernel, PK_POST_BWD, p, grid, sizeof(PqSmem), posterior_persist_counter_words(p.Tc),
                         poison, st, (flags & ACVAE_FLAG_INT_CNT_ZEROED) != 0);

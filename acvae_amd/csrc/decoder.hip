@@ -359,10 +359,10 @@ extern "C" int acvae_posterior_bwd(const void* const* params, void* const* grads
   float* wt_ih[2] = {sc + L.wt_ih0, sc + L.wt_ih1};
   {   // the transposed weights of the dX = dY . W products: one launch (they depend on the parameters only)
     TransposeBatch tb;
-    tb.add(P(TP_Q_TML_W), 2 * Hq, wt_ml, 2 * E, 2 * E, 2 * Hq);                             // [2Hq][2E]
+    tb.add({P(TP_Q_TML_W), 2 * Hq, wt_ml, 2 * E, 2 * E, 2 * Hq});                           // [2Hq][2E]
     for (int dir = 0; dir < 2; ++dir) {
-      tb.add(P(TP_Q_WIH + dir * 4), E, wt_ih[dir], 3 * Hq, 3 * Hq, E);                      // [E][3Hq]
-      if (persist) tb.add(P(TP_Q_WHH + dir * 4), Hq, dir ? sc + L.wt2 : wt, 3 * Hq, 3 * Hq, Hq);   // [Hq][3Hq]
+      tb.add({P(TP_Q_WIH + dir * 4), E, wt_ih[dir], 3 * Hq, 3 * Hq, E});                    // [E][3Hq]
+      if (persist) tb.add({P(TP_Q_WHH + dir * 4), Hq, dir ? sc + L.wt2 : wt, 3 * Hq, 3 * Hq, Hq}); // [Hq][3Hq]
     }
     ACVAE_TRY(acvae_transpose_batch(tb, st.s));
   }
@@ -373,7 +373,7 @@ extern "C" int acvae_posterior_bwd(const void* const* params, void* const* grads
                               Tc, 2 * Hq, st));
   ACVAE_TRY(gemm_tn(dml, 2 * E, hid, 2 * Hq, G(TP_Q_TML_W), 2 * Hq, 2 * E, 2 * Hq, R, tn, st));
   acvae::ColsumBatch cb;                     // the five bias gradients of the call: one launch at its end
-  cb.add(dml, R, 2 * E, G(TP_Q_TML_B));
+  cb.add({dml, R, 2 * E, G(TP_Q_TML_B)});
   float* dx = sc + L.dx;
   if (persist) {                 // BPTT of both directions in one launch; the parameter products below are unchanged
     PqbParams pb;
@@ -410,9 +410,9 @@ extern "C" int acvae_posterior_bwd(const void* const* params, void* const* grads
       }
     }
     ACVAE_TRY(gemm_tn(dgi, 3 * Hq, X, E, G(TP_Q_WIH + o), E, 3 * Hq, E, R, tn, st));
-    cb.add(dgi, R, 3 * Hq, G(TP_Q_BIH + o));
+    cb.add({dgi, R, 3 * Hq, G(TP_Q_BIH + o)});
     ACVAE_TRY(gemm_tn(dgh, 3 * Hq, hprev, Hq, G(TP_Q_WHH + o), Hq, 3 * Hq, Hq, R, tn, st));
-    cb.add(dgh, R, 3 * Hq, G(TP_Q_BHH + o));
+    cb.add({dgh, R, 3 * Hq, G(TP_Q_BHH + o)});
     ACVAE_TRY(gemm(dgi, 3 * Hq, wt_ih[dir], 3 * Hq, nullptr, dx, E, R, E, 3 * Hq, dir, st));
   }
   ACVAE_TRY(acvae::colsum_batch(cb, dpart, L.dpart_doubles, st));
@@ -624,15 +624,15 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
   auto transposes = [&](hipStream_t ts) -> int {
     if (!train) return ACVAE_OK;
     TransposeBatch tb;
-    tb.add(P(TP_DEC_CLS_W), H, sv + L.wt_cls, V, V, H);                     // [H][V]
-    tb.add(P(TP_DEC_WIH), 3 * E, sv + L.wt_dih, 3 * H, 3 * H, 3 * E);       // [3E][3H]
-    tb.add(P(TP_DEC_WHH), H, sv + L.wt_dhh, 3 * H, 3 * H, H);               // [H][3H]
-    tb.add(P(TP_DEC_ATT_W), E + H, sv + L.wt_datt, A, A, E + H);            // [H+E][A]: rows 0:H query half, H: memory half
-    tb.add(P(TP_P_WIH), 3 * E, sv + L.wt_pih, 4 * Hp, 4 * Hp, 3 * E);       // [3E][4Hp]
-    tb.add(P(TP_P_WHH), Hp, sv + L.wt_phh, 4 * Hp, 4 * Hp, Hp);             // [Hp][4Hp]
-    tb.add(P(TP_P_ML_W), Hp, sv + L.wt_pml, 2 * E, 2 * E, Hp);              // [Hp][2E]
-    tb.add(P(TP_P_ATT_W), 2 * E, sv + L.wt_patt, E, E, 2 * E);              // [2E][E]
-    tb.add(P(TP_MLO_W), H, sv + L.wt_mlo, 2 * E, 2 * E, H);                 // [H][2E]
+    tb.add({P(TP_DEC_CLS_W), H, sv + L.wt_cls, V, V, H});                   // [H][V]
+    tb.add({P(TP_DEC_WIH), 3 * E, sv + L.wt_dih, 3 * H, 3 * H, 3 * E});     // [3E][3H]
+    tb.add({P(TP_DEC_WHH), H, sv + L.wt_dhh, 3 * H, 3 * H, H});             // [H][3H]
+    tb.add({P(TP_DEC_ATT_W), E + H, sv + L.wt_datt, A, A, E + H});          // [H+E][A]: rows 0:H query half, H: memory half
+    tb.add({P(TP_P_WIH), 3 * E, sv + L.wt_pih, 4 * Hp, 4 * Hp, 3 * E});     // [3E][4Hp]
+    tb.add({P(TP_P_WHH), Hp, sv + L.wt_phh, 4 * Hp, 4 * Hp, Hp});           // [Hp][4Hp]
+    tb.add({P(TP_P_ML_W), Hp, sv + L.wt_pml, 2 * E, 2 * E, Hp});            // [Hp][2E]
+    tb.add({P(TP_P_ATT_W), 2 * E, sv + L.wt_patt, E, E, 2 * E});            // [2E][E]
+    tb.add({P(TP_MLO_W), H, sv + L.wt_mlo, 2 * E, 2 * E, H});               // [H][2E]
     return acvae_transpose_batch(tb, ts);
   };
   float* lse = sv + L.lse;
@@ -705,11 +705,11 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
   // h_{t-1} of the prior LSTM for its weight gradient (one shifted copy of hp_all after the loop instead of a copy per step)
   {                    // (and the final states) - five small copies in one launch
     acvae::CopyRowsBatch cb;
-    cb.add(hpprev, (long)Tc * Hp, nullptr, 0, N, Hp);
-    if (Tc > 1) cb.add(hpprev + Hp, (long)Tc * Hp, hp_all, (long)Tc * Hp, N, (Tc - 1) * Hp);
-    if (h_final) cb.add(h_final, H, outputs + (long)(Tc - 1) * H, (long)Tc * H, N, H);
-    if (hp_final) cb.add(hp_final, Hp, hp_all + (long)(Tc - 1) * Hp, (long)Tc * Hp, N, Hp);
-    if (cp_final) cb.add(cp_final, Hp, c_all + (long)(Tc - 1) * Hp, (long)Tc * Hp, N, Hp);
+    cb.add({hpprev, (long)Tc * Hp, nullptr, 0, N, Hp});
+    if (Tc > 1) cb.add({hpprev + Hp, (long)Tc * Hp, hp_all, (long)Tc * Hp, N, (Tc - 1) * Hp});
+    if (h_final) cb.add({h_final, H, outputs + (long)(Tc - 1) * H, (long)Tc * H, N, H});
+    if (hp_final) cb.add({hp_final, Hp, hp_all + (long)(Tc - 1) * Hp, (long)Tc * Hp, N, Hp});
+    if (cp_final) cb.add({cp_final, Hp, c_all + (long)(Tc - 1) * Hp, (long)Tc * Hp, N, Hp});
     ACVAE_TRY(acvae::copy_rows_batch(cb, st));
   }
   if (train) {  // p_means_utt = mean_log_out(mean_with_lens + max_with_lens of the GRU outputs), vae_model.py:722-728
@@ -814,14 +814,14 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     acvae::ColsumBatch cb;
     if (d_p_means_utt) {
       ACVAE_TRY(gemm_tn(d_p_means_utt, 2 * E, sv + L.pool_hid, H, G(TP_MLO_W), H, 2 * E, H, N, ws, c));
-      cb.add(d_p_means_utt, N, 2 * E, G(TP_MLO_B));
+      cb.add({d_p_means_utt, N, 2 * E, G(TP_MLO_B)});
     } else {
       ACVAE_TRY(zero(G(TP_MLO_W), (long)2 * E * H, c));
       ACVAE_TRY(zero(G(TP_MLO_B), 2 * E, c));
     }
     if (d_logits) {
       ACVAE_TRY(gemm_tn(d_logits, V, outputs, H, G(TP_DEC_CLS_W), H, V, H, R, ws, c));
-      cb.add(d_logits, R, V, G(TP_DEC_CLS_B));
+      cb.add({d_logits, R, V, G(TP_DEC_CLS_B)});
     } else {
       ACVAE_TRY(zero(G(TP_DEC_CLS_W), (long)V * H, c));
       ACVAE_TRY(zero(G(TP_DEC_CLS_B), V, c));
@@ -905,8 +905,8 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     ACVAE_TRY(gemm_tn(dgh, 3 * H, hprev_d, H, G(TP_DEC_WHH), H, 3 * H, H, R, ws, c));
     {   // the four bias-shaped gradients of the decoder in one launch
       acvae::ColsumBatch cb;
-      cb.add(dgi, R, 3 * H, G(TP_DEC_BIH)); cb.add(dgh, R, 3 * H, G(TP_DEC_BHH));
-      cb.add(dencproj, N * S, A, G(TP_DEC_ATT_B)); cb.add(dvpart, dv_rows, A, G(TP_DEC_ATT_V));
+      cb.add({dgi, R, 3 * H, G(TP_DEC_BIH)}); cb.add({dgh, R, 3 * H, G(TP_DEC_BHH)});
+      cb.add({dencproj, N * S, A, G(TP_DEC_ATT_B)}); cb.add({dvpart, dv_rows, A, G(TP_DEC_ATT_V)});
       ACVAE_TRY(acvae::colsum_batch(cb, dp, L.dpart_doubles, c));
     }
     // attention parameters: W = [query half | memory half]
@@ -992,8 +992,8 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     ACVAE_TRY(gemm_tn(dgates, 4 * Hp, hpprev, Hp, G(TP_P_WHH), Hp, 4 * Hp, Hp, R, tn_p, sp));
     {   // the prior's bias-shaped gradients in one launch (the LSTM's two biases share theirs)
       acvae::ColsumBatch cb;
-      cb.add(dml_all, R, 2 * E, G(TP_P_ML_B)); cb.add(dgates, R, 4 * Hp, G(TP_P_BIH), G(TP_P_BHH));
-      cb.add(dencproj_p, N * S, E, G(TP_P_ATT_B)); cb.add(dvpart_p, N, E, G(TP_P_ATT_V));
+      cb.add({dml_all, R, 2 * E, G(TP_P_ML_B)}); cb.add({dgates, R, 4 * Hp, G(TP_P_BIH), G(TP_P_BHH)});
+      cb.add({dencproj_p, N * S, E, G(TP_P_ATT_B)}); cb.add({dvpart_p, N, E, G(TP_P_ATT_V)});
       ACVAE_TRY(acvae::colsum_batch(cb, dpart_p, L.dpart_doubles, sp));
     }
     // d emb_p = drnn[:, 0:E] + dqp . W_att[:, :E]
@@ -1251,9 +1251,9 @@ int beam_layout(int N, int beam, int T, int S, int E, int H, int A, int V, BeamL
 }
 
 struct GatherJob { const float* src; float* dst; int width; };
-__global__ __launch_bounds__(256) void beam_gather_kernel(GatherJob a, GatherJob b, GatherJob c, GatherJob d,
-                                                          const int64_t* __restrict__ parent) {
-  const GatherJob j = blockIdx.y == 0 ? a : blockIdx.y == 1 ? b : blockIdx.y == 2 ? c : d;
+using GatherTable = acvae::JobTable<GatherJob, 4>;
+__global__ __launch_bounds__(256) void beam_gather_kernel(GatherTable g, const int64_t* __restrict__ parent) {
+  const GatherJob j = g.job[blockIdx.y];
   const long r = blockIdx.x, p = parent[r];
   for (int i = threadIdx.x; i < j.width; i += blockDim.x) j.dst[r * j.width + i] = j.src[p * j.width + i];
 }
@@ -1328,8 +1328,9 @@ extern "C" int acvae_beam_search(const void* const* params, const float* mem, co
     ACVAE_TRY(acvae_topk_flat_batched(sc + L.scores, (int64_t)beam * V, (int64_t)beam * V, beam, V, topk, idx_t, par_t,
                                       nxt_t, N, beam, stream));
     if (t + 1 < T) {                                     // vae_model.py:961-968: next step's states follow their parents
-      hipLaunchKernelGGL(beam_gather_kernel, dim3(R, 4), dim3(256), 0, st.s, GatherJob{h2, h, H}, GatherJob{hp2, hp, E},
-                         GatherJob{cp2, cp, E}, GatherJob{z, lz, E}, par_t);
+      GatherTable g;
+      g.add({h2, h, H}); g.add({hp2, hp, E}); g.add({cp2, cp, E}); g.add({z, lz, E});
+      hipLaunchKernelGGL(beam_gather_kernel, dim3(R, g.n), dim3(256), 0, st.s, g, par_t);
       w_t = nxt_t;
     }
   }

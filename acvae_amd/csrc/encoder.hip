@@ -263,13 +263,13 @@ int encoder_fwd_t(const void* const* params, const float* feats, float* audio_em
     for (int b = 1; b <= L.nb; ++b) {
       const int H = L.H[b], W = L.W[b], C = kChan[b], Cin = kChan[b - 1];
       if (b > 1 && use_wino<TA>(H, W, Cin, C)) {
-        wb.add(P(p_conv(b, 1)), saved + L.wf1[b], C, Cin, false);
-        if (training && use_wino<TA>(H, W, C, Cin)) wb.add(P(p_conv(b, 1)), saved + L.wd1[b], C, Cin, true);
+        wb.add({P(p_conv(b, 1)), saved + L.wf1[b], C, Cin, false});
+        if (training && use_wino<TA>(H, W, C, Cin)) wb.add({P(p_conv(b, 1)), saved + L.wd1[b], C, Cin, true});
         wready[b][0] = true;
       }
       if (use_wino<TA>(H, W, C, C)) {
-        wb.add(P(p_conv(b, 2)), saved + L.wf2[b], C, C, false);
-        if (training) wb.add(P(p_conv(b, 2)), saved + L.wd2[b], C, C, true);
+        wb.add({P(p_conv(b, 2)), saved + L.wf2[b], C, C, false});
+        if (training) wb.add({P(p_conv(b, 2)), saved + L.wd2[b], C, C, true});
         wready[b][1] = true;
       }
     }
@@ -280,13 +280,13 @@ int encoder_fwd_t(const void* const* params, const float* feats, float* audio_em
     for (int b = 1; b <= L.nb; ++b) {
       const int C = kChan[b], Cin = kChan[b - 1];
       if (b > 1 && !wready[b][0]) {
-        rb.add(P(p_conv(b, 1)), saved + L.wf1[b], C, Cin, false);
-        if (training) rb.add(P(p_conv(b, 1)), saved + L.wd1[b], C, Cin, true);
+        rb.add({P(p_conv(b, 1)), saved + L.wf1[b], C, Cin, false});
+        if (training) rb.add({P(p_conv(b, 1)), saved + L.wd1[b], C, Cin, true});
         wready[b][0] = true;
       }
       if (!wready[b][1]) {
-        rb.add(P(p_conv(b, 2)), saved + L.wf2[b], C, C, false);
-        if (training) rb.add(P(p_conv(b, 2)), saved + L.wd2[b], C, C, true);
+        rb.add({P(p_conv(b, 2)), saved + L.wf2[b], C, C, false});
+        if (training) rb.add({P(p_conv(b, 2)), saved + L.wd2[b], C, C, true});
         wready[b][1] = true;
       }
     }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "job_table.h"
 namespace acvae {
 int caps_to_long(const float* caps, int64_t* out, long n, hipStream_t st);
 int select_word(const int64_t* caps, long ld_caps, const int64_t* seqs, long ld_seqs, int64_t* words, long ld_words,
@@ -32,21 +33,15 @@ int pool_bwd(const float* d, const int64_t* lens, const int* argmax, float* dx, 
 int colsum_rows(const float* x, long ld, int rows, int cols, float* out, int accumulate, hipStream_t st);
 int add_rows(float* dst, long ld_d, const float* src, long ld_s, int rows, int cols, hipStream_t st);
 int copy_rows(float* dst, long ld_d, const float* src, long ld_s, int rows, int cols, hipStream_t st);
-// up to 8 copy_rows jobs (src == nullptr: zero fill) in ONE launch; the jobs must not overlap
-struct CopyRowsBatch {
-  static constexpr int MAXJ = 8;
-  float* dst[MAXJ]; const float* src[MAXJ]; long ld_d[MAXJ], ld_s[MAXJ]; int rows[MAXJ], cols[MAXJ]; int n = 0;
-  void add(float* d, long ldd, const float* s, long lds, int r, int c) {
-    dst[n] = d; src[n] = s; ld_d[n] = ldd; ld_s[n] = lds; rows[n] = r; cols[n] = c; ++n;
-  }
-};
+// copy_rows jobs (src == nullptr: zero fill) in ONE launch; the jobs must not overlap
+struct CopyRowsJob { float* dst; long ld_d; const float* src; long ld_s; int rows, cols; };
+using CopyRowsBatch = JobTable<CopyRowsJob, 8>;
 int copy_rows_batch(const CopyRowsBatch& b, hipStream_t st);
-// up to 10 regions of 32-bit words zeroed in ONE launch: the tickets / arrival counters / accumulators a composite call starts
-// from (each was a 5-us hipMemsetAsync in front of the call's first kernel; words % 1 == 0, 4-byte aligned)
-struct ZeroBatch {
-  static constexpr int MAXJ = 10;
-  void* p[MAXJ]; long words[MAXJ]; int n = 0;        // n > MAXJ: more regions were added than fit (zero_batch refuses)
-  void add(void* ptr, long w) { if (ptr && w > 0) { if (n < MAXJ) { p[n] = ptr; words[n] = w; } ++n; } }
+// regions of 32-bit words zeroed in ONE launch: the tickets / arrival counters / accumulators a composite call starts from (each
+// was a 5-us hipMemsetAsync in front of the call's first kernel; 4-byte aligned).  A null region or one of no words is skipped.
+struct ZeroRegion { void* p; long words; };
+struct ZeroBatch : JobTable<ZeroRegion, 16> {
+  void add(void* p, long words) { if (p && words > 0) JobTable::add({p, words}); }
 };
 int zero_batch(const ZeroBatch& b, hipStream_t st);
 }  // namespace acvae

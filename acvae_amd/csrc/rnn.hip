@@ -278,22 +278,17 @@ __global__ void copy_rows_kernel(float* __restrict__ dst, long ld_d, const float
 
 // several copy_rows jobs in one launch (blockIdx.y = job): the decode forward ended in five 5-us copies of a few KB each
 __global__ void copy_rows_batch_kernel(acvae::CopyRowsBatch b) {
-  const int j = blockIdx.y;
-  const long total = (long)b.rows[j] * b.cols[j];
-  const int cols = b.cols[j];
-  float* dst = b.dst[j];
-  const float* src = b.src[j];
-  const long ld_d = b.ld_d[j], ld_s = b.ld_s[j];
+  const acvae::CopyRowsJob& j = b.job[blockIdx.y];
+  const long total = (long)j.rows * j.cols;
   for (long i = blockIdx.x * (long)TH + threadIdx.x; i < total; i += (long)gridDim.x * TH) {
-    const int r = (int)(i / cols), c = (int)(i % cols);
-    dst[r * ld_d + c] = src ? src[r * ld_s + c] : 0.f;
+    const int r = (int)(i / j.cols), c = (int)(i % j.cols);
+    j.dst[r * j.ld_d + c] = j.src ? j.src[r * j.ld_s + c] : 0.f;
   }
 }
 
 __global__ void zero_batch_kernel(acvae::ZeroBatch b) {
-  const int j = blockIdx.y;
-  unsigned* p = static_cast<unsigned*>(b.p[j]);
-  const long n = b.words[j];
+  unsigned* p = static_cast<unsigned*>(b.job[blockIdx.y].p);
+  const long n = b.job[blockIdx.y].words;
   for (long i = blockIdx.x * (long)TH + threadIdx.x; i < n; i += (long)gridDim.x * TH) p[i] = 0u;
 }
 
@@ -302,19 +297,21 @@ __global__ void zero_batch_kernel(acvae::ZeroBatch b) {
 namespace acvae {
 #define LAUNCH(k, g, ...) hipLaunchKernelGGL(k, dim3(g), dim3(TH), 0, st, __VA_ARGS__)
 int zero_batch(const ZeroBatch& b, hipStream_t st) {
+  if (!b.ok()) return ACVAE_EINVAL;
   if (b.n <= 0) return ACVAE_OK;
-  if (b.n > ZeroBatch::MAXJ) return ACVAE_EINVAL;
   long most = 1;
-  for (int j = 0; j < b.n; ++j) if (b.words[j] > most) most = b.words[j];
+  for (int j = 0; j < b.n; ++j) if (b.job[j].words > most) most = b.job[j].words;
   hipLaunchKernelGGL(zero_batch_kernel, dim3(grid1(most), b.n), dim3(TH), 0, st, b);
   ACVAE_LAUNCH_CHECK(); return ACVAE_OK;
 }
 int copy_rows_batch(const CopyRowsBatch& b, hipStream_t st) {
+  if (!b.ok()) return ACVAE_EINVAL;
   if (b.n <= 0) return ACVAE_OK;
   long most = 1;
   for (int j = 0; j < b.n; ++j) {
-    if (!b.dst[j] || b.rows[j] <= 0 || b.cols[j] <= 0) return ACVAE_EINVAL;
-    const long t = (long)b.rows[j] * b.cols[j];
+    const CopyRowsJob& c = b.job[j];
+    if (!c.dst || c.rows <= 0 || c.cols <= 0) return ACVAE_EINVAL;
+    const long t = (long)c.rows * c.cols;
     if (t > most) most = t;
   }
   hipLaunchKernelGGL(copy_rows_batch_kernel, dim3(grid1(most), b.n), dim3(TH), 0, st, b);
