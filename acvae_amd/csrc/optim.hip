@@ -93,3 +93,155 @@ extern "C" int acvae_adam_step(float* params, const float* grads, float* exp_avg
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// AdamW / amsgrad / SGD over the same flat buffer (the reference takes its optimiser from conf["optimizer"],
+// runners/pytorch_runner_vae.py:219).  One streaming kernel body, the optimiser kind a template parameter; every
+// element follows the operation order of torch.optim.<X>(foreach=False), so the result agrees with torch to fp32
+// elementwise rounding.  float4 main loop, scalar tail in block 0 (as sqsum_kernel).  Bytes per parameter:
+// Adam/AdamW 28 (+8 amsgrad), SGD 12 (+4 reading the momentum buffer, +4 writing it).
+namespace {
+enum OptKind { OPT_ADAM = 0, OPT_SGD = 1 };
+
+struct OptArgs {
+  float* p; const float* g; float* s0; float* s1; float* s2;   // Adam: exp_avg, exp_avg_sq, max_exp_avg_sq; SGD: buf
+  long n;
+  float lr, a, b, c, d, wd, decay;       // Adam: a = 1-beta1, b = beta2, c = 1-beta2, d = eps; SGD: a = momentum, b = 1-dampening
+  float step_size, bc2_sqrt;             // Adam: lr / bc1, sqrt(bc2)
+  int flags;                             // OPT_F_*
+  float grad_scale, max_norm;
+  const float* total_norm;
+};
+constexpr int OPT_F_DECOUPLED = 1, OPT_F_NESTEROV = 2, OPT_F_FIRST = 4;
+
+// torch's lerp: weight < 0.5 ? a + w*(b-a) : b - (b-a)*(1-w)
+__device__ __forceinline__ float lerp_t(float a, float b, float w) {
+  return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.f - w);
+}
+
+// One element; STATE = amsgrad (Adam) / momentum != 0 (SGD).  Only the state that the kind uses is touched.
+template <int KIND, bool STATE>
+__device__ __forceinline__ void opt_elem(const OptArgs& A, float coef, float& p, float g, float& s0, float& s1, float& s2) {
+  g *= coef;
+  if (KIND == OPT_ADAM) {
+    if (A.wd != 0.f) {
+      if (A.flags & OPT_F_DECOUPLED) p *= A.decay;     // param.mul_(1 - lr*wd)
+      else g += A.wd * p;                              // grad.add(param, alpha=wd)
+    }
+    s0 = lerp_t(s0, g, A.a);                           // exp_avg.lerp_(grad, 1-beta1)
+    s1 = s1 * A.b + A.c * (g * g);                     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1-beta2)
+    float v = s1;
+    if (STATE) { s2 = fmaxf(s2, s1); v = s2; }         // torch.maximum(max_exp_avg_sq, exp_avg_sq)
+    const float denom = sqrtf(v) / A.bc2_sqrt + A.d;
+    p = p + (-A.step_size) * (s0 / denom);             // addcdiv_(exp_avg, denom, value=-step_size)
+  } else {
+    if (A.wd != 0.f) g += A.wd * p;
+    if (STATE) {
+      s0 = (A.flags & OPT_F_FIRST) ? g : s0 * A.a + A.b * g;
+      g = (A.flags & OPT_F_NESTEROV) ? g + A.a * s0 : s0;
+    }
+    p = p + (-A.lr) * g;
+  }
+}
+
+template <int KIND, bool STATE>
+__global__ __launch_bounds__(TH) void opt_kernel(OptArgs A) {
+  float coef = A.grad_scale;                           // clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max=1)
+  if (A.total_norm && A.max_norm > 0.f) {
+    float c = A.max_norm / (A.total_norm[0] + 1e-6f);
+    coef *= c < 1.f ? c : 1.f;
+  }
+  constexpr bool ADAM = KIND == OPT_ADAM;
+  // which state arrays are read / written (SGD's first step writes the buffer without reading it)
+  const bool r0 = ADAM || (STATE && !(A.flags & OPT_F_FIRST));
+  const bool w0 = ADAM || STATE;
+  const bool u1 = ADAM, u2 = ADAM && STATE;
+  const long n4 = A.n >> 2;
+  float4* p4 = reinterpret_cast<float4*>(A.p);
+  const float4* g4 = reinterpret_cast<const float4*>(A.g);
+  float4* s04 = reinterpret_cast<float4*>(A.s0);
+  float4* s14 = reinterpret_cast<float4*>(A.s1);
+  float4* s24 = reinterpret_cast<float4*>(A.s2);
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long i = blockIdx.x * (long)TH + threadIdx.x; i < n4; i += (long)gridDim.x * TH) {
+    float4 p = p4[i];
+    const float4 g = g4[i];
+    float4 s0 = r0 ? s04[i] : z, s1 = u1 ? s14[i] : z, s2 = u2 ? s24[i] : z;
+    opt_elem<KIND, STATE>(A, coef, p.x, g.x, s0.x, s1.x, s2.x);
+    opt_elem<KIND, STATE>(A, coef, p.y, g.y, s0.y, s1.y, s2.y);
+    opt_elem<KIND, STATE>(A, coef, p.z, g.z, s0.z, s1.z, s2.z);
+    opt_elem<KIND, STATE>(A, coef, p.w, g.w, s0.w, s1.w, s2.w);
+    p4[i] = p;
+    if (w0) s04[i] = s0;
+    if (u1) s14[i] = s1;
+    if (u2) s24[i] = s2;
+  }
+  if (blockIdx.x == 0)
+    for (long i = (n4 << 2) + threadIdx.x; i < A.n; i += TH) {
+      float p = A.p[i], s0 = r0 ? A.s0[i] : 0.f, s1 = u1 ? A.s1[i] : 0.f, s2 = u2 ? A.s2[i] : 0.f;
+      opt_elem<KIND, STATE>(A, coef, p, A.g[i], s0, s1, s2);
+      A.p[i] = p;
+      if (w0) A.s0[i] = s0;
+      if (u1) A.s1[i] = s1;
+      if (u2) A.s2[i] = s2;
+    }
+}
+
+bool aligned_or_null(const void* p) { return !p || aligned16(p); }
+
+int launch_opt(int kind, bool state, const OptArgs& A, void* stream) {
+  long nb = (A.n / 4 + TH - 1) / TH;
+  if (nb < 1) nb = 1;
+  if (nb > 4096) nb = 4096;
+  hipStream_t st = (hipStream_t)stream;
+  if (kind == OPT_ADAM) {
+    if (state) hipLaunchKernelGGL((opt_kernel<OPT_ADAM, true>), dim3((int)nb), dim3(TH), 0, st, A);
+    else hipLaunchKernelGGL((opt_kernel<OPT_ADAM, false>), dim3((int)nb), dim3(TH), 0, st, A);
+  } else {
+    if (state) hipLaunchKernelGGL((opt_kernel<OPT_SGD, true>), dim3((int)nb), dim3(TH), 0, st, A);
+    else hipLaunchKernelGGL((opt_kernel<OPT_SGD, false>), dim3((int)nb), dim3(TH), 0, st, A);
+  }
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+}  // namespace
+
+extern "C" int acvae_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                float* max_exp_avg_sq, int64_t n, double lr, double beta1, double beta2, double eps,
+                                double weight_decay, int decoupled, int amsgrad, int64_t step, float grad_scale,
+                                float max_grad_norm, const float* total_norm, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || (amsgrad && !max_exp_avg_sq) || n <= 0 || step <= 0)
+    return ACVAE_EINVAL;
+  if (!aligned16(params) || !aligned16(grads) || !aligned16(exp_avg) || !aligned16(exp_avg_sq) ||
+      (amsgrad && !aligned16(max_exp_avg_sq)))
+    return ACVAE_EALIGN;
+  // hyperparameters arrive in double and every derived scalar is formed in double, then rounded once, as torch's Python
+  // scalars reach its fp32 kernels (1 - beta2 from a float 0.999f would be off by 1.3e-5 relative)
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  OptArgs A{};
+  A.p = params; A.g = grads; A.s0 = exp_avg; A.s1 = exp_avg_sq; A.s2 = amsgrad ? max_exp_avg_sq : nullptr;
+  A.n = (long)n; A.lr = (float)lr;
+  A.a = (float)(1.0 - beta1); A.b = (float)beta2; A.c = (float)(1.0 - beta2); A.d = (float)eps;
+  A.wd = (float)weight_decay; A.decay = (float)(1.0 - lr * weight_decay);
+  A.step_size = (float)(lr / bc1); A.bc2_sqrt = (float)sqrt(bc2);
+  A.flags = decoupled ? OPT_F_DECOUPLED : 0;
+  A.grad_scale = grad_scale; A.max_norm = max_grad_norm; A.total_norm = total_norm;
+  return launch_opt(OPT_ADAM, amsgrad != 0, A, stream);
+}
+
+extern "C" int acvae_sgd_step(float* params, const float* grads, float* momentum_buffer, int64_t n, double lr,
+                              double momentum, double dampening, double weight_decay, int nesterov, int first,
+                              float grad_scale, float max_grad_norm, const float* total_norm, void* stream) {
+  const bool mom = momentum != 0.0;
+  if (!params || !grads || (mom && !momentum_buffer) || n <= 0) return ACVAE_EINVAL;
+  if (nesterov && (!mom || dampening != 0.0)) return ACVAE_EINVAL;
+  if (!aligned16(params) || !aligned16(grads) || !aligned_or_null(mom ? momentum_buffer : nullptr)) return ACVAE_EALIGN;
+  OptArgs A{};
+  A.p = params; A.g = grads; A.s0 = mom ? momentum_buffer : nullptr;
+  A.n = (long)n; A.lr = (float)lr;
+  A.a = (float)momentum; A.b = (float)(1.0 - dampening); A.wd = (float)weight_decay;
+  A.flags = (nesterov ? OPT_F_NESTEROV : 0) | (first ? OPT_F_FIRST : 0);
+  A.grad_scale = grad_scale; A.max_norm = max_grad_norm; A.total_norm = total_norm;
+  return launch_opt(OPT_SGD, mom, A, stream);
+}

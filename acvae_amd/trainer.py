@@ -1,6 +1,7 @@
 """Train-step harness: the body of ``Runner.train``'s inner loop (``runners/pytorch_runner_vae.py:286,
 311-324``) around the HIP model — zero_grad, ``_forward`` (:76-98), loss = CE + kl_weight*KL (+ alpha*MSE),
-backward, ``clip_grad_norm_(max_grad_norm)``, ``Adam.step`` — with the MI355X-specific plumbing:
+backward, ``clip_grad_norm_(max_grad_norm)``, ``optimizer.step`` (Adam, AdamW or SGD from the config, :219; see
+acvae_amd/optim.py) — with the MI355X-specific plumbing:
 
   * all parameters live in ONE flat fp32 buffer and all gradients in another (the backward kernels write
     straight into it), so the global-norm clip is one reduction and Adam is one fused pass
@@ -22,6 +23,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .optim import FlatOptimizer, check_group, resolve
 from .train_util import LabelSmoothingLoss, MSELoss, Normal_kl_loss, combine_losses
 
 
@@ -105,15 +107,36 @@ def kl_weight_for(epoch, epochs, beta):
     return max(0.5, float(epoch) / epochs * beta)
 
 
+def _group_property(key):
+    def get(self):
+        return self.optimizer.param_groups[0].get(key)
+
+    def set(self, value):
+        self.optimizer.param_groups[0][key] = tuple(value) if key == "betas" else value
+    return property(get, set, doc=f"optimizer.param_groups[0][{key!r}]")
+
+
 class TrainStep:
-    def __init__(self, model, vocab_size, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
+    """One training step (see the module docstring).  ``optimizer`` / ``optimizer_args`` are the reference's
+    conf["optimizer"] / conf["optimizer_args"]: "Adam", "AdamW" or "SGD" with torch's arguments and torch's defaults
+    (``lr`` defaults to 5e-4 for all three; ``betas`` / ``eps`` / ``weight_decay`` given here are overridden by the same
+    key in ``optimizer_args``).  ``self.optimizer`` is a ``torch.optim.Optimizer`` (acvae_amd.optim.FlatOptimizer) that LR
+    schedulers can drive; ``lr``, ``betas``, ``eps`` and ``weight_decay`` are views of its param group."""
+
+    lr = _group_property("lr")
+    betas = _group_property("betas")
+    eps = _group_property("eps")
+    weight_decay = _group_property("weight_decay")
+
+    def __init__(self, model, vocab_size, lr=5e-4, betas=None, eps=None, weight_decay=None, max_grad_norm=1.0,
                  label_smoothing=True, smoothing=0.1, alpha=1.0, global_loss="MSE", process_group=None,
-                 broadcast_buffers=True, data_parallel=True, precision=None):
+                 broadcast_buffers=True, data_parallel=True, precision=None, optimizer="Adam", optimizer_args=None):
+        group = resolve(optimizer, optimizer_args, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.optimizer_name = optimizer
         self.model = model
         if precision is not None:                   # "f32" | "bf16" (bf16 forward / fp32 loss: BASELINE configs[2])
             model.encoder.compute_dtype = precision
         self.vocab = vocab_size
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
         self.smoothing = smoothing if label_smoothing else 0.0
         self.alpha, self.global_loss = alpha, global_loss
@@ -130,7 +153,9 @@ class TrainStep:
         self.max_steps_in_flight = int(os.environ.get("ACVAE_STEPS_IN_FLIGHT", "2"))
         self._in_flight = []
         self._copy_stream = None
-        self._flatten()
+        self._flatten(group)
+        self.optimizer = FlatOptimizer(self, model.parameters(), optimizer, group)
+        self._pending = None                        # (gscale, total_norm, skipped, stream) while step() applies the update
         # Buckets in flat order, each announced from inside the backward as soon as its gradients are queued:
         #   0 decoder + prior + heads (everything acvae_decode_bwd writes, 76 MB at V=5000): behind the decode backward,
         #     i.e. before the encoder backward has even started;
@@ -168,7 +193,7 @@ class TrainStep:
             (self.pg is not None or dist.get_world_size() > 1)
 
     # ------------------------------------------------------------------ flat parameter / gradient storage
-    def _flatten(self):
+    def _flatten(self, group):
         model = self.model
         enc_params = set(model.encoder.parameters())
         head = model.encoder._head()                                # embed_pooled / fc1: no gradient on this path
@@ -190,8 +215,16 @@ class TrainStep:
         total = sum(sizes)
         self.flat_p = torch.zeros(total, device=dev)
         self.flat_g = torch.zeros(total, device=dev)
-        self.exp_avg = torch.zeros(total, device=dev)
-        self.exp_avg_sq = torch.zeros(total, device=dev)
+        # optimiser state: only what the chosen optimiser keeps (Adam: exactly the two moments, as always)
+        self.exp_avg = self.exp_avg_sq = self.max_exp_avg_sq = self.momentum_buffer = None
+        self._sgd_started = set()                   # SGD with momentum: parameters whose buffer exists
+        if "betas" in group:
+            self.exp_avg = torch.zeros(total, device=dev)
+            self.exp_avg_sq = torch.zeros(total, device=dev)
+            if group["amsgrad"]:
+                self.max_exp_avg_sq = torch.zeros(total, device=dev)
+        elif group["momentum"] != 0:
+            self.momentum_buffer = torch.zeros(total, device=dev)
         views, off = {}, 0
         for p, sz in zip(order, sizes):
             pv = self.flat_p[off:off + p.numel()].view_as(p)
@@ -325,13 +358,11 @@ class TrainStep:
             _lib.call("acvae_grad_norm", self.flat_g, n, gscale, self.norm_partials, self.total_norm, st)
             tn = self.total_norm
         self.step_count += 1
-        # torch.optim.Adam leaves a parameter whose .grad is None alone (no moment decay, no update): the fused pass
-        # then runs over the segments between such parameters (their gradient slices are zero, so the norm is unaffected).
-        # On this path every parameter gets a gradient every step and the loop runs once over the whole buffer.
-        for a, b in self._segments(skipped, n):
-            _lib.call("acvae_adam_step", self.flat_p[a:b], self.flat_g[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b], b - a,
-                      self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count, gscale,
-                      float(self.max_grad_norm or 0.0), tn, st)
+        self._pending = (gscale, tn, skipped, st)
+        try:
+            self.optimizer.step()                  # the instance attribute: an LR scheduler's step tracking sees the call
+        finally:
+            self._pending = None
         parts["loss"] = loss.detach()
         parts["grad_norm"] = self.total_norm
         # DDP's broadcast_buffers: rank 0's BatchNorm running statistics reach the other ranks before the next forward
@@ -352,6 +383,70 @@ class TrainStep:
                 # device's status word: turn it into an error at the first synchronisation point the loop has anyway
                 _lib.check_persist_status(self.flat_p.device)
         return parts
+
+    def _apply_update(self):
+        """The fused update of the step that step() is running, with the hyperparameters of param_groups[0] as they are
+        now (host floats: no synchronisation)."""
+        if self._pending is None:
+            raise RuntimeError("TrainStep.optimizer.step() applies the update of the step that TrainStep.step() is running "
+                               "(it needs that step's gradients and norm): call TrainStep.step(...) instead")
+        gscale, tn, skipped, st = self._pending
+        g = self.optimizer.param_groups[0]
+        check_group(self.optimizer_name, g)
+        n, mg = self.n_active, float(self.max_grad_norm or 0.0)
+        if self.optimizer_name == "SGD":
+            mom = float(g["momentum"])
+            if mom != 0 and self.momentum_buffer is None:
+                raise RuntimeError("SGD momentum became non-zero, but TrainStep was built with momentum == 0 (no buffer)")
+            # torch.optim.SGD starts a parameter's buffer from its first gradient: split the segments by whether the
+            # buffer exists, so that every launch has one `first` flag
+            segs = self._sgd_segments(skipped, n) if mom != 0 else [(a, b, False) for a, b in self._segments(skipped, n)]
+            for a, b, first in segs:
+                _lib.call("acvae_sgd_step", self.flat_p[a:b], self.flat_g[a:b],
+                          self.momentum_buffer[a:b] if mom != 0 else None, b - a, g["lr"], mom, g["dampening"],
+                          g["weight_decay"], int(bool(g["nesterov"])), int(first), gscale, mg, tn, st)
+            if mom != 0:
+                self._sgd_started.update(p for p, _ in self._active_params(skipped, n))
+            return
+        if bool(g["amsgrad"]) != (self.max_exp_avg_sq is not None):
+            raise RuntimeError("amsgrad cannot change after TrainStep was built (it decides which state exists)")
+        b1, b2 = g["betas"]
+        # torch.optim.Adam leaves a parameter whose .grad is None alone (no moment decay, no update): the fused pass
+        # then runs over the segments between such parameters (their gradient slices are zero, so the norm is unaffected).
+        # On this path every parameter gets a gradient every step and the loop runs once over the whole buffer.
+        for a, b in self._segments(skipped, n):
+            if not g["amsgrad"] and not g["decoupled_weight_decay"]:
+                _lib.call("acvae_adam_step", self.flat_p[a:b], self.flat_g[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b],
+                          b - a, g["lr"], b1, b2, g["eps"], g["weight_decay"], self.step_count, gscale, mg, tn, st)
+            else:
+                _lib.call("acvae_adamw_step", self.flat_p[a:b], self.flat_g[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b],
+                          self.max_exp_avg_sq[a:b] if g["amsgrad"] else None, b - a, g["lr"], b1, b2, g["eps"],
+                          g["weight_decay"], int(bool(g["decoupled_weight_decay"])), int(bool(g["amsgrad"])),
+                          self.step_count, gscale, mg, tn, st)
+
+    def _active_params(self, skipped, n):
+        """(parameter, offset) of every parameter in the active range that has a gradient this step."""
+        skip = {a for a, _ in skipped}
+        out, off = [], 0
+        for p in self.order:
+            if off >= n:
+                break
+            if off not in skip:
+                out.append((p, off))
+            off += (p.numel() + 3) // 4 * 4
+        return out
+
+    def _sgd_segments(self, skipped, n):
+        """[(a, b, first)]: maximal runs of parameters with a gradient whose momentum buffer does (first=False) or does
+        not yet (first=True) exist."""
+        segs = []
+        for p, off in self._active_params(skipped, n):
+            end, first = off + (p.numel() + 3) // 4 * 4, p not in self._sgd_started
+            if segs and segs[-1][1] == off and segs[-1][2] == first:
+                segs[-1][1] = end
+            else:
+                segs.append([off, end, first])
+        return [tuple(s) for s in segs]
 
     def synchronize(self):
         """Wait for every queued step and raise if one of their persistent launches gave up (acvae_persist_status_register)."""
@@ -406,49 +501,84 @@ class TrainStep:
             off += (p.numel() + 3) // 4 * 4
         return table
 
+    def _state_buffers(self):
+        """{torch state key: flat buffer} of the chosen optimiser."""
+        if self.optimizer_name == "SGD":
+            return {} if self.momentum_buffer is None else {"momentum_buffer": self.momentum_buffer}
+        bufs = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+        if self.max_exp_avg_sq is not None:
+            bufs["max_exp_avg_sq"] = self.max_exp_avg_sq
+        return bufs
+
     def optimizer_state_dict(self):
-        """The moments in ``torch.optim.Adam.state_dict()`` layout, parameters indexed in ``model.parameters()`` order
-        (the optimiser of the reference is built from it, ``runners/pytorch_runner_vae.py:233-236``), so that
-        ``{"model": model.state_dict(), "optimizer": ts.optimizer_state_dict()}`` is the checkpoint the reference writes
-        (``:380-388``) and a ``torch.optim.Adam`` over a reference model loads it."""
+        """The optimiser state in the ``state_dict()`` layout of ``torch.optim.<optimizer>`` (Adam / AdamW: ``step``,
+        ``exp_avg``, ``exp_avg_sq`` and ``max_exp_avg_sq`` with amsgrad; SGD: ``momentum_buffer``), parameters indexed in
+        ``model.parameters()`` order (the optimiser of the reference is built from it, ``runners/pytorch_runner_vae.py:
+        219, 233-236``), the param group with the keys of the torch class, so that ``{"model": model.state_dict(),
+        "optimizer": ts.optimizer_state_dict()}`` is the checkpoint the reference writes (``:380-388``) and a
+        ``torch.optim.<optimizer>`` over a reference model loads it.  ``ts.optimizer.state_dict()`` is this."""
         table = self._offsets()
-        params = list(self.model.parameters())     # the reference builds Adam over ALL model.parameters() (:233-236)
+        params = list(self.model.parameters())     # the reference builds its optimiser over ALL model.parameters()
+        bufs = self._state_buffers()
+        sgd = self.optimizer_name == "SGD"
         state = {}
         for i, p in enumerate(params):
-            # torch.optim.Adam holds no state for a parameter that never had a gradient (frozen ones, and the pooled
+            # torch's optimisers hold no state for a parameter that never had a gradient (frozen ones, and the pooled
             # head embed_pooled / fc1 whose output this path does not consume): no entry, like a reference checkpoint
-            if self.step_count == 0 or p not in table or p in self.never:
+            if not bufs or p not in table or p in self.never:
+                continue
+            if (sgd and p not in self._sgd_started) or (not sgd and self.step_count == 0):
                 continue
             o = table[p]
-            state[i] = {"step": torch.tensor(float(self.step_count)),
-                        "exp_avg": self.exp_avg[o:o + p.numel()].view_as(p).clone(),
-                        "exp_avg_sq": self.exp_avg_sq[o:o + p.numel()].view_as(p).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
-                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-                 "fused": None, "params": list(range(len(params)))}
+            st = {} if sgd else {"step": torch.tensor(float(self.step_count))}
+            for k, flat in bufs.items():
+                st[k] = flat[o:o + p.numel()].view_as(p).clone()
+            state[i] = st
+        group = {k: v for k, v in self.optimizer.param_groups[0].items() if k != "params"}
+        group["params"] = list(range(len(params)))
         return {"state": state, "param_groups": [group]}
 
     def load_optimizer_state_dict(self, sd):
-        """Inverse of ``optimizer_state_dict`` (also accepts the state dict of a ``torch.optim.Adam`` built over the
-        same model): resume training where the checkpoint left off."""
+        """Inverse of ``optimizer_state_dict`` (also accepts the state dict of the matching ``torch.optim`` class built
+        over the same model): resume training where the checkpoint left off.  ``ts.optimizer.load_state_dict()`` is this."""
         table = self._offsets()
         params = list(self.model.parameters())
-        group = sd["param_groups"][0]
-        self.lr, self.betas, self.eps = group["lr"], tuple(group["betas"]), group["eps"]
-        self.weight_decay = group.get("weight_decay", 0.0)
+        if len(sd["param_groups"]) != 1:
+            raise ValueError("TrainStep's optimizer has exactly one param group")
+        group = {k: v for k, v in sd["param_groups"][0].items() if k != "params"}
+        check_group(self.optimizer_name, group)
+        bufs = self._state_buffers()
+        sgd = self.optimizer_name == "SGD"
+        if sgd and group.get("momentum", 0) != 0 and not bufs:
+            raise ValueError("checkpoint has SGD momentum, but this TrainStep was built with momentum == 0 (no buffer)")
+        if not sgd and bool(group.get("amsgrad", False)) != ("max_exp_avg_sq" in bufs):
+            raise ValueError(f"checkpoint has amsgrad={bool(group.get('amsgrad', False))}, this TrainStep the opposite")
+        pg = self.optimizer.param_groups[0]
+        for k, v in group.items():
+            pg[k] = tuple(v) if k == "betas" else v
         steps = set()
-        self.exp_avg.zero_(); self.exp_avg_sq.zero_()
+        for flat in bufs.values():
+            flat.zero_()
+        self._sgd_started = set()
         for i, st in sd["state"].items():
             p = params[int(i)]
             if p not in table:
                 continue                                   # frozen here: nothing to resume
-            if tuple(st["exp_avg"].shape) != tuple(p.shape):
-                raise ValueError(f"optimizer state {i}: shape {tuple(st['exp_avg'].shape)} does not match parameter "
-                                 f"{tuple(p.shape)} (state indexed over a different parameter list?)")
             o = table[p]
-            self.exp_avg[o:o + p.numel()].copy_(st["exp_avg"].reshape(-1))
-            self.exp_avg_sq[o:o + p.numel()].copy_(st["exp_avg_sq"].reshape(-1))
-            steps.add(int(float(st["step"])))
+            for k, flat in bufs.items():
+                if st.get(k) is None:
+                    if sgd:
+                        continue
+                    raise ValueError(f"optimizer state {i}: no {k!r}")
+                if tuple(st[k].shape) != tuple(p.shape):
+                    raise ValueError(f"optimizer state {i}: shape {tuple(st[k].shape)} does not match parameter "
+                                     f"{tuple(p.shape)} (state indexed over a different parameter list?)")
+                flat[o:o + p.numel()].copy_(st[k].reshape(-1))
+                if sgd:
+                    self._sgd_started.add(p)
+            if "step" in st:
+                steps.add(int(float(st["step"])))
         # one step counter for the flat buffer: per-parameter counts that differ (legal under DDP's
         # find_unused_parameters) resume at the largest, which is exact for every parameter that was never skipped
-        self.step_count = max(steps) if steps else 0
+        if not sgd:
+            self.step_count = max(steps) if steps else 0

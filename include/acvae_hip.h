@@ -444,6 +444,24 @@ int acvae_grad_norm(const float* grads, int64_t n, float grad_scale, float* part
 int acvae_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                     float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
                     float max_grad_norm, const float* total_norm, void* stream);
+/* The other optimisers of conf["optimizer"] (runners/pytorch_runner_vae.py:219), same clip contract as
+ * acvae_adam_step: coef = grad_scale * min(1, max_grad_norm / (*total_norm + 1e-6)), the clip skipped when total_norm
+ * is NULL or max_grad_norm <= 0; no host synchronisation.  Elementwise in the operation order of torch.optim.<X>
+ * (foreach=False).  Every pointer 16-B aligned (ACVAE_EALIGN otherwise); NULL / n <= 0 / step <= 0 -> ACVAE_EINVAL.
+ * acvae_adamw_step: torch.optim.Adam (decoupled = 0: weight_decay * p folded into the gradient) or AdamW (decoupled = 1:
+ *   p *= 1 - lr * weight_decay first); amsgrad = 1 keeps max_exp_avg_sq (may be NULL otherwise) and divides by its root.
+ *   The hyperparameters are double (torch's are Python floats): 1 - beta, lr / bias correction, 1 - lr * weight_decay
+ *   are formed in double on the host and rounded to float once, as torch's scalars reach its fp32 kernels.
+ * acvae_sgd_step: torch.optim.SGD.  momentum_buffer may be NULL when momentum == 0; first = 1 on a parameter's first
+ *   update sets the buffer to the (clipped, decayed) gradient itself, later ones apply buf = momentum*buf + (1-dampening)*g.
+ *   nesterov needs momentum != 0 and dampening == 0 (ACVAE_EINVAL otherwise). */
+int acvae_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                     int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                     int amsgrad, int64_t step, float grad_scale, float max_grad_norm, const float* total_norm,
+                     void* stream);
+int acvae_sgd_step(float* params, const float* grads, float* momentum_buffer, int64_t n, double lr, double momentum,
+                   double dampening, double weight_decay, int nesterov, int first, float grad_scale, float max_grad_norm,
+                   const float* total_norm, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Opt-in kernel timing (bench.py's live roofline figure): while enabled, the conv launches are bracketed
