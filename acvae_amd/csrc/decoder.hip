@@ -101,23 +101,29 @@ enum {
 static_assert(TP_COUNT == ACVAE_TEXT_NPARAMS, "text parameter table out of sync with the header");
 
 // ------------------------------------------------------------------------------------------ posterior
+// Stacked layers (num_layers = NL): layer k keeps its own hidden output and cell saves; the input of layer k >= 1 is the output of
+// layer k - 1 with the inter-layer dropout applied in place (hidden[k - 1] after the forward).  NL = 1 gives the one-layer map.
+constexpr int POST_MAX_LAYERS = 16;
 struct PostLayout {
   // saved
-  long words, x, hidden, save_f, save_r, hprev_f, hprev_r, argmax, saved_total;
+  long words, x, hidden[POST_MAX_LAYERS], save_f[POST_MAX_LAYERS], save_r[POST_MAX_LAYERS], hprev_f[POST_MAX_LAYERS],
+      hprev_r[POST_MAX_LAYERS], argmax, saved_total;
   // scratch
   long gi_f, gi_r, gh, hf, ml, dml, dhid, dgi_f, dgi_r, dgh_f, dgh_r, dh_a, dh_b, dx, wt, wt2, wt_ih0, wt_ih1, wt_ml, pq_hbuf, pq_cnt, tn, dpart, skws,
-       scratch_total;
-  long tn_floats, dpart_doubles;
+       dhid2, wtu_hh0, wtu_hh1, wtu_ih0, wtu_ih1, scratch_total;
+  long tn_floats, dpart_doubles, pq_cnt_words;
 };
-int post_layout(int N, int Tc, int E, int Hq, int V, PostLayout& L) {
-  if (N <= 0 || Tc <= 0 || E <= 0 || Hq <= 0 || V <= 0) return ACVAE_EINVAL;
+int post_layout(int N, int Tc, int E, int Hq, int V, int NL, PostLayout& L) {
+  if (N <= 0 || Tc <= 0 || E <= 0 || Hq <= 0 || V <= 0 || NL < 1 || NL > POST_MAX_LAYERS) return ACVAE_EINVAL;
   const long R = (long)N * Tc;
   Bump s;
   L.words = s.take(R * 2);  // int64
   L.x = s.take(R * E);
-  L.hidden = s.take(R * 2 * Hq);
-  L.save_f = s.take(R * 4 * Hq); L.save_r = s.take(R * 4 * Hq);
-  L.hprev_f = s.take(R * Hq); L.hprev_r = s.take(R * Hq);
+  for (int k = 0; k < NL; ++k) {
+    L.hidden[k] = s.take(R * 2 * Hq);
+    L.save_f[k] = s.take(R * 4 * Hq); L.save_r[k] = s.take(R * 4 * Hq);
+    L.hprev_f[k] = s.take(R * Hq); L.hprev_r[k] = s.take(R * Hq);
+  }
   L.argmax = s.take((long)N * 2 * Hq);
   L.saved_total = s.off;
   Bump c;
@@ -134,16 +140,23 @@ int post_layout(int N, int Tc, int E, int Hq, int V, PostLayout& L) {
   L.wt2 = c.take((long)3 * Hq * Hq);                        // persistent BPTT: both directions' transposed weight_hh at once
   // the backward's other transposed weights (round 4: all five transposes of the call in one launch in front of it)
   L.wt_ih0 = c.take((long)3 * Hq * E); L.wt_ih1 = c.take((long)3 * Hq * E); L.wt_ml = c.take((long)2 * E * 2 * Hq);
-  L.pq_hbuf = c.take((long)4 * N * Hq);                     // persistent forward: h in flight, [direction][parity][N][Hq]
-  L.pq_cnt = c.take(acvae::posterior_persist_counter_words(Tc));
+  L.pq_hbuf = c.take((long)NL * 4 * N * Hq);                // persistent forward: h in flight, [layer][direction][parity][N][Hq]
+  L.pq_cnt_words = acvae::posterior_persist_counter_words(Tc);
+  L.pq_cnt = c.take(NL * L.pq_cnt_words);                   // one set of arrival counters per layer, all zeroed at the entry
   long tn = tn_ws_floats(2 * E, 2 * Hq, (int)R);
   long t2 = tn_ws_floats(3 * Hq, E, (int)R); if (t2 > tn) tn = t2;
   t2 = tn_ws_floats(3 * Hq, Hq, (int)R); if (t2 > tn) tn = t2;
+  if (NL > 1) { t2 = tn_ws_floats(3 * Hq, 2 * Hq, (int)R); if (t2 > tn) tn = t2; }    // dW_ih of the upper layers (K = 2Hq)
   L.tn_floats = tn;
   L.tn = c.take(tn);
   L.dpart_doubles = 4 * acvae::colsum_scratch_doubles(2 * E > 3 * Hq ? 2 * E : 3 * Hq);      // room for the batched column sums
   L.dpart = c.take(2 * L.dpart_doubles);
   L.skws = c.take(acvae_skinny_ws_floats());
+  // the upper layers' backward: the second half of the dhid ping-pong and their transposed weights (shared by the layers in turn)
+  const long up = NL > 1 ? 1 : 0;
+  L.dhid2 = c.take(up * R * 2 * Hq);
+  L.wtu_hh0 = c.take(up * 3 * Hq * Hq); L.wtu_hh1 = c.take(up * 3 * Hq * Hq);
+  L.wtu_ih0 = c.take(up * 3 * Hq * 2 * Hq); L.wtu_ih1 = c.take(up * 3 * Hq * 2 * Hq);
   L.scratch_total = c.off;
   return ACVAE_OK;
 }
@@ -246,23 +259,46 @@ int dec_layout(int N, int Tc, int S, int E, int H, int A, int V, int Eenc, DecLa
 // ==========================================================================================
 // posterior
 // ==========================================================================================
-extern "C" int64_t acvae_posterior_saved_bytes(int N, int Tc, int E, int Hq, int V) {
+extern "C" int64_t acvae_posterior_stack_saved_bytes(int N, int Tc, int E, int Hq, int V, int num_layers) {
   PostLayout L;
-  return post_layout(N, Tc, E, Hq, V, L) == ACVAE_OK ? L.saved_total * 4 : -1;
+  return post_layout(N, Tc, E, Hq, V, num_layers, L) == ACVAE_OK ? L.saved_total * 4 : -1;
+}
+extern "C" int64_t acvae_posterior_stack_scratch_bytes(int N, int Tc, int E, int Hq, int V, int num_layers) {
+  PostLayout L;
+  return post_layout(N, Tc, E, Hq, V, num_layers, L) == ACVAE_OK ? L.scratch_total * 4 : -1;
+}
+extern "C" int64_t acvae_posterior_saved_bytes(int N, int Tc, int E, int Hq, int V) {
+  return acvae_posterior_stack_saved_bytes(N, Tc, E, Hq, V, 1);
 }
 extern "C" int64_t acvae_posterior_scratch_bytes(int N, int Tc, int E, int Hq, int V) {
-  PostLayout L;
-  return post_layout(N, Tc, E, Hq, V, L) == ACVAE_OK ? L.scratch_total * 4 : -1;
+  return acvae_posterior_stack_scratch_bytes(N, Tc, E, Hq, V, 1);
 }
 
-extern "C" int acvae_posterior_fwd(const void* const* params, const int64_t* caps, int64_t ld_caps, const int64_t* lens1,
-                                   const float* eps_q, float* q_means, float* q_logs, float* q_z, float* q_means_utt,
-                                   void* saved_v, int64_t saved_bytes, void* scratch_v, int64_t scratch_bytes, int N,
-                                   int Tc, int E, int Hq, int V, void* stream, int flags) {
+namespace {
+// the four tensors {w_ih, w_hh, b_ih, b_hh} of direction dir of layer k: the text table for layer 0, the upper table above it
+struct PostWeights {
+  const void* const* params;
+  const void* const* upper;        // 8 (num_layers - 1) entries: per layer the forward four, then the _reverse four
+  const float* at(int k, int dir, int j) const {
+    return (const float*)(k == 0 ? params[TP_Q_WIH + dir * 4 + j] : upper[(long)(k - 1) * 8 + dir * 4 + j]);
+  }
+};
+bool post_keep_ok(int num_layers, const uint8_t* keep, float keep_scale) {
+  return !keep || (num_layers > 1 && keep_scale >= 0.f);
+}
+}  // namespace
+
+extern "C" int acvae_posterior_stack_fwd(const void* const* params, const void* const* upper, int num_layers,
+                                         const uint8_t* keep, float keep_scale, const int64_t* caps, int64_t ld_caps,
+                                         const int64_t* lens1, const float* eps_q, float* q_means, float* q_logs,
+                                         float* q_z, float* q_means_utt, void* saved_v, int64_t saved_bytes,
+                                         void* scratch_v, int64_t scratch_bytes, int N, int Tc, int E, int Hq, int V,
+                                         void* stream, int flags) {
   PostLayout L;
-  ACVAE_TRY(post_layout(N, Tc, E, Hq, V, L));
+  ACVAE_TRY(post_layout(N, Tc, E, Hq, V, num_layers, L));
   if (!params || !caps || !lens1 || !eps_q || !q_means || !q_logs || !q_z || !q_means_utt || !saved_v || !scratch_v)
     return ACVAE_EINVAL;
+  if ((num_layers > 1 && !upper) || !post_keep_ok(num_layers, keep, keep_scale)) return ACVAE_EINVAL;
   if (saved_bytes < L.saved_total * 4 || scratch_bytes < L.scratch_total * 4) return ACVAE_EWORKSPACE;
   float* sv = (float*)saved_v;
   float* sc = (float*)scratch_v;
@@ -272,50 +308,59 @@ extern "C" int acvae_posterior_fwd(const void* const* params, const int64_t* cap
     acvae::ZeroBatch zb;
     zb_skinny(zb, st.skws);
     if (persist_q) {
-      zb.add(sc + L.pq_cnt, acvae::posterior_persist_counter_words(Tc));
-      zb.add(sc + L.pq_hbuf, (long)4 * N * Hq);
+      zb.add(sc + L.pq_cnt, num_layers * L.pq_cnt_words);
+      zb.add(sc + L.pq_hbuf, (long)num_layers * 4 * N * Hq);
       flags |= ACVAE_FLAG_INT_CNT_ZEROED;
     }
     ACVAE_TRY(acvae::zero_batch(zb, st.s));
   }
   auto P = [&](int i) { return (const float*)params[i]; };
+  const PostWeights W{params, upper};
   const int R = N * Tc;
   int64_t* words = (int64_t*)(sv + L.words);
-  float* X = sv + L.x;
-  float* hid = sv + L.hidden;
   ACVAE_TRY(acvae::gather_words(caps, ld_caps, 1, words, N, Tc, st));            // x[:, :-1] restricted to Tc steps
-  ACVAE_TRY(acvae::embed_gather(words, 1, P(TP_Q_EMB), V, X, E, R, E, st));
-  if (persist_q) {
-    // both directions, all steps: one launch (decode_persist.hip); the hoisted input projections first
-    PqParams pq;
+  ACVAE_TRY(acvae::embed_gather(words, 1, P(TP_Q_EMB), V, sv + L.x, E, R, E, st));
+  float* hid = nullptr;
+  for (int layer = 0; layer < num_layers; ++layer) {
+    // input of this layer: the embedded words, or the (dropped-out) output of the layer below
+    const float* X = layer ? sv + L.hidden[layer - 1] : sv + L.x;
+    const int K = layer ? 2 * Hq : E;
+    hid = sv + L.hidden[layer];
+    if (persist_q) {
+      // both directions, all steps: one launch (decode_persist.hip); the hoisted input projections first
+      PqParams pq;
+      for (int dir = 0; dir < 2; ++dir) {
+        float* gi = sc + (dir ? L.gi_r : L.gi_f);
+        ACVAE_TRY(gemm(X, K, W.at(layer, dir, 0), K, W.at(layer, dir, 2), gi, 3 * Hq, R, 3 * Hq, K, 0, st));
+        pq.w_hh[dir] = W.at(layer, dir, 1); pq.b_hh[dir] = W.at(layer, dir, 3); pq.gi[dir] = gi;
+        pq.save[dir] = sv + (dir ? L.save_r[layer] : L.save_f[layer]);
+        pq.hprev[dir] = sv + (dir ? L.hprev_r[layer] : L.hprev_f[layer]);
+      }
+      pq.lens1 = lens1; pq.hid = hid; pq.hbuf = sc + L.pq_hbuf + (long)layer * 4 * N * Hq;
+      pq.cnt = (unsigned*)(sc + L.pq_cnt + layer * L.pq_cnt_words);
+      pq.N = N; pq.Tc = Tc; pq.Hq = Hq;
+      ACVAE_TRY(acvae::posterior_persist_fwd(pq, st.s, flags));          // hbuf and the counters: zeroed at the entry
+    } else
     for (int dir = 0; dir < 2; ++dir) {
-      const int o = dir * 4;
       float* gi = sc + (dir ? L.gi_r : L.gi_f);
-      ACVAE_TRY(gemm(X, E, P(TP_Q_WIH + o), E, P(TP_Q_BIH + o), gi, 3 * Hq, R, 3 * Hq, E, 0, st));
-      pq.w_hh[dir] = P(TP_Q_WHH + o); pq.b_hh[dir] = P(TP_Q_BHH + o); pq.gi[dir] = gi;
-      pq.save[dir] = sv + (dir ? L.save_r : L.save_f);
-      pq.hprev[dir] = sv + (dir ? L.hprev_r : L.hprev_f);
+      float* save = sv + (dir ? L.save_r[layer] : L.save_f[layer]);
+      float* hprev = sv + (dir ? L.hprev_r[layer] : L.hprev_f[layer]);
+      float* h = sc + L.hf;
+      float* gh = sc + L.gh;
+      ACVAE_TRY(gemm(X, K, W.at(layer, dir, 0), K, W.at(layer, dir, 2), gi, 3 * Hq, R, 3 * Hq, K, 0, st));
+      ACVAE_TRY(acvae::copy_rows(h, Hq, nullptr, 0, N, Hq, st));
+      for (int k = 0; k < Tc; ++k) {
+        const int t = dir ? Tc - 1 - k : k;
+        ACVAE_TRY(gemm(h, Hq, W.at(layer, dir, 1), Hq, W.at(layer, dir, 3), gh, 3 * Hq, N, 3 * Hq, Hq, 0, st));
+        ACVAE_TRY(acvae::gru_fwd(gi + (long)t * 3 * Hq, (long)Tc * 3 * Hq, gh, 3 * Hq, h, Hq, h, Hq,
+                                 hid + (long)t * 2 * Hq + dir * Hq, (long)Tc * 2 * Hq, save + (long)t * 4 * Hq,
+                                 (long)Tc * 4 * Hq, hprev + (long)t * Hq, (long)Tc * Hq, lens1, t, N, Hq, st));
+      }
     }
-    pq.lens1 = lens1; pq.hid = hid; pq.hbuf = sc + L.pq_hbuf; pq.cnt = (unsigned*)(sc + L.pq_cnt);
-    pq.N = N; pq.Tc = Tc; pq.Hq = Hq;
-    ACVAE_TRY(acvae::posterior_persist_fwd(pq, st.s, flags));          // hbuf and the counters: zeroed at the entry
-  } else
-  for (int dir = 0; dir < 2; ++dir) {
-    const int o = dir * 4;
-    float* gi = sc + (dir ? L.gi_r : L.gi_f);
-    float* save = sv + (dir ? L.save_r : L.save_f);
-    float* hprev = sv + (dir ? L.hprev_r : L.hprev_f);
-    float* h = sc + L.hf;
-    float* gh = sc + L.gh;
-    ACVAE_TRY(gemm(X, E, P(TP_Q_WIH + o), E, P(TP_Q_BIH + o), gi, 3 * Hq, R, 3 * Hq, E, 0, st));
-    ACVAE_TRY(acvae::copy_rows(h, Hq, nullptr, 0, N, Hq, st));
-    for (int k = 0; k < Tc; ++k) {
-      const int t = dir ? Tc - 1 - k : k;
-      ACVAE_TRY(gemm(h, Hq, P(TP_Q_WHH + o), Hq, P(TP_Q_BHH + o), gh, 3 * Hq, N, 3 * Hq, Hq, 0, st));
-      ACVAE_TRY(acvae::gru_fwd(gi + (long)t * 3 * Hq, (long)Tc * 3 * Hq, gh, 3 * Hq, h, Hq, h, Hq,
-                               hid + (long)t * 2 * Hq + dir * Hq, (long)Tc * 2 * Hq, save + (long)t * 4 * Hq,
-                               (long)Tc * 4 * Hq, hprev + (long)t * Hq, (long)Tc * Hq, lens1, t, N, Hq, st));
-    }
+    // nn.GRU's dropout between layers (training only): the output of a lower layer becomes the next layer's input in place
+    if (keep && layer + 1 < num_layers)
+      ACVAE_TRY(acvae::dropout_rows(hid, (long)Tc * 2 * Hq, 2 * Hq, keep + (long)layer * R * 2 * Hq, (long)Tc * 2 * Hq,
+                                    2 * Hq, keep_scale, N, Tc, 2 * Hq, st));
   }
   float* ml = sc + L.ml;
   ACVAE_TRY(gemm(hid, 2 * Hq, P(TP_Q_TML_W), 2 * Hq, P(TP_Q_TML_B), ml, 2 * E, R, 2 * E, 2 * Hq, 0, st));
@@ -324,20 +369,34 @@ extern "C" int acvae_posterior_fwd(const void* const* params, const int64_t* cap
   return ACVAE_OK;
 }
 
-extern "C" int acvae_posterior_bwd(const void* const* params, void* const* grads, const int64_t* lens1,
-                                   const float* eps_q, const float* q_logs, const float* d_q_means,
-                                   const float* d_q_logs, const float* d_q_z, const float* d_q_means_utt, void* saved_v,
-                                   int64_t saved_bytes, void* scratch_v, int64_t scratch_bytes, int N, int Tc, int E,
-                                   int Hq, int V, void* stream, int flags) {
+extern "C" int acvae_posterior_fwd(const void* const* params, const int64_t* caps, int64_t ld_caps, const int64_t* lens1,
+                                   const float* eps_q, float* q_means, float* q_logs, float* q_z, float* q_means_utt,
+                                   void* saved_v, int64_t saved_bytes, void* scratch_v, int64_t scratch_bytes, int N,
+                                   int Tc, int E, int Hq, int V, void* stream, int flags) {
+  return acvae_posterior_stack_fwd(params, nullptr, 1, nullptr, 0.f, caps, ld_caps, lens1, eps_q, q_means, q_logs, q_z,
+                                   q_means_utt, saved_v, saved_bytes, scratch_v, scratch_bytes, N, Tc, E, Hq, V, stream,
+                                   flags);
+}
+
+extern "C" int acvae_posterior_stack_bwd(const void* const* params, void* const* grads, const void* const* upper,
+                                         void* const* upper_grads, int num_layers, const uint8_t* keep, float keep_scale,
+                                         const int64_t* lens1, const float* eps_q, const float* q_logs,
+                                         const float* d_q_means, const float* d_q_logs, const float* d_q_z,
+                                         const float* d_q_means_utt, void* saved_v, int64_t saved_bytes,
+                                         void* scratch_v, int64_t scratch_bytes, int N, int Tc, int E, int Hq, int V,
+                                         void* stream, int flags) {
   PostLayout L;
-  ACVAE_TRY(post_layout(N, Tc, E, Hq, V, L));
+  ACVAE_TRY(post_layout(N, Tc, E, Hq, V, num_layers, L));
   if (!params || !grads || !lens1 || !eps_q || !q_logs || !saved_v || !scratch_v) return ACVAE_EINVAL;
+  if ((num_layers > 1 && (!upper || !upper_grads)) || !post_keep_ok(num_layers, keep, keep_scale)) return ACVAE_EINVAL;
   if (saved_bytes < L.saved_total * 4 || scratch_bytes < L.scratch_total * 4) return ACVAE_EWORKSPACE;
   float* sv = (float*)saved_v;
   float* sc = (float*)scratch_v;
   Ctx st{(hipStream_t)stream, sc + L.skws};
   auto P = [&](int i) { return (const float*)params[i]; };
   auto G = [&](int i) { return (float*)grads[i]; };
+  const PostWeights W{params, upper};
+  auto GU = [&](int layer, int dir, int j) { return (float*)upper_grads[(long)(layer - 1) * 8 + dir * 4 + j]; };
   const int R = N * Tc;
   TnWs tn{sc + L.tn, L.tn_floats * 4};
   double* dpart = (double*)(sc + L.dpart);
@@ -345,13 +404,13 @@ extern "C" int acvae_posterior_bwd(const void* const* params, void* const* grads
   {
     acvae::ZeroBatch zb;
     zb_skinny(zb, st.skws); zb_colsum(zb, dpart); zb_tn(zb, tn);
-    if (persist) { zb.add(sc + L.pq_cnt, acvae::posterior_persist_counter_words(Tc)); flags |= ACVAE_FLAG_INT_CNT_ZEROED; }
+    if (persist) { zb.add(sc + L.pq_cnt, num_layers * L.pq_cnt_words); flags |= ACVAE_FLAG_INT_CNT_ZEROED; }
     zb.add(G(TP_Q_EMB), (long)V * E);          // the embedding-table gradient starts from zero (embed_scatter adds rows)
     ACVAE_TRY(acvae::zero_batch(zb, st.s));
   }
   const int64_t* words = (const int64_t*)(sv + L.words);
   float* X = sv + L.x;
-  float* hid = sv + L.hidden;
+  float* hid = sv + L.hidden[num_layers - 1];
   float* dml = sc + L.dml;
   float* dhid = sc + L.dhid;
   float* wt = sc + L.wt;
@@ -372,42 +431,92 @@ extern "C" int acvae_posterior_bwd(const void* const* params, void* const* grads
     ACVAE_TRY(acvae::pool_bwd(d_q_means_utt, lens1, (const int*)(sv + L.argmax), dhid, (long)Tc * 2 * Hq, 2 * Hq, 1, N,
                               Tc, 2 * Hq, st));
   ACVAE_TRY(gemm_tn(dml, 2 * E, hid, 2 * Hq, G(TP_Q_TML_W), 2 * Hq, 2 * E, 2 * Hq, R, tn, st));
-  acvae::ColsumBatch cb;                     // the five bias gradients of the call: one launch at its end
-  cb.add({dml, R, 2 * E, G(TP_Q_TML_B)});
-  float* dx = sc + L.dx;
-  if (persist) {                 // BPTT of both directions in one launch; the parameter products below are unchanged
-    PqbParams pb;
-    for (int dir = 0; dir < 2; ++dir) {
-      pb.wt[dir] = dir ? sc + L.wt2 : wt;                    // transposed weight_hh, made at the entry
-      pb.save[dir] = sv + (dir ? L.save_r : L.save_f);
-      pb.hprev[dir] = sv + (dir ? L.hprev_r : L.hprev_f);
-      pb.dgi[dir] = sc + (dir ? L.dgi_r : L.dgi_f);
-      pb.dgh[dir] = sc + (dir ? L.dgh_r : L.dgh_f);
-    }
-    pb.dhid = dhid; pb.lens1 = lens1; pb.cnt = (unsigned*)(sc + L.pq_cnt);
-    pb.N = N; pb.Tc = Tc; pb.Hq = Hq;
-    ACVAE_TRY(acvae::posterior_persist_bwd(pb, st.s, flags));
-  }
-  for (int dir = 0; dir < 2; ++dir) {
-    const int o = dir * 4;
-    float* save = sv + (dir ? L.save_r : L.save_f);
-    float* hprev = sv + (dir ? L.hprev_r : L.hprev_f);
+  // BPTT of one direction of one layer from dhid into dgi / dgh, step by step (wt_hh: its transposed weight_hh)
+  auto bptt_dir = [&](int layer, int dir, const float* wt_hh) -> int {
+    const float* save = sv + (dir ? L.save_r[layer] : L.save_f[layer]);
+    const float* hprev = sv + (dir ? L.hprev_r[layer] : L.hprev_f[layer]);
     float* dgi = sc + (dir ? L.dgi_r : L.dgi_f);
     float* dgh = sc + (dir ? L.dgh_r : L.dgh_f);
     float* dh = sc + L.dh_a;
     float* dh2 = sc + L.dh_b;
+    ACVAE_TRY(acvae::copy_rows(dh, Hq, nullptr, 0, N, Hq, st));
+    for (int k = 0; k < Tc; ++k) {
+      const int t = dir ? k : Tc - 1 - k;  // reverse of the forward order
+      ACVAE_TRY(acvae::gru_bwd(dh, Hq, dhid + (long)t * 2 * Hq + dir * Hq, (long)Tc * 2 * Hq, save + (long)t * 4 * Hq,
+                               (long)Tc * 4 * Hq, hprev + (long)t * Hq, (long)Tc * Hq, dgi + (long)t * 3 * Hq,
+                               (long)Tc * 3 * Hq, dgh + (long)t * 3 * Hq, (long)Tc * 3 * Hq, dh2, Hq, lens1, t, N, Hq,
+                               st));
+      ACVAE_TRY(gemm(dgh + (long)t * 3 * Hq, (long)Tc * 3 * Hq, wt_hh, 3 * Hq, nullptr, dh2, Hq, N, Hq, 3 * Hq, 1, st));
+      float* tmp = dh; dh = dh2; dh2 = tmp;
+    }
+    return ACVAE_OK;
+  };
+  // ... and of both directions: one persistent launch, or the two per-step loops
+  auto bptt = [&](int layer, const float* const wt_hh[2]) -> int {
+    if (!persist) {
+      for (int dir = 0; dir < 2; ++dir) ACVAE_TRY(bptt_dir(layer, dir, wt_hh[dir]));
+      return ACVAE_OK;
+    }
+    PqbParams pb;
+    for (int dir = 0; dir < 2; ++dir) {
+      pb.wt[dir] = wt_hh[dir];
+      pb.save[dir] = sv + (dir ? L.save_r[layer] : L.save_f[layer]);
+      pb.hprev[dir] = sv + (dir ? L.hprev_r[layer] : L.hprev_f[layer]);
+      pb.dgi[dir] = sc + (dir ? L.dgi_r : L.dgi_f);
+      pb.dgh[dir] = sc + (dir ? L.dgh_r : L.dgh_f);
+    }
+    pb.dhid = dhid; pb.lens1 = lens1; pb.cnt = (unsigned*)(sc + L.pq_cnt + layer * L.pq_cnt_words);
+    pb.N = N; pb.Tc = Tc; pb.Hq = Hq;
+    return acvae::posterior_persist_bwd(pb, st.s, flags);
+  };
+  // the upper layers, top-down: BPTT, their parameter products, and dX = dgi_f . W_ih_f + dgi_r . W_ih_r through the
+  // inter-layer dropout into the gradient of the output of the layer below (the other half of the dhid ping-pong)
+  float* dnext = sc + L.dhid2;
+  for (int layer = num_layers - 1; layer >= 1; --layer) {
+    float* wtu_hh[2] = {sc + L.wtu_hh0, sc + L.wtu_hh1};
+    float* wtu_ih[2] = {sc + L.wtu_ih0, sc + L.wtu_ih1};
+    {
+      TransposeBatch tb;
+      for (int dir = 0; dir < 2; ++dir) {
+        tb.add({W.at(layer, dir, 0), 2 * Hq, wtu_ih[dir], 3 * Hq, 3 * Hq, 2 * Hq});               // [2Hq][3Hq]
+        tb.add({W.at(layer, dir, 1), Hq, wtu_hh[dir], 3 * Hq, 3 * Hq, Hq});                      // [Hq][3Hq]
+      }
+      ACVAE_TRY(acvae_transpose_batch(tb, st.s));
+    }
+    ACVAE_TRY(bptt(layer, wtu_hh));
+    const float* Xk = sv + L.hidden[layer - 1];                      // this layer's input, after the dropout
+    acvae::ColsumBatch cbu;
+    for (int dir = 0; dir < 2; ++dir) {
+      const float* hprev = sv + (dir ? L.hprev_r[layer] : L.hprev_f[layer]);
+      float* dgi = sc + (dir ? L.dgi_r : L.dgi_f);
+      float* dgh = sc + (dir ? L.dgh_r : L.dgh_f);
+      ACVAE_TRY(gemm_tn(dgi, 3 * Hq, Xk, 2 * Hq, GU(layer, dir, 0), 2 * Hq, 3 * Hq, 2 * Hq, R, tn, st));
+      cbu.add({dgi, R, 3 * Hq, GU(layer, dir, 2)});
+      ACVAE_TRY(gemm_tn(dgh, 3 * Hq, hprev, Hq, GU(layer, dir, 1), Hq, 3 * Hq, Hq, R, tn, st));
+      cbu.add({dgh, R, 3 * Hq, GU(layer, dir, 3)});
+      ACVAE_TRY(gemm(dgi, 3 * Hq, wtu_ih[dir], 3 * Hq, nullptr, dnext, 2 * Hq, R, 2 * Hq, 3 * Hq, dir, st));
+    }
+    ACVAE_TRY(acvae::colsum_batch(cbu, dpart, L.dpart_doubles, st));   // before the layer below overwrites dgi / dgh
+    if (keep)
+      ACVAE_TRY(acvae::dropout_rows(dnext, (long)Tc * 2 * Hq, 2 * Hq, keep + (long)(layer - 1) * R * 2 * Hq,
+                                    (long)Tc * 2 * Hq, 2 * Hq, keep_scale, N, Tc, 2 * Hq, st));
+    float* tmp = dhid; dhid = dnext; dnext = tmp;
+  }
+  acvae::ColsumBatch cb;                     // the five bias gradients of layer 0 and token_mean_log: one launch at the end
+  cb.add({dml, R, 2 * E, G(TP_Q_TML_B)});
+  float* dx = sc + L.dx;
+  if (persist) {                 // BPTT of both directions in one launch; the parameter products below are unchanged
+    const float* wt_hh[2] = {wt, sc + L.wt2};                  // transposed weight_hh, made at the entry
+    ACVAE_TRY(bptt(0, wt_hh));
+  }
+  for (int dir = 0; dir < 2; ++dir) {
+    const int o = dir * 4;
+    const float* hprev = sv + (dir ? L.hprev_r[0] : L.hprev_f[0]);
+    float* dgi = sc + (dir ? L.dgi_r : L.dgi_f);
+    float* dgh = sc + (dir ? L.dgh_r : L.dgh_f);
     if (!persist) {
       ACVAE_TRY(transp(P(TP_Q_WHH + o), Hq, wt, 3 * Hq, 3 * Hq, Hq, st));                   // [Hq][3Hq]
-      ACVAE_TRY(acvae::copy_rows(dh, Hq, nullptr, 0, N, Hq, st));
-      for (int k = 0; k < Tc; ++k) {
-        const int t = dir ? k : Tc - 1 - k;  // reverse of the forward order
-        ACVAE_TRY(acvae::gru_bwd(dh, Hq, dhid + (long)t * 2 * Hq + dir * Hq, (long)Tc * 2 * Hq, save + (long)t * 4 * Hq,
-                                 (long)Tc * 4 * Hq, hprev + (long)t * Hq, (long)Tc * Hq, dgi + (long)t * 3 * Hq,
-                                 (long)Tc * 3 * Hq, dgh + (long)t * 3 * Hq, (long)Tc * 3 * Hq, dh2, Hq, lens1, t, N, Hq,
-                                 st));
-        ACVAE_TRY(gemm(dgh + (long)t * 3 * Hq, (long)Tc * 3 * Hq, wt, 3 * Hq, nullptr, dh2, Hq, N, Hq, 3 * Hq, 1, st));
-        float* tmp = dh; dh = dh2; dh2 = tmp;
-      }
+      ACVAE_TRY(bptt_dir(0, dir, wt));
     }
     ACVAE_TRY(gemm_tn(dgi, 3 * Hq, X, E, G(TP_Q_WIH + o), E, 3 * Hq, E, R, tn, st));
     cb.add({dgi, R, 3 * Hq, G(TP_Q_BIH + o)});
@@ -418,6 +527,16 @@ extern "C" int acvae_posterior_bwd(const void* const* params, void* const* grads
   ACVAE_TRY(acvae::colsum_batch(cb, dpart, L.dpart_doubles, st));
   ACVAE_TRY(acvae::embed_scatter(words, dx, E, G(TP_Q_EMB), V, R, E, st));
   return ACVAE_OK;
+}
+
+extern "C" int acvae_posterior_bwd(const void* const* params, void* const* grads, const int64_t* lens1,
+                                   const float* eps_q, const float* q_logs, const float* d_q_means,
+                                   const float* d_q_logs, const float* d_q_z, const float* d_q_means_utt, void* saved_v,
+                                   int64_t saved_bytes, void* scratch_v, int64_t scratch_bytes, int N, int Tc, int E,
+                                   int Hq, int V, void* stream, int flags) {
+  return acvae_posterior_stack_bwd(params, grads, nullptr, nullptr, 1, nullptr, 0.f, lens1, eps_q, q_logs, d_q_means,
+                                   d_q_logs, d_q_z, d_q_means_utt, saved_v, saved_bytes, scratch_v, scratch_bytes, N, Tc,
+                                   E, Hq, V, stream, flags);
 }
 
 // ==========================================================================================

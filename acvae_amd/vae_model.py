@@ -144,7 +144,8 @@ class Hybrid_VAEModel(CaptionModel):
         # model.defer_param_grads = False keeps everything on the main stream
         self.defer_param_grads = True
         self.staged = None         # device copies of caps / cap_lens-1 made by the last training forward
-        self.noise = None          # optional replay: dict(eps_q=[N,Tc,E], eps_p=[Tc,N,E]) consumed by the next forward
+        self.noise = None          # optional replay: dict(eps_q=[N,Tc,E], eps_p=[Tc,N,E], q_keep=[Lq-1,N,Tc,2Hq] (a stacked
+        #                            posterior's dropout masks, text_encoder.posterior_keep_masks)) consumed by the next forward
         self._grad_views = None    # {param: flat-gradient view}, set by the train-step harness
         self._grad_ready_cb = None # called with "text" once every text-side gradient has been written
 
@@ -375,8 +376,20 @@ class Hybrid_VAEModel(CaptionModel):
             main = torch.cuda.current_stream()
             side = self._post_stream(main) if self.use_side_stream else main
             eps_q = None if self.noise is None else self.noise.get("eps_q")
-            if eps_q is None:                                      # same generator order as the reference: the
-                lens1 = np.asarray(cap_lens) - 1                   # posterior's randn precedes the per-step draws
+            q_keep = None if self.noise is None else self.noise.get("q_keep")
+            lens1 = np.asarray(cap_lens) - 1
+            q_p = self.qnet.keep_p()
+            if q_p > 0:
+                # a stacked posterior's inter-layer dropout masks: nn.GRU draws them inside self.network(...), i.e. in front
+                # of the posterior's randn (text_encoder.py:190,196); uploaded from the page-locked ring, in front of the encoder
+                q, Tc = self.qnet, int(lens1.max())
+                if q_keep is None:
+                    q_keep = _lib.h2d_fill((q.num_layers - 1, feats.shape[0], Tc, 2 * q.hidden_size), torch.uint8,
+                                           feats.device, lambda buf: text_encoder.posterior_keep_masks(
+                                               lens1, Tc, q.hidden_size, q.num_layers, q_p, out=buf))
+                else:
+                    q_keep = _lib.h2d(q_keep, feats.device, torch.uint8).contiguous()
+            if eps_q is None:          # same generator order as the reference: the posterior's randn precedes the per-step draws
                 eps_q = torch.randn(feats.shape[0], int(lens1.max()), self.decoder.embed_size)
             # Host-side draws and the small H2D copies of the decode loop go in front of the encoder launch: a
             # pageable-memory copy waits for the stream to drain, which behind the encoder would stall the host.
@@ -384,13 +397,15 @@ class Hybrid_VAEModel(CaptionModel):
             if side is not main:
                 side.wait_stream(main)
                 prep["caps_d"].record_stream(side)
+                if q_p > 0:
+                    q_keep.record_stream(side)                     # read by the posterior's forward and backward there
             # The encoder is queued FIRST and the posterior second (it still starts at once: the side stream only waits
             # for what main held before this point).  Autograd runs the later-created node first, so in the backward
             # the posterior's kernels and its gradient bucket are queued before the long encoder backward: under data
             # parallelism the 20 MB posterior bucket then travels beside the encoder backward instead of behind it.
             encoded = self.encoder(feats, feat_lens)
             with torch.cuda.stream(side):
-                qnetout = self.qnet(prep["caps_d"], cap_lens, eps=eps_q)
+                qnetout = self.qnet(prep["caps_d"], cap_lens, eps=eps_q, keep=q_keep)
             if side is not main:
                 main.wait_stream(side)
                 for v in qnetout.values():

@@ -364,6 +364,34 @@ int acvae_posterior_bwd(const void* const* params, void* const* grads, const int
                         const float* d_q_means_utt, void* saved, int64_t saved_bytes, void* scratch,
                         int64_t scratch_bytes, int N, int Tc, int E, int Hq, int V, void* stream, int flags);
 
+/* A2 with stacked layers: PosteriorRNN_hybrid(num_layers = num_layers >= 1), i.e. nn.GRU(E, Hq, num_layers, bidirectional=True,
+ * dropout=p).  Layer 0 is the one-layer posterior above (its eight tensors come from `params`); layer k >= 1 runs the same
+ * packed BiGRU over the [N,Tc,2Hq] output [fw | bw] of layer k-1 instead of the embedded words, from a zero hidden state.
+ * token_mean_log, the reparameterisation and q_means_utt (mean_with_lens + max_with_lens) read the TOP layer only.
+ *   upper / upper_grads: 8 (num_layers - 1) entries; for k = 1 .. num_layers-1 torch's order
+ *     network.{weight_ih_lk [3Hq][2Hq], weight_hh_lk [3Hq][Hq], bias_ih_lk, bias_hh_lk} then the same four of _lk_reverse
+ *     (NULL tables when num_layers == 1).  Gradients are WRITTEN.
+ *   keep: uint8 [num_layers-1][N][Tc][2Hq] (nonzero = kept), the inter-layer dropout of nn.GRU in training mode: the output of
+ *     layer k < num_layers-1 is multiplied by keep[k] * keep_scale (keep_scale = 1/(1-p) as torch forms it in fp32) before
+ *     layer k+1 reads it; the backward applies the same mask.  NULL = no dropout (eval mode, p = 0).  Entries at padded
+ *     positions (t >= lens1[n]) are never read by a recurrence.  A mask needs num_layers > 1.
+ * The same call with num_layers = 1 is acvae_posterior_fwd / _bwd (which are this code path, bit for bit).  num_layers is at
+ * most 16.  The saved buffer of the forward holds every layer's outputs and cell saves; the backward reads it, and the
+ * same upper table, keep mask and keep_scale must be passed to both. */
+int64_t acvae_posterior_stack_saved_bytes(int N, int Tc, int E, int Hq, int V, int num_layers);
+int64_t acvae_posterior_stack_scratch_bytes(int N, int Tc, int E, int Hq, int V, int num_layers);
+int acvae_posterior_stack_fwd(const void* const* params, const void* const* upper, int num_layers, const uint8_t* keep,
+                              float keep_scale, const int64_t* caps, int64_t ld_caps, const int64_t* lens1,
+                              const float* eps_q, float* q_means, float* q_logs, float* q_z, float* q_means_utt,
+                              void* saved, int64_t saved_bytes, void* scratch, int64_t scratch_bytes, int N, int Tc,
+                              int E, int Hq, int V, void* stream, int flags);
+int acvae_posterior_stack_bwd(const void* const* params, void* const* grads, const void* const* upper,
+                              void* const* upper_grads, int num_layers, const uint8_t* keep, float keep_scale,
+                              const int64_t* lens1, const float* eps_q, const float* q_logs, const float* d_q_means,
+                              const float* d_q_logs, const float* d_q_z, const float* d_q_means_utt, void* saved,
+                              int64_t saved_bytes, void* scratch, int64_t scratch_bytes, int N, int Tc, int E, int Hq,
+                              int V, void* stream, int flags);
+
 /* The teacher-forced decode loop (all words known, no step feeds the prior's z to the decoder: acvae_decode_fwd with every
  * ss flag set and every dis flag clear) runs as ONE persistent launch (csrc/decode_persist.hip) when N <= 32, S <= 512,
  * E is a power of two in 32..2048, H, A are multiples of 32 and the whole grid fits the device at once; its results are
