@@ -97,14 +97,21 @@ def forward_batch_shared_encoder(model, batch, device=None, **kwargs):
     return model.inference_forward(rep, **kwargs)
 
 
-def forward_batch(model, batch, mode, device=None, **kwargs):
+def forward_batch(model, batch, mode, device=None, augment=None, **kwargs):
     """Runner._forward (pytorch_runner_vae.py:76-108).  ``batch`` is what ``collate_fn`` returned.  In evaluation mode
     with beam_size > 1 and a method other than "dbs", ``batch[0]`` (the keys) is replaced by the replicated keys, as
-    the reference does in place."""
+    the reference does in place.  In training mode the uploaded features get the training-time augmentation of
+    ``augment`` (one ``AugmentParams`` per clip), or of the batch's own column when ``CaptionDataset(...,
+    augment=...)`` made it (acvae_amd.augment.apply)."""
     assert mode in ("train", "validation", "eval")
     device = device if device is not None else next(model.parameters()).device
     if mode == "train":
         feats = batch[0].to(device)
+        from . import augment as _augment
+        if augment is None:
+            augment = _augment.batch_params(batch)
+        if augment is not None:
+            feats = _augment.apply(feats, batch[-2], augment)
         caps, feat_lens, cap_lens = batch[1], batch[-2], batch[-1]
         lens1 = np.asarray(cap_lens) - 1
         output = model(feats, feat_lens, caps, cap_lens, **kwargs)

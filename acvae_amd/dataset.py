@@ -44,11 +44,18 @@ class CaptionEvalDataset(torch.utils.data.Dataset):
 
 class CaptionDataset(CaptionEvalDataset):
     """Items ``(feature, caption ids with <start>/<end>, audio_id)`` addressed by ``(audio_idx, cap_idx)``
-    (caption_dataset.py:89-112); the length is the number of captions."""
+    (caption_dataset.py:89-112); the length is the number of captions.
 
-    def __init__(self, features: Features, caption_info: List, vocabulary, transform: Optional[List] = None):
+    ``augment`` (an ``acvae_amd.augment.Augment``, e.g. ``parse_augments(conf["augments"])``) draws the reference's
+    training-time transforms for every item after ``transform``: the feature comes back cropped where a crop fired and
+    the item gains a 4th field, its ``AugmentParams``, which ``acvae_amd.augment.apply`` (``TrainStep.step(...,
+    augment=batch[3])``) turns into the rolls and masks on the device.  Without ``augment`` the items are unchanged."""
+
+    def __init__(self, features: Features, caption_info: List, vocabulary, transform: Optional[List] = None,
+                 augment=None):
         super().__init__(features, [info["audio_id"] for info in caption_info], transform)
         self._caption_info, self._vocabulary = caption_info, vocabulary
+        self._augment = augment
 
     def __getitem__(self, index: Tuple[int, int]):
         audio_idx, cap_idx = index
@@ -56,7 +63,11 @@ class CaptionDataset(CaptionEvalDataset):
         tokens = self._caption_info[audio_idx]["captions"][cap_idx]["tokens"].split()
         voc = self._vocabulary
         caption = torch.as_tensor([voc("<start>")] + [voc(token) for token in tokens] + [voc("<end>")])
-        return self._feature(audio_id), caption, audio_id
+        feature = self._feature(audio_id)
+        if self._augment is None:
+            return feature, caption, audio_id
+        feature, params = self._augment.draw(feature.numpy())
+        return torch.as_tensor(feature), caption, audio_id, params
 
     def __len__(self):
         return sum(len(item["captions"]) for item in self._caption_info)

@@ -335,13 +335,20 @@ class TrainStep:
         d._acvae_ready = ev
         return d
 
-    def step(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, kl_weight=0.5):
+    def step(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, kl_weight=0.5, augment=None):
+        """One training step.  ``augment``: one ``acvae_amd.augment.AugmentParams`` per clip (a batch's column from
+        ``CaptionDataset(..., augment=...)``): the rolls and masks run on the device before the encoder."""
         self.sync_buffers()
         ready = getattr(feats, "_acvae_ready", None)
         if ready is not None:                       # a batch uploaded by prefetch(): order this step behind its copy
             cur = torch.cuda.current_stream()
             cur.wait_event(ready)
             feats.record_stream(cur)
+        if augment is not None:
+            from .augment import apply
+            if not feats.is_cuda:
+                feats = _lib.h2d(torch.as_tensor(feats).float(), self.flat_p.device)
+            feats = apply(feats, feat_lens, augment)
         self._decode_event = self._decode_aux_event = self._text_event = None
         self._decode_deferred = self._projemb_seen = False
         for p in self.order:

@@ -492,6 +492,25 @@ int acvae_sgd_step(float* params, const float* grads, float* momentum_buffer, in
                    const float* total_norm, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training-time augmentation, datasets/augment.py:time_roll + spec_augment's time_mask / freq_mask (:30-65), on the
+ * uploaded batch in [N, T, F] (F % 4 == 0, `in` / `out` 16-B aligned or ACVAE_EALIGN, `out` never aliases `in`).
+ * The random draws are the host's (acvae_amd/augment.py); `params` is an int32 table [N, K], K = ACVAE_AUG_TABLE_WIDTH,
+ * one row per clip:
+ *   [shift, n_time, n_freq, time masks (start, end) x ACVAE_AUG_MAX_MASKS, freq masks (start, end) x ACVAE_AUG_MAX_MASKS]
+ * Per clip n of length L = lens[n] (clamped to [0, T]): output row i < L = input row (i - shift) mod L (np.roll); then
+ * each mask in table order (the time masks [start, end) x all F, then the freq masks all L x [start, end)) overwrites its
+ * region with the mean over all L * F cells of the clip as it stands just before that mask (fixed-order fp64 sums, the
+ * mean rounded to fp32: bit-reproducible).  Rows >= L are copied unchanged.  Every index is clamped to the clip, so a bad
+ * table cannot reach outside it.  One workgroup per clip, no workspace.  N <= 0, T <= 0, F % 4 != 0, F > ACVAE_AUG_MAX_F,
+ * T * F > INT32_MAX, a NULL pointer or K != ACVAE_AUG_TABLE_WIDTH -> ACVAE_EINVAL before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+#define ACVAE_AUG_MAX_MASKS 8
+#define ACVAE_AUG_TABLE_WIDTH 35        /* 3 + 2 * 2 * ACVAE_AUG_MAX_MASKS */
+#define ACVAE_AUG_MAX_F 1024            /* mel bins per frame */
+int acvae_spec_augment(const float* in, float* out, const int* lens, const int* params, int N, int T, int F, int K,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Opt-in kernel timing (bench.py's live roofline figure): while enabled, the conv launches are bracketed
  * by HIP events on their stream; acvae_prof_read waits for them and returns the summed duration and the
  * launch count of a tag, then clears it.  Tags: 0 = conv3x3 implicit GEMM (forward + data gradient),
