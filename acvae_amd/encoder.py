@@ -88,8 +88,8 @@ class _Cnn10Fn(torch.autograd.Function):
         masks = None
         if training and mod.dropout_masks is not None:
             masks = [m.to(device=dev, dtype=torch.uint8).contiguous() for m in mod.dropout_masks]
-            if len(masks) != mod.N_BLOCKS + 2:
-                raise ValueError(f"dropout_masks must hold the {mod.N_BLOCKS + 2} masks of the forward in call order")
+            if len(masks) != mod._n_dropout_sites():
+                raise ValueError(f"dropout_masks must hold the {mod._n_dropout_sites()} masks of the forward in call order")
         seed = mod._next_seed() if training else 0
         mt = ptr_table(masks) if masks is not None else None
         _lib.call("acvae_encoder_fwd", ptr_table(tensors), feats, ae, pooled, saved, saved_b, scratch, scratch_b, arch,
@@ -174,6 +174,14 @@ class _PannsCnn(nn.Module):
     def _blocks(self):
         return [getattr(self, f"conv_block{b}") for b in range(1, self.N_BLOCKS + 1)]
 
+    def _n_dropout_sites(self):
+        return self.N_BLOCKS + 2
+
+    def _deep_block(self):
+        """(module, block id): the block whose gradients acvae_encoder_bwd_hooked announces first - the data-parallel
+        train step's deep encoder bucket"""
+        return getattr(self, f"conv_block{self.N_BLOCKS}"), self.N_BLOCKS
+
     def _head(self):
         return getattr(self, self.HEAD)
 
@@ -235,3 +243,129 @@ class Cnn14_16k(_PannsCnn):
     up to 2048 channels, the sixth pooled (1,1), time / 32, ``fc1`` (2048 x 2048) as the pooled head.  With a 512-wide
     decoder ``Hybrid_VAEModel`` adds the ``ln`` projection 2048 -> 512 (``models/vae_model.py:695-697``)."""
     ARCH, N_BLOCKS, TIME_DIV, OUT_CHANNELS, HEAD = 1, 6, 32, 2048, "fc1"
+
+
+class _ResnetBasicBlock(nn.Module):
+    """_ResnetBasicBlock (reference models/encoder.py:980-1036): parameter container.  Creation and initialisation follow
+    the reference's order, so a seeded construction draws the same weights."""
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
+        super().__init__()
+        self.stride = stride
+        self.conv1 = nn.Conv2d(inplanes, planes, 3, 1, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = downsample
+        init_layer(self.conv1); init_bn(self.bn1); init_layer(self.conv2); init_bn(self.bn2)
+        nn.init.constant_(self.bn2.weight, 0)      # a fresh block's residual branch contributes nothing
+
+    def forward(self, *a, **k):
+        raise RuntimeError("_ResnetBasicBlock is a parameter container on the HIP path; call the encoder's forward")
+
+
+class _ResNet(nn.Module):
+    """_ResNet(_ResnetBasicBlock, [3, 4, 6, 3]) (reference :1096-1167), parameters only."""
+
+    def __init__(self, layers=(3, 4, 6, 3)):
+        super().__init__()
+        inplanes = 64
+        for i, (planes, n) in enumerate(zip((64, 128, 256, 512), layers)):
+            stride = 1 if i == 0 else 2
+            downsample = None
+            if stride == 2:
+                # AvgPool2d(2) has no parameters: the state-dict keys are downsample.1.weight and downsample.2.*
+                downsample = nn.Sequential(nn.AvgPool2d(kernel_size=2), nn.Conv2d(inplanes, planes, 1, 1, bias=False),
+                                           nn.BatchNorm2d(planes))
+                init_layer(downsample[1]); init_bn(downsample[2])
+            blocks = [_ResnetBasicBlock(inplanes, planes, stride, downsample)]
+            inplanes = planes
+            blocks += [_ResnetBasicBlock(inplanes, planes) for _ in range(1, n)]
+            setattr(self, f"layer{i + 1}", nn.Sequential(*blocks))
+
+    def blocks(self):
+        return [b for i in range(1, 5) for b in getattr(self, f"layer{i}")]
+
+
+class ResNet38(_PannsCnn):
+    """PANNs ResNet38 audio encoder (reference ``models/encoder.py:1169-1234``): bn0, ConvBlock(1, 64) pooled 2x2, 16
+    residual basic blocks at 64-512 channels, a 2x2 average pool, ConvBlock(512, 2048) pooled (1, 1), ``fc1`` head.
+    time / 32, 2048-wide ``audio_embeds`` (with a 512-wide decoder ``Hybrid_VAEModel`` adds the ``ln`` projection).
+    State-dict names, shapes and order are the reference's, so a PANNs ``ResNet38_mAP=0.434.pth`` loads through
+    ``acvae_amd.train_util.load_pretrained_model``.  fp32 only."""
+    ARCH, N_BLOCKS, TIME_DIV, OUT_CHANNELS, HEAD = 2, 0, 32, 2048, "fc1"
+
+    def __init__(self, inputdim, embed_size, **kwargs):
+        nn.Module.__init__(self)
+        self.inputdim = inputdim
+        self.embed_size = embed_size
+        self.bn0 = nn.BatchNorm2d(64)
+        self.conv_block1 = ConvBlock(1, 64)
+        self.resnet = _ResNet()
+        self.conv_block_after1 = ConvBlock(512, 2048)
+        self.fc1 = nn.Linear(2048, 2048)
+        init_bn(self.bn0)
+        init_layer(self.fc1)
+        self.p_block, self.p_fc = 0.2, 0.5      # ConvBlock-level and head dropout; inside the blocks p_block / 2 = 0.1
+        self.compute_dtype = kwargs.get("compute_dtype", "f32")
+        self.dropout_masks = None               # optional explicit keep-masks, the 21 sites in forward order
+        self._seed_base, self._calls = None, 0
+        self.keep_saved = False
+        self._last_saved = None
+        self._grad_views = None
+        self._grad_ready_cb = None
+
+    def _arch(self):
+        if self.compute_dtype != "f32":
+            raise ValueError(f"ResNet38 runs in fp32 only (compute_dtype={self.compute_dtype!r})")
+        return self.ARCH
+
+    def _n_dropout_sites(self):
+        return 21
+
+    def _deep_block(self):
+        return self.conv_block_after1, 0
+
+    def _param_table(self):
+        t = _bn_tensors(self.bn0)
+        cb = self.conv_block1
+        t += [cb.conv1.weight, cb.conv2.weight] + _bn_tensors(cb.bn1) + _bn_tensors(cb.bn2)
+        for blk in self.resnet.blocks():
+            t += [blk.conv1.weight] + _bn_tensors(blk.bn1) + [blk.conv2.weight] + _bn_tensors(blk.bn2)
+            if blk.downsample is not None:
+                t += [blk.downsample[1].weight] + _bn_tensors(blk.downsample[2])
+        ca = self.conv_block_after1
+        t += [ca.conv1.weight, ca.conv2.weight] + _bn_tensors(ca.bn1) + _bn_tensors(ca.bn2)
+        t += [self.fc1.weight, self.fc1.bias]
+        return t
+
+    def site_shapes(self, N, T):
+        """[N, C, H, W] of the 36 ReLU sites and (second value) of the 21 dropout sites for input [N, T, 64]."""
+        relu, drop = [], []
+        h, w = T, 64
+        relu += [(N, 64, h, w)] * 2
+        h, w = h // 2, w // 2
+        drop.append((N, 64, h, w))
+        for blk in self.resnet.blocks():
+            if blk.stride == 2:
+                h, w = h // 2, w // 2
+            C = blk.conv1.out_channels
+            relu += [(N, C, h, w)] * 2
+            drop.append((N, C, h, w))
+        h, w = h // 2, w // 2
+        drop += [(N, 512, h, w), (N, 2048, h, w), (N, 2048), (N, 2048)]
+        relu += [(N, 2048, h, w)] * 2
+        return relu, drop
+
+    def relu_masks(self):
+        """The ReLU decisions of the last forward (``keep_saved = True`` before it): 36 bool tensors [N,C,H,W] in forward
+        order - conv_block1 bn1 / bn2, each block's relu(bn1) and residual ReLU, conv_block_after1 bn1 / bn2."""
+        if self._last_saved is None:
+            raise RuntimeError("relu_masks(): set keep_saved = True before the forward")
+        saved, arch, N, T, F = self._last_saved
+        out = []
+        for site, shape in enumerate(self.site_shapes(N, T)[0]):
+            m = torch.empty(*shape, dtype=torch.uint8, device=saved.device)
+            _lib.call("acvae_encoder_relu_mask", saved, saved.numel(), arch, N, T, F, site, m, _lib.current_stream())
+            out.append(m.bool())
+        return out

@@ -195,3 +195,21 @@ def generate_length_mask(lens):
     lens = torch.as_tensor(lens)
     T = int(lens.max())
     return torch.arange(T).unsqueeze(0) < lens.view(-1, 1)
+
+
+def load_pretrained_model(model: nn.Module, pretrained, outputfun):
+    """Reference utils/train_util.py:17-30: load the entries of a checkpoint (a state dict, or one wrapped under "model")
+    whose names exist in `model` with the same shape; everything else keeps its current value.  A PANNs checkpoint's
+    spectrogram_extractor.*, logmel_extractor.* and fc_audioset.* have no counterpart and are skipped.  A missing file is
+    reported through `outputfun` and nothing is loaded."""
+    import os
+    if not os.path.exists(pretrained):
+        outputfun(f"Loading pretrained model from {pretrained} failed!")
+        return
+    state_dict = torch.load(pretrained, map_location="cpu")
+    if "model" in state_dict:
+        state_dict = state_dict["model"]
+    model_dict = model.state_dict()
+    pretrained_dict = {k: v for k, v in state_dict.items() if k in model_dict and model_dict[k].shape == v.shape}
+    model_dict.update(pretrained_dict)
+    model.load_state_dict(model_dict, strict=True)

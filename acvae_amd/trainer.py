@@ -204,7 +204,7 @@ class TrainStep:
         text = [p for p in text if p not in qset] + [p for p in text if p in qset]   # decode-written first, posterior last
         n_q = sum(1 for p in text if p in qset)
         enc = [p for p in params if p in enc_params and p not in never]
-        deep = set(getattr(model.encoder, f"conv_block{model.encoder.N_BLOCKS}").parameters())
+        deep = set(model.encoder._deep_block()[0].parameters())
         enc = [p for p in enc if p not in deep] + [p for p in enc if p in deep]
         n_deep = sum(1 for p in enc if p in deep)
         tail = [p for p in params if p in never]
@@ -288,7 +288,7 @@ class TrainStep:
                 self.exchange.ready(0, after=(self._decode_event, self._decode_aux_event))
             self.exchange.ready(1)
         elif isinstance(tag, tuple):
-            if tag[1] == self.model.encoder.N_BLOCKS:
+            if tag[1] == self.model.encoder._deep_block()[1]:
                 self.exchange.ready(3)
         else:
             self.exchange.ready(3)

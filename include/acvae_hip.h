@@ -199,6 +199,24 @@ int acvae_loss_combine_bwd(const float* grad_out, float w_kl, float w_mse, float
 #define ACVAE_ENC_NPARAMS 55          /* Cnn10 */
 #define ACVAE_ARCH_CNN10 0
 #define ACVAE_ARCH_CNN14_16K 1
+/* ACVAE_ARCH_RESNET38 (models/encoder.py:1169-1234, the PANNs ResNet38): bn0, conv_block1 = ConvBlock(1, 64) pooled 2x2,
+ * 16 residual basic blocks (layers [3, 4, 6, 3] at 64 / 128 / 256 / 512 channels; the first block of layers 2-4 pools its
+ * input 2x2 and has a downsample AvgPool2d(2) + conv1x1 + BatchNorm2d), avg_pool2d(2), conv_block_after1 =
+ * ConvBlock(512, 2048) pooled (1, 1), the fc1 head: S = T/32, audio_embeds [N,S,2048].  fp32 only: ACVAE_ENC_BF16, T < 32
+ * or F != 64 with this arch is ACVAE_EINVAL before any launch.  Its table has 241 entries, the reference's state-dict order:
+ *   [0..4]    bn0.*                       [5] conv_block1.conv1.weight  [6] conv_block1.conv2.weight
+ *   [7..11]   conv_block1.bn1.*           [12..16] conv_block1.bn2.*
+ *   from 17, per block resnet.layerL.i in order: conv1.weight, bn1.* (5), conv2.weight, bn2.* (5) and, in layer2.0 /
+ *             layer3.0 / layer4.0, downsample.1.weight [C][Cin][1][1], downsample.2.* (5): 12 or 18 entries
+ *   [227] conv_block_after1.conv1.weight [228] .conv2.weight [229..233] .bn1.* [234..238] .bn2.*  [239, 240] fc1.{weight,bias}
+ * 21 dropout sites (masks in this order, NCHW / [N,2048]): 0 after conv_block1 (p_block), 1..16 inside block k = site-1
+ * after relu(bn1) (p = p_block / 2: the reference's 0.1 beside its 0.2), 17 after the pool behind the resnet (p_block), 18
+ * after conv_block_after1 (p_block), 19 and 20 around fc1 (p_fc).
+ * 36 ReLU sites (acvae_encoder_relu_mask): 0, 1 conv_block1 bn1 / bn2; 2+2k block k's relu(bn1), 3+2k block k's residual
+ * relu(bn2(..) + identity) (decision: out > 0); 34, 35 conv_block_after1 bn1 / bn2.
+ * acvae_encoder_bwd_hooked calls block_done ONCE, with block = 0, when the gradients of conv_block_after1 (47.2 M of the
+ * encoder's 72.7 M parameters) are queued. */
+#define ACVAE_ARCH_RESNET38 2
 /* OR-ed into `arch`: BASELINE configs[2] "bf16 forward / fp32 loss".  The conv stack's activations (raw conv outputs,
  * pooled tensors, their gradients) and the repacked conv weights are STORED in bf16 and the 3x3 convolutions run on
  * v_mfma_f32_32x32x16_bf16; accumulation, BatchNorm statistics (taken from the rounded tensor that is stored), parameter
@@ -306,6 +324,34 @@ int acvae_conv3x3_dgrad_bf16(const void* dY, const float* W_oihw, void* dX, void
 int acvae_conv3x3_wgrad_bf16(const void* dY, const void* X, const float* in_scale, const float* in_shift, float* dW_oihw,
                              void* ws, int64_t ws_bytes, int N, int H, int W, int Cin, int Cout, void* stream);
 int64_t acvae_bn_workspace_bytes(int N, int H, int W, int C);
+/* The ResNet38 kernels one by one (resnet.hip), NHWC fp32; bn* = [4][C] scale | shift | mean | invstd as above.
+ *   acvae_res_join_fwd   out = relu(y2*bn2.scale + bn2.shift + (yd ? yd*bnd.scale + bnd.shift : x))   (yd == NULL: identity x)
+ *   acvae_res_join_bwd   g = dO * (out > 0) -> G; dbeta2 = sum g, dgamma2 = sum g*yhat2 (and the same for bnd where yd != NULL,
+ *                        yhat = (y - mean) * invstd); dy2 / dyd = BatchNorm backward of g (training != 0: batch statistics)
+ *   acvae_conv1x1_fwd    Y[m][co] = sum_ci X[m][ci] W[co][ci]; partials (optional) [acvae_conv1x1_partials_rows][2][Cout] =
+ *                        per 64-pixel tile sum y | sum y^2 (Cin % 16 == 0, Cout % 64 == 0)
+ *   acvae_conv1x1_dgrad  dX (+)= dY . W      acvae_conv1x1_wgrad  dW[co][ci] = sum_m dY[m][co] X[m][ci] (fixed-order slab sum)
+ *   acvae_avg_pool2_fwd  P = dropout(avg_pool2x2(X)) (floors odd H / W; p_drop = 0: none; mask: explicit NCHW keep-mask)
+ *   acvae_avg_pool2_bwd  dX = upsample(dP * dropout) / 4 (pool != 0; 0 behind the last full window) or dP * dropout (pool == 0),
+ *                        plus add (if not NULL); dX is [N,H,W,C] */
+int acvae_res_join_fwd(const float* y2, const float* bn2, const float* yd, const float* bnd, const float* x, float* out, int N,
+                       int H, int W, int C, void* stream);
+int64_t acvae_res_join_bwd_workspace_bytes(int N, int H, int W, int C);
+int acvae_res_join_bwd(const float* dO, const float* out, const float* y2, const float* bn2, const float* yd, const float* bnd,
+                       float* G, float* dy2, float* dyd, float* dgamma2, float* dbeta2, float* dgammad, float* dbetad,
+                       int training, void* ws, int64_t ws_bytes, int N, int H, int W, int C, void* stream);
+int acvae_conv1x1_partials_rows(int N, int H, int W);
+int acvae_conv1x1_fwd(const float* X, const float* W_oi, float* Y, float* partials, int N, int H, int W, int Cin, int Cout,
+                      void* stream);
+int acvae_conv1x1_dgrad(const float* dY, const float* W_oi, float* dX, int accumulate, int N, int H, int W, int Cin, int Cout,
+                        void* stream);
+int64_t acvae_conv1x1_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout);
+int acvae_conv1x1_wgrad(const float* dY, const float* X, float* dW_oi, void* ws, int64_t ws_bytes, int N, int H, int W, int Cin,
+                        int Cout, void* stream);
+int acvae_avg_pool2_fwd(const float* X, float* P, int N, int H, int W, int C, float p_drop, uint64_t seed, int site,
+                        const uint8_t* mask, void* stream);
+int acvae_avg_pool2_bwd(const float* dP, const float* add, float* dX, int N, int H, int W, int C, int pool, float p_drop,
+                        uint64_t seed, int site, const uint8_t* mask, void* stream);
 int acvae_bn_mel_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
                      int64_t* num_batches_tracked, int training, float* bn_out, void* ws, int64_t ws_bytes, int64_t rows,
                      int F, void* stream);
