@@ -92,6 +92,8 @@ int colsum2(const float* x, int P, int width, double* dpart, float* out, float* 
 struct ColsumJob { const float* x; int P, width; float* out; float* out_b; int R; long d0; };
 using ColsumBatch = RangeTable<ColsumJob, 6, int>;
 int colsum_batch(ColsumBatch& b, double* dpart, long dpart_doubles, hipStream_t st);
+// colsum_batch's plan (fills R, d0 and the ranges): true = one launch, false = one colsum2 per job
+bool colsum_batch_plan(ColsumBatch& b, long dpart_doubles, long* dsum_doubles);
 int conv1_first_blocks(int N, int T);
 template <class TY>
 int conv1_first_fwd(const float* x, const float* scale0, const float* shift0, const float* W1, TY* Y,

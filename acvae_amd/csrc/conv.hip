@@ -1580,20 +1580,25 @@ int colsum2(const float* partials, int P, int width, double* dpart, float* out, 
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }
-int colsum_batch(ColsumBatch& b, double* dpart, long dpart_doubles, hipStream_t st) {
-  if (!b.ok()) return ACVAE_EINVAL;
-  if (b.n <= 0) return ACVAE_OK;
+// The batch's plan, for a table that is ok() and not empty: fills every job's R and d0 and the table's ranges, and tells whether
+// the batch goes out as ONE launch (false: one colsum2 per job).  colsum_batch and the plan query (acvae_colsum_batch_plan)
+// both call it.  *dsum_doubles: the group sums of all jobs (behind the tickets in dpart).
+bool colsum_batch_plan(ColsumBatch& b, long dpart_doubles, long* dsum_doubles) {
   long d = 0;
-  int maxr = 1;
   for (int j = 0; j < b.n; ++j) {
     ColsumJob& c = b.job[j];
     c.R = cs_groups(c.P);
     c.d0 = d;
     d += (long)c.R * c.width;
-    if (c.R > maxr) maxr = c.R;
   }
   const int blocks = b.seal([](const ColsumJob& c) { return cdiv(c.width, 64); });
-  if (b.n == 1 || blocks > CS_TICKETS || CS_TICKETS / 2 + d > dpart_doubles) {         // one launch each, as before
+  if (dsum_doubles) *dsum_doubles = d;
+  return !(b.n == 1 || blocks > CS_TICKETS || CS_TICKETS / 2 + d > dpart_doubles);
+}
+int colsum_batch(ColsumBatch& b, double* dpart, long dpart_doubles, hipStream_t st) {
+  if (!b.ok()) return ACVAE_EINVAL;
+  if (b.n <= 0) return ACVAE_OK;
+  if (!colsum_batch_plan(b, dpart_doubles, nullptr)) {         // one launch each, as before
     for (int j = 0; j < b.n; ++j) {
       const ColsumJob& c = b.job[j];
       ACVAE_TRY(colsum2(c.x, c.P, c.width, dpart, c.out, nullptr, 0, st));
@@ -1601,7 +1606,10 @@ int colsum_batch(ColsumBatch& b, double* dpart, long dpart_doubles, hipStream_t 
     }
     return ACVAE_OK;
   }
-  hipLaunchKernelGGL(colsum_batch_kernel, dim3(blocks, maxr), dim3(256), 0, st, b, dpart);
+  int maxr = 1;
+  for (int j = 0; j < b.n; ++j)
+    if (b.job[j].R > maxr) maxr = b.job[j].R;
+  hipLaunchKernelGGL(colsum_batch_kernel, dim3(b.start[b.n], maxr), dim3(256), 0, st, b, dpart);
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }

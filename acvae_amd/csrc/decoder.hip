@@ -616,6 +616,8 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
     zb_skinny(zb, st.skws); zb_skinny(zb, sp.skws);
     if (attws_ready) { zb.add(sc + L.attfws_d, 256); zb.add(sc + L.attfws_p, 256); }
     if (persist_fwd) { zb.add(sc + L.pd_cnt, acvae::decode_persist_counter_words(Tc)); flags |= ACVAE_FLAG_INT_CNT_ZEROED; }
+    // h_{-1} of both chains: read by the first step on either stream, so it is zeroed here, in front of the fork
+    zb.add(sc + L.h0, (long)N * (H > Hp ? H : Hp));
     ACVAE_TRY(acvae::zero_batch(zb, st.s));
   }
 
@@ -646,8 +648,7 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
     return gemm(mem, E, P(TP_P_ATT_W) + E, 2 * E, P(TP_P_ATT_B), encproj_p, E, N * S, E, E, 0, c);
   };
   auto encproj_dec = [&]() -> int {
-    ACVAE_TRY(gemm(mem, E, P(TP_DEC_ATT_W) + H, E + H, P(TP_DEC_ATT_B), encproj_d, A, N * S, A, E, 0, st));
-    return acvae::copy_rows(zeros, H > Hp ? H : Hp, nullptr, 0, N, H > Hp ? H : Hp, st);
+    return gemm(mem, E, P(TP_DEC_ATT_W) + H, E + H, P(TP_DEC_ATT_B), encproj_d, A, N * S, A, E, 0, st);
   };
 
   // ---- per-range helpers; (t0,cnt) is either (0,Tc) [rows contiguous] or (t,1) [row stride Tc*C]

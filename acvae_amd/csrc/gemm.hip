@@ -317,6 +317,30 @@ int acvae_gemm_nt_pair(const float* A0, int64_t lda0, const float* B0, int64_t l
   return ACVAE_OK;
 }
 
+// The skinny dispatcher's plan: 0 = the 128-row tile kernel, else the split count S of the 32x32-tile kernel (1 = no split).
+// The dispatcher and the plan query (acvae_gemm_nt_split_plan) both call it.
+static int skinny_plan(int M, int N, int Ktot, bool dual, bool have_ws) {
+  // The 128-row tile kernel needs >= ~100 workgroups to fill the chip; mid-sized products (M = N*Tc = 672 rows
+  // against 512..2048 columns) would launch 24-96 of them and run 100-140 us, so they take the 32x32-tile kernel too.
+  const long big_blocks = (long)cdiv(M, 128) * cdiv(N, N <= 64 ? 64 : 128);
+  if (!(M <= 64 || dual || (big_blocks < 100 && M <= 4096))) return 0;
+  const int tiles = cdiv(N, 32) * cdiv(M, 32);
+  // split K over more workgroups when there are few tiles and K is long (the serial decode/BPTT steps)
+  int S = 1;
+  static const bool splitk_on = !(getenv("ACVAE_SKINNY_SPLITK") && getenv("ACVAE_SKINNY_SPLITK")[0] == '0');  // tuning switch
+  // Only the long-K, few-tile products of the BPTT steps gain: the release/acquire hand-off costs a few us
+  // (measured: 48 tiles x K=512 went 6.8 -> 9.8 us with S=2, 16 tiles x K=2048 went 25 -> 13.7 us with S=8).
+  if (have_ws && splitk_on && tiles <= 16 && Ktot >= 1024) {
+    S = 128 / tiles;
+    const int maxs = Ktot / 256;       // keep >= 256 k per slice
+    if (S > maxs) S = maxs;
+    if (S > 8) S = 8;
+    if (S < 1) S = 1;
+    if ((long)tiles * S > SK_MAX_TILES) S = 1;
+  }
+  return S;
+}
+
 int acvae_gemm_nt_dual(const float* A1, int64_t lda1, const float* B1, int64_t ldb1, int K1, const float* A2,
                        int64_t lda2, const float* B2, int64_t ldb2, int K2, const float* bias, float* C, int64_t ldc,
                        int M, int N, int accumulate, hipStream_t st, float* skws) {
@@ -324,25 +348,8 @@ int acvae_gemm_nt_dual(const float* A1, int64_t lda1, const float* B1, int64_t l
   if (A2 && (!B2 || K2 <= 0)) return ACVAE_EINVAL;
   bool vec = vec_ok(A1, lda1, K1) && vec_ok(B1, ldb1, K1);
   if (A2) vec = vec && vec_ok(A2, lda2, K2) && vec_ok(B2, ldb2, K2);
-  // The 128-row tile kernel needs >= ~100 workgroups to fill the chip; mid-sized products (M = N*Tc = 672 rows
-  // against 512..2048 columns) would launch 24-96 of them and run 100-140 us, so they take the 32x32-tile kernel too.
-  const long big_blocks = (long)cdiv(M, 128) * cdiv(N, N <= 64 ? 64 : 128);
-  if (M <= 64 || A2 || (big_blocks < 100 && M <= 4096)) {
-    const int tiles = cdiv(N, 32) * cdiv(M, 32);
-    // split K over more workgroups when there are few tiles and K is long (the serial decode/BPTT steps)
-    int S = 1;
-    const int Ktot = K1 + (A2 ? K2 : 0);
-    static const bool splitk_on = !(getenv("ACVAE_SKINNY_SPLITK") && getenv("ACVAE_SKINNY_SPLITK")[0] == '0');  // tuning switch
-    // Only the long-K, few-tile products of the BPTT steps gain: the release/acquire hand-off costs a few us
-    // (measured: 48 tiles x K=512 went 6.8 -> 9.8 us with S=2, 16 tiles x K=2048 went 25 -> 13.7 us with S=8).
-    if (skws && splitk_on && tiles <= 16 && Ktot >= 1024) {
-      S = 128 / tiles;
-      const int maxs = Ktot / 256;       // keep >= 256 k per slice
-      if (S > maxs) S = maxs;
-      if (S > 8) S = 8;
-      if (S < 1) S = 1;
-      if ((long)tiles * S > SK_MAX_TILES) S = 1;
-    }
+  const int S = skinny_plan(M, N, K1 + (A2 ? K2 : 0), A2 != nullptr, skws != nullptr);
+  if (S > 0) {
     dim3 grid(cdiv(N, 32), cdiv(M, 32), S);
     unsigned* cnt = (unsigned*)skws;
     float* slabs = skws ? skws + SK_MAX_TILES : nullptr;
@@ -421,20 +428,31 @@ extern "C" int acvae_gemm_tn(const float* A, int64_t lda, const float* B, int64_
   return ACVAE_OK;
 }
 
+// The fused TN call's plan: the K-slices it launches (k_per k each); 1 = it falls back to acvae_gemm_tn without a workspace
+// (one slice, or a workspace too small for the slabs, or more tiles than tickets).  The call and the plan query
+// (acvae_gemm_tn_fused_plan) both use it.
+static int tn_fused_slices(int M, int N, int K, bool have_ws, int64_t ws_bytes, int* k_per_out) {
+  int s = tn_splits(M, N, K);
+  const bool narrow = (M <= 64);
+  const long tiles = (long)cdiv(M, narrow ? 64 : 128) * cdiv(N, narrow ? 256 : 128);
+  if (s > 1 && (!have_ws || ws_bytes < (int64_t)TN_TICKETS * 4 + (int64_t)s * M * N * (int64_t)sizeof(float) ||
+                tiles > TN_TICKETS))
+    return 1;
+  const int k_per = cdiv(cdiv(K, s), BKT) * BKT;
+  s = cdiv(K, k_per);
+  if (k_per_out) *k_per_out = k_per;
+  return s;
+}
+
 // ws = [TN_TICKETS words of tickets (zeroed once per composite call) | slabs]
 int acvae_gemm_tn_fused(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K,
                         int accumulate, float* ws, int64_t ws_bytes, hipStream_t st) {
   if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return ACVAE_EINVAL;
-  int s = tn_splits(M, N, K);
+  int k_per = 0;
+  const int s = tn_fused_slices(M, N, K, ws != nullptr, ws_bytes, &k_per);
+  if (s <= 1) return acvae_gemm_tn(A, lda, B, ldb, C, ldc, M, N, K, accumulate, nullptr, 0, st);  // one slice per tile, no workspace
   const bool narrow = (M <= 64);
-  dim3 grid(cdiv(M, narrow ? 64 : 128), cdiv(N, narrow ? 256 : 128), 1);
-  if (s > 1 && (!ws || ws_bytes < (int64_t)TN_TICKETS * 4 + (int64_t)s * M * N * (int64_t)sizeof(float) ||
-                (long)grid.x * grid.y > TN_TICKETS))
-    return acvae_gemm_tn(A, lda, B, ldb, C, ldc, M, N, K, accumulate, nullptr, 0, st);     // one slice per tile, no workspace
-  int k_per = cdiv(cdiv(K, s), BKT) * BKT;
-  s = cdiv(K, k_per);
-  if (s <= 1) return acvae_gemm_tn(A, lda, B, ldb, C, ldc, M, N, K, accumulate, nullptr, 0, st);
-  grid.z = s;
+  dim3 grid(cdiv(M, narrow ? 64 : 128), cdiv(N, narrow ? 256 : 128), s);
   const bool vec = aligned16(A) && aligned16(B) && (lda & 3) == 0 && (ldb & 3) == 0 && (M & 3) == 0 && (N & 3) == 0;
   unsigned* tickets = reinterpret_cast<unsigned*>(ws);
   float* slab = ws + TN_TICKETS;
@@ -455,4 +473,48 @@ extern "C" int acvae_transpose(const float* in, int64_t ld_in, float* out, int64
                      ld_in, out, ld_out, rows, cols);
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
+}
+
+// ---- C entry points of the internal forms above, for tests: the composite drivers reach them only at their own shapes.
+// reset_tickets = 1 zeroes the workspace's tickets in front of the launch (a composite driver's entry); 0 relies on every
+// earlier reducer having left its ticket at zero.
+extern "C" int64_t acvae_gemm_nt_splitk_workspace_bytes(void) { return acvae_skinny_ws_floats() * (int64_t)sizeof(float); }
+extern "C" int acvae_gemm_nt_split_plan(int M, int N, int K1, int K2, int with_ws) {
+  if (M <= 0 || N <= 0 || K1 <= 0 || K2 < 0) return ACVAE_EINVAL;
+  return skinny_plan(M, N, K1 + K2, K2 > 0, with_ws != 0);
+}
+extern "C" int acvae_gemm_nt_dual_ws(const float* A1, int64_t lda1, const float* B1, int64_t ldb1, int K1, const float* A2,
+                                     int64_t lda2, const float* B2, int64_t ldb2, int K2, const float* bias, float* C,
+                                     int64_t ldc, int M, int N, int accumulate, float* ws, int64_t ws_bytes, int reset_tickets,
+                                     void* stream) {
+  if (!A1 || !B1 || !C || M <= 0 || N <= 0 || K1 <= 0 || (A2 && (!B2 || K2 <= 0))) return ACVAE_EINVAL;
+  if (ws && ws_bytes < acvae_gemm_nt_splitk_workspace_bytes()) return ACVAE_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (ws && reset_tickets) ACVAE_TRY(acvae_skinny_ws_reset(ws, st));
+  return acvae_gemm_nt_dual(A1, lda1, B1, ldb1, K1, A2, lda2, B2, ldb2, K2, bias, C, ldc, M, N, accumulate, st, ws);
+}
+extern "C" int acvae_gemm_nt_pair_c(const float* A0, int64_t lda0, const float* B0, int64_t ldb0, int K0, const float* bias0,
+                                    float* C0, int64_t ldc0, int N0, int acc0, const float* A1, int64_t lda1, const float* B1,
+                                    int64_t ldb1, int K1, const float* bias1, float* C1, int64_t ldc1, int N1, int acc1, int M,
+                                    void* stream) {
+  return acvae_gemm_nt_pair(A0, lda0, B0, ldb0, K0, bias0, C0, ldc0, N0, acc0, A1, lda1, B1, ldb1, K1, bias1, C1, ldc1, N1,
+                            acc1, M, (hipStream_t)stream);
+}
+extern "C" int64_t acvae_gemm_tn_fused_workspace_bytes(int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return -1;
+  const int s = tn_splits(M, N, K);
+  return s > 1 ? (int64_t)TN_TICKETS * 4 + (int64_t)s * M * N * (int64_t)sizeof(float) : 0;
+}
+extern "C" int acvae_gemm_tn_fused_plan(int M, int N, int K, int64_t ws_bytes) {
+  if (M <= 0 || N <= 0 || K <= 0) return ACVAE_EINVAL;
+  return tn_fused_slices(M, N, K, ws_bytes > 0, ws_bytes, nullptr);
+}
+extern "C" int acvae_gemm_tn_fused_c(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M,
+                                     int N, int K, int accumulate, float* ws, int64_t ws_bytes, int reset_tickets,
+                                     void* stream) {
+  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return ACVAE_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (ws && reset_tickets && ws_bytes >= (int64_t)TN_TICKETS * 4)
+    if (hipMemsetAsync(ws, 0, TN_TICKETS * sizeof(unsigned), st) != hipSuccess) return (int)hipGetLastError();
+  return acvae_gemm_tn_fused(A, lda, B, ldb, C, ldc, M, N, K, accumulate, ws, ws_bytes, st);
 }

@@ -374,3 +374,48 @@ extern "C" int acvae_colsum(const float* x, int rows, int cols, float* out, void
   ACVAE_TRY(acvae::colsum_tickets_reset((double*)ws, (hipStream_t)stream));
   return acvae::colsum2(x, rows, cols, (double*)ws, out, nullptr, 0, (hipStream_t)stream);
 }
+
+// Several column sums in one call (colsum_batch, the text side's batched bias gradients): job j sums x[j] [P[j], width[j]]
+// into out[j] (and out_b[j], if the table and its entry are given).  ws: the tickets and group sums of every job
+// (acvae_colsum_batch_workspace_bytes for one launch; a smaller one, down to the largest single job's acvae_colsum share,
+// sends the jobs out one launch each).
+static int colsum_table(int n, const int* P, const int* width, acvae::ColsumBatch& b) {
+  if (n <= 0 || n > acvae::ColsumBatch::capacity || !P || !width) return ACVAE_EINVAL;
+  for (int j = 0; j < n; ++j) {
+    if (P[j] <= 0 || width[j] <= 0) return ACVAE_EINVAL;
+    b.add({nullptr, P[j], width[j], nullptr, nullptr, 0, 0});
+  }
+  return ACVAE_OK;
+}
+extern "C" int64_t acvae_colsum_batch_workspace_bytes(int n, const int* P, const int* width) {
+  acvae::ColsumBatch b;
+  if (colsum_table(n, P, width, b) != ACVAE_OK) return -1;
+  long d = 0;
+  acvae::colsum_batch_plan(b, 0, &d);
+  return ((int64_t)acvae::colsum_ticket_words() / 2 + d) * 8;
+}
+extern "C" int acvae_colsum_batch_plan(int n, const int* P, const int* width, int64_t ws_bytes) {
+  acvae::ColsumBatch b;
+  ACVAE_TRY(colsum_table(n, P, width, b));
+  return acvae::colsum_batch_plan(b, (long)(ws_bytes / 8), nullptr) ? 1 : 0;
+}
+extern "C" int acvae_colsum_batch(int n, const void* const* x, const int* P, const int* width, const void* const* out,
+                                  const void* const* out_b, void* ws, int64_t ws_bytes, int reset_tickets, void* stream) {
+  acvae::ColsumBatch b;
+  ACVAE_TRY(colsum_table(n, P, width, b));
+  if (!x || !out || !ws) return ACVAE_EINVAL;
+  for (int j = 0; j < n; ++j) {
+    if (!x[j] || !out[j]) return ACVAE_EINVAL;
+    b.job[j].x = (const float*)x[j];
+    b.job[j].out = (float*)out[j];
+    b.job[j].out_b = out_b ? (float*)out_b[j] : nullptr;
+  }
+  // the one-launch-per-job fallback needs the tickets and the group sums of its largest job
+  acvae::ColsumBatch plan = b;
+  acvae::colsum_batch_plan(plan, 0, nullptr);
+  for (int j = 0; j < n; ++j)
+    if (ws_bytes < ((int64_t)acvae::colsum_ticket_words() / 2 + (int64_t)plan.job[j].R * width[j]) * 8) return ACVAE_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (reset_tickets) ACVAE_TRY(acvae::colsum_tickets_reset((double*)ws, st));
+  return acvae::colsum_batch(b, (double*)ws, (long)(ws_bytes / 8), st);
+}

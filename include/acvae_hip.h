@@ -73,6 +73,40 @@ int64_t acvae_gemm_tn_workspace_bytes(int M, int N, int K);
 /* out[c] = sum_r x[r,c] of a contiguous [rows, cols] matrix (bias gradients); deterministic (fixed-order fp64 combine) */
 int64_t acvae_colsum_workspace_bytes(int cols);
 int acvae_colsum(const float* x, int rows, int cols, float* out, void* ws, int64_t ws_bytes, void* stream);
+
+/* The cross-workgroup reductions of the composite drivers, as C entry points for the tests (the drivers reach them only at
+ * their own shapes).  Each hands partial results from workgroup to workgroup: the last to arrive at a ticket sums them and
+ * resets the ticket.  reset_tickets = 1 zeroes the workspace's tickets first, as a composite call does at its entry;
+ * 0 relies on every earlier reducer on that workspace having left its ticket at zero.  The *_plan queries are host
+ * arithmetic and come from the functions the dispatchers use.
+ *   acvae_gemm_nt_dual_ws  C = A1 . B1^T (+ A2 . B2^T if A2) (+ bias) (+ C): the NT product with the split-K workspace of
+ *                          acvae_gemm_nt_splitk_workspace_bytes() (ws = NULL: no split, as acvae_gemm_nt);
+ *                          acvae_gemm_nt_split_plan: 0 = the 128-row tile kernel, else its split count S (1: no split);
+ *                          K2 > 0 means the dual form
+ *   acvae_gemm_nt_pair_c   two independent NT products of M <= 64 rows in one launch (no split)
+ *   acvae_gemm_tn_fused_c  acvae_gemm_tn with the slab sum in the same launch: ws = tickets | slabs of
+ *                          acvae_gemm_tn_fused_workspace_bytes (0: one slice); acvae_gemm_tn_fused_plan: the slices it
+ *                          launches with ws_bytes of workspace (1: it falls back to acvae_gemm_tn without one)
+ *   acvae_colsum_batch     up to 6 column sums (as acvae_colsum) in one launch: x / out / out_b are host tables of device
+ *                          pointers (out_b or its entries may be NULL), P / width host int arrays; ws: tickets | group
+ *                          sums, acvae_colsum_batch_workspace_bytes for one launch;  acvae_colsum_batch_plan: 1 = one
+ *                          launch, 0 = one launch per job (one job, more than 128 column blocks, or a smaller ws) */
+int64_t acvae_gemm_nt_splitk_workspace_bytes(void);
+int acvae_gemm_nt_split_plan(int M, int N, int K1, int K2, int with_ws);
+int acvae_gemm_nt_dual_ws(const float* A1, int64_t lda1, const float* B1, int64_t ldb1, int K1, const float* A2,
+                          int64_t lda2, const float* B2, int64_t ldb2, int K2, const float* bias, float* C, int64_t ldc,
+                          int M, int N, int accumulate, float* ws, int64_t ws_bytes, int reset_tickets, void* stream);
+int acvae_gemm_nt_pair_c(const float* A0, int64_t lda0, const float* B0, int64_t ldb0, int K0, const float* bias0, float* C0,
+                         int64_t ldc0, int N0, int acc0, const float* A1, int64_t lda1, const float* B1, int64_t ldb1, int K1,
+                         const float* bias1, float* C1, int64_t ldc1, int N1, int acc1, int M, void* stream);
+int64_t acvae_gemm_tn_fused_workspace_bytes(int M, int N, int K);
+int acvae_gemm_tn_fused_plan(int M, int N, int K, int64_t ws_bytes);
+int acvae_gemm_tn_fused_c(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N,
+                          int K, int accumulate, float* ws, int64_t ws_bytes, int reset_tickets, void* stream);
+int64_t acvae_colsum_batch_workspace_bytes(int n, const int* P, const int* width);
+int acvae_colsum_batch_plan(int n, const int* P, const int* width, int64_t ws_bytes);
+int acvae_colsum_batch(int n, const void* const* x, const int* P, const int* width, const void* const* out,
+                       const void* const* out_b, void* ws, int64_t ws_bytes, int reset_tickets, void* stream);
 /* out[c,r] = in[r,c] */
 int acvae_transpose(const float* in, int64_t ld_in, float* out, int64_t ld_out, int rows, int cols, void* stream);
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from acvae_amd import _lib
 from acvae_amd.decoder import VAERNNBahdanauAttnDecoder
 from acvae_amd.encoder import Cnn10
 from acvae_amd.trainer import TrainStep
@@ -190,11 +191,29 @@ def test_backward_is_bit_reproducible_from_the_first_run(B, T):
     still holds the previous (identical) values - a kernel on the second stream that outlives its operands, or reads what it has
     not been handed yet, shows up exactly there (round 4: the trailing parameter-gradient products read the encoder memory in
     place after autograd had released it; only this comparison caught it)."""
+    _assert_four_runs_bit_identical(B, T, dis_ratio=0)
+
+
+@pytest.mark.parametrize("path", ["prior_feeds_decoder", "per_step_chains"])
+def test_backward_is_bit_reproducible_on_the_two_chain_paths(path):
+    """As above, on the forward paths whose two chains run on two streams step by step: dis_ratio > 0 (the prior's z feeds the
+    decoder: the prior chain, then the decoder chain) and the per-step launches instead of the persistent one (both chains side
+    by side).  Both read the zero h_{-1} on the prior chain's stream at step 0; it is zeroed in front of the fork (it used to be
+    zeroed on the first stream behind the fork, with no edge to the reader).  The side stream stays on in both."""
+    if path == "prior_feeds_decoder":
+        _assert_four_runs_bit_identical(5, 999, dis_ratio=0.5)
+    else:
+        with _lib.override(persist=False):
+            _assert_four_runs_bit_identical(5, 999, dis_ratio=0)
+
+
+def _assert_four_runs_bit_identical(B, T, dis_ratio):
     import os, sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
     import acvae_oracle as O
     from acvae_amd.train_util import LabelSmoothingLoss, MSELoss, Normal_kl_loss
     model = build(5).train()
+    assert model.use_side_stream
     model.encoder.p_block = model.encoder.p_fc = 0.0
     feats, caps, fl, cl = O.synthetic_batch(B, T, V, L, seed=4, ragged=True)
     g = torch.Generator().manual_seed(3)
@@ -205,7 +224,8 @@ def test_backward_is_bit_reproducible_from_the_first_run(B, T):
             p.grad = None
         model.noise = noise
         random.seed(9)
-        out = model(feats.cuda(), fl.copy(), caps, cl, ss_ratio=1.0, dis_ratio=0)
+        torch.manual_seed(9)             # the dis_ratio coins (and any dropout) are drawn on the CPU generator
+        out = model(feats.cuda(), fl.copy(), caps, cl, ss_ratio=1.0, dis_ratio=dis_ratio)
         lens1 = np.asarray(cl) - 1
         loss = (LabelSmoothingLoss(V, 0.1).masked(out["logits"], caps[:, 1:].to(torch.long), lens1)
                 + 0.5 * Normal_kl_loss()(out["q_means"], out["q_logs"], out["p_means"], out["p_logs"])
