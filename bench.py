@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — training-step throughput of the AC-VAE hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +13,10 @@ every rank processes its own 32-clip batch; gradients are averaged over RCCL.  E
 from page-locked host memory inside the timed region (prefetched during the previous step).  Rank 0 prints ONE JSON line.
 --dump-outputs DIR: rank 0 also writes what the last timed step handed its caller as DIR/<name>.npy (dump_outputs); the
 inputs and weights are seeded, so two builds run with the same arguments can be compared array for array.
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump, the result line (with the live
+`roofline` figures of the timed steps).  --full also measures what takes runs of its own, after the dump: the same loop on
+one resident tensor and with the upload queued inline (config.resident_ms_per_step / inline_upload_ms_per_step), and, on one
+GPU, the CPU baseline (cpu_baseline, about a minute of host work; --no-cpu-baseline leaves it out).
 """
 import argparse
 import json
@@ -154,7 +158,9 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=8)     # steps 1-7 of a fresh process run 31-34 ms, later ones 28.7
                                                          # (tools/step_times.py): allocator, event and clock warm-up
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also time the resident-tensor and inline-upload loops and (1 GPU) the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
                     help="f32 = BASELINE configs[1] (the headline, default); bf16 = configs[2]: bf16 forward / fp32 loss "
                          "(conv stack on the bf16 MFMA pipe, activations stored in bf16; text side, loss, parameters fp32)")
@@ -181,6 +187,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
                "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+        if args.full:
+            cmd.append("--full")
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         cmd += ["--dtype", args.dtype]
@@ -224,7 +232,7 @@ def main():
     # The feature batch of EVERY step arrives as a page-locked host buffer, as a DataLoader(pin_memory=True) hands it over, and
     # is uploaded inside the timed region (Runner._forward: `feats = batch[0].to(device)`, runners/pytorch_runner_vae.py:80):
     # TrainStep.prefetch queues the NEXT step's copy on a copy stream while the current step runs.  The first batch is
-    # resident before the timed region starts.  (config.resident_ms_per_step: the same loop on one resident tensor.)
+    # resident before the timed region starts.  (--full, config.resident_ms_per_step: the same loop on one resident tensor.)
     pinned = feats_host.pin_memory()
 
     def step(x=None):
@@ -268,10 +276,10 @@ def main():
     _lib.lib().acvae_prof_enable(0)
     loss = float(parts["loss"])
     ts.synchronize()                                  # raises if a persistent launch of the run gave up
-    if args.dump_outputs and rank == 0:               # before the extra steps below change the parameters again
+    if args.dump_outputs and rank == 0:               # before the extra steps of --full change the parameters again
         dump_outputs(args.dump_outputs, model, parts)
-    # Beside it: the same loop on ONE resident tensor (no upload at all), and with the upload queued in front of each step on
-    # the compute stream (no prefetch: what `feats.to(device)` inside the step costs when nothing hides it).
+    # --full, beside it: the same loop on ONE resident tensor (no upload at all), and with the upload queued in front of each
+    # step on the compute stream (no prefetch: what `feats.to(device)` inside the step costs when nothing hides it).
     EXTRA = 8
     def timed(fn):
         for _ in range(2):
@@ -282,8 +290,9 @@ def main():
             fn()
         torch.cuda.synchronize()
         return max_over_ranks((time.perf_counter() - t1) / EXTRA * 1e3, device="cuda")
-    resident_ms = timed(lambda: step())
-    inline_ms = timed(lambda: step(pinned.cuda(non_blocking=True)))
+    if args.full:
+        resident_ms = timed(lambda: step())
+        inline_ms = timed(lambda: step(pinned.cuda(non_blocking=True)))
 
     if rank == 0:
         n_gpus = world
@@ -336,10 +345,11 @@ def main():
                        "input": "every step's feature batch (8.2 MB) is uploaded from page-locked host memory INSIDE the timed "
                                 "region, prefetched on a copy stream during the previous step (TrainStep.prefetch)",
                        "pcie_inclusive_ms_per_step": ms_per_step,
-                       "resident_ms_per_step": resident_ms, "inline_upload_ms_per_step": inline_ms,
-                       "pcie_inclusive_note": f"ms_per_step IS the upload-inclusive figure; resident_ms_per_step = {EXTRA} extra "
-                                              "steps on one resident tensor (no upload), inline_upload_ms_per_step = the upload "
-                                              "queued in front of each step on the compute stream (no prefetch)"},
+                       **({"resident_ms_per_step": resident_ms, "inline_upload_ms_per_step": inline_ms,
+                           "pcie_inclusive_note": f"ms_per_step IS the upload-inclusive figure; resident_ms_per_step = {EXTRA} "
+                                                  "extra steps on one resident tensor (no upload), inline_upload_ms_per_step = "
+                                                  "the upload queued in front of each step on the compute stream (no prefetch)"}
+                          if args.full else {})},
             "roofline": {"bound": "mfma", "kernel": kernel,
                          "achieved": executed, "peak": peak, "unit": "TFLOP/s",
                          "frac": executed / peak, "traffic": None if bf16 else traffic,
@@ -354,7 +364,7 @@ def main():
                                  "multiplies, so it can exceed the peak); step_frac = executed conv flops of the whole step (fwd + dgrad + "
                                  "wgrad) over ms_per_step"},
         }
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

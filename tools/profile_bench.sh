@@ -14,7 +14,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-python3 "$ROOT/bench.py" --steps 20 --warmup 3 $EXTRA > "$OUT/bench.json"
+python3 "$ROOT/bench.py" --steps 20 --warmup 3 --full $EXTRA > "$OUT/bench.json"
 rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o stats --output-format csv -- python3 "$ROOT/bench.py" --steps 20 --warmup 3 --no-cpu-baseline $EXTRA > "$OUT/bench_under_rocprof.json"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch --output-format csv -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline $EXTRA > /dev/null
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/write" -o write --output-format csv -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline $EXTRA > /dev/null
