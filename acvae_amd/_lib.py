@@ -4,6 +4,7 @@ symbol declared in the header is not exported, importing/using the product path 
 import ctypes
 import os
 import re
+import threading
 
 import numpy as np
 import torch
@@ -75,18 +76,38 @@ class options:
 
 
 class override:
+    """`with override(persist=False): ...` sets options for the block.  The options are process-wide (a backward pass reads
+    them on autograd's own thread), so blocks entered from several host threads may overlap: the options are always the
+    values from before the first open block with every open block's settings applied in the order they were entered.
+    (Restoring "what was there on entering" would let a block that leaves first undo one still open, or a block that
+    entered inside another leave that one's values behind for good.)"""
+    _lock = threading.Lock()
+    _open = []
+    _base = None
+
     def __init__(self, **kw):
         self.kw = kw
 
-    def __enter__(self):
-        self.old = {k: getattr(options, k) for k in self.kw}
-        for k, v in self.kw.items():
+    @staticmethod
+    def _apply():
+        vals = dict(override._base)
+        for o in override._open:
+            vals.update(o.kw)
+        for k, v in vals.items():
             setattr(options, k, v)
+
+    def __enter__(self):
+        with override._lock:
+            if not override._open:
+                override._base = {k: v for k, v in vars(options).items() if not k.startswith("_")}
+            override._open.append(self)
+            override._apply()
         return self
 
     def __exit__(self, *exc):
-        for k, v in self.old.items():
-            setattr(options, k, v)
+        with override._lock:
+            override._open.remove(self)
+            override._apply()
         return False
 
 

@@ -96,3 +96,42 @@ def test_hot_kernels_keep_everything_in_registers():
         for n, u in hits.items():
             assert u.get("scratch", -1) == 0, f"{n}: {u.get('scratch')} bytes per lane of scratch"
             assert u.get("vgprs", 999) <= 256, (n, u)
+
+
+def test_overlapping_overrides_from_two_threads_restore_the_defaults():
+    """Two host threads each run a step under `_lib.override(...)` (test_decode_persist_gpu.py does, with two models on two
+    streams); their blocks overlap: A enters, B enters, A leaves, B leaves.  B saw A's value on entry, so restoring "what
+    was there on entry" left the option at A's value after both had left - and every later step in the process silently
+    ran without the split-over-frames attention.  Once the last override has left, the options are the defaults again,
+    whichever order the blocks leave in."""
+    import threading
+    defaults = (_lib.options.persist, _lib.options.defer, _lib.options.attn_split)
+    for b_leaves_first in (False, True):
+        a_in, b_in, a_out = threading.Event(), threading.Event(), threading.Event()
+        seen = {}
+
+        def a():
+            with _lib.override(attn_split=False, persist=not defaults[0]):
+                a_in.set()
+                b_in.wait(10)
+                if b_leaves_first:
+                    a_out.wait(10)
+            a_out.set()
+
+        def b():
+            a_in.wait(10)
+            with _lib.override(attn_split=False, defer=not defaults[1]):
+                b_in.set()
+                if not b_leaves_first:
+                    a_out.wait(10)
+                seen["inside"] = (_lib.options.attn_split, _lib.options.defer)
+            if b_leaves_first:
+                seen["a_still_in"] = (_lib.options.attn_split, _lib.options.persist)
+                a_out.set()
+
+        ts = [threading.Thread(target=f) for f in (a, b)]
+        [t.start() for t in ts]; [t.join(20) for t in ts]
+        assert seen["inside"] == (False, not defaults[1])
+        if b_leaves_first:                     # A's block is still open: its values hold
+            assert seen["a_still_in"] == (False, not defaults[0])
+        assert (_lib.options.persist, _lib.options.defer, _lib.options.attn_split) == defaults, b_leaves_first

@@ -1,7 +1,8 @@
-"""GPU: size-independent properties at BASELINE.json's full sizes, where the CPU oracle is too slow to be the
-checker: batch-independence in eval mode, run-to-run bitwise determinism of the training step, conservation
-properties of the attention weights and of the losses, the T=3000 long-audio configuration (C4) and the
-N=5 z-samples-per-clip inference twin (C5)."""
+"""GPU: BASELINE.json's full sizes.  Properties that need no oracle (batch-independence in eval mode, run-to-run bitwise
+determinism of the training step, conservation properties of the attention weights and of the losses, the T=3000
+long-audio configuration (C4), the N=5 z-samples-per-clip inference twin (C5)), and one oracle step per shape for the loss
+triplet, the greedy tokens and the global gradient norm.  Every parameter gradient against the oracle at these shapes:
+test_fullsize_grads_gpu.py."""
 import random
 
 import numpy as np
