@@ -391,6 +391,22 @@ def sample_next_word(logits, method="greedy", temp=1, noise=None):
     return w_t.view(-1).detach().long(), logprobs.gather(1, w_t).squeeze(1), noise
 
 
+def decision_margin(logits, method="greedy", temp=1, noise=None):
+    """How far each row's sample_next_word decision is from changing (a test's guard for token-exact comparisons; it
+    draws nothing): best minus second-best score for greedy (log-probabilities) and gumbel ((logprobs + g) / temp), the
+    relative gap (s1 - s2) / s1 of the scores exp(logprobs / temp) / q for the multinomial branch.  [N] float64."""
+    lp = torch.log_softmax(logits.double(), dim=1)
+    if method == "greedy":
+        sc = lp
+    elif method == "gumbel":
+        sc = (lp + noise.double()) / temp
+    else:
+        sc = torch.exp(lp / temp) / noise.double()
+    top = sc.topk(2, dim=1).values
+    gap = top[:, 0] - top[:, 1]
+    return gap if method in ("greedy", "gumbel") else gap / top[:, 0]
+
+
 def _embed_size(state):
     """embed_size of the decoder / prior (models/vae_model.py:676: mean_log_out = Linear(E, 2E)); with projected pretrained
     embeddings (Sequential(Embedding, Linear)) the Embedding's width is NOT it, and the GRU's hidden size need not be."""
@@ -402,7 +418,8 @@ def hybrid_forward(state, feats, feat_lens, caps=None, cap_lens=None, *, ss_rati
                    mutate_lens=True, dec_dropout=0.0):
     """4-input form = train_forward, 2-input form = inference_forward(greedy).
     `noise` (optional): dict(dropout=[masks...], eps_q=[N,Tc,E], eps_p=[Tc,N,E]) to replay; else drawn
-    from torch's CPU generator in the reference's call order.  `record` receives the drawn noise."""
+    from torch's CPU generator in the reference's call order.  `record` receives the drawn noise and, at inference, the
+    margin of every token decision: record["margins"] [N, steps] (see decision_margin; +inf once a row has finished)."""
     masks = list(noise["dropout"]) if noise is not None and "dropout" in noise else None
     rec_masks: List[torch.Tensor] = []
     relu_probe = [] if record is not None else None
@@ -425,6 +442,7 @@ def hybrid_forward(state, feats, feat_lens, caps=None, cap_lens=None, *, ss_rati
     seqs = torch.full((N, steps), END_IDX, dtype=torch.long)                  # prepare_output :762-790
     logits, outputs, slp, attw = [], [], [], []
     p_means, p_logs, p_z, eps_p, sample_noise, dec_keep = [], [], [], [], [], []
+    margins = []
     h = mem.new_zeros(N, H)
     hc = (mem.new_zeros(N, E), mem.new_zeros(N, E))                           # PriorRNN.init_hidden :240-245
     last_z = mem.new_zeros(N, E)
@@ -452,6 +470,9 @@ def hybrid_forward(state, feats, feat_lens, caps=None, cap_lens=None, *, ss_rati
         w_t, lp, sn_used = sample_next_word(d["logits"], method, temp, sn)     # word_model.py:173-207
         if sn_used is not None:
             sample_noise.append(sn_used)
+        if record is not None and not train:
+            mg = decision_margin(d["logits"], method, temp, sn_used)
+            margins.append(mg if unfinished is None else torch.where(unfinished, mg, torch.full_like(mg, math.inf)))
         seqs[:, t] = w_t
         logits.append(d["logits"]); outputs.append(d["output"]); slp.append(lp); attw.append(d["weights"])
         p_means.append(pr["mean"]); p_logs.append(pr["log"]); p_z.append(pr["z"])
@@ -482,15 +503,19 @@ def hybrid_forward(state, feats, feat_lens, caps=None, cap_lens=None, *, ss_rati
         record["relu_z"] = relu_probe
         record["dec_keep"] = torch.stack(dec_keep, 0) if dec_keep else None
         record["sample_noise"] = torch.stack(sample_noise, 0) if sample_noise else None
+        if not train:
+            record["margins"] = torch.stack(margins, 1)
     return out
 
 
 # ----------------------------------------------------------------------------
 # N1  Hybrid_VAEModel.beam_search   models/vae_model.py:896-995 (validation, beam_size=3)
 # ----------------------------------------------------------------------------
-def beam_search(state, feats, feat_lens, beam_size=3, max_length=MAX_LENGTH, eps=None):
+def beam_search(state, feats, feat_lens, beam_size=3, max_length=MAX_LENGTH, eps=None, record=None):
     """Instance-by-instance beam search; returns seqs i64 [N,max_length] (beam 0 of each clip; `done_beams` is
-    never filled in the reference, :986-995).  eps (optional): [N, max_length, beam, E] replay of the randn draws."""
+    never filled in the reference, :986-995).  eps (optional): [N, max_length, beam, E] replay of the randn draws.
+    record (optional dict): record["margins"][i] lists clip i's decision margins - the k-th minus the (k+1)-th flat
+    score of every step (which beams survive) and the top-1 minus top-2 flat score of the last step (which is beam 0)."""
     enc = cnn10_forward(state, feats, feat_lens, training=False)
     if "ln.weight" in state:
         enc["audio_embeds"] = F.linear(enc["audio_embeds"], state["ln.weight"], state["ln.bias"])
@@ -500,6 +525,8 @@ def beam_search(state, feats, feat_lens, beam_size=3, max_length=MAX_LENGTH, eps
     H = state["decoder.model.weight_hh_l0"].shape[1]
     V = state["decoder.classifier.weight"].shape[0]
     seqs_out = torch.full((N, max_length), END_IDX, dtype=torch.long)
+    if record is not None:
+        record["margins"] = [[] for _ in range(N)]
     for i in range(N):
         mem = mem_all[i].unsqueeze(0).repeat(beam_size, 1, 1)
         lens = lens_all[i].repeat(beam_size)
@@ -518,6 +545,8 @@ def beam_search(state, feats, feat_lens, beam_size=3, max_length=MAX_LENGTH, eps
             d = decoder_step(state, w.unsqueeze(1), h, mem, lens, pr["z"])
             logprobs = torch.log_softmax(d["logits"], dim=1)
             logprobs = top_k_logprobs.unsqueeze(1).expand_as(logprobs) + logprobs
+            if record is not None:
+                record["margins"][i].extend(_topk_margins(logprobs.view(-1), beam_size, t == max_length - 1))
             top_k_logprobs, top_k_words = logprobs.view(-1).topk(beam_size, 0, True, True)
             prev = torch.div(top_k_words, V, rounding_mode="trunc")
             next_w = top_k_words % V
@@ -527,17 +556,31 @@ def beam_search(state, feats, feat_lens, beam_size=3, max_length=MAX_LENGTH, eps
     return seqs_out
 
 
+def _topk_margins(flat, k, last):
+    """Margins of a flat top-k decision: the k-th minus the (k+1)-th score (set membership) and, when `last`, the
+    first minus the second (which candidate is beam 0).  Python floats in float64."""
+    if flat.numel() <= k:
+        return [math.inf]
+    top = flat.double().topk(k + 1).values
+    out = [float(top[k - 1] - top[k])]
+    if last:
+        out.append(float(top[0] - top[1]))
+    return out
+
+
 # ----------------------------------------------------------------------------
 # N3  CaptionModel.diverse_beam_search   models/word_model.py:297-394 with the Hybrid_VAEModel hooks
 #     (prepare_dbs_decoder_input / dbs_step / dbs_process_step, models/vae_model.py:997-1040)
 # ----------------------------------------------------------------------------
 def diverse_beam_search(state, feats, feat_lens, beam_size=5, group_size=5, diversity_lambda=0.5, temperature=1.0,
-                        group_nbest=True, max_length=MAX_LENGTH):
+                        group_nbest=True, max_length=MAX_LENGTH, record=None):
     """Group g of a clip runs one step behind group g-1 (global step t = local step + g); at a local step its
     log-probabilities are lowered by lambda x (how often the earlier groups chose each word at that local step).
     Per group `bdash = beam_size // group_size` beams; finished beams are scored by logprob / length.  Returns seqs
     i64 [N, beam_size (group_nbest) or group_size, max_length], <end>-filled.  The randn draws of the prior come
-    from torch's CPU generator in call order (clip, t, group)."""
+    from torch's CPU generator in call order (clip, t, group).  record (optional dict): record["margins"][i] lists clip
+    i's decision margins - the bdash-th minus the (bdash+1)-th flat score of every group step and the gaps between
+    neighbours in the final ranking of each group's finished beams (as far as the ranking decides the output)."""
     enc = cnn10_forward(state, feats, feat_lens, training=False)
     if "ln.weight" in state:
         enc["audio_embeds"] = F.linear(enc["audio_embeds"], state["ln.weight"], state["ln.bias"])
@@ -548,6 +591,8 @@ def diverse_beam_search(state, feats, feat_lens, beam_size=5, group_size=5, dive
     V = state["decoder.classifier.weight"].shape[0]
     bdash = beam_size // group_size
     out = torch.full((N, beam_size if group_nbest else group_size, max_length), END_IDX, dtype=torch.long)
+    if record is not None:
+        record["margins"] = [[] for _ in range(N)]
     for i in range(N):
         mem = mem_all[i].unsqueeze(0).repeat(bdash, 1, 1)
         lens = lens_all[i].repeat(bdash)
@@ -580,6 +625,8 @@ def diverse_beam_search(state, feats, feat_lens, beam_size=5, group_size=5, dive
                     lp = lp - counts.unsqueeze(0) * diversity_lambda
                 lp = score[g].unsqueeze(1) + lp
                 flat = lp[0] if lt == 0 else lp.reshape(-1)
+                if record is not None:
+                    record["margins"][i].extend(_topk_margins(flat, bdash, False))
                 top, words = flat.topk(bdash, 0, True, True)
                 score[g] = top
                 parent = torch.div(words, V, rounding_mode="floor")
@@ -593,7 +640,12 @@ def diverse_beam_search(state, feats, feat_lens, beam_size=5, group_size=5, dive
                         done[g].append({"seq": seq[g][b].clone(), "score": score[g][b].item() / (lt + 1)})
                 score[g][ended] -= 1000
                 carry[g] = (d["state"], pr["hiddens_state"], pr["z"], nxt, parent)
-        done = [sorted(d_, key=lambda x: -x["score"])[:bdash] for d_ in done]
+        done = [sorted(d_, key=lambda x: -x["score"]) for d_ in done]
+        if record is not None:
+            for d_ in done:                    # the first bdash entries and their order (group_nbest) / the first one
+                keep = min(len(d_), bdash + 1 if group_nbest else 2)
+                record["margins"][i].extend(d_[j]["score"] - d_[j + 1]["score"] for j in range(keep - 1))
+        done = [d_[:bdash] for d_ in done]
         chosen = sum(done, []) if group_nbest else [d_[0] for d_ in done]
         for r, beam in enumerate(chosen):
             out[i, r, :len(beam["seq"])] = beam["seq"]

@@ -325,15 +325,22 @@ def test_g9_beam_search_token_exact():
 def test_beam_search_call_equals_the_step_api_loop():
     """The one-call beam search against the reference's loop written with the sub-module step API (PriorRNN.forward /
     decoder.forward per step, state and history re-gathered by prev_word_inds every step, vae_model.py:905-921,961-979)
-    on a ragged batch: same tokens and the same attention-weight history, bit for bit."""
+    on a ragged batch: same tokens and the same attention-weight history, bit for bit.  Also at full size (V=5000, beam 5 on
+    9 clips: R = 45 rows, past the skinny GEMMs' 32-row tile and with top-k over 25 000 scores per clip), which ties the
+    one-call search to the step API that tests/test_fullsize_decode_gpu.py checks against the oracle."""
+    _beam_call_vs_step_loop(V=300, beam=3, ml=12, feat_lens=[160, 150, 97, 64, 33], seed=3)
+    _beam_call_vs_step_loop(V=5000, beam=5, ml=20, feat_lens=[160, 160, 150, 131, 97, 97, 64, 48, 33], seed=4)
+
+
+def _beam_call_vs_step_loop(V, beam, ml, feat_lens, seed):
     from acvae_amd import _lib
-    V, E, beam, ml = 300, 512, 3, 12
-    torch.manual_seed(3)
+    E = 512
+    torch.manual_seed(seed)
     model = build_model(V, E)
     model.eval()
-    feats = torch.randn(5, 160, 64)
-    feat_lens = np.array([160, 150, 97, 64, 33])
-    eps = torch.randn(5, ml, beam, E)
+    feats = torch.randn(len(feat_lens), max(feat_lens), 64)
+    feat_lens = np.array(feat_lens)
+    eps = torch.randn(len(feat_lens), ml, beam, E)
     with torch.no_grad():
         enc = model.encoder(feats.cuda(), feat_lens.copy())
         model.noise = dict(eps_beam=eps)
