@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "common.h"
 #include "job_table.h"
+#include "bn_bwd.h"
 
 struct DropoutSpec {
   float p;              // drop probability; 0 disables
@@ -98,10 +99,12 @@ int conv1_first_blocks(int N, int T);
 template <class TY>
 int conv1_first_fwd(const float* x, const float* scale0, const float* shift0, const float* W1, TY* Y,
                     float* partials, int N, int T, int F, hipStream_t st);
+// bn != nullptr (fp32 only): dY is the upstream gradient of the BatchNorm + ReLU after the conv, whose backward apply the
+// kernel performs on the fly (its sums must be in bn->sum_g / sum_gy: bn_bwd_sums)
 template <class TY>
 int conv1_first_bwd(const float* x, const float* scale0, const float* shift0, const float* mean0, const float* invstd0,
                     const float* W1, const TY* dY, float* dw_part, float* bn_part, float* dW1, float* dgamma0,
-                    float* dbeta0, double* dpart, int N, int T, int F, hipStream_t st);
+                    float* dbeta0, double* dpart, int N, int T, int F, hipStream_t st, const BnBwdApply* bn = nullptr);
 // pool: 2x2 average pool after BN+ReLU (ConvBlock pool_size (2,2)); !pool: pool_size (1,1) (Cnn14's last block)
 template <class T>
 int bn_relu_pool(const T* Y, const float* scale, const float* shift, T* P, int N, int H, int W, int C,
@@ -113,6 +116,12 @@ template <class T>
 int bn_bwd(const T* Y, const T* dO, int upstream, const float* scale, const float* shift, const float* mean,
            const float* invstd, float* partials, float* sum_g, float* sum_gy, T* dY, double* dpart, int N, int H,
            int W, int C, DropoutSpec drop, hipStream_t st, bool batch_stats = true, int ready_rows = 0);
+// bn_bwd's first part alone (the reduction and its column sums into sum_g / sum_gy), for a consumer that applies the rest to
+// its operand itself (conv1_first_bwd with a BnBwdApply)
+template <class T>
+int bn_bwd_sums(const T* Y, const T* dO, int upstream, const float* scale, const float* shift, const float* mean,
+                const float* invstd, float* partials, float* sum_g, float* sum_gy, double* dpart, int N, int H, int W, int C,
+                DropoutSpec drop, hipStream_t st, int ready_rows = 0);
 template <class T>
 int relu_mask(const T* Y, const float* scale, const float* shift, uint8_t* out, int N, int H, int W, int C, hipStream_t st);
 template <class T>

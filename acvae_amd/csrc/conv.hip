@@ -854,8 +854,10 @@ __global__ __launch_bounds__(256) void conv1_first_fwd_kernel(const float* __res
 // Backward of the first conv: dW1 partials [blocks][64*9] and bn0 grad partials [blocks][2][64]
 // (sum over pixels of dxin and dxin*xhat per mel bin), dxin[q] = sum_tap D[q - tap][tap],
 // D[p][tap] = sum_co dY[p][co] * W1[co][tap].
-template <class TY>
-__global__ __launch_bounds__(256) void conv1_first_bwd_kernel(const float* __restrict__ x,
+// BN: dY is the upstream gradient of the BatchNorm + ReLU that follows the conv (bn1), and the conv's output gradient is that
+// backward's apply, dZ(bn.Y, dY), computed here as the pixels are gathered instead of in a pass of its own; 0 outside the image.
+template <class TY, bool BN>
+__global__ __launch_bounds__(256, 3) void conv1_first_bwd_kernel(const float* __restrict__ x,
                                                               const float* __restrict__ scale0,
                                                               const float* __restrict__ shift0,
                                                               const float* __restrict__ mean0,
@@ -863,7 +865,8 @@ __global__ __launch_bounds__(256) void conv1_first_bwd_kernel(const float* __res
                                                               const float* __restrict__ W1,
                                                               const TY* __restrict__ dY,
                                                               float* __restrict__ dw_part, float* __restrict__ bn_part,
-                                                              int T, int F) {
+                                                              int T, int F, BnBwdApply bn) {
+  static_assert(!BN || std::is_same<TY, float>::value, "the fused BatchNorm backward is an fp32 operand");
   __shared__ float wl[64 * 9];
   __shared__ float patch[(C1_RB + 2) * 66];
   // D (13.5 KB) is dead once the input gradient has been gathered from it; the weight-gradient partials then reuse the
@@ -872,6 +875,9 @@ __global__ __launch_bounds__(256) void conv1_first_bwd_kernel(const float* __res
   __shared__ float scratch[D_FLOATS > WACC_FLOATS ? D_FLOATS : WACC_FLOATS];
   float* D = scratch;
   float (*wacc)[576] = reinterpret_cast<float (*)[576]>(scratch);
+  // BN: the constants of bn1's backward per channel quad, read from here as each pixel's operand is formed (in registers
+  // they would take the kernel from 3 to 2 waves per SIMD)
+  __shared__ BnBwdQuad bnk[BN ? 16 : 1];
   const int nblk_t = (T + C1_RB - 1) / C1_RB;
   const int n = blockIdx.x / nblk_t, t0 = (blockIdx.x % nblk_t) * C1_RB;
   for (int i = threadIdx.x; i < 64 * 9; i += 256) wl[i] = W1[i];
@@ -882,6 +888,8 @@ __global__ __launch_bounds__(256) void conv1_first_bwd_kernel(const float* __res
     if (t >= 0 && t < T && w >= 0 && w < F) v = x[((long)n * T + t) * F + w] * scale0[w] + shift0[w];
     patch[i] = v;
   }
+  if (BN && threadIdx.x < 16)
+    bnk[threadIdx.x] = bn_bwd_quad(bn.scale, bn.shift, bn.mean, bn.invstd, bn.sum_g, bn.sum_gy, threadIdx.x * 4, bn.invn);
   __syncthreads();
   const int cq = threadIdx.x & 15, pp = threadIdx.x >> 4;
   float wreg[4][9];
@@ -898,20 +906,34 @@ __global__ __launch_bounds__(256) void conv1_first_bwd_kernel(const float* __res
   // lane and pixel): the loads of the next four pixels are in flight while these four are reduced.
   constexpr int C1_IT = (C1_RB + 2) * 64 / 16, C1_UN = 4;
   static_assert(C1_IT % C1_UN == 0, "pixel loop is unrolled by four");
-  auto fetch = [&](int it, float4& g) {
+  // (BN: the raw pair of a pixel lives from its load to the end of the iteration in front of its use, where it becomes dZ)
+  auto inimg_at = [&](int it) {
+    const int pix = pp + it * 16;
+    const int t = t0 + (pix >> 6) - 1;
+    return t >= 0 && t < T && (pix & 63) < F;
+  };
+  auto fetch = [&](int it, float4& g, float4& y) {
     const int pix = pp + it * 16;
     const int r = pix >> 6, w = pix & 63;
     const int t = t0 + r - 1;
-    g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (t >= 0 && t < T && w < F) g = load4(dY + (((long)n * T + t) * F + w) * 64 + cq * 4);
+    g = y = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (inimg_at(it)) {
+      const long o = (((long)n * T + t) * F + w) * 64 + cq * 4;
+      g = load4(dY + o);
+      if (BN) y = load4(bn.Y + o);
+    }
   };
-  float4 gq[C1_UN], gn[C1_UN];
+  auto operand = [&](int it, float4 g, float4 y) { return BN && inimg_at(it) ? bn_bwd_dz(y, g, bnk[cq]) : g; };
+  float4 gq[C1_UN], gn[C1_UN], yn[C1_UN];
 #pragma unroll
-  for (int u = 0; u < C1_UN; ++u) fetch(u, gq[u]);
+  for (int u = 0; u < C1_UN; ++u) {
+    fetch(u, gn[u], yn[u]);
+    gq[u] = operand(u, gn[u], yn[u]);
+  }
   for (int it0 = 0; it0 < C1_IT; it0 += C1_UN) {
     if (it0 + C1_UN < C1_IT) {
 #pragma unroll
-      for (int u = 0; u < C1_UN; ++u) fetch(it0 + C1_UN + u, gn[u]);
+      for (int u = 0; u < C1_UN; ++u) fetch(it0 + C1_UN + u, gn[u], yn[u]);
     }
 #pragma unroll
     for (int u = 0; u < C1_UN; ++u) {
@@ -940,7 +962,7 @@ __global__ __launch_bounds__(256) void conv1_first_bwd_kernel(const float* __res
       }
     }
 #pragma unroll
-    for (int u = 0; u < C1_UN; ++u) gq[u] = gn[u];
+    for (int u = 0; u < C1_UN; ++u) gq[u] = operand(it0 + C1_UN + u, gn[u], yn[u]);
   }
   __syncthreads();   // D complete
   // dxin for own pixels and the per-mel reductions
@@ -1179,21 +1201,8 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ Y, const T* __restrict
     const int w = (int)(p % W);
     const long t = p / W;
     const int h = (int)(t % H), n = (int)(t / H);
-    const float4 sc = *reinterpret_cast<const float4*>(scale + c), sh = *reinterpret_cast<const float4*>(shift + c);
-    const float4 mu = *reinterpret_cast<const float4*>(mean + c), is = *reinterpret_cast<const float4*>(invstd + c);
-    const float4 sg = *reinterpret_cast<const float4*>(sum_g + c), sgy = *reinterpret_cast<const float4*>(sum_gy + c);
-    const float4 y = load4(Y + 4 * i);
-    float4 g = upstream4<UP>(dO, drop, n, h, w, c, H, W, C);
-    if (y.x * sc.x + sh.x <= 0.f) g.x = 0.f;
-    if (y.y * sc.y + sh.y <= 0.f) g.y = 0.f;
-    if (y.z * sc.z + sh.z <= 0.f) g.z = 0.f;
-    if (y.w * sc.w + sh.w <= 0.f) g.w = 0.f;
-    float4 o;
-    o.x = sc.x * (g.x - sg.x * invn - ((y.x - mu.x) * is.x) * (sgy.x * invn));
-    o.y = sc.y * (g.y - sg.y * invn - ((y.y - mu.y) * is.y) * (sgy.y * invn));
-    o.z = sc.z * (g.z - sg.z * invn - ((y.z - mu.z) * is.z) * (sgy.z * invn));
-    o.w = sc.w * (g.w - sg.w * invn - ((y.w - mu.w) * is.w) * (sgy.w * invn));
-    store4(dYout + 4 * i, o);
+    const BnBwdQuad k = bn_bwd_quad(scale, shift, mean, invstd, sum_g, sum_gy, c, invn);
+    store4(dYout + 4 * i, bn_bwd_dz(load4(Y + 4 * i), upstream4<UP>(dO, drop, n, h, w, c, H, W, C), k));
   }
 }
 
@@ -1212,24 +1221,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_plain_kernel(const T* __rest
                                                                  const float* __restrict__ sum_g, const float* __restrict__ sum_gy,
                                                                  T* __restrict__ dYout, long total, int C4, float invn) {
   const long tid = blockIdx.x * 256L + threadIdx.x, stride = gridDim.x * 256L;       // stride % C4 == 0 (launcher)
-  const int c = (int)(tid % C4) * 4;
-  const float4 sc = *reinterpret_cast<const float4*>(scale + c), sh = *reinterpret_cast<const float4*>(shift + c);
-  const float4 mu = *reinterpret_cast<const float4*>(mean + c), is = *reinterpret_cast<const float4*>(invstd + c);
-  float4 a = *reinterpret_cast<const float4*>(sum_g + c), b = *reinterpret_cast<const float4*>(sum_gy + c);
-  a.x *= invn; a.y *= invn; a.z *= invn; a.w *= invn;
-  b.x *= invn; b.y *= invn; b.z *= invn; b.w *= invn;
-  auto one = [&](float4 y, float4 g) {
-    if (y.x * sc.x + sh.x <= 0.f) g.x = 0.f;
-    if (y.y * sc.y + sh.y <= 0.f) g.y = 0.f;
-    if (y.z * sc.z + sh.z <= 0.f) g.z = 0.f;
-    if (y.w * sc.w + sh.w <= 0.f) g.w = 0.f;
-    float4 o;
-    o.x = sc.x * (g.x - a.x - ((y.x - mu.x) * is.x) * b.x);
-    o.y = sc.y * (g.y - a.y - ((y.y - mu.y) * is.y) * b.y);
-    o.z = sc.z * (g.z - a.z - ((y.z - mu.z) * is.z) * b.z);
-    o.w = sc.w * (g.w - a.w - ((y.w - mu.w) * is.w) * b.w);
-    return o;
-  };
+  const BnBwdQuad k = bn_bwd_quad(scale, shift, mean, invstd, sum_g, sum_gy, (int)(tid % C4) * 4, invn);
+  auto one = [&](float4 y, float4 g) { return bn_bwd_dz(y, g, k); };
   long i = tid;
   for (; i + stride < total; i += 2 * stride) {
     const float4 y0 = load4(Y + 4 * i), g0 = load4(dO + 4 * i);
@@ -1274,11 +1267,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const T* __restr
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     const PoolIdx q = pool_idx(i, C4, Wc, Hc);
     const int c = q.c4 * 4;
-    const float4 sc = *reinterpret_cast<const float4*>(scale + c), sh = *reinterpret_cast<const float4*>(shift + c);
-    const float4 mu = *reinterpret_cast<const float4*>(mean + c), is = *reinterpret_cast<const float4*>(invstd + c);
-    float4 a = *reinterpret_cast<const float4*>(sum_g + c), b = *reinterpret_cast<const float4*>(sum_gy + c);
-    a.x *= invn; a.y *= invn; a.z *= invn; a.w *= invn;
-    b.x *= invn; b.y *= invn; b.z *= invn; b.w *= invn;
+    const BnBwdQuad kq = bn_bwd_quad(scale, shift, mean, invstd, sum_g, sum_gy, c, invn);
     const long base = (((long)q.n * H + 2 * q.ho) * W + 2 * q.wo) * C + c;
     const bool hx = 2 * q.ho + 1 < H, wx = 2 * q.wo + 1 < W;
     const long off[4] = {0, (long)C, (long)W * C, (long)W * C + C};
@@ -1288,20 +1277,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_kernel(const T* __restr
     for (int k = 0; k < 4; ++k) y[k] = ok[k] ? load4(Y + base + off[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 gp = pool_upstream(dO, drop, q, Ho, Wo, C);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (!ok[k]) continue;
-      float4 g = gp;
-      if (y[k].x * sc.x + sh.x <= 0.f) g.x = 0.f;
-      if (y[k].y * sc.y + sh.y <= 0.f) g.y = 0.f;
-      if (y[k].z * sc.z + sh.z <= 0.f) g.z = 0.f;
-      if (y[k].w * sc.w + sh.w <= 0.f) g.w = 0.f;
-      float4 o;
-      o.x = sc.x * (g.x - a.x - ((y[k].x - mu.x) * is.x) * b.x);
-      o.y = sc.y * (g.y - a.y - ((y[k].y - mu.y) * is.y) * b.y);
-      o.z = sc.z * (g.z - a.z - ((y[k].z - mu.z) * is.z) * b.z);
-      o.w = sc.w * (g.w - a.w - ((y[k].w - mu.w) * is.w) * b.w);
-      store4(dYout + base + off[k], o);
-    }
+    for (int k = 0; k < 4; ++k)
+      if (ok[k]) store4(dYout + base + off[k], bn_bwd_dz(y[k], gp, kq));
   }
 }
 // partials [blocks][2][C] as bn_bwd_reduce_kernel; a block owns `win_per_block` FULL windows (partial ones carry no gradient)
@@ -1651,18 +1628,25 @@ template int conv1_first_fwd<bf16_t>(const float*, const float*, const float*, c
 template <class TY>
 int conv1_first_bwd(const float* x, const float* scale0, const float* shift0, const float* mean0, const float* invstd0,
                     const float* W1, const TY* dY, float* dw_part, float* bn_part, float* dW1, float* dgamma0,
-                    float* dbeta0, double* dpart, int N, int T, int F, hipStream_t st) {
+                    float* dbeta0, double* dpart, int N, int T, int F, hipStream_t st, const BnBwdApply* bn) {
   if (F != 64) return ACVAE_EUNSUPPORTED;
   const int nb = conv1_first_blocks(N, T);
-  hipLaunchKernelGGL(conv1_first_bwd_kernel<TY>, dim3(nb), dim3(256), 0, st, x, scale0, shift0, mean0, invstd0, W1, dY,
-                     dw_part, bn_part, T, F);
+  if (bn) {
+    if (!std::is_same<TY, float>::value) return ACVAE_EUNSUPPORTED;
+    hipLaunchKernelGGL((conv1_first_bwd_kernel<float, true>), dim3(nb), dim3(256), 0, st, x, scale0, shift0, mean0, invstd0, W1,
+                       (const float*)dY, dw_part, bn_part, T, F, *bn);
+  } else {
+    hipLaunchKernelGGL((conv1_first_bwd_kernel<TY, false>), dim3(nb), dim3(256), 0, st, x, scale0, shift0, mean0, invstd0, W1, dY,
+                       dw_part, bn_part, T, F, BnBwdApply{});
+  }
+  ACVAE_LAUNCH_CHECK();
   ACVAE_TRY(colsum2(dw_part, nb, 576, dpart, dW1, nullptr, 0, st));
   // bn0: y = xhat*gamma + beta with xin = scale0*x + shift0  ->  dbeta = sum dxin, dgamma = sum dxin*xhat
   ACVAE_TRY(colsum2(bn_part, nb, 128, dpart, dbeta0, dgamma0, 64, st));
   return ACVAE_OK;
 }
-template int conv1_first_bwd<float>(const float*, const float*, const float*, const float*, const float*, const float*, const float*, float*, float*, float*, float*, float*, double*, int, int, int, hipStream_t);
-template int conv1_first_bwd<bf16_t>(const float*, const float*, const float*, const float*, const float*, const float*, const bf16_t*, float*, float*, float*, float*, float*, double*, int, int, int, hipStream_t);
+template int conv1_first_bwd<float>(const float*, const float*, const float*, const float*, const float*, const float*, const float*, float*, float*, float*, float*, float*, double*, int, int, int, hipStream_t, const BnBwdApply*);
+template int conv1_first_bwd<bf16_t>(const float*, const float*, const float*, const float*, const float*, const float*, const bf16_t*, float*, float*, float*, float*, float*, double*, int, int, int, hipStream_t, const BnBwdApply*);
 
 template <class T>
 int bn_relu_pool(const T* Y, const float* scale, const float* shift, T* P, int N, int H, int W, int C,
@@ -1688,43 +1672,57 @@ static int bnb_pix(int C) {
   return npl * 32 < 32 ? 32 : npl * 32;
 }
 int bn_bwd_blocks(int N, int H, int W, int C) { return cdiv((long)N * H * W, bnb_pix(C)); }
+// the window-per-thread passes of UP_POOL (one dropout hash and one upstream load for four pixels)
+static bool bn_bwd_pool_path(int N, int H, int W, int C) { return (long)N * H * W * C < (1L << 31) && H >= 2 && W >= 2; }
 template <class T>
-int bn_bwd(const T* Y, const T* dO, int upstream, const float* scale, const float* shift, const float* mean,
-           const float* invstd, float* partials, float* sum_g, float* sum_gy, T* dY, double* dpart, int N, int H,
-           int W, int C, DropoutSpec drop, hipStream_t st, bool batch_stats, int ready_rows) {
+int bn_bwd_sums(const T* Y, const T* dO, int upstream, const float* scale, const float* shift, const float* mean,
+                const float* invstd, float* partials, float* sum_g, float* sum_gy, double* dpart, int N, int H, int W, int C,
+                DropoutSpec drop, hipStream_t st, int ready_rows) {
   const int Cc = C < 1024 ? C : 1024;
   if (C % 4 != 0 || 1024 % Cc != 0 || C % Cc != 0) return ACVAE_EUNSUPPORTED;
   if (ready_rows > 0 && upstream != UP_PLAIN) return ACVAE_EINVAL;
   const dim3 rgrid(bn_bwd_blocks(N, H, W, C), C / Cc);
-  const int nb = rgrid.x;
   const size_t shm = 256 * 8 * sizeof(float);
-  const long total = (long)N * H * W * (C / 4);
-#define BN_BWD_LAUNCH(UP_)                                                                                             \
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<UP_, T>), rgrid, dim3(256), shm, st, Y, dO, scale, shift, mean, invstd, partials, \
-                     N, H, W, C, bnb_pix(C), drop);                                                                       \
-  ACVAE_TRY(colsum2(partials, nb, 2 * C, dpart, sum_g, sum_gy, C, st)); /* sum_g (= dbeta) | sum_gy (= dgamma) */        \
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<UP_, T>), dim3(ew_grid(total)), dim3(256), 0, st, Y, dO, scale, shift, mean,  \
-                     invstd, sum_g, sum_gy, dY, N, H, W, C, drop, batch_stats ? 1 : 0)
-  const float invn = batch_stats ? 1.0f / (float)((long)N * H * W) : 0.f;
-  const bool small = (long)N * H * W * C < (1L << 31);
-  if (upstream == UP_POOL && small && H >= 2 && W >= 2) {
-    // a thread per pooled element: one dropout hash and one upstream load for four pixels
+  int rows = (int)rgrid.x;
+  if (ready_rows > 0) {
+    rows = ready_rows;                   // the data gradient that produced dO left its partial sums: no reduction pass
+  } else if (upstream == UP_POOL && bn_bwd_pool_path(N, H, W, C)) {
     const long wins = (long)N * (H / 2) * (W / 2);
     const int wpb = bnb_pix(C) / 4 > 0 ? bnb_pix(C) / 4 : 1;
     const dim3 pgrid((unsigned)cdiv(wins, wpb), C / Cc);            // <= nb of the layout: a window is four pixels
     hipLaunchKernelGGL((bn_bwd_reduce_pool_kernel<T>), pgrid, dim3(256), shm, st, Y, dO, scale, shift, mean, invstd, partials, N, H, W,
                        C, wpb, drop);
-    ACVAE_TRY(colsum2(partials, (int)pgrid.x, 2 * C, dpart, sum_g, sum_gy, C, st));
+    rows = (int)pgrid.x;
+  } else if (upstream == UP_POOL) {
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<UP_POOL, T>), rgrid, dim3(256), shm, st, Y, dO, scale, shift, mean, invstd, partials,
+                       N, H, W, C, bnb_pix(C), drop);
+  } else if (upstream == UP_DROP) {
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<UP_DROP, T>), rgrid, dim3(256), shm, st, Y, dO, scale, shift, mean, invstd, partials,
+                       N, H, W, C, bnb_pix(C), drop);
+  } else {
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<UP_PLAIN, T>), rgrid, dim3(256), shm, st, Y, dO, scale, shift, mean, invstd, partials,
+                       N, H, W, C, bnb_pix(C), drop);
+  }
+  ACVAE_LAUNCH_CHECK();
+  return colsum2(partials, rows, 2 * C, dpart, sum_g, sum_gy, C, st);    // sum_g (= dbeta) | sum_gy (= dgamma)
+}
+template <class T>
+int bn_bwd_apply(const T* Y, const T* dO, int upstream, const float* scale, const float* shift, const float* mean,
+                 const float* invstd, const float* sum_g, const float* sum_gy, T* dY, int N, int H, int W, int C,
+                 DropoutSpec drop, hipStream_t st, bool batch_stats) {
+  const float invn = bn_bwd_invn(N, H, W, batch_stats);
+  const long total = (long)N * H * W * (C / 4);
+  if (upstream == UP_POOL && bn_bwd_pool_path(N, H, W, C)) {
     const long totalp = (long)N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
     hipLaunchKernelGGL((bn_bwd_apply_pool_kernel<T>), dim3(ew_grid(totalp)), dim3(256), 0, st, Y, dO, scale, shift, mean, invstd,
                        sum_g, sum_gy, dY, N, H, W, C, drop, invn);
-  } else if (upstream == UP_POOL) { BN_BWD_LAUNCH(UP_POOL); }
-  else if (upstream == UP_DROP) { BN_BWD_LAUNCH(UP_DROP); }
-  else {
-    if (ready_rows <= 0)
-      hipLaunchKernelGGL((bn_bwd_reduce_kernel<UP_PLAIN, T>), rgrid, dim3(256), shm, st, Y, dO, scale, shift, mean, invstd, partials,
-                         N, H, W, C, bnb_pix(C), drop);
-    ACVAE_TRY(colsum2(partials, ready_rows > 0 ? ready_rows : nb, 2 * C, dpart, sum_g, sum_gy, C, st));
+  } else if (upstream == UP_POOL) {
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<UP_POOL, T>), dim3(ew_grid(total)), dim3(256), 0, st, Y, dO, scale, shift, mean,
+                       invstd, sum_g, sum_gy, dY, N, H, W, C, drop, batch_stats ? 1 : 0);
+  } else if (upstream == UP_DROP) {
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<UP_DROP, T>), dim3(ew_grid(total)), dim3(256), 0, st, Y, dO, scale, shift, mean,
+                       invstd, sum_g, sum_gy, dY, N, H, W, C, drop, batch_stats ? 1 : 0);
+  } else {
     // grid stride a multiple of C/4 (256 is one for C <= 1024; an even grid makes it one for C = 2048)
     int g = ew_grid((total + 1) / 2);
     if ((C / 4) > 256 && (g & 1)) ++g;
@@ -1735,10 +1733,19 @@ int bn_bwd(const T* Y, const T* dO, int upstream, const float* scale, const floa
       hipLaunchKernelGGL((bn_bwd_apply_kernel<UP_PLAIN, T>), dim3(ew_grid(total)), dim3(256), 0, st, Y, dO, scale, shift, mean,
                          invstd, sum_g, sum_gy, dY, N, H, W, C, drop, batch_stats ? 1 : 0);
   }
-#undef BN_BWD_LAUNCH
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }
+template <class T>
+int bn_bwd(const T* Y, const T* dO, int upstream, const float* scale, const float* shift, const float* mean,
+           const float* invstd, float* partials, float* sum_g, float* sum_gy, T* dY, double* dpart, int N, int H,
+           int W, int C, DropoutSpec drop, hipStream_t st, bool batch_stats, int ready_rows) {
+  ACVAE_TRY(bn_bwd_sums(Y, dO, upstream, scale, shift, mean, invstd, partials, sum_g, sum_gy, dpart, N, H, W, C, drop, st,
+                        ready_rows));
+  return bn_bwd_apply(Y, dO, upstream, scale, shift, mean, invstd, sum_g, sum_gy, dY, N, H, W, C, drop, st, batch_stats);
+}
+template int bn_bwd_sums<float>(const float*, const float*, int, const float*, const float*, const float*, const float*, float*, float*, float*, double*, int, int, int, int, DropoutSpec, hipStream_t, int);
+template int bn_bwd_sums<bf16_t>(const bf16_t*, const bf16_t*, int, const float*, const float*, const float*, const float*, float*, float*, float*, double*, int, int, int, int, DropoutSpec, hipStream_t, int);
 template int bn_bwd<float>(const float*, const float*, int, const float*, const float*, const float*, const float*, float*, float*, float*, float*, double*, int, int, int, int, DropoutSpec, hipStream_t, bool, int);
 template int bn_bwd<bf16_t>(const bf16_t*, const bf16_t*, int, const float*, const float*, const float*, const float*, float*, float*, float*, bf16_t*, double*, int, int, int, int, DropoutSpec, hipStream_t, bool, int);
 

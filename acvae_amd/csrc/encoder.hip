@@ -799,10 +799,15 @@ int encoder_bwd_t(const void* const* params, void* const* grads, const float* fe
     acvae::WinoBnReduce red{(const float*)Y1, n1.scale, n1.shift, n1.mean, n1.invstd};
     ACVAE_TRY(conv_dgrad<TA>((const TA*)dya, P(p_conv(b, 2)), wd_ready ? (TA*)(saved + L.wd2[b]) : wd, dyb, N, H, W, C, C, st, wd_ready,
                              sizeof(TA) == 4 ? &red : nullptr, bnpart, &red_rows));
-    // conv1 / bn1
+    // conv1 / bn1 (block 1, fp32: the first conv's backward applies bn1's backward to dyb as it gathers it; only the sums here)
     DropoutSpec none{0.f, nullptr, 0, 0};
-    ACVAE_TRY(acvae::bn_bwd<TA>(Y1, dyb, UP_PLAIN, n1.scale, n1.shift, n1.mean, n1.invstd, bnpart, G(p_bn(b, 1, 1)),
-                            G(p_bn(b, 1, 0)), dya, dpart, N, H, W, C, none, st, training != 0, red_rows));
+    const bool fold1 = b == 1 && sizeof(TA) == 4;
+    if (fold1)
+      ACVAE_TRY(acvae::bn_bwd_sums<TA>(Y1, dyb, UP_PLAIN, n1.scale, n1.shift, n1.mean, n1.invstd, bnpart, G(p_bn(b, 1, 1)),
+                                       G(p_bn(b, 1, 0)), dpart, N, H, W, C, none, st, red_rows));
+    else
+      ACVAE_TRY(acvae::bn_bwd<TA>(Y1, dyb, UP_PLAIN, n1.scale, n1.shift, n1.mean, n1.invstd, bnpart, G(p_bn(b, 1, 1)),
+                                  G(p_bn(b, 1, 0)), dya, dpart, N, H, W, C, none, st, training != 0, red_rows));
     if (b > 1) {
       ACVAE_TRY(conv_wgrad<TA>((const TA*)dya, (const TA*)(saved + L.p[b - 1]), nullptr, nullptr, G(p_conv(b, 1)), slab, N, H,
                                W, Cin, C, st));
@@ -813,9 +818,12 @@ int encoder_bwd_t(const void* const* params, void* const* grads, const float* fe
       TA* t = dp_cur; dp_cur = dp_nxt; dp_nxt = t;
     } else {
       BnPtrs b0 = bn_at(saved, L, 0);
-      ACVAE_TRY(acvae::conv1_first_bwd<TA>(feats, b0.scale, b0.shift, b0.mean, b0.invstd, P(p_conv(1, 1)), (const TA*)dya,
-                                       scratch + L.s_c1w, scratch + L.s_c1b, G(p_conv(1, 1)), G(p_bn0(0)), G(p_bn0(1)),
-                                       dpart, N, T, F, st));
+      const BnBwdApply a1{(const float*)Y1, n1.scale, n1.shift, n1.mean, n1.invstd, G(p_bn(1, 1, 1)), G(p_bn(1, 1, 0)),
+                          bn_bwd_invn(N, H, W, training != 0)};
+      ACVAE_TRY(acvae::conv1_first_bwd<TA>(feats, b0.scale, b0.shift, b0.mean, b0.invstd, P(p_conv(1, 1)),
+                                           fold1 ? (const TA*)dyb : (const TA*)dya, scratch + L.s_c1w, scratch + L.s_c1b,
+                                           G(p_conv(1, 1)), G(p_bn0(0)), G(p_bn0(1)), dpart, N, T, F, st,
+                                           fold1 ? &a1 : nullptr));
     }
     if (block_done) ((void (*)(int, void*))block_done)(b, user);
   }

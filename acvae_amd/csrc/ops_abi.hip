@@ -240,6 +240,32 @@ extern "C" int acvae_conv1_first_bwd(const float* x, const float* bn0, const flo
                                 dW1, dgamma0, dbeta0, (double*)(ws + L.dpart), N, T, F, (hipStream_t)stream);
 }
 
+// the same with the backward of the BatchNorm + ReLU after the conv (bn1) folded in: dO is the gradient at bn1's ReLU output;
+// bn1's column sums run first, then the first conv's backward applies the rest to dO as it gathers it (no dY pass)
+extern "C" int acvae_conv1_first_bwd_bn(const float* x, const float* bn0, const float* W1_oihw, const float* Y1, const float* dO,
+                                        const float* bn1, float* dgamma1, float* dbeta1, float* dW1, float* dgamma0, float* dbeta0,
+                                        void* ws_v, int64_t ws_bytes, int N, int T, int F, int training, void* stream) {
+  if (N <= 0 || T <= 0 || !x || !bn0 || !W1_oihw || !Y1 || !dO || !bn1 || !dgamma1 || !dbeta1 || !dW1 || !dgamma0 || !dbeta0 ||
+      !ws_v)
+    return ACVAE_EINVAL;
+  if (F != 64) return ACVAE_EUNSUPPORTED;
+  const ConvWs L = conv_ws(N, T, F, 1, 64);
+  const long bnpart = al64((long)acvae::bn_bwd_blocks(N, T, F, 64) * 2 * 64);      // bn1's partial sums, behind the conv's part
+  if (ws_bytes < (L.total + bnpart) * 4) return ACVAE_EWORKSPACE;
+  if (!aligned16(ws_v)) return ACVAE_EALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = (float*)ws_v;
+  double* dpart = (double*)(ws + L.dpart);
+  const long nb = acvae::conv1_first_blocks(N, T);
+  DropoutSpec none{0.f, nullptr, 0, 0};
+  ACVAE_TRY(acvae::colsum_tickets_reset(dpart, st));
+  ACVAE_TRY(acvae::bn_bwd_sums(Y1, dO, UP_PLAIN, bn1, bn1 + 64, bn1 + 128, bn1 + 192, ws + L.total, dbeta1, dgamma1, dpart, N, T,
+                               F, 64, none, st));
+  const BnBwdApply a1{Y1, bn1, bn1 + 64, bn1 + 128, bn1 + 192, dbeta1, dgamma1, bn_bwd_invn(N, T, F, training != 0)};
+  return acvae::conv1_first_bwd(x, bn0, bn0 + 64, bn0 + 128, bn0 + 192, W1_oihw, dO, ws + L.slab, ws + L.slab + nb * 576, dW1,
+                                dgamma0, dbeta0, dpart, N, T, F, st, &a1);
+}
+
 // ------------------------------------------------------------------------------------------ BatchNorm pieces
 extern "C" int64_t acvae_bn_workspace_bytes(int N, int H, int W, int C) {
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return -1;

@@ -323,6 +323,14 @@ int acvae_conv3x3_wgrad(const float* dY, const float* X, const float* in_scale, 
                         void* ws, int64_t ws_bytes, int N, int H, int W, int Cin, int Cout, void* stream);
 int acvae_conv1_first_bwd(const float* x, const float* bn0, const float* W1_oihw, const float* dY, float* dW1,
                           float* dgamma0, float* dbeta0, void* ws, int64_t ws_bytes, int N, int T, int F, void* stream);
+/* acvae_conv1_first_bwd with the backward of the BatchNorm + ReLU that follows the first convolution (bn1) folded in:
+ * dO [N,T,64,64] is the gradient at bn1's ReLU output, Y1 the convolution's output, bn1 = [4][64] its bn_out.  Returns
+ * bn1's dgamma1 / dbeta1 and the outputs acvae_conv1_first_bwd gives for the dY of acvae_bn_relu_bwd (upstream 0, same
+ * training flag), bit for bit, without writing that dY.  The workspace must cover acvae_conv3x3_workspace_bytes(N, T, F, 1,
+ * 64) + acvae_bn_workspace_bytes(N, T, F, 64). */
+int acvae_conv1_first_bwd_bn(const float* x, const float* bn0, const float* W1_oihw, const float* Y1, const float* dO,
+                             const float* bn1, float* dgamma1, float* dbeta1, float* dW1, float* dgamma0, float* dbeta0,
+                             void* ws, int64_t ws_bytes, int N, int T, int F, int training, void* stream);
 /* Winograd F(2x2,3x3) forms of the forward convolution and the data gradient (conv_wino.hip): same contracts, fp32
  * throughout, 2.25x fewer matrix-pipe flops; results differ from the implicit-GEMM forms by fp32 rounding only.
  * W a power of two in 4..64, Cin % 16 == 0, Cout % 64 == 0 (dgrad: the roles of Cin / Cout swap), otherwise
