@@ -226,6 +226,30 @@ extern "C" int acvae_conv3x3_wgrad_bf16(const void* dY, const void* X, const flo
                               W, Cin, Cout, (hipStream_t)stream);
 }
 
+// the first convolution with a bf16 output (the bf16 encoder's conv_block1.conv1): fp32 features and weights, Y rounded to bf16
+// and this layer's BatchNorm taken from the rounded Y; in_scale / in_shift are bn0's per-MEL affine [64] as in acvae_conv3x3_fwd
+extern "C" int acvae_conv1_first_fwd_bf16(const float* x, const float* in_scale, const float* in_shift, const float* W1_oihw,
+                                          void* Y, const float* gamma, const float* beta, float* running_mean,
+                                          float* running_var, int64_t* num_batches_tracked, int training, float* bn_out,
+                                          void* ws_v, int64_t ws_bytes, int N, int T, int F, void* stream) {
+  if (!conv_dims_ok(N, T, F, 1, 64) || !x || !in_scale || !in_shift || !W1_oihw || !Y || !ws_v) return ACVAE_EINVAL;
+  if (bn_out && (!gamma || !beta || !running_mean || !running_var)) return ACVAE_EINVAL;
+  if (F != 64) return ACVAE_EUNSUPPORTED;
+  const ConvWs L = conv_ws(N, T, F, 1, 64);
+  if (ws_bytes < L.total * 4) return ACVAE_EWORKSPACE;
+  if (!aligned16(ws_v)) return ACVAE_EALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = (float*)ws_v;
+  float* partials = (bn_out && training) ? ws + L.partials : nullptr;
+  ACVAE_TRY(acvae::conv1_first_fwd(x, in_scale, in_shift, W1_oihw, (bf16_t*)Y, partials, N, T, F, st));
+  if (bn_out) ACVAE_TRY(acvae::colsum_tickets_reset((double*)(ws + L.dpart), st));
+  if (bn_out)
+    ACVAE_TRY(acvae::bn_finalize(partials, acvae::conv1_first_blocks(N, T), 64, (double)N * T * F, gamma, beta, running_mean,
+                                 running_var, num_batches_tracked, training, bn_out, bn_out + 64, bn_out + 128, bn_out + 192,
+                                 (double*)(ws + L.dpart), st));
+  return ACVAE_OK;
+}
+
 extern "C" int acvae_conv1_first_bwd(const float* x, const float* bn0, const float* W1_oihw, const float* dY, float* dW1,
                                      float* dgamma0, float* dbeta0, void* ws_v, int64_t ws_bytes, int N, int T, int F,
                                      void* stream) {
@@ -238,6 +262,22 @@ extern "C" int acvae_conv1_first_bwd(const float* x, const float* bn0, const flo
   ACVAE_TRY(acvae::colsum_tickets_reset((double*)(ws + L.dpart), (hipStream_t)stream));
   return acvae::conv1_first_bwd(x, bn0, bn0 + 64, bn0 + 128, bn0 + 192, W1_oihw, dY, ws + L.slab, ws + L.slab + nb * 576,
                                 dW1, dgamma0, dbeta0, (double*)(ws + L.dpart), N, T, F, (hipStream_t)stream);
+}
+
+// the same for a bf16 dY (the bf16 encoder's block 1: dY is the stored gradient at the first conv's output)
+extern "C" int acvae_conv1_first_bwd_bf16(const float* x, const float* bn0, const float* W1_oihw, const void* dY, float* dW1,
+                                          float* dgamma0, float* dbeta0, void* ws_v, int64_t ws_bytes, int N, int T, int F,
+                                          void* stream) {
+  if (N <= 0 || T <= 0 || !x || !bn0 || !W1_oihw || !dY || !dW1 || !dgamma0 || !dbeta0 || !ws_v) return ACVAE_EINVAL;
+  if (F != 64) return ACVAE_EUNSUPPORTED;
+  const ConvWs L = conv_ws(N, T, F, 1, 64);
+  if (ws_bytes < L.total * 4) return ACVAE_EWORKSPACE;
+  float* ws = (float*)ws_v;
+  const long nb = acvae::conv1_first_blocks(N, T);
+  ACVAE_TRY(acvae::colsum_tickets_reset((double*)(ws + L.dpart), (hipStream_t)stream));
+  return acvae::conv1_first_bwd(x, bn0, bn0 + 64, bn0 + 128, bn0 + 192, W1_oihw, (const bf16_t*)dY, ws + L.slab,
+                                ws + L.slab + nb * 576, dW1, dgamma0, dbeta0, (double*)(ws + L.dpart), N, T, F,
+                                (hipStream_t)stream);
 }
 
 // the same with the backward of the BatchNorm + ReLU after the conv (bn1) folded in: dO is the gradient at bn1's ReLU output;
@@ -312,6 +352,31 @@ extern "C" int acvae_bn_relu_bwd(const float* Y, const float* dO, int upstream, 
   // sum_g (= dbeta) and sum_gy (= dgamma) are also inputs of the apply pass: written first, then read
   return acvae::bn_bwd(Y, dO, upstream, bn, bn + C, bn + 2 * C, bn + 3 * C, ws, dbeta, dgamma, dY,
                        (double*)(ws + (part > p0 ? part : p0)), N, H, W, C, d, (hipStream_t)stream, training != 0);
+}
+
+// bf16 storage: Y / P / dO / dY bf16 NHWC, everything else as in the fp32 forms
+extern "C" int acvae_bn_relu_pool_fwd_bf16(const void* Y, const float* bn, void* P, int N, int H, int W, int C, int pool,
+                                           float p_drop, uint64_t seed, int site, const uint8_t* keep_mask, void* stream) {
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || !Y || !bn || !P) return ACVAE_EINVAL;
+  DropoutSpec d{p_drop, keep_mask, seed, (uint32_t)site};
+  return acvae::bn_relu_pool((const bf16_t*)Y, bn, bn + C, (bf16_t*)P, N, H, W, C, d, (hipStream_t)stream, pool != 0);
+}
+
+extern "C" int acvae_bn_relu_bwd_bf16(const void* Y, const void* dO, int upstream, const float* bn, float* dgamma,
+                                      float* dbeta, void* dY, void* ws_v, int64_t ws_bytes, int N, int H, int W, int C,
+                                      int training, float p_drop, uint64_t seed, int site, const uint8_t* keep_mask,
+                                      void* stream) {
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || !Y || !dO || !bn || !dgamma || !dbeta || !dY || !ws_v) return ACVAE_EINVAL;
+  if (upstream != UP_PLAIN && upstream != UP_POOL && upstream != UP_DROP) return ACVAE_EINVAL;
+  if (ws_bytes < acvae_bn_workspace_bytes(N, H, W, C)) return ACVAE_EWORKSPACE;
+  float* ws = (float*)ws_v;
+  const long part = al64((long)acvae::bn_bwd_blocks(N, H, W, C) * 2 * C);
+  const long p0 = al64((long)acvae::bn0_partials_rows((long)N * H) * 128);
+  DropoutSpec d{p_drop, keep_mask, seed, (uint32_t)site};
+  ACVAE_TRY(acvae::colsum_tickets_reset((double*)(ws + (part > p0 ? part : p0)), (hipStream_t)stream));
+  return acvae::bn_bwd((const bf16_t*)Y, (const bf16_t*)dO, upstream, bn, bn + C, bn + 2 * C, bn + 3 * C, ws, dbeta, dgamma,
+                       (bf16_t*)dY, (double*)(ws + (part > p0 ? part : p0)), N, H, W, C, d, (hipStream_t)stream,
+                       training != 0);
 }
 
 // ------------------------------------------------------------------------------------------ recurrent cells

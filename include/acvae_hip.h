@@ -366,6 +366,22 @@ int acvae_conv3x3_dgrad_bf16(const void* dY, const float* W_oihw, void* dX, void
 int acvae_conv3x3_wgrad_bf16(const void* dY, const void* X, const float* in_scale, const float* in_shift, float* dW_oihw,
                              void* ws, int64_t ws_bytes, int N, int H, int W, int Cin, int Cout, void* stream);
 int64_t acvae_bn_workspace_bytes(int N, int H, int W, int C);
+/* bf16-storage forms of the first convolution and of the BatchNorm pieces, as the bf16 encoder runs them: same contracts
+ * as the fp32 forms, Y / P / dO / dY bf16 NHWC, fp32 arithmetic inside, bf16 outputs rounded to nearest even.
+ *   acvae_conv1_first_fwd_bf16  acvae_conv3x3_fwd with Cin == 1 (x fp32 [N,T,64] features, in_scale / in_shift bn0's
+ *                       affine [64]) writing a bf16 Y; bn_out from the statistics of the ROUNDED Y.
+ *   acvae_conv1_first_bwd_bf16  acvae_conv1_first_bwd for a bf16 dY. */
+int acvae_conv1_first_fwd_bf16(const float* x, const float* in_scale, const float* in_shift, const float* W1_oihw, void* Y,
+                               const float* gamma, const float* beta, float* running_mean, float* running_var,
+                               int64_t* num_batches_tracked, int training, float* bn_out, void* ws, int64_t ws_bytes, int N,
+                               int T, int F, void* stream);
+int acvae_conv1_first_bwd_bf16(const float* x, const float* bn0, const float* W1_oihw, const void* dY, float* dW1,
+                               float* dgamma0, float* dbeta0, void* ws, int64_t ws_bytes, int N, int T, int F, void* stream);
+int acvae_bn_relu_pool_fwd_bf16(const void* Y, const float* bn, void* P, int N, int H, int W, int C, int pool, float p_drop,
+                                uint64_t seed, int site, const uint8_t* keep_mask, void* stream);
+int acvae_bn_relu_bwd_bf16(const void* Y, const void* dO, int upstream, const float* bn, float* dgamma, float* dbeta,
+                           void* dY, void* ws, int64_t ws_bytes, int N, int H, int W, int C, int training, float p_drop,
+                           uint64_t seed, int site, const uint8_t* keep_mask, void* stream);
 /* The ResNet38 kernels one by one (resnet.hip), NHWC fp32; bn* = [4][C] scale | shift | mean | invstd as above.
  *   acvae_res_join_fwd   out = relu(y2*bn2.scale + bn2.shift + (yd ? yd*bnd.scale + bnd.shift : x))   (yd == NULL: identity x)
  *   acvae_res_join_bwd   g = dO * (out > 0) -> G; dbeta2 = sum g, dgamma2 = sum g*yhat2 (and the same for bnd where yd != NULL,

@@ -215,10 +215,61 @@ def _relu_site(z, site, relu_probe, relu_force):
     return F.relu(z)
 
 
+def to_bf16(x):
+    """x rounded to bf16 (round to nearest even) through fp32, as the kernels round, kept in x's dtype."""
+    return x.float().bfloat16().to(x.dtype)
+
+
+class _Store(torch.autograd.Function):
+    """A tensor the bf16 encoder stores in bf16: rounded on the way forward, and its gradient rounded on the way back."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return to_bf16(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return to_bf16(g)
+
+
+class _WRound(torch.autograd.Function):
+    """A weight the bf16 encoder multiplies as bf16 (its repack): rounded forward, its fp32 gradient passed through."""
+
+    @staticmethod
+    def forward(ctx, w):
+        return to_bf16(w)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+def _store(x):
+    return _Store.apply(x)
+
+
+def _wround(w):
+    return _WRound.apply(w)
+
+
+def _keep(x):
+    return x
+
+
 def cnn10_forward(state, feats, feat_lens, training=True, masks=None, record=None, prefix="encoder",
-                  mutate_lens=True, relu_probe=None, relu_force=None):
+                  mutate_lens=True, relu_probe=None, relu_force=None, enc_storage="f32"):
     """models/encoder.py:672-707 (Cnn10) and :906-964 (Cnn14_16k, recognised by its conv_block6 / fc1 entries).
-    Returns dict(audio_embeds[N,S,C], audio_embeds_pooled[N,C], audio_embeds_lens i64[N], state None)."""
+    Returns dict(audio_embeds[N,S,C], audio_embeds_pooled[N,C], audio_embeds_lens i64[N], state None).
+
+    enc_storage="bf16" (test infrastructure): the arithmetic of the bf16-storage HIP encoder (ACVAE_ENC_BF16).  Its kernels
+    keep every conv output Y1 / Y2, conv2's operand relu(bn1(Y1)) and each block's output P in bf16, and the gradients of
+    those tensors too; they multiply the 3x3 weights with Cin >= 64 as bf16 and return fp32 weight gradients.  The first
+    conv (Cin = 1) multiplies fp32 weights; bn0, the head and the BatchNorm parameters and statistics stay fp32."""
+    if enc_storage not in ("f32", "bf16"):
+        raise ValueError(f"enc_storage must be 'f32' or 'bf16', not {enc_storage!r}")
+    bf16 = enc_storage == "bf16"
+    store = _store if bf16 else _keep
+    wround = _wround if bf16 else _keep
     arch = ENCODERS["Cnn14_16k" if prefix + ".fc1.weight" in state else "Cnn10"]
     nblocks = len(arch["channels"])
     x = feats.unsqueeze(1)                                     # :676
@@ -231,17 +282,18 @@ def cnn10_forward(state, feats, feat_lens, training=True, masks=None, record=Non
     x = x.transpose(1, 3)
     for b in range(1, nblocks + 1):                            # :683-690 / :928-939, ConvBlock.forward :633-649
         p = f"{prefix}.conv_block{b}"
-        x = F.conv2d(x, state[p + ".conv1.weight"], None, 1, 1)
-        x = _relu_site(_bn(state, p + ".bn1", x, training), 2 * b - 2, relu_probe, relu_force)
+        w1 = state[p + ".conv1.weight"]
+        x = store(F.conv2d(x, w1 if b == 1 else wround(w1), None, 1, 1))
+        x = store(_relu_site(_bn(state, p + ".bn1", x, training), 2 * b - 2, relu_probe, relu_force))
         _bn_track(state, p + ".bn1", training)
-        x = F.conv2d(x, state[p + ".conv2.weight"], None, 1, 1)
+        x = store(F.conv2d(x, wround(state[p + ".conv2.weight"]), None, 1, 1))
         x = _relu_site(_bn(state, p + ".bn2", x, training), 2 * b - 1, relu_probe, relu_force)
         _bn_track(state, p + ".bn2", training)
         if b < nblocks or arch["pool_last"]:
             x = F.avg_pool2d(x, kernel_size=(2, 2))
         else:
             x = F.avg_pool2d(x, kernel_size=(1, 1))            # Cnn14_16k block 6, :938
-        x = _dropout(x, 0.2, training, masks, record)
+        x = store(_dropout(x, 0.2, training, masks, record))
     x = torch.mean(x, dim=3)                                   # :691  [N,512,S]
     x1 = torch.max(x, dim=2).values                            # :693 (unmasked)
     x2 = torch.mean(x, dim=2)
@@ -415,16 +467,18 @@ def _embed_size(state):
 
 def hybrid_forward(state, feats, feat_lens, caps=None, cap_lens=None, *, ss_ratio=1.0, dis_ratio=0,
                    training=True, method="greedy", temp=1, max_length=MAX_LENGTH, noise=None, record=None,
-                   mutate_lens=True, dec_dropout=0.0):
+                   mutate_lens=True, dec_dropout=0.0, enc_storage="f32"):
     """4-input form = train_forward, 2-input form = inference_forward(greedy).
     `noise` (optional): dict(dropout=[masks...], eps_q=[N,Tc,E], eps_p=[Tc,N,E]) to replay; else drawn
     from torch's CPU generator in the reference's call order.  `record` receives the drawn noise and, at inference, the
-    margin of every token decision: record["margins"] [N, steps] (see decision_margin; +inf once a row has finished)."""
+    margin of every token decision: record["margins"] [N, steps] (see decision_margin; +inf once a row has finished).
+    `enc_storage`: the encoder's arithmetic, "f32" or "bf16" (cnn10_forward)."""
     masks = list(noise["dropout"]) if noise is not None and "dropout" in noise else None
     rec_masks: List[torch.Tensor] = []
     relu_probe = [] if record is not None else None
     enc = cnn10_forward(state, feats, feat_lens, training, masks, rec_masks, mutate_lens=mutate_lens,
-                        relu_probe=relu_probe, relu_force=None if noise is None else noise.get("relu_force"))
+                        relu_probe=relu_probe, relu_force=None if noise is None else noise.get("relu_force"),
+                        enc_storage=enc_storage)
     if "ln.weight" in state:                                                  # vae_model.py:743-744
         enc["audio_embeds"] = F.linear(enc["audio_embeds"], state["ln.weight"], state["ln.bias"])
     mem, mem_lens = enc["audio_embeds"], enc["audio_embeds_lens"]
@@ -738,9 +792,10 @@ class OracleTrainer:
     zero_grad, forward, loss, backward, clip_grad_norm_(max_grad_norm), Adam.step."""
 
     def __init__(self, state, vocab, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
-                 smoothing=0.1, kl_weight=0.5, alpha=1.0, dec_dropout=0.0):
+                 smoothing=0.1, kl_weight=0.5, alpha=1.0, dec_dropout=0.0, enc_storage="f32"):
         self.state, self.vocab = state, vocab
         self.dec_dropout = dec_dropout
+        self.enc_storage = enc_storage
         self.keys = trainable_keys(state)
         for k in self.keys:
             state[k].requires_grad_(True)
@@ -757,7 +812,7 @@ class OracleTrainer:
             st[k].grad = None
         out = hybrid_forward(st, feats, np.array(feat_lens).copy(), caps, cap_lens, ss_ratio=ss_ratio,
                              dis_ratio=dis_ratio, training=True, noise=noise, record=record,
-                             dec_dropout=self.dec_dropout)
+                             dec_dropout=self.dec_dropout, enc_storage=self.enc_storage)
         loss, ce, kl, mse = train_loss(out, caps, cap_lens, self.vocab, self.smoothing, self.kl_weight, self.alpha)
         loss.backward()
         grads = {k: st[k].grad for k in self.keys if st[k].grad is not None}

@@ -253,16 +253,22 @@ def run_conv_bf16(N, H, W, Cin, Cout, act, seed=0):
 
     y = torch.empty(N, H, W, Cout, device="cuda", dtype=torch.bfloat16)
     g_, b_ = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.2
-    rm, rv = torch.zeros(Cout, device="cuda"), torch.ones(Cout, device="cuda")
+    rm0, rv0 = torch.randn(Cout, generator=g) * 0.1, torch.rand(Cout, generator=g) + 0.5
+    rm, rv = rm0.cuda(), rv0.cuda()
+    nbt = torch.zeros((), dtype=torch.int64, device="cuda")
     bn = torch.empty(4, Cout, device="cuda")
-    _lib.call("acvae_conv3x3_fwd_bf16", xd, w.cuda(), scd, shd, y, g_.cuda(), b_.cuda(), rm, rv, None, 1, bn, ws, wsb, N, H,
+    _lib.call("acvae_conv3x3_fwd_bf16", xd, w.cuda(), scd, shd, y, g_.cuda(), b_.cuda(), rm, rv, nbt, 1, bn, ws, wsb, N, H,
               W, Cin, Cout, S())
     check_bf16(y, nhwc(y_ref), 9 * Cin, "fwd")
-    # the statistics are those of the stored (rounded) tensor
+    # the statistics are those of the stored (rounded) tensor; the running buffers take the unbiased variance
     ys = y.float().cpu().double()
     mu, var = ys.mean((0, 1, 2)), ys.var((0, 1, 2), unbiased=False)
     np.testing.assert_allclose(bn[2].cpu().double(), mu, rtol=1e-4, atol=3e-6)
     np.testing.assert_allclose(bn[3].cpu().double(), 1 / torch.sqrt(var + 1e-5), rtol=3e-5)
+    cnt = N * H * W
+    np.testing.assert_allclose(rm.cpu().double(), 0.9 * rm0.double() + 0.1 * mu, rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(rv.cpu().double(), 0.9 * rv0.double() + 0.1 * var * cnt / (cnt - 1), rtol=1e-5)
+    assert int(nbt) == 1
     dw = torch.empty(Cout, Cin, 3, 3, device="cuda")
     _lib.call("acvae_conv3x3_wgrad_bf16", dyd, xd, scd, shd, dw, ws, wsb, N, H, W, Cin, Cout, S())
     assert_every_element(dw, wd.grad, N * H * W, "wgrad " + what)
