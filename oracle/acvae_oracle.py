@@ -470,8 +470,13 @@ def hybrid_forward(state, feats, feat_lens, caps=None, cap_lens=None, *, ss_rati
                    mutate_lens=True, dec_dropout=0.0, enc_storage="f32"):
     """4-input form = train_forward, 2-input form = inference_forward(greedy).
     `noise` (optional): dict(dropout=[masks...], eps_q=[N,Tc,E], eps_p=[Tc,N,E]) to replay; else drawn
-    from torch's CPU generator in the reference's call order.  `record` receives the drawn noise and, at inference, the
-    margin of every token decision: record["margins"] [N, steps] (see decision_margin; +inf once a row has finished).
+    from torch's CPU generator in the reference's call order.  noise["fed_words"] (optional, [N, steps] long, training):
+    at a step t >= 1 whose scheduled-sampling coin says "model word", fed_words[:, t - 1] is fed instead of the oracle's
+    own seqs[:, t - 1] (another implementation's words, so that both differentiate the same graph); the coins are still
+    drawn from `random` and the oracle's own seqs are still written from its own logits.  `record` receives the drawn
+    noise and the margin of every token decision: record["margins"] [N, steps] (see decision_margin; +inf once a row has
+    finished); in training also record["ss_flags"] (the coins, True = caption word) and record["fed_words"] [N, steps],
+    the word fed at each step.
     `enc_storage`: the encoder's arithmetic, "f32" or "bf16" (cnn10_forward)."""
     masks = list(noise["dropout"]) if noise is not None and "dropout" in noise else None
     rec_masks: List[torch.Tensor] = []
@@ -497,17 +502,27 @@ def hybrid_forward(state, feats, feat_lens, caps=None, cap_lens=None, *, ss_rati
     logits, outputs, slp, attw = [], [], [], []
     p_means, p_logs, p_z, eps_p, sample_noise, dec_keep = [], [], [], [], [], []
     margins = []
+    ss_flags, fed = [], []
+    replay_words = None if noise is None else noise.get("fed_words")
     h = mem.new_zeros(N, H)
     hc = (mem.new_zeros(N, E), mem.new_zeros(N, E))                           # PriorRNN.init_hidden :240-245
     last_z = mem.new_zeros(N, E)
     unfinished = None
     for t in range(steps):
-        if train and random.random() < ss_ratio:                              # :826
+        coin = bool(train and random.random() < ss_ratio)                     # :826
+        ss_flags.append(coin)
+        if coin:
             word = caps[:, t].long()
         elif t == 0:
             word = torch.full((N,), START_IDX, dtype=torch.long)
+        elif replay_words is not None:                                        # another implementation's model words
+            word = torch.as_tensor(replay_words)[:, t - 1].long().clone()
         else:
-            word = seqs[:, t - 1]
+            # a copy, not the reference's view of seqs (:840): seqs[:, t] is written below, and autograd refuses the
+            # backward of an embedding whose index was modified in place.  Same values; the word is an integer, so
+            # the gradient is that of the loss with the fed words held constant.
+            word = seqs[:, t - 1].clone()
+        fed.append(word)
         e = None if noise is None else noise["eps_p"][t]
         pr = prior_step(state, word.unsqueeze(1), mem, hc, last_z, mem_lens, e)
         eps_p.append(pr["_eps"])
@@ -524,8 +539,8 @@ def hybrid_forward(state, feats, feat_lens, caps=None, cap_lens=None, *, ss_rati
         w_t, lp, sn_used = sample_next_word(d["logits"], method, temp, sn)     # word_model.py:173-207
         if sn_used is not None:
             sample_noise.append(sn_used)
-        if record is not None and not train:
-            mg = decision_margin(d["logits"], method, temp, sn_used)
+        if record is not None:
+            mg = decision_margin(d["logits"].detach(), method, temp, sn_used)
             margins.append(mg if unfinished is None else torch.where(unfinished, mg, torch.full_like(mg, math.inf)))
         seqs[:, t] = w_t
         logits.append(d["logits"]); outputs.append(d["output"]); slp.append(lp); attw.append(d["weights"])
@@ -557,8 +572,10 @@ def hybrid_forward(state, feats, feat_lens, caps=None, cap_lens=None, *, ss_rati
         record["relu_z"] = relu_probe
         record["dec_keep"] = torch.stack(dec_keep, 0) if dec_keep else None
         record["sample_noise"] = torch.stack(sample_noise, 0) if sample_noise else None
-        if not train:
-            record["margins"] = torch.stack(margins, 1)
+        record["margins"] = torch.stack(margins, 1)
+        if train:
+            record["ss_flags"] = ss_flags
+            record["fed_words"] = torch.stack(fed, 1)
     return out
 
 
@@ -806,12 +823,14 @@ class OracleTrainer:
         self.t = 0
 
     def step(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, noise=None, record=None,
-             apply_update=True):
+             apply_update=True, method="greedy", temp=1):
+        """`noise` / `record` go to hybrid_forward unchanged (with ss_ratio < 1: noise["fed_words"], record["ss_flags"] /
+        ["fed_words"] / ["margins"]); `method` / `temp` choose how the model's own words are drawn (sample_next_word)."""
         st = self.state
         for k in self.keys:
             st[k].grad = None
         out = hybrid_forward(st, feats, np.array(feat_lens).copy(), caps, cap_lens, ss_ratio=ss_ratio,
-                             dis_ratio=dis_ratio, training=True, noise=noise, record=record,
+                             dis_ratio=dis_ratio, training=True, method=method, temp=temp, noise=noise, record=record,
                              dec_dropout=self.dec_dropout, enc_storage=self.enc_storage)
         loss, ce, kl, mse = train_loss(out, caps, cap_lens, self.vocab, self.smoothing, self.kl_weight, self.alpha)
         loss.backward()

@@ -65,7 +65,9 @@ def main():
         if ss < 1.0:
             # The reference cannot back-propagate with ss_ratio < 1: the word fed to nn.Embedding is a
             # view of output["seqs"], which is written in place afterwards (models/vae_model.py:831,855)
-            # -> autograd "modified by an inplace operation".  Forward-only comparison for that mode.
+            # -> autograd "modified by an inplace operation".  Forward-only comparison for that mode.  (The oracle
+            # feeds a copy of that word and can: its ss_ratio < 1 gradients are pinned by tests/test_sched_sampling_cpu.py
+            # against the float64 loss's central differences instead, since the reference offers nothing to compare with.)
             torch.manual_seed(11); random.seed(11)
             with torch.no_grad():
                 rout = model(feats, feat_lens.copy(), caps, cap_lens, ss_ratio=ss, dis_ratio=dis)

@@ -1,5 +1,6 @@
-"""Comparison helpers shared by the GPU parity tests (test_model_gpu.py, test_fullsize_grads_gpu.py): element-wise closeness,
-and every parameter gradient of the HIP model against the oracle's autograd under the HIP path's own ReLU decisions."""
+"""Comparison helpers shared by the GPU parity tests (test_model_gpu.py, test_fullsize_grads_gpu.py,
+test_sched_sampling_gpu.py): element-wise closeness, every parameter gradient of the HIP model against the oracle's autograd
+under the HIP path's own ReLU decisions, and the HIP path's own words against the oracle's decisions one by one."""
 import torch
 
 
@@ -20,7 +21,7 @@ def grads_match_oracle(model, named, natural_grads, rec, oracle_grads_under, tol
     to `tol_enc` relative L2 (or the bound `tol_enc_of` gives that tensor by name), text-side tensors to 2e-3 / 2e-4 x max.
     Returns the oracle gradients that were matched."""
     def check(ref_grads):
-        worst = (0.0, None)
+        worst, worst_text = (0.0, None), (0.0, None)
         for k, ref in ref_grads.items():
             a = named[k].grad.detach().cpu().double(); b = ref.double()
             if k.startswith("encoder."):
@@ -31,7 +32,9 @@ def grads_match_oracle(model, named, natural_grads, rec, oracle_grads_under, tol
                 e = float(((a - b).abs() / lim).max())
             if e > worst[0]:
                 worst = (e, k)
-        return worst
+            if e > worst_text[0] and not k.startswith("encoder."):
+                worst_text = (e, k)
+        return worst + worst_text
     assert set(k for k, p in named.items() if p.grad is not None) == set(natural_grads)
     masks = [m.cpu() for m in model.encoder.relu_masks()]
     nflip, zmax = 0, 0.0
@@ -43,6 +46,28 @@ def grads_match_oracle(model, named, natural_grads, rec, oracle_grads_under, tol
     assert zmax < flip_zone, f"{nflip} ReLU decisions differ from the oracle, one at |z| = {zmax:.2e}"
     ref = natural_grads if nflip == 0 else oracle_grads_under({i: m for i, m in enumerate(masks)})
     w = check(ref)
-    print(f"grads_match_oracle: worst tensor {w[1]} at {w[0]:.3f} x its tolerance ({nflip} ReLU decisions differ from z > 0)")
+    print(f"grads_match_oracle: worst tensor {w[1]} at {w[0]:.3f} x its tolerance, worst text-side tensor {w[3]} at {w[2]:.3f} x "
+          f"({nflip} ReLU decisions differ from z > 0)")
     assert w[0] <= 1.0, f"{w[1]}: {w[0]:.2f} x tolerance under the HIP path's own ReLU decisions ({nflip} differ from z > 0)"
     return ref
+
+
+def words_match_by_margin(tag, hip_seqs, hip_logits, ora_out, margins, max_left_out=0.10):
+    """Token check per decision, not free-running: `ora_out` is the oracle's training forward fed the HIP path's own words
+    (noise["fed_words"]), so its logits at every (row, step) answer the same input as the HIP logits there; the HIP word must
+    equal the oracle's own decision wherever the oracle's margin (record["margins"]) exceeds 20 x the largest |logit
+    difference| of this run.  At most `max_left_out` of the decisions may fall under that threshold: a case that leaves out
+    more fails instead of passing on nothing.  Returns (share left out, threshold)."""
+    hip_seqs = torch.as_tensor(hip_seqs).cpu()
+    d = float((hip_logits.detach().cpu().double() - ora_out["logits"].detach().double()).abs().max())
+    thr = 20 * d
+    keep = margins > thr
+    share = 1.0 - float(keep.double().mean())
+    wrong = (hip_seqs != ora_out["seqs"]) & keep
+    print(f"{tag}: max |logit difference| {d:.2e}, margin threshold {thr:.2e}, {int((~keep).sum())}/{keep.numel()} decisions "
+          f"({share:.1%}) left out, smallest margin {float(margins.min()):.2e}, "
+          f"{int((hip_seqs != ora_out['seqs']).sum())} words differ in all")
+    assert share <= max_left_out, f"{tag}: {share:.1%} of the decisions are within {thr:.2e} of a tie (choose another seed)"
+    assert not bool(wrong.any()), f"{tag}: {int(wrong.sum())} words differ from the oracle's decision at margins above " \
+                                  f"{thr:.2e} (smallest such margin {float(margins[wrong].min()):.2e})"
+    return share, thr

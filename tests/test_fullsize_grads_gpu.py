@@ -8,7 +8,17 @@ The global gradient norm (test_fullsize_gpu.py) cannot stand in for the tensors:
 such as decoder.classifier.weight moves it by ~1e-5 even when its gradient is zeroed.  So each tensor is held to
 grads_match_oracle's bounds.  One oracle step per shape (module cache), several HIP launch paths per shape against it, all
 through _lib.override; the encoder is the same in every variant, so its ReLU decisions must be too, and the oracle is re-run
-under them at most once per shape."""
+under them at most once per shape.
+
+Scheduled sampling (the `ss` entry of a case, ss_ratio < 1): one false coin takes the forward off the persistent launch and
+the second stream - it goes step by step and chooses each fed word on the device - while the backward keeps its persistent,
+deferred form and scatters the embedding-table gradients to the fed words.  Free-running token equality cannot carry that
+comparison (at these sizes 2-3 % of the greedy decisions lie within 2e-4 of a tie, and one other word changes the rest of
+the clip), so the oracle is re-run ONCE per case fed the HIP default run's own words (noise["fed_words"]) and ReLU decisions
+together; loss and gradients are held against that run, and the HIP words against its decisions one by one
+(words_match_by_margin).  Every variant of a case must produce the default run's words.  Seeds: with SEED = 9 and build(5)'s
+weights the oracle alone (CPU) leaves out, at a threshold of 2e-4, 0.15 % / 0.30 % / 0.30 % / 0.14 % / 0.30 % of the
+decisions of the five ss cases below, in the order of CASES (the condition for a seed: no more than 5 %)."""
 import os
 import random
 
@@ -17,7 +27,7 @@ import torch
 
 import acvae_oracle as O
 from acvae_amd import _lib
-from parity_util import grads_match_oracle
+from parity_util import grads_match_oracle, words_match_by_margin
 from test_fullsize_gpu import C4_FEAT_LENS, L, V, build
 from test_model_gpu import hip_loss
 
@@ -34,6 +44,12 @@ CASES = {
     "B3_T1601": dict(B=3, T=1601),                            # S = 100, rc_splits = 2
     "B33_T403": dict(B=33, T=403),                            # N > 32: neither persistent launch is eligible
     "B32_T1000_dis": dict(B=32, T=1000, dis=0.5),             # the prior's z feeds the decoder: per-step chains on two streams
+    # scheduled sampling: ss = 0.5 draws mixed coins from random.seed(SEED) (asserted), ss = 0.0 only false ones
+    "B32_T1000_ss": dict(B=32, T=1000, ss=0.5),               # per-step forward + persistent deferred backward, and the rest
+    "B32_T1000_ss0": dict(B=32, T=1000, ss=0.0, variants=("default",)),           # no caption word fed after step 0
+    "B16_T3000_ss": dict(B=16, T=3000, feat_lens=C4_FEAT_LENS, ss=0.5, variants=("default", "no_persist")),   # rc_splits = 3
+    "B33_T403_ss": dict(B=33, T=403, ss=0.5, variants=("default", "no_persist_no_split")),    # N > 32: no persistent launch
+    "B32_T1000_ss_dis": dict(B=32, T=1000, ss=0.5, dis=0.5, variants=("default",)),   # model words and prior-z steps together
 }
 VARIANTS = {
     "default": {},
@@ -46,15 +62,20 @@ VARIANTS = {
 # - when a step fed the prior's z to the decoder, the decode backward never defers (acvae_decode_bwd_defers: the prior BPTT
 #   waits for the decoder's dz), so defer=False is the default path.
 SAME_PATH = {("B33_T403", "no_persist"), ("B32_T1000_dis", "no_defer")}
-PARAMS = [(c, v) for c in CASES for v in VARIANTS if (c, v) not in SAME_PATH]
-PERSISTENT = {"B32_T1000", "B16_T3000", "B3_T1601"}           # both persistent launches eligible in the default run
+PARAMS = [(c, v) for c in CASES for v in CASES[c].get("variants", VARIANTS) if (c, v) not in SAME_PATH]
+# both persistent launches eligible in the default run (under scheduled sampling: the persistent decode BACKWARD only)
+PERSISTENT = {"B32_T1000", "B16_T3000", "B3_T1601", "B32_T1000_ss", "B16_T3000_ss"}
 POSTERIOR_PERSISTENT = PERSISTENT | {"B32_T1000_dis"}         # the persistent posterior (N <= 32; dis_ratio does not matter)
 # Encoder tensors whose fp32 oracle is itself further from the truth than grads_match_oracle's 5e-4.  At B=16, T=3000 the CPU
 # weight gradient of conv_block1.conv2 sums 16 x 3000 x 64 = 3.1M products per element in fp32: against the oracle run in
 # float64 under the same ReLU decisions, the fp32 oracle is 6.5e-4 off (relative L2) and the HIP kernel 6.4e-6 off, so the
 # HIP-vs-oracle distance (6.5e-4) is the oracle's own error.  The bound below is ~2x that; every other tensor keeps 5e-4
 # (the fp32 oracle's next-largest distance from float64 there: conv_block1.conv1 3.3e-4, conv_block2.conv1 1.9e-4).
-TOL_ENC_OF = {"B16_T3000": {"encoder.conv_block1.conv2.weight": 1.5e-3}}
+# The same batch under scheduled sampling (B16_T3000_ss; the oracle fed the HIP run's words, tools/fp64_grad_check.py
+# B16_T3000_ss): fp32 oracle 6.8e-4 from float64, HIP 6.4e-6, HIP-vs-oracle 6.8e-4 (1.36 x the general 5e-4); bound ~2x the
+# oracle's own distance.  Next-largest there: conv_block1.conv1 3.1e-4, conv_block2.conv1 2.0e-4 (fp32 oracle from float64).
+TOL_ENC_OF = {"B16_T3000": {"encoder.conv_block1.conv2.weight": 1.5e-3},
+              "B16_T3000_ss": {"encoder.conv_block1.conv2.weight": 1.4e-3}}
 
 _CACHE = {}
 
@@ -77,15 +98,15 @@ def _patched(flags, run):
 
 
 def _case(name):
-    """The oracle's step at one shape, computed once; the cache holds one shape at a time (its ReLU pre-activations are
-    gigabytes at B=16, T=3000)."""
+    """The oracle's natural step at one shape (it draws and records the noise, and under scheduled sampling the coins),
+    computed once; the cache holds one shape at a time (its ReLU pre-activations are gigabytes at B=16, T=3000)."""
     c = _CACHE.get("case")
     if c is not None and c["name"] == name:
         return c
     _CACHE.clear()
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     p = CASES[name]
-    B, T, dis = p["B"], p["T"], p.get("dis", 0)
+    B, T, dis, ss = p["B"], p["T"], p.get("dis", 0), p.get("ss", 1.0)
     state = {k: v.detach().cpu().clone() for k, v in build(5).state_dict().items()}
     feats, caps, fl, cl = O.synthetic_batch(B, T, V, L, seed=4, ragged=True)
     if "feat_lens" in p:
@@ -97,26 +118,63 @@ def _case(name):
     rec = {}
     torch.manual_seed(SEED); random.seed(SEED)
     st = {k: v.clone() for k, v in state.items()}
-    ores = _patched(flags, lambda: O.OracleTrainer(st, V).step(feats, fl.copy(), caps, cl, 1.0, dis, record=rec,
+    ores = _patched(flags, lambda: O.OracleTrainer(st, V).step(feats, fl.copy(), caps, cl, ss, dis, record=rec,
                                                                apply_update=False))
-    c = dict(name=name, state=state, feats=feats, caps=caps, fl=fl, cl=cl, dis=dis, flags=flags, rec=rec,
-             grads=ores["grads"], loss=float(ores["loss"]), seqs=ores["out"]["seqs"], under=None, masks=None, dec={})
+    c = dict(name=name, state=state, feats=feats, caps=caps, fl=fl, cl=cl, dis=dis, ss=ss, flags=flags, rec=rec,
+             grads=ores["grads"], loss=float(ores["loss"]), seqs=ores["out"]["seqs"], under=None, masks=None, dec={},
+             fed=None)         # fed: the HIP default run's words, which the oracle is fed in a scheduled-sampling case
     del ores
+    if ss < 1.0:
+        coins = rec["ss_flags"]
+        false_t = [t for t, f in enumerate(coins) if not f]
+        assert false_t and max(false_t) >= 1, coins
+        assert (True in coins) == (ss > 0.0), coins                    # mixed coins at ss = 0.5, only false ones at ss = 0
+        # the oracle's natural run fed model words at all (a third of them at least differ from the caption word)
+        differ = float((rec["fed_words"][:, false_t] != caps[:, false_t].long()).double().mean())
+        print(f"{name}: coins {''.join('T' if f else 'f' for f in coins)}; {differ:.0%} of the words fed at false-coin steps "
+              f"differ from the caption word")
+        assert differ >= 1 / 3, differ
     _CACHE["case"] = c
     return c
+
+
+def _oracle_step_under(c, force, fed_words=None):
+    """The oracle's step on the case's noise under the ReLU decisions `force` and, for a scheduled-sampling case, fed the
+    words `fed_words` at its false-coin steps.  Returns grads, loss, logits, the oracle's own words and their margins."""
+    rec = c["rec"]
+    noise = dict(dropout=[m.clone() for m in rec["dropout"]], eps_q=rec["eps_q"], eps_p=rec["eps_p"], relu_force=force,
+                 fed_words=fed_words)
+    st = {k: v.clone() for k, v in c["state"].items()}
+    torch.manual_seed(SEED); random.seed(SEED)
+    res = _patched(c["flags"], lambda: O.OracleTrainer(st, V).step(
+        c["feats"], c["fl"].copy(), c["caps"], c["cl"], c["ss"], c["dis"], noise=noise, apply_update=False))
+    logits = res["out"]["logits"].detach()
+    margins = torch.stack([O.decision_margin(logits[:, t]) for t in range(logits.shape[1])], 1)
+    return dict(grads=res["grads"], loss=float(res["loss"]), logits=logits, seqs=res["out"]["seqs"], margins=margins)
 
 
 def _oracle_under(c):
     def under(force):
         if c["under"] is None:
-            rec = c["rec"]
-            noise = dict(dropout=[m.clone() for m in rec["dropout"]], eps_q=rec["eps_q"], eps_p=rec["eps_p"], relu_force=force)
-            st = {k: v.clone() for k, v in c["state"].items()}
-            torch.manual_seed(SEED); random.seed(SEED)
-            c["under"] = _patched(c["flags"], lambda: O.OracleTrainer(st, V).step(
-                c["feats"], c["fl"].copy(), c["caps"], c["cl"], 1.0, c["dis"], noise=noise, apply_update=False))["grads"]
-        return c["under"]
+            c["under"] = _oracle_step_under(c, force, c["fed"])
+        return c["under"]["grads"]
     return under
+
+
+def _ss_reference(c, variant, seqs, force):
+    """Scheduled sampling: the oracle run that `variant`'s HIP run is held against - fed the HIP default run's words and
+    under its ReLU decisions, computed once per case (c["under"]).  Every variant must produce those words (its forward is
+    step by step in all of them); one that does not is reported with the margin of its first other decision and gets an
+    oracle run of its own."""
+    if c["fed"] is None:
+        c["fed"] = seqs
+    if torch.equal(seqs, c["fed"]):
+        _oracle_under(c)(force)
+        return c["under"], True
+    n, t = (int(x) for x in torch.nonzero(seqs != c["fed"])[0])
+    print(f"{c['name']}-{variant}: FINDING: words differ from the default variant's, first at clip {n} step {t}, where the "
+          f"oracle's margin is {float(c['under']['margins'][n, t]):.3e}")
+    return _oracle_step_under(c, force, seqs), False
 
 
 def _hip(c, variant):
@@ -132,14 +190,23 @@ def _hip(c, variant):
     model._grad_ready_cb = lambda tag, *a: tags.append(tag)
     with _lib.override(**VARIANTS[variant]):
         torch.manual_seed(SEED); random.seed(SEED)
-        out = _patched(c["flags"], lambda: model(c["feats"].cuda(), c["fl"].copy(), c["caps"], c["cl"], ss_ratio=1.0,
+        out = _patched(c["flags"], lambda: model(c["feats"].cuda(), c["fl"].copy(), c["caps"], c["cl"], ss_ratio=c["ss"],
                                                  dis_ratio=c["dis"]))
         loss = hip_loss(out, c["caps"], c["cl"], V)[0]
         loss.backward()
     torch.cuda.synchronize()
     model.check_persistent_launches()
-    assert abs(float(loss.detach()) - c["loss"]) <= 1e-4 * max(1.0, abs(c["loss"])), (float(loss.detach()), c["loss"])
-    assert torch.equal(out["seqs"].cpu(), c["seqs"])
+    want, same_words = c["loss"], True
+    if c["ss"] < 1.0:       # against the oracle fed this run's words, word by word where the oracle's decision is not a near tie
+        force = {i: m.cpu() for i, m in enumerate(model.encoder.relu_masks())}
+        ref, same_words = _ss_reference(c, variant, out["seqs"].cpu(), force)
+        want = ref["loss"]
+        words_match_by_margin(f"{c['name']}-{variant}", out["seqs"], out["logits"], ref, ref["margins"])
+        c["ref"] = ref
+    else:
+        assert torch.equal(out["seqs"].cpu(), c["seqs"])
+    assert abs(float(loss.detach()) - want) <= 1e-4 * max(1.0, abs(want)), (float(loss.detach()), want)
+    assert same_words, "a variant's words differ from the default variant's (see the FINDING line)"
     c["dec"][variant] = {k: p.grad.detach().cpu().clone() for k, p in model.named_parameters()
                          if k.startswith(("decoder.", "qnet.")) and p.grad is not None}
     return model, [t for t in tags if t.startswith("decode")]
@@ -166,7 +233,11 @@ def test_every_parameter_gradient_vs_oracle_at_full_size(case, variant):
         assert all(torch.equal(a, b) for a, b in zip(masks, c["masks"])), "ReLU decisions differ between variants"
     del masks
     named = dict(model.named_parameters())
-    grads_match_oracle(model, named, c["grads"], c["rec"], _oracle_under(c), tol_enc_of=TOL_ENC_OF.get(case))
+    if c["ss"] < 1.0:       # c["ref"]: the oracle fed this run's words under this run's ReLU decisions (_hip)
+        ref = c["ref"]["grads"]
+        grads_match_oracle(model, named, ref, c["rec"], lambda force: ref, tol_enc_of=TOL_ENC_OF.get(case))
+    else:
+        grads_match_oracle(model, named, c["grads"], c["rec"], _oracle_under(c), tol_enc_of=TOL_ENC_OF.get(case))
     # the intended path ran
     deferred = not c["dis"] and variant != "no_defer"
     assert tags == ["decode_deferred" if deferred else "decode"], tags
@@ -179,5 +250,32 @@ def test_every_parameter_gradient_vs_oracle_at_full_size(case, variant):
         assert _differs(_dec_grads(c, "default"), c["dec"][variant], "qnet."), "the persistent posterior did not run"
     if variant == "no_persist_no_split":
         # the split-over-frames attention combines its softmax in another order than the one-workgroup form
-        other = "default" if case == "B33_T403" else "no_persist"
+        other = "default" if case.startswith("B33_T403") else "no_persist"
         assert _differs(_dec_grads(c, other), c["dec"][variant]), "the split-over-frames attention did not run"
+
+
+def test_ss_ratio_just_below_one_with_all_true_coins_is_the_teacher_forced_run():
+    """The fed word is the only thing scheduled sampling changes: with ss_ratio just below 1 and coins that all come up
+    "caption word", the step stays on the teacher-forced path (persistent forward, second stream) and is bit-identical in
+    logits and in every gradient to the same step at ss_ratio = 1.0."""
+    feats, caps, fl, cl = O.synthetic_batch(32, 1000, V, L, seed=4, ragged=True)
+    ss = 1.0 - 1e-9
+    random.seed(SEED)
+    assert all(random.random() < ss for _ in range(L - 1))
+    f = feats.cuda()
+
+    def run(ss_ratio):
+        model = build(5).train()
+        torch.manual_seed(SEED); random.seed(SEED)           # the model draws dropout masks and eps itself, the same ones
+        out = model(f, fl.copy(), caps, cl, ss_ratio=ss_ratio, dis_ratio=0)
+        hip_loss(out, caps, cl, V)[0].backward()
+        torch.cuda.synchronize()
+        model.check_persistent_launches()
+        return out["logits"].detach().clone(), {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+
+    la, ga = run(1.0)
+    lb, gb = run(ss)
+    assert torch.equal(la, lb)
+    assert set(ga) == set(gb)
+    for k in ga:
+        assert torch.equal(ga[k], gb[k]), k

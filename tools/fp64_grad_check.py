@@ -3,7 +3,8 @@
     python tools/fp64_grad_check.py [CASE]          (CASE: a key of that file's CASES, default B16_T3000; needs an MI355X)
 
 Runs the HIP training step (default launch path) and the fp32 oracle as the test does, then the oracle once more in float64
-(weights, features and noise cast to double) under the HIP path's own ReLU decisions, and prints for every encoder tensor the
+(weights, features and noise cast to double) under the HIP path's own ReLU decisions (and, for a scheduled-sampling case,
+fed the HIP path's own words), and prints for every encoder tensor the
 relative L2 distance of the fp32 oracle and of the HIP gradient from float64.  A per-tensor bound in the test's TOL_ENC_OF
 rests on these numbers (the fp32 oracle's own distance from float64); re-check it after a change to the encoder kernels."""
 import os
@@ -37,10 +38,10 @@ def main(name):
     rec = c["rec"]
     st64 = {k: (v.double() if v.dtype.is_floating_point else v.clone()) for k, v in c["state"].items()}
     noise = dict(dropout=[m.clone() for m in rec["dropout"]], eps_q=rec["eps_q"].double(), eps_p=rec["eps_p"].double(),
-                 relu_force=force)
+                 relu_force=force, fed_words=c["fed"])      # a scheduled-sampling case: the HIP run's own words, as in the test
     torch.manual_seed(M.SEED); random.seed(M.SEED)
     g64 = M._patched(c["flags"], lambda: O.OracleTrainer(st64, M.V).step(
-        c["feats"].double(), c["fl"].copy(), c["caps"].double(), c["cl"], 1.0, c["dis"], noise=noise,
+        c["feats"].double(), c["fl"].copy(), c["caps"].double(), c["cl"], c["ss"], c["dis"], noise=noise,
         apply_update=False))["grads"]
     bounds = M.TOL_ENC_OF.get(name, {})
     print(f"{name}: {time.time() - t0:.0f} s; relative L2 from the float64 oracle (test bound: 5e-4 unless listed)")
