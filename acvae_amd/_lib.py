@@ -62,6 +62,7 @@ FLAG_NO_PERSIST = int(_defs["ACVAE_FLAG_NO_PERSIST"])
 FLAG_DEFER_PARAM_GRADS = int(_defs["ACVAE_FLAG_DEFER_PARAM_GRADS"])
 FLAG_NO_ATTN_SPLIT = int(_defs["ACVAE_FLAG_NO_ATTN_SPLIT"])
 FLAG_TEST_STALL = int(_defs["ACVAE_FLAG_TEST_STALL"])
+FLAG_ROLLOUT_GRAD = int(_defs["ACVAE_FLAG_ROLLOUT_GRAD"])
 _lib = None
 
 

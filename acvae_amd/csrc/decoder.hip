@@ -13,6 +13,7 @@
 // argmax run once over all N*Tc rows.  Buffers are batch-major [N,Tc,*] like the reference's outputs;
 // "step t" addresses column t with row stride Tc*C.
 #include <cstdlib>
+#include <vector>
 #include "common.h"
 #include "conv.h"
 #include "rnn.h"
@@ -546,6 +547,10 @@ extern "C" int64_t acvae_decode_saved_bytes(int N, int Tc, int S, int E, int H, 
   DecLayout L;
   return dec_layout(N, Tc, S, E, H, A, V, Eenc, L) == ACVAE_OK ? L.saved_total * 4 : -1;
 }
+extern "C" int64_t acvae_decode_saved_lse_offset(int N, int Tc, int S, int E, int H, int A, int V, int Eenc) {
+  DecLayout L;
+  return dec_layout(N, Tc, S, E, H, A, V, Eenc, L) == ACVAE_OK ? L.lse * 4 : -1;
+}
 extern "C" int64_t acvae_decode_scratch_bytes(int N, int Tc, int S, int E, int H, int A, int V, int Eenc) {
   DecLayout L;
   if (dec_layout(N, Tc, S, E, H, A, V, Eenc, L) != ACVAE_OK) return -1;
@@ -588,6 +593,9 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
       !p_means || !p_logs || !p_z || !saved_v || !scratch_v)
     return ACVAE_EINVAL;
   const bool train = caps != nullptr;
+  // a rollout whose `saved` the backward accepts: the transposed weights are made as in training (the fed words and the
+  // finished-row state are kept either way)
+  const bool rollout_grad = !train && (flags & ACVAE_FLAG_ROLLOUT_GRAD);
   if (train && (!lens1 || !q_z || !ss_flags_host || !dis_flags_host || !p_means_utt)) return ACVAE_EINVAL;
   if (train && H != E) return ACVAE_EUNSUPPORTED;  // mean_log_out = Linear(embed_size, .) is fed the GRU output
   if (saved_bytes < L.saved_total * 4 || scratch_bytes < L.scratch_fwd * 4) return ACVAE_EWORKSPACE;
@@ -742,7 +750,7 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
   // the backward's transposed weights (one launch for the nine): queued on the prior chain's stream where that stream has
   // nothing else to do - beside the persistent launch / behind the prior chain - and joined with it before the call returns
   auto transposes = [&](hipStream_t ts) -> int {
-    if (!train) return ACVAE_OK;
+    if (!train && !rollout_grad) return ACVAE_OK;
     TransposeBatch tb;
     tb.add({P(TP_DEC_CLS_W), H, sv + L.wt_cls, V, V, H});                   // [H][V]
     tb.add({P(TP_DEC_WIH), 3 * E, sv + L.wt_dih, 3 * H, 3 * H, 3 * E});     // [3E][3H]
@@ -863,12 +871,21 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
   if (emb_keep && !(emb_drop_p > 0.f && emb_drop_p <= 1.f)) return ACVAE_EINVAL;   // p = 1: nn.Dropout zeroes everything
   DecLayout L;
   ACVAE_TRY(dec_layout(N, Tc, S, E, H, A, V, Eenc, L));
-  if (!params || !grads || !mem_in || !mem_lens || !lens1 || !eps_p || !dis_flags_host || !outputs || !attn_w ||
-      !p_logs || !d_mem_in || !d_q_z || !saved_v || !scratch_v)
+  // ACVAE_FLAG_ROLLOUT_GRAD: `saved` of a rollout (caps == NULL) made with the same flag.  No caption lengths and no utterance head
+  // (d_p_means_utt must be NULL), every step fed the prior's z to the decoder whatever dis_flags_host says, no posterior.
+  const bool rollout = (flags & ACVAE_FLAG_ROLLOUT_GRAD) != 0;
+  if (!params || !grads || !mem_in || !mem_lens || !eps_p || !outputs || !attn_w || !p_logs || !d_mem_in || !saved_v ||
+      !scratch_v)
     return ACVAE_EINVAL;
+  if (rollout ? d_p_means_utt != nullptr : (!lens1 || !dis_flags_host || !d_q_z)) return ACVAE_EINVAL;
   if (saved_bytes < L.saved_total * 4 || scratch_bytes < L.scratch_bwd * 4) return ACVAE_EWORKSPACE;
   float* sv = (float*)saved_v;
   float* sc = (float*)scratch_v;
+  std::vector<int> rollout_flags;
+  if (rollout) {
+    rollout_flags.assign(Tc, 1);
+    dis_flags_host = rollout_flags.data();
+  }
   bool prior_feeds_decoder = false;
   for (int t = 0; t < Tc; ++t) prior_feeds_decoder = prior_feeds_decoder || dis_flags_host[t] != 0;
   // st: decoder chain; sp: prior chain, on the second stream when given (it has its own accumulators; the two meet in
@@ -935,7 +952,7 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     if (d_p_means_utt) {
       ACVAE_TRY(gemm_tn(d_p_means_utt, 2 * E, sv + L.pool_hid, H, G(TP_MLO_W), H, 2 * E, H, N, ws, c));
       cb.add({d_p_means_utt, N, 2 * E, G(TP_MLO_B)});
-    } else {
+    } else if (G(TP_MLO_W) && G(TP_MLO_B)) {      // (a rollout's caller passes none: the head took no part)
       ACVAE_TRY(zero(G(TP_MLO_W), (long)2 * E * H, c));
       ACVAE_TRY(zero(G(TP_MLO_B), 2 * E, c));
     }
@@ -1010,6 +1027,7 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
   // encoder backward back by the whole 0.6 ms of parameter-gradient products in front of it).
   auto dec_dz = [&](const Ctx& c) -> int {
     ACVAE_TRY(gemm(dgi, 3 * H, wt_dih + (long)2 * E * 3 * H, 3 * H, nullptr, dz_dec, E, R, E, 3 * H, 0, c));  // d z
+    if (!d_q_z) return ACVAE_OK;         // (rollout: no posterior sample went in)
     if (!prior_feeds_decoder) {
       ACVAE_TRY(acvae::copy_rows(d_q_z, E, dz_dec, E, R, E, c));
     } else {

@@ -301,6 +301,72 @@ __global__ __launch_bounds__(EW_THREADS) void ce_bwd_kernel(const float* __restr
   for (int c = threadIdx.x; c < V; c += EW_THREADS) d[c] = g * (expf(x[c] - l) - (c == tg ? on : off));
 }
 
+// ------------------------------------------------------------------ self-critical sequence training (policy gradient)
+// utils/train_util.py:398-409: loss = mean_n sum_t -sampled_logprobs[n,t] * reward[n] * mask[n,t], mask[n,0] = 1,
+// mask[n,t] = seqs[n,t-1] != <end>.  coef[n,t] = -reward[n] * mask[n,t] / N is d loss / d sampled_logprobs; the loss is
+// sum(coef * sampled_logprobs) by one workgroup in a fixed order (each thread its strided share in double, then the fixed tree).
+__global__ __launch_bounds__(EW_THREADS) void scst_loss_kernel(const float* __restrict__ slp,
+                                                               const int64_t* __restrict__ seqs,
+                                                               const float* __restrict__ reward, int end_idx,
+                                                               float* __restrict__ coef, float* __restrict__ loss, int N,
+                                                               int T) {
+  __shared__ double redd[EW_THREADS / 64];
+  const float inv_n = 1.f / (float)N;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < N * T; i += EW_THREADS) {
+    const int n = i / T, t = i % T;
+    const bool live = t == 0 || seqs[i - 1] != (int64_t)end_idx;
+    const float c = live ? -reward[n] * inv_n : 0.f;
+    coef[i] = c;
+    if (c != 0.f) acc += (double)c * (double)slp[i];       // a dead step's log-probability is never read into the sum
+  }
+  acc = wave_sum_d(acc);
+  if ((threadIdx.x & 63) == 0) redd[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < EW_THREADS / 64; ++i) t += redd[i];
+    loss[0] = (float)t;
+  }
+}
+
+// d_logits[r,v] = coef[r] * ((v == seqs[r]) - exp(logits[r,v] - lse[r])): the gradient of coef[r] * log_softmax(logits[r])[seqs[r]].
+// One workgroup per row; HBM-bound (one read and one write of the row), 16-byte accesses when the rows allow it (VEC).  A row
+// whose coef is 0 is written as zeros and its logits are not read (they may hold anything, NaN included).
+template <bool VEC>
+__global__ __launch_bounds__(EW_THREADS) void logprob_bwd_kernel(const float* __restrict__ logits, long ld,
+                                                                 const float* __restrict__ lse,
+                                                                 const int64_t* __restrict__ seqs,
+                                                                 const float* __restrict__ coef,
+                                                                 float* __restrict__ dlogits, int V) {
+  const long r = blockIdx.x;
+  const float g = coef[r];
+  float* d = dlogits + r * ld;
+  if (g == 0.f) {
+    if (VEC) {
+      for (int c = threadIdx.x; c < V / 4; c += EW_THREADS) ((float4*)d)[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      for (int c = threadIdx.x; c < V; c += EW_THREADS) d[c] = 0.f;
+    }
+    return;
+  }
+  const float* x = logits + r * ld;
+  const float l = lse[r];
+  const int w = (int)seqs[r];
+  if (VEC) {
+    for (int c = threadIdx.x; c < V / 4; c += EW_THREADS) {
+      const float4 v = ((const float4*)x)[c];
+      float4 o;
+      o.x = g * ((4 * c == w ? 1.f : 0.f) - expf(v.x - l));
+      o.y = g * ((4 * c + 1 == w ? 1.f : 0.f) - expf(v.y - l));
+      o.z = g * ((4 * c + 2 == w ? 1.f : 0.f) - expf(v.z - l));
+      o.w = g * ((4 * c + 3 == w ? 1.f : 0.f) - expf(v.w - l));
+      ((float4*)d)[c] = o;
+    }
+  } else {
+    for (int c = threadIdx.x; c < V; c += EW_THREADS) d[c] = g * ((c == w ? 1.f : 0.f) - expf(x[c] - l));
+  }
+}
 
 // ------------------------------------------------------------------ beam-search helpers (N1)
 // out[n,c] = logits[n,c] - lse[n] + prev[n]      (log_softmax + accumulated beam log-prob, vae_model.py:909-912)
@@ -572,6 +638,31 @@ extern "C" int acvae_ls_ce_bwd(const float* logits, int64_t ld_n, int64_t ld_t, 
   if ((reduction == 0 && !grad_rows) || (reduction != 0 && !grad_out)) return ACVAE_EINVAL;
   hipLaunchKernelGGL(ce_bwd_kernel, dim3(N * T), dim3(EW_THREADS), 0, (hipStream_t)stream, logits, ld_n, ld_t, targets,
                      tg_sn, lens1, lse, smoothing, reduction, grad_out, grad_rows, dlogits, N, T, V);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_scst_loss_fwd(const float* sampled_logprobs, const int64_t* seqs, const float* reward, int end_idx,
+                                   float* coef, float* loss, int N, int Tc, void* stream) {
+  if (!sampled_logprobs || !seqs || !reward || !coef || !loss || N <= 0 || Tc <= 0 || (long)N * Tc > (1L << 30))
+    return ACVAE_EINVAL;
+  hipLaunchKernelGGL(scst_loss_kernel, dim3(1), dim3(EW_THREADS), 0, (hipStream_t)stream, sampled_logprobs, seqs, reward,
+                     end_idx, coef, loss, N, Tc);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_logprob_bwd(const float* logits, int64_t ld, const float* lse, const int64_t* seqs, const float* coef,
+                                 float* d_logits, int64_t rows, int V, void* stream) {
+  if (!logits || !lse || !seqs || !coef || !d_logits || rows <= 0 || rows > 0x7fffffffL || V <= 0 || ld < V)
+    return ACVAE_EINVAL;
+  const bool vec = V % 4 == 0 && ld % 4 == 0 && aligned16(logits) && aligned16(d_logits);
+  if (vec)
+    hipLaunchKernelGGL(logprob_bwd_kernel<true>, dim3((unsigned)rows), dim3(EW_THREADS), 0, (hipStream_t)stream, logits,
+                       (long)ld, lse, seqs, coef, d_logits, V);
+  else
+    hipLaunchKernelGGL(logprob_bwd_kernel<false>, dim3((unsigned)rows), dim3(EW_THREADS), 0, (hipStream_t)stream, logits,
+                       (long)ld, lse, seqs, coef, d_logits, V);
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }

@@ -2,7 +2,12 @@
 (``LabelSmoothingLoss`` :234-251, ``Normal_kl_loss`` :253-266, length-mask helpers :198-231) and of the
 masked dict-style losses of ``losses/loss.py`` (:12-70).  Same constructor arguments and forward
 signatures; the arithmetic is in libacvae_hip.so (acvae_ls_ce_*, acvae_gauss_kl_*, acvae_mse_*).
+
+Self-critical sequence training: ``scst_Loss`` / ``Nscst_Loss`` (:292-413) and the sentence scoring of
+``utils/score_util.py`` (``compute_batch_score`` / ``compur_batch_score_samplen``).  The reward arithmetic runs on the host
+in numpy as in the reference; the loss and its gradient are acvae_scst_loss_fwd / acvae_logprob_bwd.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -188,6 +193,152 @@ class MSELoss(nn.Module):
 
     def forward(self, a, b):
         return _MSEFn.apply(a, b)
+
+
+# ---- self-critical sequence training
+def _need_scorer(scorer):
+    if scorer is None:
+        raise ValueError("SCST needs a scorer: pass scorer=<object with compute_score(references, hypotheses) -> (score, "
+                         "per-key scores)>, e.g. pycocoevalcap's Cider(); this package imports no scorer of its own")
+    return scorer
+
+
+def _sentence(row, start_idx, end_idx, vocabulary):
+    words = []
+    for w_t in row:
+        if w_t == start_idx:
+            continue
+        if w_t == end_idx:
+            break
+        words.append(vocabulary.idx2word[w_t])
+    return " ".join(words)
+
+
+def compute_batch_score(decode_res, key2refs, keys, start_idx, end_idx, vocabulary, scorer):
+    """utils/score_util.py:5-52 - decode_res [N, max_length] token ids -> one score per row; rows that share a key are
+    scored once, by the first of them."""
+    scorer = _need_scorer(scorer)
+    decode_res = np.asarray(decode_res)
+    hypothesis, references = {}, {}
+    for i in range(len(keys)):
+        if keys[i] in hypothesis:
+            continue
+        hypothesis[keys[i]] = [_sentence(decode_res[i], start_idx, end_idx, vocabulary)]
+        references[keys[i]] = key2refs[keys[i]]
+    _, scores = scorer.compute_score(references, hypothesis)
+    key2score = {key: scores[i] for i, key in enumerate(references.keys())}
+    return np.array([key2score[keys[i]] for i in range(decode_res.shape[0])], dtype=np.float64)
+
+
+def compur_batch_score_samplen(decode_res, key2refs, keys, start_idx, end_idx, vocabulary, scorer):
+    """utils/score_util.py:56-96 (the name is the reference's) - every row scored on its own against key2refs[keys[i]]."""
+    scorer = _need_scorer(scorer)
+    decode_res = np.asarray(decode_res)
+    hypothesis, references = {}, {}
+    for i in range(len(keys)):
+        hypothesis[i] = [_sentence(decode_res[i], start_idx, end_idx, vocabulary)]
+        references[i] = key2refs[keys[i]]
+    _, scores = scorer.compute_score(references, hypothesis)
+    return scores
+
+
+class _ScstLossFn(torch.autograd.Function):
+    """mean_n sum_t -sampled_logprobs * reward * mask with mask[n,0] = 1, mask[n,t] = seqs[n,t-1] != <end> (:401-409)."""
+
+    @staticmethod
+    def forward(ctx, slp, seqs, reward, end_idx):
+        _lib.require_cuda(slp, seqs)
+        slp = slp.contiguous().float()
+        N, T = slp.shape
+        dev = slp.device
+        seqs = seqs.to(device=dev, dtype=torch.long).contiguous()
+        reward = _lib.h2d(torch.as_tensor(np.asarray(reward, dtype=np.float32)), dev).contiguous()
+        coef = torch.empty(N, T, device=dev)
+        out = _dev_scalar(dev)
+        _lib.call("acvae_scst_loss_fwd", slp, seqs, reward, int(end_idx), coef, out, N, T, _lib.current_stream())
+        ctx.coef = coef
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.coef * g, None, None, None
+
+
+def scst_policy_loss(sampled_logprobs, seqs, reward, end_idx):
+    """The loss line shared by scst_Loss, Nscst_Loss and the wrappers of acvae_amd.seq_train_model; reward: host [N]."""
+    return _ScstLossFn.apply(sampled_logprobs, seqs, reward, end_idx)
+
+
+def _seqs_to_host(*seqs):
+    """Token tensors -> numpy with ONE device synchronisation for all of them."""
+    if all(torch.is_tensor(s) and s.is_cuda for s in seqs):
+        flat = torch.cat([s.reshape(-1) for s in seqs]).cpu().numpy()
+        out, off = [], 0
+        for s in seqs:
+            out.append(flat[off:off + s.numel()].reshape(tuple(s.shape)))
+            off += s.numel()
+        return out
+    return [s.cpu().numpy() if torch.is_tensor(s) else np.asarray(s) for s in seqs]
+
+
+class scst_Loss(nn.Module):
+    """utils/train_util.py:355-413 - forward(output with "greedy_seqs", "sampled_seqs", "sampled_logprobs", keys, key2refs,
+    vocabulary) adds "reward" (sampled score - greedy score), "score" and "loss" to `output`."""
+
+    def __init__(self, scorer, reduction="mean", device=0):
+        super().__init__()
+        self.reduction = reduction
+        self.scorer = scorer
+        self.device = device
+        self.pad_idx, self.start_idx, self.end_idx = 0, 1, 2
+
+    def get_critical_reward(self, greedy_seqs, sampled_seqs, keys, key2refs, vocabulary, scorer):
+        greedy_seqs, sampled_seqs = _seqs_to_host(greedy_seqs, sampled_seqs)
+        args = (key2refs, keys, self.start_idx, self.end_idx, vocabulary, scorer)
+        sampled_score = compute_batch_score(sampled_seqs, *args)
+        greedy_score = compute_batch_score(greedy_seqs, *args)
+        return {"reward": sampled_score - greedy_score, "score": sampled_score}
+
+    def forward(self, output, keys, key2refs, vocabulary):
+        rs = self.get_critical_reward(output["greedy_seqs"], output["sampled_seqs"], keys, key2refs, vocabulary,
+                                      self.scorer)
+        output["reward"] = torch.as_tensor(rs["reward"])
+        output["score"] = torch.as_tensor(rs["score"])
+        output["loss"] = scst_policy_loss(output["sampled_logprobs"], output["sampled_seqs"], rs["reward"], self.end_idx)
+        return output
+
+
+def leave_one_out_reward(sampled_score, sample_n):
+    """:315-321 - rows clip-major [N * sample_n]: each sample's score minus the mean score of its clip's other samples."""
+    s = np.asarray(sampled_score, dtype=np.float64).reshape(-1, sample_n)
+    baseline = (s.sum(1, keepdims=True) - s) / (s.shape[1] - 1)
+    return (s - baseline).reshape(-1)
+
+
+class Nscst_Loss(nn.Module):
+    """utils/train_util.py:292-353 - sample_n rollouts per clip, clip-major rows; the baseline of a rollout is the mean
+    score of the clip's other rollouts.  forward(output with "sampled_seqs", "sampled_logprobs", keys [N clips], ...) ->
+    {"reward": mean reward, "score", "loss"}."""
+
+    def __init__(self, scorer, reduction="mean", sample_n=5, device=0):
+        super().__init__()
+        self.reduction = reduction
+        self.sample_n = sample_n
+        self.scorer = scorer
+        self.device = device
+        self.pad_idx, self.start_idx, self.end_idx = 0, 1, 2
+
+    def get_critical_reward(self, sampled_seqs, keys, key2refs, vocabulary):
+        sampled_seqs, = _seqs_to_host(sampled_seqs)
+        score = np.asarray(compur_batch_score_samplen(sampled_seqs, key2refs, keys, self.start_idx, self.end_idx,
+                                                      vocabulary, self.scorer), dtype=np.float64)
+        return {"reward": leave_one_out_reward(score, self.sample_n), "score": score.reshape(-1)}
+
+    def forward(self, output, keys, key2refs, vocabulary):
+        keys = [key for key in keys for _ in range(self.sample_n)]
+        rs = self.get_critical_reward(output["sampled_seqs"], keys, key2refs, vocabulary)
+        loss = scst_policy_loss(output["sampled_logprobs"], output["sampled_seqs"], rs["reward"], self.end_idx)
+        return {"reward": torch.as_tensor(rs["reward"]).mean(), "score": torch.as_tensor(rs["score"]), "loss": loss}
 
 
 # ---- length helpers (utils/train_util.py:198-231); host-side index logic, used by callers of the modules

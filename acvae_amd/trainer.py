@@ -354,6 +354,35 @@ class TrainStep:
         for p in self.order:
             p.grad = None                                             # optimizer.zero_grad(set_to_none=True)
         loss, parts, _ = self.forward_loss(feats, feat_lens, caps, cap_lens, ss_ratio, dis_ratio, kl_weight)
+        return self._backward_and_update(loss, parts)
+
+    def scst_step(self, feats, feat_lens, keys, key2refs, vocabulary, scorer, sample_n=1, max_length=None, **kwargs):
+        """One self-critical training step (models/seq_train_model.py): greedy baseline and sampled rollout through
+        ``ScstWrapper`` (``sample_n == 1``) or ``sample_n`` rollouts per clip over one encoder pass through ``NScstWrapper``,
+        then the same backward, clip and fused update as ``step()``.  The reward needs the words on the host: one
+        synchronisation per step, between the rollouts and the loss.  Parameters the loss does not reach (the posterior,
+        ``mean_log_out``) get no gradient and the optimiser leaves them and their state alone, as torch's does.
+        ``kwargs``: ``temperature`` / ``temp`` / ``method`` / ``rng`` as the wrappers take them."""
+        if self.world > 1:
+            raise NotImplementedError("data-parallel SCST: the gradient exchange waits for the posterior's bucket, which a "
+                                      "rollout never announces; run scst_step in a single process")
+        from .seq_train_model import NScstWrapper, ScstWrapper
+        self.sync_buffers()
+        self._decode_event = self._decode_aux_event = self._text_event = None
+        self._decode_deferred = self._projemb_seen = False
+        for p in self.order:
+            p.grad = None
+        kwargs = dict(kwargs, scorer=scorer, max_length=self.model.max_length if max_length is None else max_length)
+        if int(sample_n) > 1:
+            out = NScstWrapper(self.model)(feats, feat_lens, keys, key2refs, vocabulary, sample_n=int(sample_n), **kwargs)
+        else:
+            out = ScstWrapper(self.model)(feats, feat_lens, keys, key2refs, vocabulary, **kwargs)
+        parts = {k: out[k] for k in ("reward", "score", "sampled_seqs") if k in out}
+        if "greedy_seqs" in out:
+            parts["greedy_seqs"] = out["greedy_seqs"]
+        return self._backward_and_update(out["loss"], parts)
+
+    def _backward_and_update(self, loss, parts):
         self.exchange.begin()
         loss.backward()
         gscale = self.exchange.finish()

@@ -11,6 +11,7 @@ reparameterisations — SURVEY F9 —, ``torch.rand(1)`` per step when dis_ratio
 outputs and wires three autograd nodes (encoder, posterior, decode loop), each ONE call into
 libacvae_hip.so for forward and one for backward.
 """
+import contextlib
 import os
 import random
 import weakref
@@ -53,43 +54,55 @@ class _DecodeFn(torch.autograd.Function):
         mem = mem.contiguous()
         method, temp, noise = sampling["sample"] if sampling and sampling.get("sample") else (0, 1.0, None)
         keep, drop_p = sampling["emb_keep"] if sampling and sampling.get("emb_keep") else (None, 0.0)
+        # a rollout whose graph is recorded (self-critical training): the call keeps what acvae_decode_bwd reads
+        rollout = bool(not train and sampling and sampling.get("rollout_grad"))
         _lib.persist_status(dev)                 # the device's status words are registered before the first persistent launch
         _lib.call("acvae_decode_fwd_sampled", ptr_table(params), mem, mem_lens_d, caps_d,
                   caps_d.stride(0) if train else 0, lens1_d, q_z, eps_p, ss_arr, dis_arr, logits, outputs, seqs, slp,
                   attw, pm, pl, pz, putt, hfin, hp, cp, saved, saved_b, scratch, scratch_b, *dims, model.start_idx,
                   model.end_idx, _lib.current_stream(), model._aux_stream(), int(method), float(temp), noise, keep,
-                  float(drop_p), _lib.call_flags())
+                  float(drop_p), _lib.call_flags() | (_lib.FLAG_ROLLOUT_GRAD if rollout else 0))
         ctx.set_materialize_grads(False)         # outputs the loss does not use (outputs, p_z, ..) arrive as None, not as zero tensors
         ctx.model, ctx.saved, ctx.dims, ctx.dis_arr = model, saved, dims, dis_arr
-        ctx.emb_keep, ctx.emb_p = keep, float(drop_p)
+        ctx.emb_keep, ctx.emb_p, ctx.rollout = keep, float(drop_p), rollout
         # outputs kept as plain ctx attributes would form tensor -> grad_fn -> ctx -> tensor cycles that are never collected
-        ctx.save_for_backward(mem, mem_lens_d, lens1_d, eps_p, outputs, attw, pl)
-        ctx.mark_non_differentiable(seqs, slp, attw, hfin, hp, cp)
+        ctx.save_for_backward(mem, mem_lens_d, lens1_d, eps_p, outputs, attw, pl, *((logits, seqs) if rollout else ()))
+        ctx.mark_non_differentiable(seqs, attw, hfin, hp, cp, *(() if rollout else (slp,)))
         if not train:
             putt = torch.zeros(0, device=dev)
             ctx.mark_non_differentiable(putt)
         return logits, outputs, seqs, slp, attw, pm, pl, pz, putt, hfin, hp, cp
 
     @staticmethod
-    def backward(ctx, d_logits, d_outputs, _s, _l, _a, d_pm, d_pl, d_pz, d_putt, *_rest):
+    def backward(ctx, d_logits, d_outputs, _s, d_slp, _a, d_pm, d_pl, d_pz, d_putt, *_rest):
         model = ctx.model
         N, Tc, S, E, H, A, V, Eenc = ctx.dims
-        mem, mem_lens_d, lens1_d, eps_p, outputs, attw, pl = ctx.saved_tensors
+        mem, mem_lens_d, lens1_d, eps_p, outputs, attw, pl = ctx.saved_tensors[:7]
         dev = mem.device
         params = model._text_table()
         grads = [None] * len(params)
         mine = set(range(0, 10)) | set(range(21, 35))
+        if ctx.rollout:
+            mine -= {31, 32}                     # mean_log_out took no part in a rollout: None, as torch leaves it
+            if d_slp is not None:                # d sampled_logprobs -> d logits, the sampled words held constant
+                logits, seqs = ctx.saved_tensors[7:]
+                off = _lib.call("acvae_decode_saved_lse_offset", *ctx.dims)
+                lse = ctx.saved[off:off + N * Tc * 4].view(torch.float32)
+                dl = torch.empty(N, Tc, V, device=dev)
+                _lib.call("acvae_logprob_bwd", logits, V, lse, seqs, d_slp.contiguous().float(), dl, N * Tc, V,
+                          _lib.current_stream())
+                d_logits = dl if d_logits is None else dl.add_(d_logits)
         for i, p in enumerate(params):
             if p is not None and p.requires_grad and i in mine:
                 grads[i] = model._grad_buffer(p)
         c = lambda t: None if t is None else t.contiguous().float()
         d_mem = torch.empty(N, S, Eenc, device=dev)
-        d_qz = torch.empty(N, Tc, E, device=dev)
+        d_qz = None if ctx.rollout else torch.empty(N, Tc, E, device=dev)
         scratch_b = _lib.call("acvae_decode_scratch_bytes", *ctx.dims)
         scratch = scratch_buffer(scratch_b, dev, tag="decode")
         ups = [c(t) for t in (d_logits, d_outputs, d_pm, d_pl, d_pz, d_putt)]
         main, aux = _lib.current_stream(), model._aux_stream()
-        flags = _lib.call_flags(defer=model.defer_param_grads)
+        flags = _lib.call_flags(defer=model.defer_param_grads) | (_lib.FLAG_ROLLOUT_GRAD if ctx.rollout else 0)
         _lib.call("acvae_decode_bwd", ptr_table(params), ptr_table(grads), mem, mem_lens_d, lens1_d, eps_p, ctx.dis_arr,
                   outputs, attw, pl, *ups, d_mem, d_qz, ctx.saved, ctx.saved.numel(), scratch, scratch_b, *ctx.dims, main,
                   aux, ctx.emb_keep, ctx.emb_p, flags)
@@ -420,6 +433,20 @@ class Hybrid_VAEModel(CaptionModel):
             return self.inference_forward(encoded, **kwargs)
         raise Exception("Number of input should be either 4 (feats, feat_lens, caps, cap_lens) or 2 (feats, feat_lens)")
 
+    def rollout_shared_encoder(self, feats, feat_lens, sample_n, **kwargs):
+        """A 2-input forward with ``sample_n`` rollouts per clip that runs the encoder ONCE per clip: the memory rows are
+        repeated on the device, clip-major (row ``n * sample_n + j``), and autograd folds the rows' memory gradients back
+        into the clip's.  In train() the replicas of a clip therefore share the encoder's dropout masks and the BatchNorm
+        statistics are those of the clips, not of the repeated batch."""
+        self._forward_token = getattr(self, "_forward_token", 0) + 1
+        encoded = self.encoder(feats, feat_lens)
+        n = int(sample_n)
+        lens = torch.as_tensor(np.asarray(encoded["audio_embeds_lens"])).repeat_interleave(n, dim=0)
+        rep = {"audio_embeds": encoded["audio_embeds"].repeat_interleave(n, dim=0),
+               "audio_embeds_pooled": encoded["audio_embeds_pooled"].repeat_interleave(n, dim=0),
+               "audio_embeds_lens": lens, "state": None}
+        return self.inference_forward(rep, **kwargs)
+
     def _host_prepare(self, N, dev, caps, cap_lens, kwargs):
         """The decode loop's host-side random decisions, in the reference's per-step order (scheduled-sampling coin
         :826, prior noise text_encoder.py:259 on the CPU generator (F9), disentangle coin :802-806), and the device
@@ -518,12 +545,18 @@ class Hybrid_VAEModel(CaptionModel):
         if mem_lens_d is None:
             mem_lens_d = _lib.h2d(encoded["audio_embeds_lens"], dev, torch.long)
         prep = encoded.pop("_prep", None) or self._host_prepare(N, dev, caps, cap_lens, kwargs)
+        # A rollout records a graph (self-critical training: sampled_logprobs differentiable, the words constants) only in
+        # train() with gradients enabled and something to train; every other 2-input forward is the inference path as before.
+        record = train or (torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()))
+        if record and not train:
+            prep["sampling"] = dict(prep.get("sampling") or {}, rollout_grad=True)
         Tc, ss_flags, dis_flags, eps_p = prep["Tc"], prep["ss_flags"], prep["dis_flags"], prep["eps_p"]
         caps_d, lens1_d = prep["caps_d"], prep["lens1_d"]
         q_z = encoded["q_z"] if train else None
         self.staged = {"caps_d": caps_d, "lens1_d": lens1_d}           # device copies the loss can reuse
-        outs = _DecodeFn.apply(self, mem, mem_lens_d, caps_d, lens1_d, q_z, eps_p, ss_flags, dis_flags, Tc,
-                               prep.get("sampling"), *self._decode_weights())
+        with contextlib.nullcontext() if record else torch.no_grad():
+            outs = _DecodeFn.apply(self, mem, mem_lens_d, caps_d, lens1_d, q_z, eps_p, ss_flags, dis_flags, Tc,
+                                   prep.get("sampling"), *self._decode_weights())
         logits, outputs, seqs, slp, attw, pm, pl, pz, putt, hfin, hp, cp = outs
         output = {"seqs": seqs, "logits": logits, "outputs": outputs, "sampled_logprobs": slp,
                   "attn_weights": attw.transpose(1, 2), "p_means": pm, "p_logs": pl, "p_z": pz,

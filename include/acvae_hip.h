@@ -42,6 +42,7 @@ int acvae_abi_version(void);
 #define ACVAE_FLAG_NO_PERSIST 1          /* decode / posterior: the per-step launches instead of the persistent kernels */
 #define ACVAE_FLAG_DEFER_PARAM_GRADS 2   /* acvae_decode_bwd: parameter gradients trail on aux_stream (see there) */
 #define ACVAE_FLAG_NO_ATTN_SPLIT 4       /* acvae_attn_fwd: never the split-over-frames form */
+#define ACVAE_FLAG_ROLLOUT_GRAD 16       /* acvae_decode_fwd_sampled with caps == NULL / acvae_decode_bwd: a differentiable rollout (see there) */
 #define ACVAE_FLAG_TEST_STALL 8          /* test aid: a persistent launch is queued one workgroup short with a short spin
                                             bound, so that its roles give up as they would if part of the grid were not
                                             resident; exercises the abort -> NaN -> status path below */
@@ -203,6 +204,21 @@ int acvae_ls_ce_fwd(const float* logits, int64_t ld_n, int64_t ld_t, const int64
 int acvae_ls_ce_bwd(const float* logits, int64_t ld_n, int64_t ld_t, const int64_t* targets, int64_t tg_sn,
                     const int64_t* lens1, const float* lse, float smoothing, int reduction, const float* grad_out,
                     const float* grad_rows, float* dlogits, int N, int T, int V, void* stream);
+/* Self-critical sequence training, utils/train_util.py:398-409 (scst_Loss / Nscst_Loss; models/seq_train_model.py:57-65):
+ *   loss = mean_n sum_t -sampled_logprobs[n,t] * reward[n] * mask[n,t],  mask[n,0] = 1, mask[n,t] = seqs[n,t-1] != end_idx.
+ * acvae_scst_loss_fwd writes coef[n,t] = -reward[n] * mask[n,t] / N (= d loss / d sampled_logprobs) and the device scalar
+ * loss = sum(coef * sampled_logprobs), summed in a fixed order (one workgroup, no atomics: bit-reproducible); entries whose
+ * coef is 0 are not read into the sum.  All of [N,Tc] contiguous, reward [N] f32, seqs i64.  The library's rollout runs
+ * every step, and rows that have finished hold end_idx, so steps behind a row's <end> count as finished.
+ * acvae_logprob_bwd: d_logits[r,v] = coef[r] * ((v == seqs[r]) - exp(logits[r,v] - lse[r])) over `rows` rows of V floats,
+ * row stride ld (>= V) for logits and d_logits alike; lse / seqs / coef [rows].  lse is NOT recomputed: pass the forward's
+ * own, which acvae_decode_fwd_sampled keeps in `saved` at byte offset acvae_decode_saved_lse_offset(dims) as f32 [N,Tc]
+ * (or acvae_row_logsoftmax_argmax's).  A row whose coef is 0 is written as zeros and its logits are not read.  One read
+ * and one write of the rows, 16-byte accesses when V and ld are multiples of 4 and both bases are 16-B aligned. */
+int acvae_scst_loss_fwd(const float* sampled_logprobs, const int64_t* seqs, const float* reward, int end_idx, float* coef,
+                        float* loss, int N, int Tc, void* stream);
+int acvae_logprob_bwd(const float* logits, int64_t ld, const float* lse, const int64_t* seqs, const float* coef,
+                      float* d_logits, int64_t rows, int V, void* stream);
 /* mean((a-b)^2) over n elements and its backward (runner :317, nn.MSELoss). */
 int acvae_mse_fwd(const float* a, const float* b, float* partials, float* out_scalar, int64_t n, void* stream);
 int acvae_mse_bwd(const float* a, const float* b, const float* grad_out, float* da, float* db, int64_t n, void* stream);
@@ -521,6 +537,8 @@ int acvae_posterior_stack_bwd(const void* const* params, void* const* grads, con
  *   GEMMs, runs the prior chain there and joins before it returns, so on return all work is ordered on `stream`. */
 int64_t acvae_decode_saved_bytes(int N, int Tc, int S, int E, int H, int A, int V, int Eenc);
 int64_t acvae_decode_scratch_bytes(int N, int Tc, int S, int E, int H, int A, int V, int Eenc);
+/* byte offset inside `saved` of the rows' log-sum-exp, f32 [N,Tc], written by every decode forward (-1: bad dims) */
+int64_t acvae_decode_saved_lse_offset(int N, int Tc, int S, int E, int H, int A, int V, int Eenc);
 int acvae_decode_fwd(const void* const* params, const float* mem_in, const int64_t* mem_lens, const int64_t* caps,
                      int64_t ld_caps, const int64_t* lens1, const float* q_z, const float* eps_p,
                      const int* ss_flags_host, const int* dis_flags_host, float* logits, float* outputs, int64_t* seqs,
@@ -554,6 +572,12 @@ int acvae_decode_fwd_sampled(const void* const* params, const float* mem_in, con
  * gradients untouched until aux_stream has drained (mem_in: without an ln projection the products read it in place).  Without the flag (0) everything is ordered on `stream` on return.  Hybrid_VAEModel, which joins
  * the second stream at the end of the backward pass, passes it unless ACVAE_DECODE_DEFER=0 (-0.07 ms per step on the
  * reference configuration). */
+/* Differentiable rollout.  acvae_decode_fwd_sampled with caps == NULL and ACVAE_FLAG_ROLLOUT_GRAD keeps in `saved` what the
+ * backward reads, as the training form does (the transposed weights; the fed words and the finished-row state are kept by
+ * every rollout).  acvae_decode_bwd with the same flag accepts that `saved`: lens1, dis_flags_host and d_q_z may be NULL,
+ * d_p_means_utt must be NULL (a rollout has no utterance head; grads[mean_log_out.*] may be NULL and is left alone), every
+ * step feeds the prior's z to the decoder (never deferred, never persistent), and the sampled words are constants.
+ * Without the flag both calls behave as before: no transposes in a rollout, ACVAE_EINVAL for a backward without lens1. */
 int acvae_decode_bwd_defers(const int* dis_flags_host, int Tc, void* stream, void* aux_stream, int flags);
 int acvae_decode_bwd(const void* const* params, void* const* grads, const float* mem_in, const int64_t* mem_lens,
                      const int64_t* lens1, const float* eps_p, const int* dis_flags_host, const float* outputs,
