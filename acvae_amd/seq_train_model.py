@@ -14,7 +14,10 @@ Where this departs from the reference, on purpose:
   * ``NScstWrapper`` encodes each clip ONCE and repeats the memory rows ``sample_n`` times on the device (the reference's
     runner repeats the features); rows are clip-major (row ``n * sample_n + j``); the replicas of a clip share the
     encoder's dropout masks;
-  * the words come back to the host once per call for the reward (one synchronisation), whatever the number of rollouts.
+  * the words come back to the host once per call for the reward (one synchronisation), whatever the number of rollouts;
+  * with ``scorer=acvae_amd.cider.CiderD(vocabulary)`` they do not come back at all: the reference side of CIDEr-D is prepared
+    and uploaded before the first rollout, the rows are scored on the device behind the last one, and ``reward`` / ``score``
+    are device tensors.
 """
 import copy
 
@@ -54,6 +57,9 @@ class ScstWrapper(nn.Module):
         sample_kwargs = _sample_kwargs(kwargs)
         scorer = train_util._need_scorer(kwargs.get("scorer"))
         output = {}
+        tables = None
+        if train_util._on_device(scorer):                      # queued in front of the rollouts; depends on the references only
+            tables = scorer.prepare(keys, key2refs, "batch", device=next(self.model.parameters()).device)
         self.model.eval()                                      # baseline (:38-41)
         with torch.no_grad():
             greedy = self.model(feats, copy.copy(feat_lens), method="greedy", **sample_kwargs)
@@ -62,7 +68,10 @@ class ScstWrapper(nn.Module):
         sampled = self.model(feats, feat_lens, method=kwargs.get("method", "sample"), **sample_kwargs)
         output["sampled_seqs"] = sampled["seqs"]
         output["sampled_logprobs"] = sampled["sampled_logprobs"]
-        rs = self.get_self_critical_reward(greedy["seqs"], sampled["seqs"], keys, key2refs, vocabulary, scorer)
+        if tables is not None:
+            rs = tables.reward(sampled["seqs"], greedy["seqs"], 1, self.model.start_idx, self.model.end_idx)
+        else:
+            rs = self.get_self_critical_reward(greedy["seqs"], sampled["seqs"], keys, key2refs, vocabulary, scorer)
         output["reward"] = torch.as_tensor(rs["reward"])
         output["score"] = torch.as_tensor(rs["score"])
         output["loss"] = train_util.scst_policy_loss(sampled["sampled_logprobs"], sampled["seqs"], rs["reward"],
@@ -93,11 +102,17 @@ class NScstWrapper(ScstWrapper):
             raise ValueError("NScstWrapper: the leave-one-out baseline needs sample_n >= 2")
         sample_kwargs = _sample_kwargs(kwargs)
         scorer = train_util._need_scorer(kwargs.get("scorer"))
+        keys_n = [k for k in keys for _ in range(sample_n)]
+        tables = None
+        if train_util._on_device(scorer):
+            tables = scorer.prepare(keys_n, key2refs, "rows", device=next(self.model.parameters()).device)
         self.model.train()
         sampled = self.model.rollout_shared_encoder(feats, feat_lens, sample_n, method=kwargs.get("method", "sample"),
                                                     **sample_kwargs)
-        keys_n = [k for k in keys for _ in range(sample_n)]
-        rs = self.get_critical_reward(sampled["seqs"], keys_n, key2refs, vocabulary, scorer, sample_n)
+        if tables is not None:
+            rs = tables.reward(sampled["seqs"], None, sample_n, self.model.start_idx, self.model.end_idx)
+        else:
+            rs = self.get_critical_reward(sampled["seqs"], keys_n, key2refs, vocabulary, scorer, sample_n)
         output = {"sampled_seqs": sampled["seqs"], "sampled_logprobs": sampled["sampled_logprobs"],
                   "reward": torch.as_tensor(rs["reward"]).reshape(-1), "score": torch.as_tensor(rs["score"]).reshape(-1)}
         output["loss"] = train_util.scst_policy_loss(sampled["sampled_logprobs"], sampled["seqs"], rs["reward"],

@@ -4,8 +4,10 @@ masked dict-style losses of ``losses/loss.py`` (:12-70).  Same constructor argum
 signatures; the arithmetic is in libacvae_hip.so (acvae_ls_ce_*, acvae_gauss_kl_*, acvae_mse_*).
 
 Self-critical sequence training: ``scst_Loss`` / ``Nscst_Loss`` (:292-413) and the sentence scoring of
-``utils/score_util.py`` (``compute_batch_score`` / ``compur_batch_score_samplen``).  The reward arithmetic runs on the host
-in numpy as in the reference; the loss and its gradient are acvae_scst_loss_fwd / acvae_logprob_bwd.
+``utils/score_util.py`` (``compute_batch_score`` / ``compur_batch_score_samplen``).  With ``scorer=acvae_amd.cider.CiderD(vocabulary)``
+the reward is computed on the device from the token ids (acvae_ciderd_scores / acvae_ciderd_reward) and the words never reach the
+host; with any other scorer object the reward arithmetic runs on the host in numpy as in the reference.  The loss and its
+gradient are acvae_scst_loss_fwd / acvae_logprob_bwd.
 """
 import numpy as np
 import torch
@@ -199,8 +201,15 @@ class MSELoss(nn.Module):
 def _need_scorer(scorer):
     if scorer is None:
         raise ValueError("SCST needs a scorer: pass scorer=<object with compute_score(references, hypotheses) -> (score, "
-                         "per-key scores)>, e.g. pycocoevalcap's Cider(); this package imports no scorer of its own")
+                         "per-key scores)>, e.g. pycocoevalcap's Cider(), or acvae_amd.cider.CiderD(vocabulary), the package's own "
+                         "CIDEr-D on the device")
     return scorer
+
+
+def _on_device(scorer):
+    """True for the package's own scorer: its reward is computed on the device, from the token ids where they lie."""
+    from .cider import CiderD
+    return isinstance(scorer, CiderD)
 
 
 def _sentence(row, start_idx, end_idx, vocabulary):
@@ -252,7 +261,10 @@ class _ScstLossFn(torch.autograd.Function):
         N, T = slp.shape
         dev = slp.device
         seqs = seqs.to(device=dev, dtype=torch.long).contiguous()
-        reward = _lib.h2d(torch.as_tensor(np.asarray(reward, dtype=np.float32)), dev).contiguous()
+        if torch.is_tensor(reward) and reward.is_cuda:          # a device reward (acvae_ciderd_reward) is used where it lies
+            reward = reward.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            reward = _lib.h2d(torch.as_tensor(np.asarray(reward, dtype=np.float32)), dev).contiguous()
         coef = torch.empty(N, T, device=dev)
         out = _dev_scalar(dev)
         _lib.call("acvae_scst_loss_fwd", slp, seqs, reward, int(end_idx), coef, out, N, T, _lib.current_stream())
@@ -265,7 +277,8 @@ class _ScstLossFn(torch.autograd.Function):
 
 
 def scst_policy_loss(sampled_logprobs, seqs, reward, end_idx):
-    """The loss line shared by scst_Loss, Nscst_Loss and the wrappers of acvae_amd.seq_train_model; reward: host [N]."""
+    """The loss line shared by scst_Loss, Nscst_Loss and the wrappers of acvae_amd.seq_train_model; reward [N]: host
+    values, or a device tensor (the f32 reward of acvae_ciderd_reward)."""
     return _ScstLossFn.apply(sampled_logprobs, seqs, reward, end_idx)
 
 
@@ -300,6 +313,12 @@ class scst_Loss(nn.Module):
         return {"reward": sampled_score - greedy_score, "score": sampled_score}
 
     def forward(self, output, keys, key2refs, vocabulary):
+        if _on_device(self.scorer):            # reward and score stay device tensors; nothing is read back
+            rs = self.scorer.prepare(keys, key2refs, "batch", device=output["sampled_seqs"].device).reward(
+                output["sampled_seqs"], output["greedy_seqs"], 1, self.start_idx, self.end_idx)
+            output["reward"], output["score"] = rs["reward"], rs["score"]
+            output["loss"] = scst_policy_loss(output["sampled_logprobs"], output["sampled_seqs"], rs["reward"], self.end_idx)
+            return output
         rs = self.get_critical_reward(output["greedy_seqs"], output["sampled_seqs"], keys, key2refs, vocabulary,
                                       self.scorer)
         output["reward"] = torch.as_tensor(rs["reward"])
@@ -336,6 +355,11 @@ class Nscst_Loss(nn.Module):
 
     def forward(self, output, keys, key2refs, vocabulary):
         keys = [key for key in keys for _ in range(self.sample_n)]
+        if _on_device(self.scorer):            # device tensors out; "reward" is the mean of the float64 rewards
+            rs = self.scorer.prepare(keys, key2refs, "rows", device=output["sampled_seqs"].device).reward(
+                output["sampled_seqs"], None, self.sample_n, self.start_idx, self.end_idx)
+            loss = scst_policy_loss(output["sampled_logprobs"], output["sampled_seqs"], rs["reward"], self.end_idx)
+            return {"reward": rs["reward_mean"][0], "score": rs["score"], "loss": loss}
         rs = self.get_critical_reward(output["sampled_seqs"], keys, key2refs, vocabulary)
         loss = scst_policy_loss(output["sampled_logprobs"], output["sampled_seqs"], rs["reward"], self.end_idx)
         return {"reward": torch.as_tensor(rs["reward"]).mean(), "score": torch.as_tensor(rs["score"]), "loss": loss}

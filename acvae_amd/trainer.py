@@ -359,8 +359,10 @@ class TrainStep:
     def scst_step(self, feats, feat_lens, keys, key2refs, vocabulary, scorer, sample_n=1, max_length=None, **kwargs):
         """One self-critical training step (models/seq_train_model.py): greedy baseline and sampled rollout through
         ``ScstWrapper`` (``sample_n == 1``) or ``sample_n`` rollouts per clip over one encoder pass through ``NScstWrapper``,
-        then the same backward, clip and fused update as ``step()``.  The reward needs the words on the host: one
-        synchronisation per step, between the rollouts and the loss.  Parameters the loss does not reach (the posterior,
+        then the same backward, clip and fused update as ``step()``.  With ``scorer=acvae_amd.cider.CiderD(vocabulary)`` the
+        reward (CIDEr-D) is computed on the device and the step has no device-to-host copy: ``reward`` / ``score`` in the
+        returned dict are device tensors.  Any other scorer needs the words on the host: one synchronisation per step,
+        between the rollouts and the loss.  Parameters the loss does not reach (the posterior,
         ``mean_log_out``) get no gradient and the optimiser leaves them and their state alone, as torch's does.
         ``kwargs``: ``temperature`` / ``temp`` / ``method`` / ``rng`` as the wrappers take them."""
         if self.world > 1:

@@ -219,6 +219,40 @@ int acvae_scst_loss_fwd(const float* sampled_logprobs, const int64_t* seqs, cons
                         float* loss, int N, int Tc, void* stream);
 int acvae_logprob_bwd(const float* logits, int64_t ld, const float* lse, const int64_t* seqs, const float* coef,
                       float* d_logits, int64_t rows, int V, void* stream);
+/* The SCST reward on the device: CIDEr-D of the rollouts' token rows against reference tables prepared on the host
+ * (acvae_amd/cider.py).  Replaces utils/score_util.py:5-96 (compute_batch_score / compur_batch_score_samplen: words to the
+ * host, strings, pycocoevalcap's dictionary scorer) and the reward lines of models/seq_train_model.py:47-65 and
+ * utils/train_util.py:315-321.  All arithmetic is float64 and every sum has a fixed order (bit-reproducible).
+ *
+ * An n-gram of k <= 4 token ids w_0..w_{k-1} is the 64-bit key sum_j (w_j + 1) << (16 j); ids outside [0, 65534) match
+ * nothing.  Tables (device, the caller's):
+ *   idf_keys / idf_vals [n_idf]   ascending keys of the batch's in-vocabulary reference n-grams and their idf; a key
+ *                                 not found has idf = log_d (ln of the number of documents)
+ *   ref_keys / ref_w [n_entries]  per reference r the slice [ref_off[r], ref_off[r+1]) of ascending keys and
+ *                                 tf * idf weights; ref_norm [n_refs, 4] its norm per order (over ALL its n-grams, the
+ *                                 out-of-vocabulary ones included), ref_len [n_refs] its number of bigrams
+ *   doc_ref [n_docs + 1]          the references of document d are [doc_ref[d], doc_ref[d+1])
+ *   row_doc / row_src [n]         per row its document and the row whose words score it (rows sharing a key)
+ *   len_factor [n_len]            exp(-delta^2 / (2 sigma^2)) for |delta| = 0 .. n_len - 1 (clamped to the last entry)
+ * acvae_ciderd_scores: token rows i64 seqs0 [n, max_length] and, with n_sets == 2, seqs1 [n, max_length] (row stride ld
+ * for both) -> score [n_sets * n]; row s * n + i is scored by the words of row row_src[i] of set s.  A row is cleaned as
+ * the reference's sentence conversion does it: start_idx skipped wherever it stands, cut at the first end_idx.  One
+ * wavefront per row.  Every index read from a table is clamped to its table, so a bad table cannot reach outside one.
+ * A NULL pointer, n <= 0, n_sets not 1 or 2, max_length outside [1, ACVAE_CIDER_MAX_LENGTH], ld < max_length, n_docs <= 0,
+ * n_refs <= 0, n_len <= 0, or a negative n_idf / n_entries (0 is fine: their arrays are then not read) -> ACVAE_EINVAL
+ * before any launch.
+ * acvae_ciderd_reward: sample_n <= 1: reward[i] = score[i] - score[n + i] (sampled - greedy, score [2 n]); sample_n >= 2:
+ * rows clip-major, reward[i] = score[i] - (sum of the clip's scores - score[i]) / (sample_n - 1) (score [n], n a
+ * multiple of sample_n or ACVAE_EINVAL); formed in float64 and rounded once to f32 reward [n]; reward_mean (optional
+ * device double) gets the mean of the float64 rewards.  One workgroup. */
+#define ACVAE_CIDER_MAX_LENGTH 64
+int acvae_ciderd_scores(const int64_t* seqs0, const int64_t* seqs1, int64_t ld, int n, int n_sets, int max_length,
+                        int start_idx, int end_idx, const uint64_t* idf_keys, const double* idf_vals, int n_idf,
+                        double log_d, const uint64_t* ref_keys, const double* ref_w, int n_entries, const int* ref_off,
+                        const double* ref_norm, const int* ref_len, int n_refs, const int* doc_ref, int n_docs,
+                        const int* row_doc, const int* row_src, const double* len_factor, int n_len, double* score,
+                        void* stream);
+int acvae_ciderd_reward(const double* score, int n, int sample_n, float* reward, double* reward_mean, void* stream);
 /* mean((a-b)^2) over n elements and its backward (runner :317, nn.MSELoss). */
 int acvae_mse_fwd(const float* a, const float* b, float* partials, float* out_scalar, int64_t n, void* stream);
 int acvae_mse_bwd(const float* a, const float* b, const float* grad_out, float* da, float* db, int64_t n, void* stream);

@@ -1,11 +1,15 @@
 """Time the self-critical training step (TrainStep.scst_step) on one MI355X.  Not product, not the project's benchmark
 (bench.py measures the cross-entropy step); it writes down numbers that had not been measured.
 
-    python tools/bench_scst.py [--B 32 --T 1000 --steps 20 --warmup 5] [--only n1|n5|n5_repeat]
+    python tools/bench_scst.py [--B 32 --T 1000 --steps 20 --warmup 5] [--only n1|n5|n5_repeat] [--scorer stub|host|device]
 
 Shape: BASELINE configs[1] (B = 32, T = 1000, V = 5000, E = 512), max_length 20, multinomial sampling with the noise made on
-the device (rng="device": the reference's CPU-generator draws of [20, N, 5000] noise cost the host more than the step), a
-stub scorer of negligible cost.  Three steps are timed, warm-up then the mean of `--steps` steps, wall clock around a
+the device (rng="device": the reference's CPU-generator draws of [20, N, 5000] noise cost the host more than the step).
+The scorer: `stub` - of negligible cost (the step without a reward's cost); `host` - CIDEr-D as a dictionary scorer on the
+host (tests/cider_util.py, what a pycocoevalcap-style scorer costs); `device` - acvae_amd.cider.CiderD, the reward computed
+on the device.  `host` and `device` score against synthetic references, 5 per clip of 8-16 words drawn from the 5000-word
+vocabulary with a seed; `device` also reports the host time of CiderD.prepare() per step and the size of its upload.
+Three steps are timed, warm-up then the mean of `--steps` steps, wall clock around a
 synchronised loop:
   n1         sample_n = 1: greedy baseline + one sampled rollout (ScstWrapper)
   n5         sample_n = 5, each clip encoded once, memory rows repeated on the device (NScstWrapper)
@@ -43,6 +47,23 @@ class CheapScorer:
 class Vocabulary:
     def __init__(self):
         self.idx2word = [f"w{i}" for i in range(V)]
+
+
+def make_scorer(kind, vocab):
+    if kind == "stub":
+        return CheapScorer()
+    if kind == "host":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from cider_util import DictCiderD
+        return DictCiderD()
+    from acvae_amd.cider import CiderD
+    return CiderD(vocab)
+
+
+def synthetic_refs(keys, vocab, seed=7, nrefs=5):
+    rng = np.random.default_rng(seed)
+    return {k: [" ".join(vocab.idx2word[int(i)] for i in rng.integers(4, V, rng.integers(8, 17))) for _ in range(nrefs)]
+            for k in keys}
 
 
 def build():
@@ -98,14 +119,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--scorer", default="stub", choices=("stub", "host", "device"))
     args = ap.parse_args()
     B, T = args.B, args.T
     g = torch.Generator().manual_seed(3)
     feats = torch.randn(B, T, 64, generator=g).cuda()
     lens = np.full(B, T)
     keys = [f"clip{i}" for i in range(B)]
-    key2refs = {k: ["w4 w5 w6"] for k in keys}
-    vocab, scorer = Vocabulary(), CheapScorer()
+    vocab = Vocabulary()
+    key2refs = {k: ["w4 w5 w6"] for k in keys} if args.scorer == "stub" else synthetic_refs(keys, vocab)
+    scorer = make_scorer(args.scorer, vocab)
     feats5 = feats.repeat_interleave(5, 0)
     lens5 = np.repeat(lens, 5)
 
@@ -136,19 +159,26 @@ def main():
         for _ in range(args.warmup):
             step()
         ts.synchronize()
+        prep = []
         t0 = time.perf_counter()
         for _ in range(args.steps):
             parts = step()
+            prep.append(getattr(scorer, "last_prepare_s", 0.0))
         ts.synchronize()
         ms = (time.perf_counter() - t0) / args.steps * 1e3
         results[mode] = ms
+        if args.scorer == "device":
+            nbytes = scorer.prepare(keys if mode == "n1" else [k for k in keys for _ in range(5)], key2refs,
+                                    "batch" if mode == "n1" else "rows").nbytes
+            print(f"{mode}: CiderD.prepare() {np.mean(prep) * 1e3:.3f} ms of host time per step (max {np.max(prep) * 1e3:.3f}), "
+                  f"one upload of {nbytes} B")
         ph = Phases(model, ts)
         ph.on = True
         nph = max(2, args.steps // 4)
         for _ in range(nph):
             step()
         ts.synchronize()
-        print(f"{mode}: {ms:.2f} ms per SCST step (B={B}, T={T}, V={V}, E={E}, max_length {MAXLEN}; mean of {args.steps} after "
+        print(f"{mode}: {ms:.2f} ms per SCST step, scorer {args.scorer} (B={B}, T={T}, V={V}, E={E}, max_length {MAXLEN}; mean of {args.steps} after "
               f"{args.warmup} warm-up; loss {float(parts['loss']):.4f})")
         print(f"{mode}: phases, mean of {nph} further steps: {ph.report(nph)}")
         ph.on = False
