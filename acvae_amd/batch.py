@@ -54,6 +54,30 @@ def collate_fn(length_idxs: List = [], sort_idx=None):
     return collate
 
 
+def collate_groups():
+    """The collate for ``CaptionGroupDataset`` items ``(feature [T,F], [caption, ...], audio_id[, AugmentParams])``: B clips
+    with k captions each -> ``[feats [B,Tmax,F], caps [N,Lmax], audio_ids (N), (the B clips' AugmentParams,) clip_index
+    int64 [N], feat_lens [B], cap_lens [N]]`` with N = B * k.  The clips keep the order of the items; the caption rows are
+    sorted by length, descending (stable), and ``clip_index[r]`` names the clip (row of ``feats``) that row r belongs to.  The
+    two length arrays come last, as ``forward_batch`` expects.  Items with different numbers of captions are refused: the
+    shared-encoder step needs equal multiplicities (``Hybrid_VAEModel.forward(..., clip_index=)``)."""
+
+    def collate(items):
+        counts = {len(item[1]) for item in items}
+        if len(counts) != 1 or 0 in counts:
+            raise ValueError(f"collate_groups: every clip must carry the same number (>= 1) of captions, got {sorted(counts)}")
+        feats, feat_lens = _pad_stack([item[0] for item in items])
+        rows = [(cap, clip) for clip, item in enumerate(items) for cap in item[1]]
+        rows.sort(key=lambda row: len(row[0]), reverse=True)
+        caps, cap_lens = _pad_stack([cap for cap, _ in rows])
+        clip_index = np.array([clip for _, clip in rows], dtype=np.int64)
+        audio_ids = tuple(items[clip][2] for clip in clip_index)
+        params = [tuple(item[3] for item in items)] if len(items[0]) > 3 else []
+        return [feats, caps, audio_ids] + params + [clip_index, feat_lens, cap_lens]
+
+    return collate
+
+
 def pack_rows(x, lens):
     """``pack_padded_sequence(x, lens, batch_first=True).data`` for lens sorted descending: rows in time-major order
     (all clips that still run at t = 0, then t = 1, ...).  One device gather; x is [N, T, ...]."""
@@ -97,12 +121,13 @@ def forward_batch_shared_encoder(model, batch, device=None, **kwargs):
     return model.inference_forward(rep, **kwargs)
 
 
-def forward_batch(model, batch, mode, device=None, augment=None, **kwargs):
+def forward_batch(model, batch, mode, device=None, augment=None, clip_index=None, **kwargs):
     """Runner._forward (pytorch_runner_vae.py:76-108).  ``batch`` is what ``collate_fn`` returned.  In evaluation mode
     with beam_size > 1 and a method other than "dbs", ``batch[0]`` (the keys) is replaced by the replicated keys, as
     the reference does in place.  In training mode the uploaded features get the training-time augmentation of
     ``augment`` (one ``AugmentParams`` per clip), or of the batch's own column when ``CaptionDataset(...,
-    augment=...)`` made it (acvae_amd.augment.apply)."""
+    augment=...)`` made it (acvae_amd.augment.apply).  For a batch of ``collate_groups`` (B clips, N caption rows) pass its
+    ``clip_index=batch[-3]``: the training forward then runs the encoder once per clip."""
     assert mode in ("train", "validation", "eval")
     device = device if device is not None else next(model.parameters()).device
     if mode == "train":
@@ -114,6 +139,8 @@ def forward_batch(model, batch, mode, device=None, augment=None, **kwargs):
             feats = _augment.apply(feats, batch[-2], augment)
         caps, feat_lens, cap_lens = batch[1], batch[-2], batch[-1]
         lens1 = np.asarray(cap_lens) - 1
+        if clip_index is not None:
+            kwargs["clip_index"] = clip_index
         output = model(feats, feat_lens, caps, cap_lens, **kwargs)
         output["packed_logits"] = pack_rows(output["logits"], lens1)           # :94-96
         output["targets"] = pack_rows(caps[:, 1:], lens1)                      # :89-90

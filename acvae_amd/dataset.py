@@ -2,7 +2,8 @@
 -> training / evaluation items, and the order in which (clip, caption) pairs are visited.
 
 Mirrors ``datasets/caption_dataset.py``: ``CaptionEvalDataset`` (:20-52), ``CaptionDataset`` (:66-112),
-``CaptionSampler`` (:199-224), ``CaptionDistributedSampler`` (:226-276).  The reference reads the log-mel features
+``CaptionSampler`` (:199-224), ``CaptionDistributedSampler`` (:226-276).  ``CaptionGroupDataset`` / ``CaptionGroupSampler`` have no
+counterpart there: they visit every clip once per epoch with k of its captions, for the step that encodes a clip once.  The reference reads the log-mel features
 ``[T, 64]`` of an ``audio_id`` from HDF5 files (h5py is not available here); these classes take any mapping or callable
 ``audio_id -> array`` instead (a dict of arrays, ``numpy.load`` on per-clip files, an HDF5 group, ...).  The annotation
 format is the reference's: ``{"audios": [{"audio_id", "captions": [{"tokens": "a b c", ...}, ...]}, ...]}``.
@@ -73,6 +74,31 @@ class CaptionDataset(CaptionEvalDataset):
         return sum(len(item["captions"]) for item in self._caption_info)
 
 
+class CaptionGroupDataset(CaptionDataset):
+    """Items ``(feature, [caption ids, ...], audio_id)`` addressed by ``(audio_idx, (cap_idx, ...))``: one clip with several
+    of its captions, for the training step that shares one encoder pass among them (``CaptionGroupSampler``,
+    ``acvae_amd.batch.collate_groups``, ``TrainStep.step(..., clip_index=)``).  The feature is fetched ONCE per item, and
+    ``augment`` crops / draws for it once (the 4th field, as in ``CaptionDataset``), so the clip's captions see one
+    augmented clip.  The length is the number of clips."""
+
+    def __getitem__(self, index: Tuple[int, Sequence[int]]):
+        audio_idx, cap_idxs = index
+        audio_id = self._audio_ids[audio_idx]
+        voc = self._vocabulary
+        captions = []
+        for cap_idx in cap_idxs:
+            tokens = self._caption_info[audio_idx]["captions"][cap_idx]["tokens"].split()
+            captions.append(torch.as_tensor([voc("<start>")] + [voc(token) for token in tokens] + [voc("<end>")]))
+        feature = self._feature(audio_id)
+        if self._augment is None:
+            return feature, captions, audio_id
+        feature, params = self._augment.draw(feature.numpy())
+        return torch.as_tensor(feature), captions, audio_id, params
+
+    def __len__(self):
+        return len(self._caption_info)
+
+
 def caption_pairs(caption_info: List, audio_subset_indices: Optional[Sequence[int]] = None) -> List[Tuple[int, int]]:
     """All (audio_idx, cap_idx) pairs, clip-major (the element list both samplers build)."""
     audio_idxs = audio_subset_indices if audio_subset_indices is not None else range(len(caption_info))
@@ -99,6 +125,36 @@ class CaptionSampler(torch.utils.data.Sampler):
         if self._num_sample is None:
             self.__iter__()
         return self._num_sample
+
+
+class CaptionGroupSampler(torch.utils.data.Sampler):
+    """One entry ``(audio_idx, (cap_idx, ...))`` per clip and epoch: ``caps_per_clip`` of the clip's captions drawn without
+    replacement (in drawn order), the clips shuffled when asked.  Every draw goes through Python's ``random``, the generator
+    ``CaptionSampler`` shuffles with, so ``random.seed`` fixes an epoch.  A clip with fewer captions than ``caps_per_clip``
+    is refused at construction: the shared-encoder step needs the same number of rows for every clip."""
+
+    def __init__(self, data_source: CaptionDataset, caps_per_clip: int, audio_subset_indices: Optional[Sequence[int]] = None,
+                 shuffle: bool = False):
+        self._caption_info = data_source._caption_info
+        self._k = int(caps_per_clip)
+        self._audio_idxs = list(audio_subset_indices if audio_subset_indices is not None else range(len(self._caption_info)))
+        self._shuffle = shuffle
+        if self._k < 1:
+            raise ValueError(f"caps_per_clip must be at least 1, got {caps_per_clip}")
+        for a in self._audio_idxs:
+            n = len(self._caption_info[a]["captions"])
+            if n < self._k:
+                raise ValueError(f"clip {self._caption_info[a]['audio_id']!r} has {n} captions, fewer than "
+                                 f"caps_per_clip={self._k}")
+
+    def __iter__(self):
+        order = list(self._audio_idxs)
+        if self._shuffle:
+            random.shuffle(order)
+        return iter([(a, tuple(random.sample(range(len(self._caption_info[a]["captions"])), self._k))) for a in order])
+
+    def __len__(self):
+        return len(self._audio_idxs)
 
 
 class CaptionDistributedSampler(torch.utils.data.Sampler):

@@ -295,9 +295,11 @@ class TrainStep:
             self.exchange.ready(2)
 
     # ------------------------------------------------------------------ one optimiser step
-    def forward_loss(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, kl_weight=0.5):
-        """Runner._forward(mode='train') + the loss line (:315-318).  Returns (loss, parts, output)."""
-        out = self.model(feats, feat_lens, caps, cap_lens, ss_ratio=ss_ratio, dis_ratio=dis_ratio)
+    def forward_loss(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, kl_weight=0.5, clip_index=None):
+        """Runner._forward(mode='train') + the loss line (:315-318).  Returns (loss, parts, output).  ``clip_index``: see
+        ``step``."""
+        share = {} if clip_index is None else {"clip_index": clip_index}
+        out = self.model(feats, feat_lens, caps, cap_lens, ss_ratio=ss_ratio, dis_ratio=dis_ratio, **share)
         staged = getattr(self.model, "staged", None) or {}
         lens1 = staged.get("lens1_d")
         if lens1 is None:
@@ -335,9 +337,16 @@ class TrainStep:
         d._acvae_ready = ev
         return d
 
-    def step(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, kl_weight=0.5, augment=None):
+    def step(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, kl_weight=0.5, augment=None,
+             clip_index=None):
         """One training step.  ``augment``: one ``acvae_amd.augment.AugmentParams`` per clip (a batch's column from
-        ``CaptionDataset(..., augment=...)``): the rolls and masks run on the device before the encoder."""
+        ``CaptionDataset(..., augment=...)``): the rolls and masks run on the device before the encoder.
+
+        ``clip_index`` (``Hybrid_VAEModel.forward``): one encoder pass shared by the captions of a clip.  ``feats`` /
+        ``feat_lens`` (and ``augment``) then hold the B clips, ``caps`` / ``cap_lens`` the N = B * k caption rows, and
+        ``clip_index[r]`` names the clip of row r (``acvae_amd.batch.collate_groups`` builds such batches).  The loss and
+        the gradients are those of the step on the batch with every clip repeated k times.  Under data parallelism nothing
+        changes: the graph has one more node between the decode loop and the encoder."""
         self.sync_buffers()
         ready = getattr(feats, "_acvae_ready", None)
         if ready is not None:                       # a batch uploaded by prefetch(): order this step behind its copy
@@ -353,7 +362,7 @@ class TrainStep:
         self._decode_deferred = self._projemb_seen = False
         for p in self.order:
             p.grad = None                                             # optimizer.zero_grad(set_to_none=True)
-        loss, parts, _ = self.forward_loss(feats, feat_lens, caps, cap_lens, ss_ratio, dis_ratio, kl_weight)
+        loss, parts, _ = self.forward_loss(feats, feat_lens, caps, cap_lens, ss_ratio, dis_ratio, kl_weight, clip_index)
         return self._backward_and_update(loss, parts)
 
     def scst_step(self, feats, feat_lens, keys, key2refs, vocabulary, scorer, sample_n=1, max_length=None, **kwargs):

@@ -3,6 +3,9 @@ global-constraint AC-VAE.  Same constructor ``Hybrid_VAEModel(Audioencoder, Text
 posterior_model=, posterior_args=, prior_model=, prior_args=)``, same forward contract
 
     forward(feats, feat_lens, caps, cap_lens, ss_ratio=, dis_ratio=)   -> training dict
+    forward(feats [B], feat_lens [B], caps [N], cap_lens [N], ss_ratio=, dis_ratio=, clip_index= [N])
+                                                                       -> training dict of N rows over ONE encoder pass
+                                                                          of the B clips (no counterpart in the reference)
     forward(feats, feat_lens, method="greedy", max_length=, ...)       -> inference dict ("seqs", ...)
 
 and the same state-dict names.  Host code here only draws the random decisions in the reference's
@@ -132,6 +135,60 @@ class _DecodeFn(torch.autograd.Function):
         ctx.saved = None
         outs = [next((g for p, g in zip(params, grads) if p is w), None) for w in model._decode_weights()]
         return (None, d_mem, None, None, None, d_qz, None, None, None, None, None, *outs)
+
+
+def clip_rows(clip_index, n_clips, n_rows):
+    """Validate the ``clip_index`` of a shared-encoder training forward (row r of the captions belongs to clip
+    ``clip_index[r]``) and build the lists its kernels read: -> (index int64 [N], offsets int32 [B + 1], rows int32 [N], k),
+    ``offsets`` / ``rows`` being the CSR lists of each clip's rows, ascending within a clip.  Raises ValueError for anything
+    but an integer array of N entries in [0, B) in which every clip occurs the same number of times k >= 1: the shared pass
+    equals the step on the repeated batch because the BatchNorm statistics over the B clips are those over the repeated batch
+    and its backward means scale by exactly k, which holds only for equal multiplicities."""
+    if isinstance(clip_index, torch.Tensor):
+        clip_index = clip_index.detach().cpu().numpy()
+    idx = np.asarray(clip_index)
+    if idx.dtype == object or idx.dtype == bool or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError(f"clip_index must be an integer array, got dtype {idx.dtype}")
+    if idx.ndim != 1 or idx.shape[0] != n_rows:
+        raise ValueError(f"clip_index must have one entry per caption row ({n_rows}), got shape {tuple(idx.shape)}")
+    if n_clips < 1 or n_rows < 1:
+        raise ValueError(f"clip_index: need at least one clip and one caption row, got {n_clips} clips and {n_rows} rows")
+    idx = idx.astype(np.int64)
+    if int(idx.min()) < 0 or int(idx.max()) >= n_clips:
+        raise ValueError(f"clip_index entries must lie in [0, {n_clips}), got [{int(idx.min())}, {int(idx.max())}]")
+    counts = np.bincount(idx, minlength=n_clips)
+    if int(counts.min()) != int(counts.max()):
+        raise ValueError(f"clip_index: every clip must occur the same number of times (got between {int(counts.min())} and "
+                         f"{int(counts.max())} rows per clip): BatchNorm over the clips equals BatchNorm over the repeated batch "
+                         "only for equal multiplicities")
+    offsets = np.zeros(n_clips + 1, dtype=np.int32)
+    np.cumsum(counts, out=offsets[1:])
+    rows = np.argsort(idx, kind="stable").astype(np.int32)
+    return idx, offsets, rows, int(counts[0])
+
+
+class _ShareRowsFn(torch.autograd.Function):
+    """Encoder memory of the B clips -> the N caption rows (acvae_rows_gather); the backward folds the rows' memory gradients
+    into their clips' in ascending row order (acvae_rows_fold: no atomics, bit-reproducible)."""
+
+    @staticmethod
+    def forward(ctx, src, index_d, offsets_d, rows_d):
+        src = src.contiguous()
+        B, N, R = src.shape[0], index_d.shape[0], src[0].numel()
+        dst = torch.empty((N,) + tuple(src.shape[1:]), device=src.device)
+        _lib.call("acvae_rows_gather", src, index_d, dst, B, N, R, _lib.current_stream())
+        ctx.dims, ctx.shape = (B, N, R), tuple(src.shape)
+        ctx.save_for_backward(offsets_d, rows_d)
+        return dst
+
+    @staticmethod
+    def backward(ctx, d_dst):
+        offsets_d, rows_d = ctx.saved_tensors
+        B, N, R = ctx.dims
+        d_dst = d_dst.contiguous().float()
+        d_src = torch.empty(ctx.shape, device=d_dst.device)
+        _lib.call("acvae_rows_fold", d_dst, offsets_d, rows_d, d_src, B, N, R, _lib.current_stream())
+        return d_src, None, None, None
 
 
 class Hybrid_VAEModel(CaptionModel):
@@ -379,10 +436,26 @@ class Hybrid_VAEModel(CaptionModel):
         return self.stepwise_forward(encoded, None, None, **kwargs)     # greedy / "gumbel" / anything else = multinomial
 
     def forward(self, *input, **kwargs):
-        """models/vae_model.py:732-760"""
+        """models/vae_model.py:732-760.
+
+        ``clip_index`` (training forward only, default None = the reference's contract, one feature row per caption row):
+        several captions per clip over one encoder pass.  ``feats`` is then [B, T, F] and ``feat_lens`` has B entries (still
+        divided in place by the encoder), ``caps`` / ``cap_lens`` have N = B * k rows and ``clip_index[r]`` names the clip of
+        row r, in any order (``acvae_amd.batch.collate_groups`` sorts the rows by caption length).  Every output has N rows.
+        The loss and every parameter gradient are those of the forward on ``feats[clip_index]``; see ``_share_rows`` for why
+        and for the two departures (shared dropout masks, ``running_var``'s Bessel factor).  ``clip_rows`` says what is
+        refused (ValueError)."""
         self._forward_token = getattr(self, "_forward_token", 0) + 1     # per-forward caches (decoder.embedding_table)
+        clip_index = kwargs.pop("clip_index", None)
+        if clip_index is not None and len(input) != 4:
+            raise ValueError("clip_index belongs to the training forward (feats, feat_lens, caps, cap_lens)")
         if len(input) == 4:
             feats, feat_lens, caps, cap_lens = input
+            # one encoder pass shared by the clips' captions: B clips, N = B * k caption rows (see _share_rows)
+            share = None if clip_index is None else clip_rows(clip_index, len(feat_lens), len(cap_lens))
+            if share is not None and feats.shape[0] != len(feat_lens):
+                raise ValueError(f"clip_index: {feats.shape[0]} feature rows for {len(feat_lens)} feature lengths")
+            n_rows = feats.shape[0] if share is None else len(cap_lens)
             # The posterior (42 serial BiGRU steps of tiny kernels) does not depend on the encoder: run it on a side
             # HIP stream beside the MFMA-bound encoder; autograd replays its backward on that stream too, where it
             # overlaps with the encoder backward.
@@ -397,16 +470,18 @@ class Hybrid_VAEModel(CaptionModel):
                 # of the posterior's randn (text_encoder.py:190,196); uploaded from the page-locked ring, in front of the encoder
                 q, Tc = self.qnet, int(lens1.max())
                 if q_keep is None:
-                    q_keep = _lib.h2d_fill((q.num_layers - 1, feats.shape[0], Tc, 2 * q.hidden_size), torch.uint8,
+                    q_keep = _lib.h2d_fill((q.num_layers - 1, n_rows, Tc, 2 * q.hidden_size), torch.uint8,
                                            feats.device, lambda buf: text_encoder.posterior_keep_masks(
                                                lens1, Tc, q.hidden_size, q.num_layers, q_p, out=buf))
                 else:
                     q_keep = _lib.h2d(q_keep, feats.device, torch.uint8).contiguous()
             if eps_q is None:          # same generator order as the reference: the posterior's randn precedes the per-step draws
-                eps_q = torch.randn(feats.shape[0], int(lens1.max()), self.decoder.embed_size)
+                eps_q = torch.randn(n_rows, int(lens1.max()), self.decoder.embed_size)
             # Host-side draws and the small H2D copies of the decode loop go in front of the encoder launch: a
             # pageable-memory copy waits for the stream to drain, which behind the encoder would stall the host.
-            prep = self._host_prepare(feats.shape[0], feats.device, caps, cap_lens, kwargs)
+            prep = self._host_prepare(n_rows, feats.device, caps, cap_lens, kwargs)
+            if share is not None:                                  # (index on the host, index / offsets / rows on the device)
+                share = (share[0],) + tuple(_lib.h2d(a, feats.device) for a in share[:3])
             if side is not main:
                 side.wait_stream(main)
                 prep["caps_d"].record_stream(side)
@@ -417,6 +492,8 @@ class Hybrid_VAEModel(CaptionModel):
             # the posterior's kernels and its gradient bucket are queued before the long encoder backward: under data
             # parallelism the 20 MB posterior bucket then travels beside the encoder backward instead of behind it.
             encoded = self.encoder(feats, feat_lens)
+            if share is not None:
+                encoded = self._share_rows(encoded, *share)
             with torch.cuda.stream(side):
                 qnetout = self.qnet(prep["caps_d"], cap_lens, eps=eps_q, keep=q_keep)
             if side is not main:
@@ -432,6 +509,25 @@ class Hybrid_VAEModel(CaptionModel):
             encoded = self.encoder(feats, feat_lens)
             return self.inference_forward(encoded, **kwargs)
         raise Exception("Number of input should be either 4 (feats, feat_lens, caps, cap_lens) or 2 (feats, feat_lens)")
+
+    def _share_rows(self, encoded, index, index_d, offsets_d, rows_d):
+        """The encoder's outputs for the B clips -> the N caption rows of ``forward(..., clip_index=)``: ``audio_embeds`` through
+        the autograd node that folds the rows' gradients back into the clips', the pooled embedding and the lengths (known on
+        the host) gathered likewise.  With an ``ln`` projection the gather acts on the encoder's own (2048-wide) rows and the
+        projection stays per row, inside the decode call.
+
+        The loss and every parameter gradient equal those of the 4-input forward on the batch in which each clip is repeated
+        k times: BatchNorm's batch mean and biased variance over the clips are those over the repeated batch, the ReLU
+        decisions are the same, every layer is linear in the upstream gradient and the BatchNorm-backward means scale by
+        exactly k.  Two departures from that step: the rows of a clip share the encoder's dropout masks, and
+        ``running_var`` carries the Bessel factor M / (M - 1) of the B clips, not kM / (kM - 1)."""
+        mem, pooled = encoded["audio_embeds"], encoded["audio_embeds_pooled"].detach().contiguous()
+        B, N = mem.shape[0], index_d.shape[0]
+        pooled_rows = torch.empty(N, pooled.shape[1], device=pooled.device)
+        _lib.call("acvae_rows_gather", pooled, index_d, pooled_rows, B, N, pooled.shape[1], _lib.current_stream())
+        lens = torch.as_tensor(encoded["audio_embeds_lens"])[torch.from_numpy(index)]
+        return {"audio_embeds": _ShareRowsFn.apply(mem, index_d, offsets_d, rows_d), "audio_embeds_pooled": pooled_rows,
+                "state": None, "audio_embeds_lens": lens, "audio_embeds_lens_dev": _lib.h2d(lens, mem.device, torch.long)}
 
     def rollout_shared_encoder(self, feats, feat_lens, sample_n, **kwargs):
         """A 2-input forward with ``sample_n`` rollouts per clip that runs the encoder ONCE per clip: the memory rows are

@@ -673,6 +673,24 @@ int acvae_spec_augment(const float* in, float* out, const int* lens, const int* 
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Rows of a [*, R] matrix gathered by an index, and the adjoint: rows folded into the row they came from.  The training
+ * step with several captions per clip (Hybrid_VAEModel.forward(..., clip_index=)) runs the encoder once over the B clips
+ * and gathers its memory [B, R = S * C] into the N caption rows; the backward folds the N rows' gradients into the B clips'.
+ *   acvae_rows_gather: dst[r, :] = src[index[r], :] for r < N.  src [B, R], index int64 [N] (device memory), dst [N, R].
+ *                      A row whose index lies outside [0, B) is written as zeros (nothing outside src is read).
+ *   acvae_rows_fold:   dst[c, :] = 0 + src[rows[offsets[c]], :] + src[rows[offsets[c] + 1], :] + ... for c < B, plain fp32
+ *                      additions in exactly that order.  src [N, R], dst [B, R]; offsets int32 [B + 1] / rows int32 [N] are the
+ *                      CSR lists of each clip's rows, built by the caller on the host (ascending within a clip for the
+ *                      adjoint of the gather).  A clip without rows gets zeros.  No atomics and one owner per output
+ *                      element: bit-reproducible.  A row number outside [0, N) contributes zero.
+ * Memory-bound: one thread per 16-byte chunk of a row / clip, no workspace, no state.  NULL pointers, B < 1, N < 1, R < 4 or
+ * R % 4 != 0 -> ACVAE_EINVAL; src / dst not 16-byte aligned -> ACVAE_EALIGN; both before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+int acvae_rows_gather(const float* src, const int64_t* index, float* dst, int B, int N, int64_t R, void* stream);
+int acvae_rows_fold(const float* src, const int* offsets, const int* rows, float* dst, int B, int N, int64_t R,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Opt-in kernel timing (bench.py's live roofline figure): while enabled, the conv launches are bracketed
  * by HIP events on their stream; acvae_prof_read waits for them and returns the summed duration and the
  * launch count of a tag, then clears it.  Tags: 0 = conv3x3 implicit GEMM (forward + data gradient),
