@@ -1478,3 +1478,180 @@ extern "C" int acvae_beam_search(const void* const* params, const float* mem, co
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }
+
+// ==========================================================================================
+// Ensemble decoding as ONE call: BaseRunner._ensemble_batch / _ensemble_batch_beam_search (runners/base_runner.py:562-694)
+// carried onto Hybrid_VAEModel's step (prior step -> z -> decoder step, models/vae_model.py:896-995; the reference's own
+// ensemble code calls model.decoder without z).  Every member keeps its own memory, attention projections and recurrent
+// states; all are fed the same word; acvae_ensemble_mix averages their word probabilities (base_runner.py:616-618,
+// 675-680) and the word is picked from the average:
+//   beam   - flat top-k over beam * V per clip at every step (the rows of a clip differ in z from t = 0 on, so the
+//            reference's "row 0 only at t = 0", :681-682, does not carry over), states gathered by parent once per member,
+//            beam 0 traced back at the end: with M = 1 the launches of acvae_beam_search in the same order, with
+//            acvae_ensemble_mix in the place of acvae_row_logsoftmax_argmax + acvae_logprob_add (bit-equal at M = 1);
+//   greedy - the mix kernel's own argmax; a row that has produced end_idx keeps emitting and feeding it, and all
+//            max_length steps run without a host read-back: seqs prefilled with end_idx, as :584, 622-630 leave it.
+// Members run one after the other on the one stream.
+// ==========================================================================================
+namespace {
+struct EnsMember { long step, encd, encp, h, hp, cp, lz, mean, logv, z, h2, hp2, cp2, attp, attw, logits, rnn; };
+struct EnsLayout { EnsMember m[ACVAE_ENSEMBLE_MAX]; long scores, topk, best, words, total; };
+int ens_layout(int M, int N, int beam, int T, const int* S, const int* E, const int* H, const int* A, int V, EnsLayout& L) {
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A || N <= 0 || beam <= 0 || T <= 0) return ACVAE_EINVAL;
+  const long R = (long)N * beam;
+  if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
+  Bump b;
+  for (int m = 0; m < M; ++m) {
+    StepLayout sl;
+    ACVAE_TRY(step_layout((int)R, S[m], E[m], H[m], A[m], V, sl));
+    EnsMember& o = L.m[m];
+    const long e = E[m], h = H[m];
+    o.step = b.take(sl.total);
+    o.encd = b.take((long)N * S[m] * A[m]);
+    o.encp = b.take((long)N * S[m] * e);
+    o.h = b.take(R * h); o.hp = b.take(R * e); o.cp = b.take(R * e); o.lz = b.take(R * e);
+    o.mean = b.take(R * e); o.logv = b.take(R * e); o.z = b.take(R * e);
+    o.h2 = b.take(R * h); o.hp2 = b.take(R * e); o.cp2 = b.take(R * e);
+    o.attp = b.take(R * S[m]);
+    o.attw = b.take(R * S[m]);
+    o.logits = b.take(R * V);
+    o.rnn = b.take(R * 3 * e);
+  }
+  L.scores = b.take(R * V);
+  L.topk = b.take(R);
+  L.best = b.take(R);
+  L.words = b.take(2 * ((long)(3 * T + 2) * R));        // int64: word [R], argmax [R], per step idx / parent / word [T][R]
+  L.total = b.off;
+  return ACVAE_OK;
+}
+
+// greedy bookkeeping of one step (base_runner.py:618-628): a finished row keeps end_idx
+__global__ void ens_greedy_pick_kernel(const int64_t* __restrict__ arg, const float* __restrict__ best,
+                                       int64_t* __restrict__ seqs, float* __restrict__ logprobs, int64_t* __restrict__ word,
+                                       int64_t end_idx, int t, int T, int R) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  int64_t w = arg[r];
+  if (t > 0 && seqs[(long)r * T + t - 1] == end_idx) w = end_idx;
+  seqs[(long)r * T + t] = w;
+  logprobs[(long)r * T + t] = best[r];
+  word[r] = w;
+}
+// one thread per clip: beam 0's words from the last step back to the first, and its final score
+__global__ void ens_trace_kernel(const int64_t* __restrict__ parent, const int64_t* __restrict__ word,
+                                 const float* __restrict__ topk, int64_t* __restrict__ seqs, float* __restrict__ logprobs,
+                                 long hist_stride, int beam, int T, int N) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  long r = (long)n * beam;
+  logprobs[n] = topk[r];
+  for (int t = T - 1; t >= 0; --t) {
+    seqs[(long)n * T + t] = word[t * hist_stride + r];
+    r = parent[t * hist_stride + r];
+  }
+}
+}  // namespace
+
+extern "C" int64_t acvae_ensemble_search_scratch_bytes(int M, int N, int beam, int max_length, const int* S, const int* E,
+                                                       const int* H, const int* A, int V) {
+  EnsLayout L;
+  return ens_layout(M, N, beam, max_length, S, E, H, A, V, L) == ACVAE_OK ? L.total * 4 : -1;
+}
+
+extern "C" int acvae_ensemble_search(const void* const* const* params, const float* const* mem,
+                                     const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
+                                     const int* H, const int* A, int M, int64_t start_idx, int64_t end_idx, int greedy,
+                                     int64_t* seqs, float* logprobs, void* scratch_v, int64_t scratch_bytes, int N, int beam,
+                                     int max_length, int V, void* stream) {
+  // ---- refusals, all before the first launch
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !params || !mem || !mem_lens || !eps || !S || !E || !H || !A) return ACVAE_EINVAL;
+  for (int m = 0; m < M; ++m)
+    if (!params[m] || !mem[m] || !mem_lens[m] || !eps[m] || H[m] != E[m]) return ACVAE_EINVAL;   // the prior LSTM is E wide
+  if (!seqs || !logprobs || !scratch_v) return ACVAE_EINVAL;
+  if (beam > 64 || (greedy && beam != 1)) return ACVAE_EINVAL;
+  if (start_idx < 0 || start_idx >= V || end_idx < 0 || end_idx >= V) return ACVAE_EINVAL;
+  EnsLayout L;
+  ACVAE_TRY(ens_layout(M, N, beam, max_length, S, E, H, A, V, L));
+  if (!greedy && beam > 16) return ACVAE_EUNSUPPORTED;   // acvae_topk_flat_batched selects k <= 16: refused here, not mid-call
+  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
+
+  const int R = N * beam, T = max_length;
+  float* sc = (float*)scratch_v;
+  hipStream_t s = (hipStream_t)stream;
+  StepLayout SL[ACVAE_ENSEMBLE_MAX];
+  // per member: the buffers that change hands from step to step (greedy swaps them, the beam search gathers by parent)
+  float *h[ACVAE_ENSEMBLE_MAX], *hp[ACVAE_ENSEMBLE_MAX], *cp[ACVAE_ENSEMBLE_MAX], *lz[ACVAE_ENSEMBLE_MAX];
+  float *h2[ACVAE_ENSEMBLE_MAX], *hp2[ACVAE_ENSEMBLE_MAX], *cp2[ACVAE_ENSEMBLE_MAX], *z[ACVAE_ENSEMBLE_MAX];
+  const float* logit_ptr[ACVAE_ENSEMBLE_MAX];
+  int64_t logit_ld[ACVAE_ENSEMBLE_MAX];
+  for (int m = 0; m < M; ++m) {
+    const EnsMember& o = L.m[m];
+    ACVAE_TRY(step_layout(R, S[m], E[m], H[m], A[m], V, SL[m]));
+    float* ssc = sc + o.step;
+    Ctx st{s, ssc + SL[m].skws};
+    ACVAE_TRY(acvae_skinny_ws_reset(st.skws, st.s));
+    ACVAE_TRY(step_attws_reset(ssc, SL[m], st.s));
+    ACVAE_TRY(acvae_attn_precompute(params[m], 0, mem[m], sc + o.encd, N, S[m], E[m], H[m], A[m], stream));
+    ACVAE_TRY(acvae_attn_precompute(params[m], 1, mem[m], sc + o.encp, N, S[m], E[m], E[m], E[m], stream));
+    h[m] = sc + o.h; hp[m] = sc + o.hp; cp[m] = sc + o.cp; lz[m] = sc + o.lz;
+    h2[m] = sc + o.h2; hp2[m] = sc + o.hp2; cp2[m] = sc + o.cp2; z[m] = sc + o.z;
+    ACVAE_TRY(zero(h[m], (long)R * H[m], s));
+    ACVAE_TRY(zero(hp[m], (long)R * E[m], s));
+    ACVAE_TRY(zero(cp[m], (long)R * E[m], s));
+    ACVAE_TRY(zero(lz[m], (long)R * E[m], s));
+    logit_ptr[m] = sc + o.logits;
+    logit_ld[m] = V;
+  }
+  float* topk = sc + L.topk;
+  float* best = sc + L.best;
+  int64_t* word = (int64_t*)(sc + L.words);
+  int64_t* arg = word + R;
+  int64_t* hist = arg + R;                               // [T][3][R]: flat index, parent row, word (beam search)
+  ACVAE_TRY(zero(topk, R, s));
+  hipLaunchKernelGGL(fill_words_kernel, dim3((R + 255) / 256), dim3(256), 0, s, word, start_idx, R);
+  const int64_t* w_t = word;
+  for (int t = 0; t < T; ++t) {
+    int64_t* idx_t = hist + (long)t * 3 * R;
+    int64_t* par_t = idx_t + R;
+    int64_t* nxt_t = par_t + R;
+    for (int m = 0; m < M; ++m) {
+      const EnsMember& o = L.m[m];
+      float* ssc = sc + o.step;
+      Ctx st{s, ssc + SL[m].skws};
+      ACVAE_TRY(prior_step(params[m], w_t, mem[m], mem_lens[m], sc + o.encp, hp[m], cp[m], lz[m],
+                           eps[m] + (long)t * R * E[m], sc + o.mean, sc + o.logv, z[m], hp2[m], cp2[m], sc + o.attp, ssc,
+                           SL[m], N, beam, S[m], E[m], V, st));
+      ACVAE_TRY(decoder_step(params[m], w_t, h[m], mem[m], mem_lens[m], sc + o.encd, z[m], sc + o.logits, h2[m],
+                             sc + o.attw, sc + o.rnn, ssc, SL[m], N, beam, S[m], E[m], H[m], A[m], V, st));
+    }
+    if (greedy) {
+      ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, nullptr, 0, arg, best, 1, R, V, stream));
+      hipLaunchKernelGGL(ens_greedy_pick_kernel, dim3((R + 255) / 256), dim3(256), 0, s, arg, best, seqs, logprobs, word,
+                         end_idx, t, T, R);
+      for (int m = 0; m < M; ++m) {                      // the new states become the next step's previous ones
+        float* x;
+        x = h[m]; h[m] = h2[m]; h2[m] = x;
+        x = hp[m]; hp[m] = hp2[m]; hp2[m] = x;
+        x = cp[m]; cp[m] = cp2[m]; cp2[m] = x;
+        x = lz[m]; lz[m] = z[m]; z[m] = x;
+      }
+      continue;
+    }
+    ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, topk, sc + L.scores, V, nullptr, nullptr, 0, R, V, stream));
+    ACVAE_TRY(acvae_topk_flat_batched(sc + L.scores, (int64_t)beam * V, (int64_t)beam * V, beam, V, topk, idx_t, par_t,
+                                      nxt_t, N, beam, stream));
+    if (t + 1 < T) {                                     // vae_model.py:961-968: next step's states follow their parents
+      for (int m = 0; m < M; ++m) {
+        GatherTable g;
+        g.add({h2[m], h[m], H[m]}); g.add({hp2[m], hp[m], E[m]}); g.add({cp2[m], cp[m], E[m]}); g.add({z[m], lz[m], E[m]});
+        hipLaunchKernelGGL(beam_gather_kernel, dim3(R, g.n), dim3(256), 0, s, g, par_t);
+      }
+      w_t = nxt_t;
+    }
+  }
+  if (!greedy)
+    hipLaunchKernelGGL(ens_trace_kernel, dim3((N + 255) / 256), dim3(256), 0, s, hist + R, hist + 2 * R, topk, seqs, logprobs,
+                       3L * R, beam, T, N);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}

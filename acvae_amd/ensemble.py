@@ -1,0 +1,163 @@
+"""Ensemble decoding: greedy and beam search over several trained models at once.
+
+Mirrors ``BaseRunner.ensemble`` / ``_ensemble_batch`` / ``_ensemble_batch_beam_search`` (``runners/base_runner.py:397-694``,
+inherited by the VAE runner): at every step the members' word probabilities are averaged (mean of softmax, then log,
+:616-618, 675-680) and the word is picked from the average.  The whole search is ONE library call
+(``acvae_ensemble_search``): per step every member runs its prior step and its decoder step on its own states, one
+``acvae_ensemble_mix`` launch forms the mixture's log-probabilities, and the pick is the mix kernel's own argmax (greedy) or
+the flat top-k of ``acvae_beam_search`` (beam).
+
+The reference's ensemble code cannot run a ``Hybrid_VAEModel`` (it calls ``model.decoder`` without ``z`` and never runs
+the prior network), so its mixing rule is carried onto this model's step as ``Hybrid_VAEModel.beam_search`` runs it.  Two
+departures, both documented in INTEGRATION.md:
+  - every member's encoder gets its own copy of ``feat_lens`` (the reference hands one array to all of them, each of which
+    divides it in place, :576-578); the caller's array is left untouched;
+  - the beam search expands the flat ``beam * V`` scores of a clip at every step, t = 0 included, because the beam rows of a
+    clip differ in ``z`` from the first step on (the reference takes row 0 only at t = 0, :681-682).
+"""
+import copy
+import ctypes
+import json
+from pathlib import Path
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .batch import collate_fn
+from .encoder import ptr_table, scratch_buffer
+from .evaluate import collect_predictions, predictions_payload
+from .seq_train_model import ScstWrapper
+from .vae_model import Hybrid_VAEModel
+
+MAX_MEMBERS = int(_lib._defs["ACVAE_ENSEMBLE_MAX"])
+
+
+class Ensemble(nn.Module):
+    """``Ensemble(models)``: the members in an ``nn.ModuleList`` (``ScstWrapper`` / ``NScstWrapper`` unwrapped, as
+    base_runner.py:428-429 does).  Members may differ in encoder class, embedding size and frame rate; vocabulary size,
+    ``start_idx`` and ``end_idx`` are shared.
+
+    ``noise`` (optional replay, consumed by the next forward as ``Hybrid_VAEModel.noise`` is):
+    ``{"eps": [tensor [N, max_length, beam, E_m] per member]}``.  Without it member m's noise is drawn on the CPU
+    generator with the calls its own ``beam_search`` would make (clip-major, ``torch.randn(beam, E_m)``), members in
+    order: ``Ensemble([m])`` under a seed consumes the generator exactly as ``m.beam_search`` does."""
+
+    def __init__(self, models):
+        super().__init__()
+        models = [m.model if isinstance(m, ScstWrapper) else m for m in models]
+        if len(models) == 0:
+            raise ValueError("Ensemble: no members")
+        if len(models) > MAX_MEMBERS:
+            raise ValueError(f"Ensemble: {len(models)} members, at most {MAX_MEMBERS}")
+        for m in models:
+            if not isinstance(m, Hybrid_VAEModel):
+                raise ValueError(f"Ensemble: members must be Hybrid_VAEModel, got {type(m).__name__}")
+        first = models[0]
+        for m in models[1:]:
+            for what in ("vocab_size", "start_idx", "end_idx"):
+                if int(getattr(m, what)) != int(getattr(first, what)):
+                    raise ValueError(f"Ensemble: members differ in {what} ({getattr(first, what)} and {getattr(m, what)})")
+        devices = {next(m.parameters()).device for m in models}
+        if len(devices) != 1:
+            raise ValueError(f"Ensemble: members on different devices {sorted(str(d) for d in devices)}")
+        self.models = nn.ModuleList(models)
+        self.vocab_size, self.start_idx, self.end_idx = int(first.vocab_size), int(first.start_idx), int(first.end_idx)
+        self.noise = None
+
+    @torch.no_grad()
+    def forward(self, feats, feat_lens, method="greedy", beam_size=5, max_length=20):
+        """-> ``{"seqs": int64 [N, max_length], "logprobs": f32}`` on the device.  ``logprobs``: greedy [N, max_length], the
+        mixture's log-probability of each chosen word (entries behind a row's ``end_idx`` carry no meaning); beam [N], beam
+        0's final score.  A greedy row that has produced ``end_idx`` keeps ``end_idx`` to the end (base_runner.py:584,
+        622-630)."""
+        if method not in ("greedy", "beam"):
+            raise ValueError(f"Ensemble: method must be 'greedy' or 'beam', not {method!r}")
+        beam = 1 if method == "greedy" else int(beam_size)
+        T = int(max_length)
+        replay = self.noise.get("eps") if self.noise is not None else None
+        self.noise = None
+        M = len(self.models)
+        if replay is not None and len(replay) != M:
+            raise ValueError(f"Ensemble: noise['eps'] holds {len(replay)} tensors for {M} members")
+        _lib.require_cuda(feats)
+        dev = feats.device
+        mems, lens, epss, tables, dims = [], [], [], [], []
+        for k, model in enumerate(self.models):
+            model.eval()                                                   # base_runner.py:573-574
+            model._forward_token = getattr(model, "_forward_token", 0) + 1     # per-forward caches, as Hybrid_VAEModel.forward
+            encoded = model.encoder(feats, copy.copy(np.asarray(feat_lens)))    # its own copy: the encoder divides it in place
+            mem = encoded["audio_embeds"].contiguous()
+            if hasattr(model, "ln"):                                       # vae_model.py:754-755, as beam_search does
+                Nn, Ss, Ee = mem.shape
+                proj = torch.empty(Nn, Ss, model.decoder.embed_size, device=dev)
+                _lib.call("acvae_gemm_nt", mem, Ee, model.ln.weight, Ee, model.ln.bias, proj, model.decoder.embed_size,
+                          Nn * Ss, model.decoder.embed_size, Ee, 0, _lib.current_stream())
+                mem = proj
+            N, S, E = mem.shape
+            H, A = model.decoder.model.hidden_size, model.decoder.attn.attn_size
+            if replay is None:
+                eps = _lib.h2d_fill((T, N, beam, E), torch.float32, dev,
+                                    lambda buf: [torch.randn(beam, E, out=buf[t, i]) for i in range(N) for t in range(T)])
+            else:
+                eps = _lib.h2d(torch.as_tensor(replay[k]).reshape(N, T, beam, E).transpose(0, 1).contiguous(), dev,
+                               torch.float32)
+            mems.append(mem)
+            lens.append(torch.as_tensor(encoded["audio_embeds_lens"]).to(device=dev, dtype=torch.long).contiguous())
+            epss.append(eps)
+            tables.append(ptr_table(model._text_table()))
+            dims.append((S, E, H, A))
+        N = mems[0].shape[0]
+        params = (ctypes.c_void_p * M)(*[ctypes.cast(t, ctypes.c_void_p).value for t in tables])
+        S_, E_, H_, A_ = (np.ascontiguousarray([d[j] for d in dims], dtype=np.int32) for j in range(4))
+        host = [a.ctypes.data for a in (S_, E_, H_, A_)]
+        seqs = torch.empty(N, T, dtype=torch.long, device=dev)
+        logprobs = torch.empty((N, T) if method == "greedy" else (N,), device=dev)
+        sb = _lib.call("acvae_ensemble_search_scratch_bytes", M, N, beam, T, *host, self.vocab_size)
+        if sb < 0:
+            raise RuntimeError(f"acvae_ensemble_search: unsupported dimensions (N={N}, beam={beam}, max_length={T})")
+        scratch = scratch_buffer(sb, dev)
+        _lib.call("acvae_ensemble_search", params, ptr_table(mems), ptr_table(lens), ptr_table(epss), *host, M,
+                  self.start_idx, self.end_idx, 1 if method == "greedy" else 0, seqs, logprobs, scratch, sb, N, beam, T,
+                  self.vocab_size, _lib.current_stream())
+        return {"seqs": seqs, "logprobs": logprobs}
+
+
+def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None, dcase_format=False, zh=False,
+                      batch_size=32, **kwargs):
+    """The decoding half of ``BaseRunner.ensemble`` (base_runner.py:433-478): ``items`` are ``(audio_id, feature [T, F])`` as
+    for ``evaluate()``, batched with ``collate_fn([1])`` (no replication); ``kwargs`` (``method``, ``beam_size``,
+    ``max_length``) go to ``Ensemble.forward``.  Writes the JSON payload of ``evaluate()`` or, with ``dcase_format``, the
+    reference's two-column CSV (``file_name``, ``caption_predicted``).  Returns the payload dict; scoring stays outside."""
+    ens = models_or_ensemble if isinstance(models_or_ensemble, Ensemble) else Ensemble(models_or_ensemble)
+    device = next(ens.parameters()).device
+    collate = collate_fn([1, ])
+    key2pred = {}
+    pending = []
+
+    def flush():
+        if not pending:
+            return
+        batch = collate(list(pending))
+        pending.clear()
+        output = ens(batch[1].to(device), batch[-1], **kwargs)
+        collect_predictions(batch[0], output["seqs"].cpu().numpy(), vocabulary, zh, key2pred)
+
+    for item in items:
+        pending.append(item)
+        if len(pending) == batch_size:
+            flush()
+    flush()
+    payload = predictions_payload(key2pred, zh)
+    if caption_output is not None:
+        with open(Path(caption_output), "w", newline="") as fh:
+            if dcase_format:                                               # base_runner.py:463-467, 475-476
+                import csv
+                writer = csv.writer(fh, lineterminator="\n")
+                writer.writerow(["file_name", "caption_predicted"])
+                for key, preds in key2pred.items():
+                    writer.writerow([key, "".join(preds[0]) if zh else preds[0]])
+            else:
+                json.dump(payload, fh, indent=4)
+    return payload

@@ -747,6 +747,47 @@ int acvae_beam_search(const void* const* params, const float* mem, const int64_t
 int acvae_dbs_scores(const float* logits, int64_t ld, float temperature, const float* counts, float diversity_lambda,
                      const float* prev, float* out, int N, int V, int rows_per_count, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ensemble decoding: BaseRunner.ensemble / _ensemble_batch / _ensemble_batch_beam_search,
+ * runners/base_runner.py:397-694, with several trained models at once: at every step the members' word probabilities
+ * are averaged and the word is picked from the average (:616-618 greedy, :675-686 beam).
+ *
+ * acvae_ensemble_mix, one launch per step (in the place of M x (acvae_row_logsoftmax_argmax + acvae_logprob_add) and a
+ * mixing pass):
+ *   out[r,c] = log( (1/M) * sum_m softmax(logits_m[r])[c] ) + prev[r]
+ * logits / ld: HOST arrays of M device pointers and leading dimensions (member m's row r at logits[m] + r * ld[m],
+ * ld[m] >= V), 1 <= M <= ACVAE_ENSEMBLE_MAX; prev [R] may be NULL (0).  out (row stride ld_out >= V) may be NULL when only
+ * the selection is wanted; argmax / best (either may be NULL; element r at r * o_stride): the first maximum column of
+ * out[r] and its value, what the greedy search picks (:618).  Arithmetic: lse_m as acvae_row_logsoftmax_argmax forms it,
+ * lp_m = logits_m - lse_m, a = max_m lp_m, s = sum_m expf(lp_m - a) in member order, out = (a + logf(s / M)) + prev; hence
+ * M = 1 is bit-equal to acvae_row_logsoftmax_argmax + acvae_logprob_add, and M copies of one matrix are bit-equal to M = 1.
+ *
+ * acvae_ensemble_search, the whole search as one call, on Hybrid_VAEModel's step (prior step -> z -> decoder step,
+ * models/vae_model.py:896-995; the reference's ensemble code never runs the prior).  HOST arrays of M entries describe
+ * the members: params[m] the member's text parameter table (ACVAE_TEXT_NPARAMS pointers), mem[m] [N,S[m],E[m]] (after the
+ * member's `ln`), mem_lens[m] int64 [N], eps[m] [max_length][N*beam][E[m]] (step-major, as acvae_beam_search), and the
+ * dimensions S / E / H / A.  V, start_idx and end_idx are shared; all members are fed the same word.
+ *   greedy != 0 (beam must be 1): the mixture's argmax; a row that has produced end_idx keeps emitting and feeding it, all
+ *     max_length steps run (no host read-back): seqs as :584, 622-630 leave it.  logprobs f32 [N,max_length]: the
+ *     mixture's log-probability of the step's argmax.
+ *   greedy == 0: beam search, flat top-k over beam * V per clip at every step, t = 0 included (as acvae_beam_search: the
+ *     rows of a clip differ in z), beam 0 traced back.  logprobs f32 [N]: beam 0's final score.  With M = 1 the launches
+ *     of acvae_beam_search in the same order: the same seqs bit for bit.
+ * seqs int64 [N,max_length].  Refused before any launch: M outside [1, ACVAE_ENSEMBLE_MAX], a NULL entry, H[m] != E[m],
+ * beam > 64, greedy with beam != 1, start_idx / end_idx outside [0, V) (ACVAE_EINVAL); N * beam > 2^20, or beam > 16
+ * without greedy (acvae_topk_flat_batched's limit) (ACVAE_EUNSUPPORTED); scratch below
+ * acvae_ensemble_search_scratch_bytes() (ACVAE_EWORKSPACE).  One stream, no host synchronisation.
+ * ------------------------------------------------------------------------------------------- */
+#define ACVAE_ENSEMBLE_MAX 8
+int acvae_ensemble_mix(const float* const* logits, const int64_t* ld, int M, const float* prev, float* out, int64_t ld_out,
+                       int64_t* argmax, float* best, int64_t o_stride, int R, int V, void* stream);
+int64_t acvae_ensemble_search_scratch_bytes(int M, int N, int beam, int max_length, const int* S, const int* E,
+                                            const int* H, const int* A, int V);
+int acvae_ensemble_search(const void* const* const* params, const float* const* mem, const int64_t* const* mem_lens,
+                          const float* const* eps, const int* S, const int* E, const int* H, const int* A, int M,
+                          int64_t start_idx, int64_t end_idx, int greedy, int64_t* seqs, float* logprobs, void* scratch,
+                          int64_t scratch_bytes, int N, int beam, int max_length, int V, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
