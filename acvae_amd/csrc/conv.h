@@ -144,8 +144,28 @@ int acvae_gemm_nt_pair(const float* A0, int64_t lda0, const float* B0, int64_t l
 constexpr int TN_TICKETS = 256;
 int acvae_gemm_tn_fused(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K,
                         int accumulate, float* ws, int64_t ws_bytes, hipStream_t st);
+// Several such products in ONE launch (the weight gradients that trail a decode backward on the second stream: a dozen one-round
+// launches in a row, each with its own tail, held CUs beside the encoder backward for most of a millisecond).  Every job keeps
+// the slices, the tile and the order of additions of its own acvae_gemm_tn_fused call (bit-identical); a job of one slice
+// writes C itself.  All jobs are live at once, so every sliced job has its own slabs and its own tickets inside the ONE
+// workspace [TN_TICKETS words | slabs]: slab0 / tk0 are filled by the plan.  Only products of the 128 x 128 vector tile
+// (M > 64; A, B 16-byte aligned; lda, ldb, M, N multiples of 4) may be added.  Ranges: workgroups (tiles x slices).
+struct TnJob {
+  const float* A; long lda; const float* B; long ldb; float* C; long ldc;
+  int M, N, K, k_per, slices, gx, gy, tk0;
+  long slab0;
+};
+using TnGroup = acvae::RangeTable<TnJob, 8, int>;
+// true and the job is in the table (a full table takes it too and stops being ok()); false: the product is not eligible
+bool acvae_gemm_tn_group_add(TnGroup& g, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
+                             int K);
+// fills k_per / slices / slab0 / tk0 and the ranges; the slab floats the group needs; -1 = more tiles than tickets (or !ok())
+long acvae_gemm_tn_group_plan(TnGroup& g);
+// ACVAE_EWORKSPACE (before any HIP call) when the tickets or ws do not hold the group: the caller then launches the products
+// one by one - a group never runs with overlapping slabs
+int acvae_gemm_tn_group(TnGroup& g, float* ws, int64_t ws_bytes, hipStream_t st);
 long acvae_skinny_ws_floats();
-long acvae_skinny_ticket_words();       // words at the head of a skinny workspace that a composite call zeroes once
+long acvae_skinny_ticket_words();      // words at the head of a skinny workspace that a composite call zeroes once
 int acvae_skinny_ws_reset(float* ws, hipStream_t st);
 // several transposes in ONE launch (out[c][r] = in[r][c]): the decode backward needs nine transposed weight matrices per step.
 // Ranges: 32 x 32 tiles.

@@ -50,6 +50,31 @@ inline int gemm_tn(const float* A, long lda, const float* B, long ldb, float* C,
                    hipStream_t st) {
   return acvae_gemm_tn_fused(A, lda, B, ldb, C, ldc, M, N, K, 0, ws.p, ws.bytes, st);     // ws: tickets (zeroed at the call's entry) | slabs
 }
+// A chain's trailing weight-gradient products, sent as ONE launch (gemm.hip: gemm_tn_group_kernel) instead of one each.  A
+// product that may not enter a group (or that the table has no room for) goes out at once as its own launch, and so does
+// every product of a group that the workspace or its tickets do not hold: the results are the same bit for bit either way.
+struct TnBatch {
+  TnGroup g;
+  TnWs ws;
+  hipStream_t st;
+  int add(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K) {
+    if (g.n < TnGroup::capacity && acvae_gemm_tn_group_add(g, A, lda, B, ldb, C, ldc, M, N, K)) return ACVAE_OK;
+    return gemm_tn(A, lda, B, ldb, C, ldc, M, N, K, ws, st);
+  }
+  int launch() {
+    const int r = acvae_gemm_tn_group(g, ws.p, ws.bytes, st);
+    if (r != ACVAE_EWORKSPACE) return r;
+    for (int l = 0; l < g.n; ++l) {
+      const TnJob& j = g.job[l];
+      ACVAE_TRY(gemm_tn(j.A, j.lda, j.B, j.ldb, j.C, j.ldc, j.M, j.N, j.K, ws, st));
+    }
+    return ACVAE_OK;
+  }
+};
+// the slab floats a product adds to its group's workspace (0: its shape keeps it out of every group)
+inline long tn_group_share(int M, int N, int K) {
+  return M > 64 && (M & 3) == 0 && (N & 3) == 0 ? acvae_gemm_tn_workspace_bytes(M, N, K) / 4 : 0;
+}
 // the regions every composite call zeroes in front of its first kernel, in ONE launch (rnn.h)
 inline void zb_skinny(acvae::ZeroBatch& zb, float* skws) { zb.add(skws, acvae_skinny_ticket_words()); }
 inline void zb_colsum(acvae::ZeroBatch& zb, double* dpart) { zb.add(dpart, acvae::colsum_ticket_words()); }
@@ -148,6 +173,13 @@ int post_layout(int N, int Tc, int E, int Hq, int V, int NL, PostLayout& L) {
   long t2 = tn_ws_floats(3 * Hq, E, (int)R); if (t2 > tn) tn = t2;
   t2 = tn_ws_floats(3 * Hq, Hq, (int)R); if (t2 > tn) tn = t2;
   if (NL > 1) { t2 = tn_ws_floats(3 * Hq, 2 * Hq, (int)R); if (t2 > tn) tn = t2; }    // dW_ih of the upper layers (K = 2Hq)
+  // the grouped launches of acvae_posterior_stack_bwd hold the slabs of ALL their products at once
+  t2 = tn_group_share(2 * E, 2 * Hq, (int)R) + 2 * tn_group_share(3 * Hq, E, (int)R) + 2 * tn_group_share(3 * Hq, Hq, (int)R) + 64 + TN_TICKETS;
+  if (t2 > tn) tn = t2;
+  if (NL > 1) {
+    t2 = 2 * tn_group_share(3 * Hq, 2 * Hq, (int)R) + 2 * tn_group_share(3 * Hq, Hq, (int)R) + 64 + TN_TICKETS;
+    if (t2 > tn) tn = t2;
+  }
   L.tn_floats = tn;
   L.tn = c.take(tn);
   L.dpart_doubles = 4 * acvae::colsum_scratch_doubles(2 * E > 3 * Hq ? 2 * E : 3 * Hq);      // room for the batched column sums
@@ -228,6 +260,16 @@ int dec_layout(int N, int Tc, int S, int E, int H, int A, int V, int Eenc, DecLa
   mx(V, H, (int)R); mx(3 * H, 3 * E, (int)R); mx(3 * H, H, (int)R); mx(A, H, (int)R); mx(A, E, N * S); mx(E, E, N * S);
   mx(4 * Hp, 3 * E, (int)R); mx(4 * Hp, Hp, (int)R); mx(2 * E, Hp, (int)R); mx(E, E, (int)R); mx(2 * E, H, N);
   mx(E, Eenc, N * S);
+  // the grouped launches (acvae_decode_bwd: dec_params, prior_params) hold the slabs of ALL their products at once
+  const long grp_d = tn_group_share(3 * H, 3 * E, (int)R) + tn_group_share(3 * H, H, (int)R) + tn_group_share(A, H, (int)R) +
+                     tn_group_share(A, E, N * S);
+  const long grp_p = tn_group_share(2 * E, Hp, (int)R) + tn_group_share(4 * Hp, 3 * E, (int)R) + tn_group_share(4 * Hp, Hp, (int)R) +
+                     tn_group_share(E, E, (int)R) + tn_group_share(E, E, N * S);
+  if (grp_d + 64 + TN_TICKETS > tn) tn = grp_d + 64 + TN_TICKETS;
+  if (grp_p + 64 + TN_TICKETS > tn) tn = grp_p + 64 + TN_TICKETS;
+  // ... and in trailing-gradient mode one launch takes the decoder's four and the prior's first three
+  const long grp_e = grp_d + grp_p - tn_group_share(E, E, (int)R) - tn_group_share(E, E, N * S);
+  if (grp_e + 64 + TN_TICKETS > tn) tn = grp_e + 64 + TN_TICKETS;
   L.tn_floats = tn;
   L.tn = b.take(tn);
   {
@@ -431,7 +473,6 @@ extern "C" int acvae_posterior_stack_bwd(const void* const* params, void* const*
   if (d_q_means_utt)
     ACVAE_TRY(acvae::pool_bwd(d_q_means_utt, lens1, (const int*)(sv + L.argmax), dhid, (long)Tc * 2 * Hq, 2 * Hq, 1, N,
                               Tc, 2 * Hq, st));
-  ACVAE_TRY(gemm_tn(dml, 2 * E, hid, 2 * Hq, G(TP_Q_TML_W), 2 * Hq, 2 * E, 2 * Hq, R, tn, st));
   // BPTT of one direction of one layer from dhid into dgi / dgh, step by step (wt_hh: its transposed weight_hh)
   auto bptt_dir = [&](int layer, int dir, const float* wt_hh) -> int {
     const float* save = sv + (dir ? L.save_r[layer] : L.save_f[layer]);
@@ -487,17 +528,19 @@ extern "C" int acvae_posterior_stack_bwd(const void* const* params, void* const*
     ACVAE_TRY(bptt(layer, wtu_hh));
     const float* Xk = sv + L.hidden[layer - 1];                      // this layer's input, after the dropout
     acvae::ColsumBatch cbu;
+    TnBatch tbu{{}, tn, st.s};                                        // the layer's four weight gradients: one launch
     for (int dir = 0; dir < 2; ++dir) {
       const float* hprev = sv + (dir ? L.hprev_r[layer] : L.hprev_f[layer]);
       float* dgi = sc + (dir ? L.dgi_r : L.dgi_f);
       float* dgh = sc + (dir ? L.dgh_r : L.dgh_f);
-      ACVAE_TRY(gemm_tn(dgi, 3 * Hq, Xk, 2 * Hq, GU(layer, dir, 0), 2 * Hq, 3 * Hq, 2 * Hq, R, tn, st));
+      ACVAE_TRY(tbu.add(dgi, 3 * Hq, Xk, 2 * Hq, GU(layer, dir, 0), 2 * Hq, 3 * Hq, 2 * Hq, R));
       cbu.add({dgi, R, 3 * Hq, GU(layer, dir, 2)});
-      ACVAE_TRY(gemm_tn(dgh, 3 * Hq, hprev, Hq, GU(layer, dir, 1), Hq, 3 * Hq, Hq, R, tn, st));
+      ACVAE_TRY(tbu.add(dgh, 3 * Hq, hprev, Hq, GU(layer, dir, 1), Hq, 3 * Hq, Hq, R));
       cbu.add({dgh, R, 3 * Hq, GU(layer, dir, 3)});
       ACVAE_TRY(gemm(dgi, 3 * Hq, wtu_ih[dir], 3 * Hq, nullptr, dnext, 2 * Hq, R, 2 * Hq, 3 * Hq, dir, st));
     }
-    ACVAE_TRY(acvae::colsum_batch(cbu, dpart, L.dpart_doubles, st));   // before the layer below overwrites dgi / dgh
+    ACVAE_TRY(tbu.launch());                                           // (both) before the layer below overwrites dgi / dgh
+    ACVAE_TRY(acvae::colsum_batch(cbu, dpart, L.dpart_doubles, st));
     if (keep)
       ACVAE_TRY(acvae::dropout_rows(dnext, (long)Tc * 2 * Hq, 2 * Hq, keep + (long)(layer - 1) * R * 2 * Hq,
                                     (long)Tc * 2 * Hq, 2 * Hq, keep_scale, N, Tc, 2 * Hq, st));
@@ -506,6 +549,10 @@ extern "C" int acvae_posterior_stack_bwd(const void* const* params, void* const*
   acvae::ColsumBatch cb;                     // the five bias gradients of layer 0 and token_mean_log: one launch at the end
   cb.add({dml, R, 2 * E, G(TP_Q_TML_B)});
   float* dx = sc + L.dx;
+  // layer 0's four weight gradients and token_mean_log's: one launch behind the BPTT (with the per-step loops the second
+  // direction overwrites the ping-pong halves dh_a / dh_b only, so the first direction's dgi / dgh are still in place)
+  TnBatch tb0{{}, tn, st.s};
+  ACVAE_TRY(tb0.add(dml, 2 * E, hid, 2 * Hq, G(TP_Q_TML_W), 2 * Hq, 2 * E, 2 * Hq, R));
   if (persist) {                 // BPTT of both directions in one launch; the parameter products below are unchanged
     const float* wt_hh[2] = {wt, sc + L.wt2};                  // transposed weight_hh, made at the entry
     ACVAE_TRY(bptt(0, wt_hh));
@@ -519,12 +566,13 @@ extern "C" int acvae_posterior_stack_bwd(const void* const* params, void* const*
       ACVAE_TRY(transp(P(TP_Q_WHH + o), Hq, wt, 3 * Hq, 3 * Hq, Hq, st));                   // [Hq][3Hq]
       ACVAE_TRY(bptt_dir(0, dir, wt));
     }
-    ACVAE_TRY(gemm_tn(dgi, 3 * Hq, X, E, G(TP_Q_WIH + o), E, 3 * Hq, E, R, tn, st));
+    ACVAE_TRY(tb0.add(dgi, 3 * Hq, X, E, G(TP_Q_WIH + o), E, 3 * Hq, E, R));
     cb.add({dgi, R, 3 * Hq, G(TP_Q_BIH + o)});
-    ACVAE_TRY(gemm_tn(dgh, 3 * Hq, hprev, Hq, G(TP_Q_WHH + o), Hq, 3 * Hq, Hq, R, tn, st));
+    ACVAE_TRY(tb0.add(dgh, 3 * Hq, hprev, Hq, G(TP_Q_WHH + o), Hq, 3 * Hq, Hq, R));
     cb.add({dgh, R, 3 * Hq, G(TP_Q_BHH + o)});
     ACVAE_TRY(gemm(dgi, 3 * Hq, wt_ih[dir], 3 * Hq, nullptr, dx, E, R, E, 3 * Hq, dir, st));
   }
+  ACVAE_TRY(tb0.launch());
   ACVAE_TRY(acvae::colsum_batch(cb, dpart, L.dpart_doubles, st));
   ACVAE_TRY(acvae::embed_scatter(words, dx, E, G(TP_Q_EMB), V, R, E, st));
   return ACVAE_OK;
@@ -1038,18 +1086,26 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     return ACVAE_OK;
   };
   // batched parameter gradients of the decoder, the embedding gradient and (with_dz) d_q_z
-  auto dec_params = [&](const Ctx& c, TnWs ws, double* dp, bool with_dz = true) -> int {
-    ACVAE_TRY(gemm_tn(dgi, 3 * H, rnn_d, 3 * E, G(TP_DEC_WIH), 3 * E, 3 * H, 3 * E, R, ws, c));
-    ACVAE_TRY(gemm_tn(dgh, 3 * H, hprev_d, H, G(TP_DEC_WHH), H, 3 * H, H, R, ws, c));
+  // the decoder's four weight gradients (attention parameters: W = [query half | memory half]): jobs of one grouped launch
+  auto dec_tn = [&](TnBatch& tb) -> int {
+    ACVAE_TRY(tb.add(dgi, 3 * H, rnn_d, 3 * E, G(TP_DEC_WIH), 3 * E, 3 * H, 3 * E, R));
+    ACVAE_TRY(tb.add(dgh, 3 * H, hprev_d, H, G(TP_DEC_WHH), H, 3 * H, H, R));
+    ACVAE_TRY(tb.add(dqd, A, hprev_d, H, G(TP_DEC_ATT_W), E + H, A, H, R));
+    return tb.add(dencproj, A, mem, E, G(TP_DEC_ATT_W) + H, E + H, A, E, N * S);
+  };
+  // (with_tn = false: the weight gradients have been launched already)
+  auto dec_params = [&](const Ctx& c, TnWs ws, double* dp, bool with_dz = true, bool with_tn = true) -> int {
+    if (with_tn) {
+      TnBatch tb{{}, ws, c};
+      ACVAE_TRY(dec_tn(tb));
+      ACVAE_TRY(tb.launch());
+    }
     {   // the four bias-shaped gradients of the decoder in one launch
       acvae::ColsumBatch cb;
       cb.add({dgi, R, 3 * H, G(TP_DEC_BIH)}); cb.add({dgh, R, 3 * H, G(TP_DEC_BHH)});
       cb.add({dencproj, N * S, A, G(TP_DEC_ATT_B)}); cb.add({dvpart, dv_rows, A, G(TP_DEC_ATT_V)});
       ACVAE_TRY(acvae::colsum_batch(cb, dp, L.dpart_doubles, c));
     }
-    // attention parameters: W = [query half | memory half]
-    ACVAE_TRY(gemm_tn(dqd, A, hprev_d, H, G(TP_DEC_ATT_W), E + H, A, H, R, ws, c));
-    ACVAE_TRY(gemm_tn(dencproj, A, mem, E, G(TP_DEC_ATT_W) + H, E + H, A, E, N * S, ws, c));
     // d(rnn_input) for the embedding and z columns
     ACVAE_TRY(gemm(dgi, 3 * H, wt_dih, 3 * H, nullptr, drnn, E, R, E, 3 * H, 0, c));                    // d emb
     if (emb_keep)          // back through the word-embedding dropout
@@ -1124,10 +1180,21 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     return gemm(dencproj_p, E, wt_patt + (long)E * E, E, nullptr, dmem_p, E, N * S, E, E, 1, sp);
   };
   // batched parameter gradients of the prior and its embedding gradient
-  auto prior_params = [&]() -> int {
-    ACVAE_TRY(gemm_tn(dml_all, 2 * E, hp_all, Hp, G(TP_P_ML_W), Hp, 2 * E, Hp, R, tn_p, sp));
-    ACVAE_TRY(gemm_tn(dgates, 4 * Hp, rnn_p, 3 * E, G(TP_P_WIH), 3 * E, 4 * Hp, 3 * E, R, tn_p, sp));
-    ACVAE_TRY(gemm_tn(dgates, 4 * Hp, hpprev, Hp, G(TP_P_WHH), Hp, 4 * Hp, Hp, R, tn_p, sp));
+  // the prior's weight gradients that need the BPTT's outputs only (LSTM, mean / log-variance head) ...
+  auto prior_tn_bptt = [&](TnBatch& tb) -> int {
+    ACVAE_TRY(tb.add(dgates, 4 * Hp, rnn_p, 3 * E, G(TP_P_WIH), 3 * E, 4 * Hp, 3 * E, R));
+    ACVAE_TRY(tb.add(dgates, 4 * Hp, hpprev, Hp, G(TP_P_WHH), Hp, 4 * Hp, Hp, R));
+    return tb.add(dml_all, 2 * E, hp_all, Hp, G(TP_P_ML_W), Hp, 2 * E, Hp, R);
+  };
+  // ... and the rest (with_bptt_tn = false: those three have been launched already): the attention's two need prior_memgrad()
+  auto prior_params = [&](bool with_bptt_tn = true) -> int {
+    {   // the weight gradients in one launch
+      TnBatch tb{{}, tn_p, sp};
+      if (with_bptt_tn) ACVAE_TRY(prior_tn_bptt(tb));
+      ACVAE_TRY(tb.add(dqp, E, rnn_p, 3 * E, G(TP_P_ATT_W), 2 * E, E, E, R));
+      ACVAE_TRY(tb.add(dencproj_p, E, mem, E, G(TP_P_ATT_W) + E, 2 * E, E, E, N * S));
+      ACVAE_TRY(tb.launch());
+    }
     {   // the prior's bias-shaped gradients in one launch (the LSTM's two biases share theirs)
       acvae::ColsumBatch cb;
       cb.add({dml_all, R, 2 * E, G(TP_P_ML_B)}); cb.add({dgates, R, 4 * Hp, G(TP_P_BIH), G(TP_P_BHH)});
@@ -1136,10 +1203,9 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     }
     // d emb_p = drnn[:, 0:E] + dqp . W_att[:, :E]
     ACVAE_TRY(gemm(dqp, E, wt_patt, E, nullptr, drnn_p, 3 * E, R, E, E, 1, sp));
-    ACVAE_TRY(gemm_tn(dqp, E, rnn_p, 3 * E, G(TP_P_ATT_W), 2 * E, E, E, R, tn_p, sp));
-    ACVAE_TRY(gemm_tn(dencproj_p, E, mem, E, G(TP_P_ATT_W) + E, 2 * E, E, E, N * S, tn_p, sp));
     return acvae::embed_scatter(words_c, drnn_p, 3 * E, G(TP_P_EMB), V, R, E, sp);       // (table zeroed at the call's entry)
   };
+  bool early_tn = false;       // trailing-gradient mode: most weight gradients went out in front of the trailing part
   if (prior_feeds_decoder) {   // the prior BPTT needs the decoder's dz: back to back
     ACVAE_TRY(dec_begin());
     for (int t = Tc - 1; t >= 0; --t) ACVAE_TRY(dec_bptt(t));
@@ -1175,6 +1241,16 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     if (!defer) {
       ACVAE_TRY(dec_params(st, tn, dpart));
       ACVAE_TRY(prior_params());
+    } else {
+      // Trailing-gradient mode: the first stream now waits for prior_memgrad() on the second (three small kernels, some
+      // 150 us during which most of the GPU is idle).  The seven weight gradients that need nothing but the launch's outputs
+      // go HERE, as one grouped launch on the first stream: work done in this window no longer runs beside the encoder
+      // backward, where it made the whole-CU workgroups of the block-4 weight gradients wait for CUs.
+      TnBatch tb{{}, tn, st.s};
+      ACVAE_TRY(dec_tn(tb));
+      ACVAE_TRY(prior_tn_bptt(tb));
+      ACVAE_TRY(tb.launch());
+      early_tn = true;
     }
   } else {                     // independent chains: feed both queues step by step
     ACVAE_TRY(dec_begin());
@@ -1205,8 +1281,8 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     ACVAE_TRY(dec_dz(st));
     ACVAE_TRY(Fork::edge(st.s, sp.s));
     if (!heads_on_aux) ACVAE_TRY(heads_params(sp, tn_p, dpart_p));
-    ACVAE_TRY(dec_params(sp, tn_p, dpart_p, false));
-    ACVAE_TRY(prior_params());
+    ACVAE_TRY(dec_params(sp, tn_p, dpart_p, false, !early_tn));
+    ACVAE_TRY(prior_params(!early_tn));
   }
   return ACVAE_OK;
 }

@@ -790,7 +790,6 @@ int encoder_bwd_t(const void* const* params, void* const* grads, const float* fe
     ACVAE_TRY(acvae::bn_bwd<TA>(Y2, dp_cur, L.pool[b] ? UP_POOL : UP_DROP, n2.scale, n2.shift, n2.mean, n2.invstd, bnpart, G(p_bn(b, 2, 1)),
                             G(p_bn(b, 2, 0)), dya, dpart, N, H, W, C, dspec(p_block, masks, seed, b - 1, training), st,
                             training != 0));
-    ACVAE_TRY(conv_wgrad<TA>((const TA*)dya, Y1, n1.scale, n1.shift, G(p_conv(b, 2)), slab, N, H, W, C, C, st));
     // the data gradient's Winograd images were built by the training forward (same parameters: the optimiser runs after us)
     // (Winograd images where that path runs, implicit-GEMM repacks elsewhere - the forward chose with the same predicate)
     const bool wd_ready = training != 0;
@@ -799,6 +798,10 @@ int encoder_bwd_t(const void* const* params, void* const* grads, const float* fe
     acvae::WinoBnReduce red{(const float*)Y1, n1.scale, n1.shift, n1.mean, n1.invstd};
     ACVAE_TRY(conv_dgrad<TA>((const TA*)dya, P(p_conv(b, 2)), wd_ready ? (TA*)(saved + L.wd2[b]) : wd, dyb, N, H, W, C, C, st, wd_ready,
                              sizeof(TA) == 4 ? &red : nullptr, bnpart, &red_rows));
+    // The weight gradient second: both read dya, and bn1's backward below overwrites it.  Its launch is one round of
+    // whole-CU workgroups, which a CU still held by the text side's trailing products (second stream) makes wait; the
+    // data gradient's thousands of small workgroups only lose that CU's share (block 4 runs first behind the decode backward).
+    ACVAE_TRY(conv_wgrad<TA>((const TA*)dya, Y1, n1.scale, n1.shift, G(p_conv(b, 2)), slab, N, H, W, C, C, st));
     // conv1 / bn1 (block 1, fp32: the first conv's backward applies bn1's backward to dyb as it gathers it; only the sums here)
     DropoutSpec none{0.f, nullptr, 0, 0};
     const bool fold1 = b == 1 && sizeof(TA) == 4;

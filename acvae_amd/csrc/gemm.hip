@@ -2,6 +2,7 @@
 // input/hidden projections, mean/log-variance heads, vocabulary classifier) and their gradients.
 // Replaces torch.nn.Linear / F.linear at models/attn_model.py:32, models/decoder.py:198,
 // models/text_encoder.py:192,255, models/vae_model.py:726 and the GEMMs inside nn.GRU / nn.LSTM.
+#include <cstdint>
 #include <cstdlib>
 #include "mfma_tile.h"
 #include "../../include/acvae_hip.h"
@@ -58,30 +59,27 @@ __global__ void slab_reduce_kernel(const float* __restrict__ slab, long slab_str
 // __threadfence() around the ticket - a write-back and an invalidate of the XCD's whole L2 per workgroup - the Winograd weight
 // gradient running beside these products on the first stream lost 18 %: 0.55 -> 0.65 ms per launch, +0.8 ms per step.)
 // Tickets: one word per output tile, zeroed once per composite call, reset by the reducer.
+// One workgroup's share of such a product: slice z (of nsplit) of tile (bx, by), `tk` the tile's ticket
 template <int WM, int WN, bool VEC4>
-__global__ __launch_bounds__(256, 2) void gemm_tn_fused_kernel(const float* __restrict__ A, long lda, const float* __restrict__ B,
-                                                               long ldb, float* __restrict__ slab, float* __restrict__ C, long ldc,
-                                                               int M, int N, int K, int k_per, int accumulate, long slab_stride,
-                                                               unsigned* __restrict__ tickets) {
-  __shared__ TnSmem<WM, WN> sm;
-  __shared__ int s_last;
+__device__ __forceinline__ void tn_fused_tile(const float* __restrict__ A, long lda, const float* __restrict__ B, long ldb,
+                                              float* __restrict__ slab, float* __restrict__ C, long ldc, int M, int N, int K,
+                                              int k_per, int accumulate, long slab_stride, unsigned* __restrict__ tk, int bx,
+                                              int by, int z, int nsplit, TnSmem<WM, WN>& sm, int& s_last) {
   PlainKMajorLoader<VEC4> al{A, lda, M, K}, bl{B, ldb, N, K};
-  const int kb = blockIdx.z * k_per;
+  const int kb = z * k_per;
   const int ke = min(K, kb + k_per);
-  tn_block<WM, WN, true>(al, bl, M, N, kb, ke, blockIdx.x, blockIdx.y, slab + (long)blockIdx.z * slab_stride, (long)N, 0, sm);
+  tn_block<WM, WN, true>(al, bl, M, N, kb, ke, bx, by, slab + (long)z * slab_stride, (long)N, 0, sm);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
-    unsigned* tk = tickets + blockIdx.y * gridDim.x + blockIdx.x;
     const unsigned t = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = t == gridDim.z - 1 ? 1 : 0;
+    s_last = t == (unsigned)nsplit - 1 ? 1 : 0;
     if (s_last) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
   if (!s_last) return;
   constexpr int TM = WM * 64, TN = WN * 64;
-  const int m0 = blockIdx.x * TM, n0 = blockIdx.y * TN;
-  const int nsplit = gridDim.z;
+  const int m0 = bx * TM, n0 = by * TN;
   for (int i = threadIdx.x; i < TM * TN; i += 256) {
     const int m = m0 + i / TN, n = n0 + i % TN;
     if (m >= M || n >= N) continue;
@@ -99,6 +97,38 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_fused_kernel(const float* __re
     float* p = C + (long)m * ldc + n;
     *p = accumulate ? *p + acc : acc;
   }
+}
+
+template <int WM, int WN, bool VEC4>
+__global__ __launch_bounds__(256, 2) void gemm_tn_fused_kernel(const float* __restrict__ A, long lda, const float* __restrict__ B,
+                                                               long ldb, float* __restrict__ slab, float* __restrict__ C, long ldc,
+                                                               int M, int N, int K, int k_per, int accumulate, long slab_stride,
+                                                               unsigned* __restrict__ tickets) {
+  __shared__ TnSmem<WM, WN> sm;
+  __shared__ int s_last;
+  tn_fused_tile<WM, WN, VEC4>(A, lda, B, ldb, slab, C, ldc, M, N, K, k_per, accumulate, slab_stride,
+                              tickets + blockIdx.y * gridDim.x + blockIdx.x, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z, sm,
+                              s_last);
+}
+
+// Several of these products in ONE launch (conv.h: TnGroup).  A block finds its job from the flat block index and its place
+// in the job's own grid (tile column fastest, then tile row, then slice); a sliced job then runs gemm_tn_fused_kernel's body on
+// its own slabs and tickets, a job of one slice gemm_tn_kernel's, straight into C: each result is its own launch's, bit for bit.
+__global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(TnGroup g, float* __restrict__ slabs,
+                                                               unsigned* __restrict__ tickets) {
+  __shared__ TnSmem<2, 2> sm;
+  __shared__ int s_last;
+  const int l = g.find((int)blockIdx.x);
+  const TnJob& j = g.job[l];
+  const int t = blockIdx.x - g.start[l];
+  const int bx = t % j.gx, by = t / j.gx % j.gy, z = t / (j.gx * j.gy);
+  if (j.slices == 1) {
+    PlainKMajorLoader<true> al{j.A, j.lda, j.M, j.K}, bl{j.B, j.ldb, j.N, j.K};
+    tn_block<2, 2>(al, bl, j.M, j.N, 0, j.K, bx, by, j.C, j.ldc, 0, sm);
+    return;
+  }
+  tn_fused_tile<2, 2, true>(j.A, j.lda, j.B, j.ldb, slabs + j.slab0, j.C, j.ldc, j.M, j.N, j.K, j.k_per, 0, (long)j.M * j.N,
+                            tickets + j.tk0 + by * j.gx + bx, bx, by, z, j.slices, sm, s_last);
 }
 
 // gridDim.z = S K-slices per output tile.  S == 1: the block owns the tile.  S > 1: every slice writes its partial
@@ -466,6 +496,49 @@ int acvae_gemm_tn_fused(const float* A, int64_t lda, const float* B, int64_t ldb
   return ACVAE_OK;
 }
 
+bool acvae_gemm_tn_group_add(TnGroup& g, const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N,
+                             int K) {
+  if (!A || !B || !C || M <= 64 || N <= 0 || K <= 0) return false;                                       // (M <= 64: the 64 x 256 tile)
+  if (!aligned16(A) || !aligned16(B) || (lda & 3) || (ldb & 3) || (M & 3) || (N & 3)) return false;      // the scalar loader
+  g.add({A, lda, B, ldb, C, ldc, M, N, K, 0, 0, 0, 0, 0, 0});
+  return true;
+}
+
+long acvae_gemm_tn_group_plan(TnGroup& g) {
+  if (!g.ok()) return -1;
+  long slab = 0;
+  int tk = 0;
+  for (int l = 0; l < g.n; ++l) {
+    TnJob& j = g.job[l];
+    j.k_per = 0;
+    j.slices = tn_fused_slices(j.M, j.N, j.K, true, INT64_MAX, &j.k_per);   // the job's own call, given the workspace it asks for
+    j.gx = cdiv(j.M, 128);
+    j.gy = cdiv(j.N, 128);
+    j.slab0 = 0;
+    j.tk0 = 0;
+    if (j.slices > 1) {
+      j.slab0 = slab;
+      slab += (long)j.slices * j.M * j.N;
+      j.tk0 = tk;
+      tk += j.gx * j.gy;
+    }
+  }
+  if (tk > TN_TICKETS) return -1;
+  g.seal([](const TnJob& j) { return j.gx * j.gy * j.slices; });
+  return slab;
+}
+
+int acvae_gemm_tn_group(TnGroup& g, float* ws, int64_t ws_bytes, hipStream_t st) {
+  if (!g.ok()) return ACVAE_EINVAL;
+  if (g.n <= 0) return ACVAE_OK;
+  const long slab = acvae_gemm_tn_group_plan(g);
+  if (slab < 0 || (slab > 0 && (!ws || ws_bytes < ((int64_t)TN_TICKETS + slab) * (int64_t)sizeof(float)))) return ACVAE_EWORKSPACE;
+  hipLaunchKernelGGL(gemm_tn_group_kernel, dim3(g.start[g.n]), dim3(256), 0, st, g, ws + TN_TICKETS,
+                     reinterpret_cast<unsigned*>(ws));
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
 extern "C" int acvae_transpose(const float* in, int64_t ld_in, float* out, int64_t ld_out, int rows, int cols,
                                void* stream) {
   if (!in || !out || rows <= 0 || cols <= 0) return ACVAE_EINVAL;
@@ -517,4 +590,36 @@ extern "C" int acvae_gemm_tn_fused_c(const float* A, int64_t lda, const float* B
   if (ws && reset_tickets && ws_bytes >= (int64_t)TN_TICKETS * 4)
     if (hipMemsetAsync(ws, 0, TN_TICKETS * sizeof(unsigned), st) != hipSuccess) return (int)hipGetLastError();
   return acvae_gemm_tn_fused(A, lda, B, ldb, C, ldc, M, N, K, accumulate, ws, ws_bytes, st);
+}
+
+// the grouped form: n jobs as host arrays (A / B / C: device pointers); ws = tickets | the slabs of every sliced job
+static int tn_group_shapes(int n, const int* M, const int* N, const int* K, TnGroup& g) {
+  if (n <= 0 || n > TnGroup::capacity || !M || !N || !K) return ACVAE_EINVAL;
+  const float* none = reinterpret_cast<const float*>(16);       // (a placeholder that passes the checks: never dereferenced)
+  for (int l = 0; l < n; ++l)
+    if (!acvae_gemm_tn_group_add(g, none, 4, none, 4, const_cast<float*>(none), 4, M[l], N[l], K[l])) return ACVAE_EINVAL;
+  return ACVAE_OK;
+}
+extern "C" int64_t acvae_gemm_tn_group_workspace_bytes(int n, const int* M, const int* N, const int* K) {
+  TnGroup g;
+  if (tn_group_shapes(n, M, N, K, g) != ACVAE_OK) return -1;
+  const long slab = acvae_gemm_tn_group_plan(g);
+  if (slab < 0) return -1;
+  return slab > 0 ? ((int64_t)TN_TICKETS + slab) * (int64_t)sizeof(float) : 0;
+}
+extern "C" int acvae_gemm_tn_group_c(int n, const void* const* A, const int64_t* lda, const void* const* B, const int64_t* ldb,
+                                     const void* const* C, const int64_t* ldc, const int* M, const int* N, const int* K, void* ws,
+                                     int64_t ws_bytes, int reset_tickets, void* stream) {
+  TnGroup g;
+  if (n <= 0 || n > TnGroup::capacity || !A || !lda || !B || !ldb || !C || !ldc || !M || !N || !K) return ACVAE_EINVAL;
+  for (int l = 0; l < n; ++l)
+    if (ldc[l] < N[l] || lda[l] < M[l] || ldb[l] < N[l] ||
+        !acvae_gemm_tn_group_add(g, (const float*)A[l], lda[l], (const float*)B[l], ldb[l], (float*)C[l], ldc[l], M[l], N[l], K[l]))
+      return ACVAE_EINVAL;
+  const long slab = acvae_gemm_tn_group_plan(g);
+  if (slab < 0 || (slab > 0 && (!ws || ws_bytes < ((int64_t)TN_TICKETS + slab) * (int64_t)sizeof(float)))) return ACVAE_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (ws && reset_tickets && ws_bytes >= (int64_t)TN_TICKETS * 4)
+    if (hipMemsetAsync(ws, 0, TN_TICKETS * sizeof(unsigned), st) != hipSuccess) return (int)hipGetLastError();
+  return acvae_gemm_tn_group(g, (float*)ws, ws_bytes, st);
 }

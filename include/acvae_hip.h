@@ -88,6 +88,13 @@ int acvae_colsum(const float* x, int rows, int cols, float* out, void* ws, int64
  *   acvae_gemm_tn_fused_c  acvae_gemm_tn with the slab sum in the same launch: ws = tickets | slabs of
  *                          acvae_gemm_tn_fused_workspace_bytes (0: one slice); acvae_gemm_tn_fused_plan: the slices it
  *                          launches with ws_bytes of workspace (1: it falls back to acvae_gemm_tn without one)
+ *   acvae_gemm_tn_group_c  up to 8 such products in ONE launch, each bit for bit what its own acvae_gemm_tn_fused_c call
+ *                          gives (accumulate = 0): A / B / C host tables of device pointers, lda / ldb / ldc / M / N / K host
+ *                          arrays.  Only products of the 128 x 128 vector tile: M > 64, M and N multiples of 4, A and B 16-B
+ *                          aligned, lda and ldb multiples of 4 (anything else, a NULL, n outside [1, 8]: ACVAE_EINVAL).  All
+ *                          jobs are live at once: ws = tickets | the slabs of EVERY sliced job,
+ *                          acvae_gemm_tn_group_workspace_bytes (0: no job is sliced; -1: bad shapes, or more sliced tiles
+ *                          than tickets); a smaller ws is ACVAE_EWORKSPACE.  All refusals come before any HIP call.
  *   acvae_colsum_batch     up to 6 column sums (as acvae_colsum) in one launch: x / out / out_b are host tables of device
  *                          pointers (out_b or its entries may be NULL), P / width host int arrays; ws: tickets | group
  *                          sums, acvae_colsum_batch_workspace_bytes for one launch;  acvae_colsum_batch_plan: 1 = one
@@ -104,6 +111,10 @@ int64_t acvae_gemm_tn_fused_workspace_bytes(int M, int N, int K);
 int acvae_gemm_tn_fused_plan(int M, int N, int K, int64_t ws_bytes);
 int acvae_gemm_tn_fused_c(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N,
                           int K, int accumulate, float* ws, int64_t ws_bytes, int reset_tickets, void* stream);
+int64_t acvae_gemm_tn_group_workspace_bytes(int n, const int* M, const int* N, const int* K);
+int acvae_gemm_tn_group_c(int n, const void* const* A, const int64_t* lda, const void* const* B, const int64_t* ldb,
+                          const void* const* C, const int64_t* ldc, const int* M, const int* N, const int* K, void* ws,
+                          int64_t ws_bytes, int reset_tickets, void* stream);
 int64_t acvae_colsum_batch_workspace_bytes(int n, const int* P, const int* width);
 int acvae_colsum_batch_plan(int n, const int* P, const int* width, int64_t ws_bytes);
 int acvae_colsum_batch(int n, const void* const* x, const int* P, const int* width, const void* const* out,
@@ -601,7 +612,9 @@ int acvae_decode_fwd_sampled(const void* const* params, const float* mem_in, con
  * Stream contract: d_mem_in and d_q_z are ordered on `stream` when the call returns.  With ACVAE_FLAG_DEFER_PARAM_GRADS, when
  * acvae_decode_bwd_defers says 1 for the same flags / streams (a second stream is given and no step fed the prior's z to the
  * decoder), everything else - the parameter gradients - is queued on `aux_stream` behind
- * the call, so that it runs beside whatever `stream` does next (the posterior's and the encoder's backward): the caller joins
+ * the call, so that it runs beside whatever `stream` does next (the posterior's and the encoder's backward; with the persistent
+ * BPTT launch the seven weight gradients that need only its outputs go out earlier, as one grouped launch on `stream` while
+ * it waits for `aux_stream`'s share of the memory gradient): the caller joins
  * aux_stream before those gradients are read on another stream, and keeps saved / scratch / outputs / mem_in / the upstream
  * gradients untouched until aux_stream has drained (mem_in: without an ln projection the products read it in place).  Without the flag (0) everything is ordered on `stream` on return.  Hybrid_VAEModel, which joins
  * the second stream at the end of the backward pass, passes it unless ACVAE_DECODE_DEFER=0 (-0.07 ms per step on the
