@@ -11,32 +11,17 @@
 // attentions and of both recurrent input projections are hoisted out of the time loop as batched MFMA
 // GEMMs whenever the words are known up front (teacher forcing), and the classifier / log-softmax /
 // argmax run once over all N*Tc rows.  Buffers are batch-major [N,Tc,*] like the reference's outputs;
-// "step t" addresses column t with row stride Tc*C.
+// "step t" addresses column t with row stride Tc*C.  The step API and the beam / ensemble search are search.hip.
 #include <cstdlib>
 #include <vector>
 #include "common.h"
 #include "conv.h"
 #include "rnn.h"
 #include "decode_persist.h"
-#include "../../include/acvae_hip.h"
+#include "text_common.h"
 
 namespace {
 
-struct Bump {
-  long off = 0;
-  long take(long n) { const long o = off; off = (off + n + 63) & ~63L; return o; }
-};
-
-// call context: the stream plus the split-K workspace of the skinny GEMM (converts to hipStream_t for everything else)
-struct Ctx {
-  hipStream_t s;
-  float* skws;
-  operator hipStream_t() const { return s; }
-};
-inline int gemm(const float* A, long lda, const float* B, long ldb, const float* bias, float* C, long ldc, int M, int N,
-                int K, int acc, const Ctx& st) {
-  return acvae_gemm_nt_dual(A, lda, B, ldb, K, nullptr, 0, nullptr, 0, 0, bias, C, ldc, M, N, acc, st.s, st.skws);
-}
 inline int gemm2(const float* A1, long lda1, const float* B1, long ldb1, int K1, const float* A2, long lda2,
                  const float* B2, long ldb2, int K2, const float* bias, float* C, long ldc, int M, int N, int acc,
                  const Ctx& st) {
@@ -82,9 +67,6 @@ inline void zb_tn(acvae::ZeroBatch& zb, TnWs ws) { zb.add(ws.p, TN_TICKETS); }
 inline int transp(const float* in, long ld_in, float* out, long ld_out, int rows, int cols, hipStream_t st) {
   return acvae_transpose(in, ld_in, out, ld_out, rows, cols, st);
 }
-inline int zero(float* p, long n, hipStream_t st) {
-  return hipMemsetAsync(p, 0, (size_t)n * sizeof(float), st) == hipSuccess ? ACVAE_OK : (int)hipGetLastError();
-}
 // fork/join of a call's work over two streams: begin() makes aux wait for everything queued on main so far, join() makes
 // main wait for everything queued on aux; with aux == main both are no-ops.  Events are released when they complete.
 struct Fork {
@@ -116,15 +98,6 @@ struct Fork {
   int join() const { return on() ? edge(aux, main_s) : ACVAE_OK; }
 };
 inline long tn_ws_floats(int M, int N, int K) { return acvae_gemm_tn_workspace_bytes(M, N, K) / 4 + 64 + TN_TICKETS; }
-
-// text-parameter table (state-dict order after the encoder; see include/acvae_hip.h)
-enum {
-  TP_DEC_EMB, TP_DEC_WIH, TP_DEC_WHH, TP_DEC_BIH, TP_DEC_BHH, TP_DEC_CLS_W, TP_DEC_CLS_B, TP_DEC_ATT_V, TP_DEC_ATT_W,
-  TP_DEC_ATT_B, TP_Q_EMB, TP_Q_WIH, TP_Q_WHH, TP_Q_BIH, TP_Q_BHH, TP_Q_WIH_R, TP_Q_WHH_R, TP_Q_BIH_R, TP_Q_BHH_R,
-  TP_Q_TML_W, TP_Q_TML_B, TP_P_EMB, TP_P_ATT_V, TP_P_ATT_W, TP_P_ATT_B, TP_P_WIH, TP_P_WHH, TP_P_BIH, TP_P_BHH,
-  TP_P_ML_W, TP_P_ML_B, TP_MLO_W, TP_MLO_B, TP_LN_W, TP_LN_B, TP_COUNT
-};
-static_assert(TP_COUNT == ACVAE_TEXT_NPARAMS, "text parameter table out of sync with the header");
 
 // ------------------------------------------------------------------------------------------ posterior
 // Stacked layers (num_layers = NL): layer k keeps its own hidden output and cell saves; the input of layer k >= 1 is the output of
@@ -1290,444 +1263,4 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
 extern "C" int acvae_caps_to_long(const float* caps, int64_t* out, int64_t n, void* stream) {
   if (!caps || !out || n <= 0) return ACVAE_EINVAL;
   return acvae::caps_to_long(caps, out, (long)n, (hipStream_t)stream);
-}
-
-// ==========================================================================================
-// single decode steps (inference only): the per-step API of the reference's pnet / decoder modules, used by the
-// beam search (models/vae_model.py:896-995) and by anyone calling the sub-modules directly
-// ==========================================================================================
-namespace {
-struct StepLayout { long skws, encproj, rnn, q, gates, gh, ml, words, attws, attws_bytes, total; };
-int step_layout(int N, int S, int E, int H, int A, int V, StepLayout& L) {
-  if (N <= 0 || S <= 0 || E <= 0 || H <= 0 || A <= 0 || V <= 1) return ACVAE_EINVAL;
-  Bump b;
-  L.skws = b.take(acvae_skinny_ws_floats());
-  L.encproj = b.take((long)N * S * (A > E ? A : E));
-  L.rnn = b.take((long)N * 3 * E);
-  L.q = b.take((long)N * (A > E ? A : E));
-  L.gates = b.take((long)N * 4 * E);
-  L.gh = b.take((long)N * 3 * H);
-  L.ml = b.take((long)N * 2 * E);
-  L.words = b.take((long)N * 2);
-  // workspace of the split-over-frames attention (acvae_attn_fwd: few query rows); its counters are zeroed by every entry point
-  L.attws_bytes = acvae_attn_fwd_workspace_bytes(N, 1, S, A, E);
-  const long w2 = acvae_attn_fwd_workspace_bytes(N, 1, S, E, E);
-  if (w2 > L.attws_bytes) L.attws_bytes = w2;
-  L.attws = b.take(L.attws_bytes / 4 + 64);
-  L.total = b.off;
-  return ACVAE_OK;
-}
-inline int step_attws_reset(float* sc, const StepLayout& L, hipStream_t st) {
-  return L.attws_bytes > 0 ? zero(sc + L.attws, 256, st) : ACVAE_OK;
-}
-}  // namespace
-
-extern "C" int64_t acvae_step_scratch_bytes(int N, int S, int E, int H, int A, int V) {
-  StepLayout L;
-  return step_layout(N, S, E, H, A, V, L) == ACVAE_OK ? L.total * 4 : -1;
-}
-
-// encproj = mem . W[:, hs_dec:]^T + b for the decoder attention (which = 0) or the prior attention (which = 1)
-extern "C" int acvae_attn_precompute(const void* const* params, int which, const float* mem, float* encproj, int N,
-                                     int S, int E, int H, int A, void* stream) {
-  if (!params || !mem || !encproj || N <= 0 || S <= 0) return ACVAE_EINVAL;
-  Ctx st{(hipStream_t)stream, nullptr};
-  auto P = [&](int i) { return (const float*)params[i]; };
-  if (which == 0) return gemm(mem, E, P(TP_DEC_ATT_W) + H, E + H, P(TP_DEC_ATT_B), encproj, A, N * S, A, E, 0, st);
-  return gemm(mem, E, P(TP_P_ATT_W) + E, 2 * E, P(TP_P_ATT_B), encproj, E, N * S, E, E, 0, st);
-}
-
-namespace {
-// One prior / decoder step over R = Nm * Tq rows: row r = n * Tq + j attends over memory n (Tq = 1: one memory per row,
-// the sub-module API; Tq = beam: the beams of a clip share its memory, no replicated copy).
-int prior_step(const void* const* params, const int64_t* word, const float* mem, const int64_t* mem_lens, const float* ep,
-               const float* h_prev, const float* c_prev, const float* last_z, const float* eps, float* mean, float* logv,
-               float* z, float* h_out, float* c_out, float* attw, float* sc, const StepLayout& L, int Nm, int Tq, int S,
-               int E, int V, const Ctx& st) {
-  auto P = [&](int i) { return (const float*)params[i]; };
-  const int N = Nm * Tq, Hp = E;
-  float* rnn = sc + L.rnn;
-  float* q = sc + L.q;
-  float* gates = sc + L.gates;
-  float* ml = sc + L.ml;
-  ACVAE_TRY(acvae::embed_gather(word, 1, P(TP_P_EMB), V, rnn, 3 * E, N, E, st));
-  ACVAE_TRY(gemm(rnn, 3 * E, P(TP_P_ATT_W), 2 * E, nullptr, q, E, N, E, E, 0, st));
-  ACVAE_TRY(acvae_attn_fwd(q, (long)Tq * E, E, ep, mem, mem_lens, P(TP_P_ATT_V), rnn + E, (long)Tq * 3 * E, 3 * E, attw,
-                           (long)Tq * S, S, Nm, Tq, S, E, E, L.attws_bytes > 0 ? sc + L.attws : nullptr, L.attws_bytes, st, 0));
-  ACVAE_TRY(acvae::copy_rows(rnn + 2 * E, 3 * E, last_z, E, N, E, st));
-  ACVAE_TRY(gemm(rnn, 3 * E, P(TP_P_WIH), 3 * E, P(TP_P_BIH), gates, 4 * Hp, N, 4 * Hp, 3 * E, 0, st));
-  ACVAE_TRY(gemm(h_prev, Hp, P(TP_P_WHH), Hp, P(TP_P_BHH), gates, 4 * Hp, N, 4 * Hp, Hp, 1, st));
-  ACVAE_TRY(acvae::lstm_fwd(gates, 4 * Hp, c_prev, Hp, h_out, Hp, c_out, Hp, nullptr, 0, N, Hp, st));
-  ACVAE_TRY(gemm(h_out, Hp, P(TP_P_ML_W), Hp, P(TP_P_ML_B), ml, 2 * E, N, 2 * E, Hp, 0, st));
-  return acvae_reparam_fwd(ml, 2 * E, eps, E, mean, logv, z, E, nullptr, 0, N, E, st);
-}
-
-int decoder_step(const void* const* params, const int64_t* word, const float* h_prev, const float* mem,
-                 const int64_t* mem_lens, const float* ed, const float* z, float* logits, float* h_out, float* attw,
-                 float* rnn_input, float* sc, const StepLayout& L, int Nm, int Tq, int S, int E, int H, int A, int V,
-                 const Ctx& st) {
-  auto P = [&](int i) { return (const float*)params[i]; };
-  const int N = Nm * Tq;
-  float* q = sc + L.q;
-  float* gi = sc + L.gates;
-  float* gh = sc + L.gh;
-  ACVAE_TRY(acvae::embed_gather(word, 1, P(TP_DEC_EMB), V, rnn_input, 3 * E, N, E, st));
-  ACVAE_TRY(gemm(h_prev, H, P(TP_DEC_ATT_W), E + H, nullptr, q, A, N, A, H, 0, st));
-  ACVAE_TRY(acvae_attn_fwd(q, (long)Tq * A, A, ed, mem, mem_lens, P(TP_DEC_ATT_V), rnn_input + E, (long)Tq * 3 * E, 3 * E,
-                           attw, (long)Tq * S, S, Nm, Tq, S, A, E, L.attws_bytes > 0 ? sc + L.attws : nullptr, L.attws_bytes, st, 0));
-  ACVAE_TRY(acvae::copy_rows(rnn_input + 2 * E, 3 * E, z, E, N, E, st));
-  ACVAE_TRY(gemm(rnn_input, 3 * E, P(TP_DEC_WIH), 3 * E, P(TP_DEC_BIH), gi, 3 * H, N, 3 * H, 3 * E, 0, st));
-  ACVAE_TRY(gemm(h_prev, H, P(TP_DEC_WHH), H, P(TP_DEC_BHH), gh, 3 * H, N, 3 * H, H, 0, st));
-  ACVAE_TRY(acvae::gru_fwd(gi, 3 * H, gh, 3 * H, h_prev, H, h_out, H, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, N,
-                           H, st));
-  return gemm(h_out, H, P(TP_DEC_CLS_W), H, P(TP_DEC_CLS_B), logits, V, N, V, H, 0, st);
-}
-}  // namespace
-
-extern "C" int acvae_prior_step_fwd(const void* const* params, const int64_t* word, const float* mem,
-                                    const int64_t* mem_lens, const float* encproj_p, const float* h_prev,
-                                    const float* c_prev, const float* last_z, const float* eps, float* mean, float* logv,
-                                    float* z, float* h_out, float* c_out, float* attw, void* scratch_v,
-                                    int64_t scratch_bytes, int N, int S, int E, int V, void* stream) {
-  StepLayout L;
-  ACVAE_TRY(step_layout(N, S, E, E, E, V, L));
-  if (!params || !word || !mem || !mem_lens || !h_prev || !c_prev || !last_z || !eps || !mean || !logv || !z ||
-      !h_out || !c_out || !attw || !scratch_v)
-    return ACVAE_EINVAL;
-  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
-  float* sc = (float*)scratch_v;
-  Ctx st{(hipStream_t)stream, sc + L.skws};
-  ACVAE_TRY(acvae_skinny_ws_reset(st.skws, st.s));
-  ACVAE_TRY(step_attws_reset(sc, L, st.s));
-  const float* ep = encproj_p;
-  if (!ep) {
-    ACVAE_TRY(acvae_attn_precompute(params, 1, mem, sc + L.encproj, N, S, E, E, E, stream));
-    ep = sc + L.encproj;
-  }
-  return prior_step(params, word, mem, mem_lens, ep, h_prev, c_prev, last_z, eps, mean, logv, z, h_out, c_out, attw, sc,
-                    L, N, 1, S, E, V, st);
-}
-
-extern "C" int acvae_decoder_step_fwd(const void* const* params, const int64_t* word, const float* h_prev,
-                                      const float* mem, const int64_t* mem_lens, const float* encproj_d, const float* z,
-                                      float* logits, float* h_out, float* attw, float* rnn_input, void* scratch_v,
-                                      int64_t scratch_bytes, int N, int S, int E, int H, int A, int V, void* stream) {
-  StepLayout L;
-  ACVAE_TRY(step_layout(N, S, E, H, A, V, L));
-  if (!params || !word || !h_prev || !mem || !mem_lens || !z || !logits || !h_out || !attw || !rnn_input || !scratch_v)
-    return ACVAE_EINVAL;
-  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
-  float* sc = (float*)scratch_v;
-  Ctx st{(hipStream_t)stream, sc + L.skws};
-  ACVAE_TRY(acvae_skinny_ws_reset(st.skws, st.s));
-  ACVAE_TRY(step_attws_reset(sc, L, st.s));
-  const float* ed = encproj_d;
-  if (!ed) {
-    ACVAE_TRY(acvae_attn_precompute(params, 0, mem, sc + L.encproj, N, S, E, H, A, stream));
-    ed = sc + L.encproj;
-  }
-  return decoder_step(params, word, h_prev, mem, mem_lens, ed, z, logits, h_out, attw, rnn_input, sc, L, N, 1, S, E, H,
-                      A, V, st);
-}
-
-// ==========================================================================================
-// validation beam search as ONE call (models/vae_model.py:896-995): all clips advance together, the
-// beams of a clip share its memory, and nothing but kernels is enqueued per step.  Instead of re-gathering the word and
-// attention-weight histories by prev_word_inds every step (:917-921, :979), each step's parent row, word and weights are
-// kept and beam 0 is traced back once at the end, which yields the same seqs[0] / attn_weights[0] (:990-995).
-// ==========================================================================================
-namespace {
-struct BeamLayout { long step, encd, encp, h, hp, cp, lz, mean, logv, z, h2, hp2, cp2, attp, logits, rnn, lse, topk, scores,
-                    attw, words, total; };
-int beam_layout(int N, int beam, int T, int S, int E, int H, int A, int V, BeamLayout& L) {
-  if (N <= 0 || beam <= 0 || T <= 0) return ACVAE_EINVAL;
-  StepLayout sl;
-  const long R = (long)N * beam;
-  if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
-  ACVAE_TRY(step_layout((int)R, S, E, H, A, V, sl));
-  Bump b;
-  L.step = b.take(sl.total);
-  L.encd = b.take((long)N * S * A);
-  L.encp = b.take((long)N * S * E);
-  L.h = b.take(R * H); L.hp = b.take(R * E); L.cp = b.take(R * E); L.lz = b.take(R * E);
-  L.mean = b.take(R * E); L.logv = b.take(R * E); L.z = b.take(R * E);
-  L.h2 = b.take(R * H); L.hp2 = b.take(R * E); L.cp2 = b.take(R * E);
-  L.attp = b.take(R * S);
-  L.logits = b.take(R * V);
-  L.rnn = b.take(R * 3 * E);
-  L.lse = b.take(R);
-  L.topk = b.take(R);
-  L.scores = b.take(R * V);
-  L.attw = b.take((long)T * R * S);
-  L.words = b.take(2 * ((long)(3 * T + 1) * R));        // int64: word [R], then per step idx / parent / word [T][R]
-  L.total = b.off;
-  return ACVAE_OK;
-}
-
-struct GatherJob { const float* src; float* dst; int width; };
-using GatherTable = acvae::JobTable<GatherJob, 4>;
-__global__ __launch_bounds__(256) void beam_gather_kernel(GatherTable g, const int64_t* __restrict__ parent) {
-  const GatherJob j = g.job[blockIdx.y];
-  const long r = blockIdx.x, p = parent[r];
-  for (int i = threadIdx.x; i < j.width; i += blockDim.x) j.dst[r * j.width + i] = j.src[p * j.width + i];
-}
-
-// one workgroup per clip: follow beam 0's parents from the last step to the first
-__global__ __launch_bounds__(256) void beam_trace_kernel(const int64_t* __restrict__ parent, const int64_t* __restrict__ word,
-                                                         const float* __restrict__ attw, int64_t* __restrict__ seqs,
-                                                         float* __restrict__ attw_out, long hist_stride, int R, int beam, int T,
-                                                         int S) {
-  const int n = blockIdx.x;
-  long r = (long)n * beam;
-  for (int t = T - 1; t >= 0; --t) {
-    const long p = parent[t * hist_stride + r];
-    if (threadIdx.x == 0) seqs[(long)n * T + t] = word[t * hist_stride + r];
-    const float* w = attw + ((long)t * R + p) * S;
-    for (int s = threadIdx.x; s < S; s += blockDim.x) attw_out[((long)n * S + s) * T + t] = w[s];
-    r = p;
-  }
-}
-__global__ void fill_words_kernel(int64_t* w, int64_t v, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) w[i] = v;
-}
-}  // namespace
-
-extern "C" int64_t acvae_beam_search_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A, int V) {
-  BeamLayout L;
-  return beam_layout(N, beam, max_length, S, E, H, A, V, L) == ACVAE_OK ? L.total * 4 : -1;
-}
-
-extern "C" int acvae_beam_search(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
-                                 int64_t start_idx, int64_t* seqs, float* attw_out, void* scratch_v, int64_t scratch_bytes,
-                                 int N, int beam, int max_length, int S, int E, int H, int A, int V, void* stream) {
-  BeamLayout L;
-  ACVAE_TRY(beam_layout(N, beam, max_length, S, E, H, A, V, L));
-  if (!params || !mem || !mem_lens || !eps || !seqs || !attw_out || !scratch_v) return ACVAE_EINVAL;
-  if (start_idx < 0 || start_idx >= V || beam > 64 || H != E) return ACVAE_EINVAL;   // the prior LSTM is E wide
-  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
-  StepLayout SL;
-  const int R = N * beam, T = max_length;
-  ACVAE_TRY(step_layout(R, S, E, H, A, V, SL));
-  float* sc = (float*)scratch_v;
-  float* ssc = sc + L.step;
-  Ctx st{(hipStream_t)stream, ssc + SL.skws};
-  ACVAE_TRY(acvae_skinny_ws_reset(st.skws, st.s));
-  ACVAE_TRY(step_attws_reset(ssc, SL, st.s));
-  ACVAE_TRY(acvae_attn_precompute(params, 0, mem, sc + L.encd, N, S, E, H, A, stream));
-  ACVAE_TRY(acvae_attn_precompute(params, 1, mem, sc + L.encp, N, S, E, E, E, stream));
-  float *h = sc + L.h, *hp = sc + L.hp, *cp = sc + L.cp, *lz = sc + L.lz;
-  float *h2 = sc + L.h2, *hp2 = sc + L.hp2, *cp2 = sc + L.cp2, *z = sc + L.z;
-  float* topk = sc + L.topk;
-  int64_t* word = (int64_t*)(sc + L.words);
-  int64_t* hist = word + R;                              // [T][3][R]: flat index, parent row, word
-  ACVAE_TRY(zero(h, (long)R * H, st));
-  ACVAE_TRY(zero(hp, (long)R * E, st));
-  ACVAE_TRY(zero(cp, (long)R * E, st));
-  ACVAE_TRY(zero(lz, (long)R * E, st));
-  ACVAE_TRY(zero(topk, R, st));
-  hipLaunchKernelGGL(fill_words_kernel, dim3((R + 255) / 256), dim3(256), 0, st.s, word, start_idx, R);
-  const int64_t* w_t = word;
-  for (int t = 0; t < T; ++t) {
-    float* attw_t = sc + L.attw + (long)t * R * S;
-    int64_t* idx_t = hist + (long)t * 3 * R;
-    int64_t* par_t = idx_t + R;
-    int64_t* nxt_t = par_t + R;
-    ACVAE_TRY(prior_step(params, w_t, mem, mem_lens, sc + L.encp, hp, cp, lz, eps + (long)t * R * E, sc + L.mean,
-                         sc + L.logv, z, hp2, cp2, sc + L.attp, ssc, SL, N, beam, S, E, V, st));
-    ACVAE_TRY(decoder_step(params, w_t, h, mem, mem_lens, sc + L.encd, z, sc + L.logits, h2, attw_t, sc + L.rnn, ssc, SL,
-                           N, beam, S, E, H, A, V, st));
-    ACVAE_TRY(acvae_row_logsoftmax_argmax(sc + L.logits, V, V, nullptr, nullptr, sc + L.lse, 1, 1, R, 1, V, stream));
-    ACVAE_TRY(acvae_logprob_add(sc + L.logits, V, sc + L.lse, topk, sc + L.scores, R, V, stream));
-    ACVAE_TRY(acvae_topk_flat_batched(sc + L.scores, (int64_t)beam * V, (int64_t)beam * V, beam, V, topk, idx_t, par_t,
-                                      nxt_t, N, beam, stream));
-    if (t + 1 < T) {                                     // vae_model.py:961-968: next step's states follow their parents
-      GatherTable g;
-      g.add({h2, h, H}); g.add({hp2, hp, E}); g.add({cp2, cp, E}); g.add({z, lz, E});
-      hipLaunchKernelGGL(beam_gather_kernel, dim3(R, g.n), dim3(256), 0, st.s, g, par_t);
-      w_t = nxt_t;
-    }
-  }
-  // hist rows are [idx | parent | word] per step: strided views for the trace
-  hipLaunchKernelGGL(beam_trace_kernel, dim3(N), dim3(256), 0, st.s, hist + R, hist + 2 * R, sc + L.attw, seqs, attw_out,
-                     3L * R, R, beam, T, S);
-  ACVAE_LAUNCH_CHECK();
-  return ACVAE_OK;
-}
-
-// ==========================================================================================
-// Ensemble decoding as ONE call: BaseRunner._ensemble_batch / _ensemble_batch_beam_search (runners/base_runner.py:562-694)
-// carried onto Hybrid_VAEModel's step (prior step -> z -> decoder step, models/vae_model.py:896-995; the reference's own
-// ensemble code calls model.decoder without z).  Every member keeps its own memory, attention projections and recurrent
-// states; all are fed the same word; acvae_ensemble_mix averages their word probabilities (base_runner.py:616-618,
-// 675-680) and the word is picked from the average:
-//   beam   - flat top-k over beam * V per clip at every step (the rows of a clip differ in z from t = 0 on, so the
-//            reference's "row 0 only at t = 0", :681-682, does not carry over), states gathered by parent once per member,
-//            beam 0 traced back at the end: with M = 1 the launches of acvae_beam_search in the same order, with
-//            acvae_ensemble_mix in the place of acvae_row_logsoftmax_argmax + acvae_logprob_add (bit-equal at M = 1);
-//   greedy - the mix kernel's own argmax; a row that has produced end_idx keeps emitting and feeding it, and all
-//            max_length steps run without a host read-back: seqs prefilled with end_idx, as :584, 622-630 leave it.
-// Members run one after the other on the one stream.
-// ==========================================================================================
-namespace {
-struct EnsMember { long step, encd, encp, h, hp, cp, lz, mean, logv, z, h2, hp2, cp2, attp, attw, logits, rnn; };
-struct EnsLayout { EnsMember m[ACVAE_ENSEMBLE_MAX]; long scores, topk, best, words, total; };
-int ens_layout(int M, int N, int beam, int T, const int* S, const int* E, const int* H, const int* A, int V, EnsLayout& L) {
-  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A || N <= 0 || beam <= 0 || T <= 0) return ACVAE_EINVAL;
-  const long R = (long)N * beam;
-  if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
-  Bump b;
-  for (int m = 0; m < M; ++m) {
-    StepLayout sl;
-    ACVAE_TRY(step_layout((int)R, S[m], E[m], H[m], A[m], V, sl));
-    EnsMember& o = L.m[m];
-    const long e = E[m], h = H[m];
-    o.step = b.take(sl.total);
-    o.encd = b.take((long)N * S[m] * A[m]);
-    o.encp = b.take((long)N * S[m] * e);
-    o.h = b.take(R * h); o.hp = b.take(R * e); o.cp = b.take(R * e); o.lz = b.take(R * e);
-    o.mean = b.take(R * e); o.logv = b.take(R * e); o.z = b.take(R * e);
-    o.h2 = b.take(R * h); o.hp2 = b.take(R * e); o.cp2 = b.take(R * e);
-    o.attp = b.take(R * S[m]);
-    o.attw = b.take(R * S[m]);
-    o.logits = b.take(R * V);
-    o.rnn = b.take(R * 3 * e);
-  }
-  L.scores = b.take(R * V);
-  L.topk = b.take(R);
-  L.best = b.take(R);
-  L.words = b.take(2 * ((long)(3 * T + 2) * R));        // int64: word [R], argmax [R], per step idx / parent / word [T][R]
-  L.total = b.off;
-  return ACVAE_OK;
-}
-
-// greedy bookkeeping of one step (base_runner.py:618-628): a finished row keeps end_idx
-__global__ void ens_greedy_pick_kernel(const int64_t* __restrict__ arg, const float* __restrict__ best,
-                                       int64_t* __restrict__ seqs, float* __restrict__ logprobs, int64_t* __restrict__ word,
-                                       int64_t end_idx, int t, int T, int R) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= R) return;
-  int64_t w = arg[r];
-  if (t > 0 && seqs[(long)r * T + t - 1] == end_idx) w = end_idx;
-  seqs[(long)r * T + t] = w;
-  logprobs[(long)r * T + t] = best[r];
-  word[r] = w;
-}
-// one thread per clip: beam 0's words from the last step back to the first, and its final score
-__global__ void ens_trace_kernel(const int64_t* __restrict__ parent, const int64_t* __restrict__ word,
-                                 const float* __restrict__ topk, int64_t* __restrict__ seqs, float* __restrict__ logprobs,
-                                 long hist_stride, int beam, int T, int N) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  long r = (long)n * beam;
-  logprobs[n] = topk[r];
-  for (int t = T - 1; t >= 0; --t) {
-    seqs[(long)n * T + t] = word[t * hist_stride + r];
-    r = parent[t * hist_stride + r];
-  }
-}
-}  // namespace
-
-extern "C" int64_t acvae_ensemble_search_scratch_bytes(int M, int N, int beam, int max_length, const int* S, const int* E,
-                                                       const int* H, const int* A, int V) {
-  EnsLayout L;
-  return ens_layout(M, N, beam, max_length, S, E, H, A, V, L) == ACVAE_OK ? L.total * 4 : -1;
-}
-
-extern "C" int acvae_ensemble_search(const void* const* const* params, const float* const* mem,
-                                     const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
-                                     const int* H, const int* A, int M, int64_t start_idx, int64_t end_idx, int greedy,
-                                     int64_t* seqs, float* logprobs, void* scratch_v, int64_t scratch_bytes, int N, int beam,
-                                     int max_length, int V, void* stream) {
-  // ---- refusals, all before the first launch
-  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !params || !mem || !mem_lens || !eps || !S || !E || !H || !A) return ACVAE_EINVAL;
-  for (int m = 0; m < M; ++m)
-    if (!params[m] || !mem[m] || !mem_lens[m] || !eps[m] || H[m] != E[m]) return ACVAE_EINVAL;   // the prior LSTM is E wide
-  if (!seqs || !logprobs || !scratch_v) return ACVAE_EINVAL;
-  if (beam > 64 || (greedy && beam != 1)) return ACVAE_EINVAL;
-  if (start_idx < 0 || start_idx >= V || end_idx < 0 || end_idx >= V) return ACVAE_EINVAL;
-  EnsLayout L;
-  ACVAE_TRY(ens_layout(M, N, beam, max_length, S, E, H, A, V, L));
-  if (!greedy && beam > 16) return ACVAE_EUNSUPPORTED;   // acvae_topk_flat_batched selects k <= 16: refused here, not mid-call
-  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
-
-  const int R = N * beam, T = max_length;
-  float* sc = (float*)scratch_v;
-  hipStream_t s = (hipStream_t)stream;
-  StepLayout SL[ACVAE_ENSEMBLE_MAX];
-  // per member: the buffers that change hands from step to step (greedy swaps them, the beam search gathers by parent)
-  float *h[ACVAE_ENSEMBLE_MAX], *hp[ACVAE_ENSEMBLE_MAX], *cp[ACVAE_ENSEMBLE_MAX], *lz[ACVAE_ENSEMBLE_MAX];
-  float *h2[ACVAE_ENSEMBLE_MAX], *hp2[ACVAE_ENSEMBLE_MAX], *cp2[ACVAE_ENSEMBLE_MAX], *z[ACVAE_ENSEMBLE_MAX];
-  const float* logit_ptr[ACVAE_ENSEMBLE_MAX];
-  int64_t logit_ld[ACVAE_ENSEMBLE_MAX];
-  for (int m = 0; m < M; ++m) {
-    const EnsMember& o = L.m[m];
-    ACVAE_TRY(step_layout(R, S[m], E[m], H[m], A[m], V, SL[m]));
-    float* ssc = sc + o.step;
-    Ctx st{s, ssc + SL[m].skws};
-    ACVAE_TRY(acvae_skinny_ws_reset(st.skws, st.s));
-    ACVAE_TRY(step_attws_reset(ssc, SL[m], st.s));
-    ACVAE_TRY(acvae_attn_precompute(params[m], 0, mem[m], sc + o.encd, N, S[m], E[m], H[m], A[m], stream));
-    ACVAE_TRY(acvae_attn_precompute(params[m], 1, mem[m], sc + o.encp, N, S[m], E[m], E[m], E[m], stream));
-    h[m] = sc + o.h; hp[m] = sc + o.hp; cp[m] = sc + o.cp; lz[m] = sc + o.lz;
-    h2[m] = sc + o.h2; hp2[m] = sc + o.hp2; cp2[m] = sc + o.cp2; z[m] = sc + o.z;
-    ACVAE_TRY(zero(h[m], (long)R * H[m], s));
-    ACVAE_TRY(zero(hp[m], (long)R * E[m], s));
-    ACVAE_TRY(zero(cp[m], (long)R * E[m], s));
-    ACVAE_TRY(zero(lz[m], (long)R * E[m], s));
-    logit_ptr[m] = sc + o.logits;
-    logit_ld[m] = V;
-  }
-  float* topk = sc + L.topk;
-  float* best = sc + L.best;
-  int64_t* word = (int64_t*)(sc + L.words);
-  int64_t* arg = word + R;
-  int64_t* hist = arg + R;                               // [T][3][R]: flat index, parent row, word (beam search)
-  ACVAE_TRY(zero(topk, R, s));
-  hipLaunchKernelGGL(fill_words_kernel, dim3((R + 255) / 256), dim3(256), 0, s, word, start_idx, R);
-  const int64_t* w_t = word;
-  for (int t = 0; t < T; ++t) {
-    int64_t* idx_t = hist + (long)t * 3 * R;
-    int64_t* par_t = idx_t + R;
-    int64_t* nxt_t = par_t + R;
-    for (int m = 0; m < M; ++m) {
-      const EnsMember& o = L.m[m];
-      float* ssc = sc + o.step;
-      Ctx st{s, ssc + SL[m].skws};
-      ACVAE_TRY(prior_step(params[m], w_t, mem[m], mem_lens[m], sc + o.encp, hp[m], cp[m], lz[m],
-                           eps[m] + (long)t * R * E[m], sc + o.mean, sc + o.logv, z[m], hp2[m], cp2[m], sc + o.attp, ssc,
-                           SL[m], N, beam, S[m], E[m], V, st));
-      ACVAE_TRY(decoder_step(params[m], w_t, h[m], mem[m], mem_lens[m], sc + o.encd, z[m], sc + o.logits, h2[m],
-                             sc + o.attw, sc + o.rnn, ssc, SL[m], N, beam, S[m], E[m], H[m], A[m], V, st));
-    }
-    if (greedy) {
-      ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, nullptr, 0, arg, best, 1, R, V, stream));
-      hipLaunchKernelGGL(ens_greedy_pick_kernel, dim3((R + 255) / 256), dim3(256), 0, s, arg, best, seqs, logprobs, word,
-                         end_idx, t, T, R);
-      for (int m = 0; m < M; ++m) {                      // the new states become the next step's previous ones
-        float* x;
-        x = h[m]; h[m] = h2[m]; h2[m] = x;
-        x = hp[m]; hp[m] = hp2[m]; hp2[m] = x;
-        x = cp[m]; cp[m] = cp2[m]; cp2[m] = x;
-        x = lz[m]; lz[m] = z[m]; z[m] = x;
-      }
-      continue;
-    }
-    ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, topk, sc + L.scores, V, nullptr, nullptr, 0, R, V, stream));
-    ACVAE_TRY(acvae_topk_flat_batched(sc + L.scores, (int64_t)beam * V, (int64_t)beam * V, beam, V, topk, idx_t, par_t,
-                                      nxt_t, N, beam, stream));
-    if (t + 1 < T) {                                     // vae_model.py:961-968: next step's states follow their parents
-      for (int m = 0; m < M; ++m) {
-        GatherTable g;
-        g.add({h2[m], h[m], H[m]}); g.add({hp2[m], hp[m], E[m]}); g.add({cp2[m], cp[m], E[m]}); g.add({z[m], lz[m], E[m]});
-        hipLaunchKernelGGL(beam_gather_kernel, dim3(R, g.n), dim3(256), 0, s, g, par_t);
-      }
-      w_t = nxt_t;
-    }
-  }
-  if (!greedy)
-    hipLaunchKernelGGL(ens_trace_kernel, dim3((N + 255) / 256), dim3(256), 0, s, hist + R, hist + 2 * R, topk, seqs, logprobs,
-                       3L * R, beam, T, N);
-  ACVAE_LAUNCH_CHECK();
-  return ACVAE_OK;
 }

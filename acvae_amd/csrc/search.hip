@@ -1,0 +1,378 @@
+// The inference search of the text side, each entry point ONE library call with no synchronisation inside:
+//   - single decode steps, the per-step API of the reference's pnet / decoder modules (acvae_prior_step_fwd,
+//     acvae_decoder_step_fwd, acvae_attn_precompute);
+//   - the search over M members' averaged word probabilities, greedy or beam (acvae_ensemble_search), and the validation
+//     beam search of one model (acvae_beam_search), which is its M = 1 case plus beam 0's attention-weight history.
+// The training-time composites are decoder.hip.
+#include <utility>
+#include "common.h"
+#include "conv.h"
+#include "rnn.h"
+#include "text_common.h"
+
+// ==========================================================================================
+// single decode steps (inference only): the per-step API of the reference's pnet / decoder modules, used by the
+// beam search (models/vae_model.py:896-995) and by anyone calling the sub-modules directly
+// ==========================================================================================
+namespace {
+struct StepLayout { long skws, encproj, rnn, q, gates, gh, ml, words, attws, attws_bytes, total; };
+int step_layout(int N, int S, int E, int H, int A, int V, StepLayout& L) {
+  if (N <= 0 || S <= 0 || E <= 0 || H <= 0 || A <= 0 || V <= 1) return ACVAE_EINVAL;
+  Bump b;
+  L.skws = b.take(acvae_skinny_ws_floats());
+  L.encproj = b.take((long)N * S * (A > E ? A : E));
+  L.rnn = b.take((long)N * 3 * E);
+  L.q = b.take((long)N * (A > E ? A : E));
+  L.gates = b.take((long)N * 4 * E);
+  L.gh = b.take((long)N * 3 * H);
+  L.ml = b.take((long)N * 2 * E);
+  L.words = b.take((long)N * 2);
+  // workspace of the split-over-frames attention (acvae_attn_fwd: few query rows); its counters are zeroed by every entry point
+  L.attws_bytes = acvae_attn_fwd_workspace_bytes(N, 1, S, A, E);
+  const long w2 = acvae_attn_fwd_workspace_bytes(N, 1, S, E, E);
+  if (w2 > L.attws_bytes) L.attws_bytes = w2;
+  L.attws = b.take(L.attws_bytes / 4 + 64);
+  L.total = b.off;
+  return ACVAE_OK;
+}
+inline int step_attws_reset(float* sc, const StepLayout& L, hipStream_t st) {
+  return L.attws_bytes > 0 ? zero(sc + L.attws, 256, st) : ACVAE_OK;
+}
+}  // namespace
+
+extern "C" int64_t acvae_step_scratch_bytes(int N, int S, int E, int H, int A, int V) {
+  StepLayout L;
+  return step_layout(N, S, E, H, A, V, L) == ACVAE_OK ? L.total * 4 : -1;
+}
+
+// encproj = mem . W[:, hs_dec:]^T + b for the decoder attention (which = 0) or the prior attention (which = 1)
+extern "C" int acvae_attn_precompute(const void* const* params, int which, const float* mem, float* encproj, int N,
+                                     int S, int E, int H, int A, void* stream) {
+  if (!params || !mem || !encproj || N <= 0 || S <= 0) return ACVAE_EINVAL;
+  Ctx st{(hipStream_t)stream, nullptr};
+  auto P = [&](int i) { return (const float*)params[i]; };
+  if (which == 0) return gemm(mem, E, P(TP_DEC_ATT_W) + H, E + H, P(TP_DEC_ATT_B), encproj, A, N * S, A, E, 0, st);
+  return gemm(mem, E, P(TP_P_ATT_W) + E, 2 * E, P(TP_P_ATT_B), encproj, E, N * S, E, E, 0, st);
+}
+
+namespace {
+// One prior / decoder step over R = Nm * Tq rows: row r = n * Tq + j attends over memory n (Tq = 1: one memory per row,
+// the sub-module API; Tq = beam: the beams of a clip share its memory, no replicated copy).
+int prior_step(const void* const* params, const int64_t* word, const float* mem, const int64_t* mem_lens, const float* ep,
+               const float* h_prev, const float* c_prev, const float* last_z, const float* eps, float* mean, float* logv,
+               float* z, float* h_out, float* c_out, float* attw, float* sc, const StepLayout& L, int Nm, int Tq, int S,
+               int E, int V, const Ctx& st) {
+  auto P = [&](int i) { return (const float*)params[i]; };
+  const int N = Nm * Tq, Hp = E;
+  float* rnn = sc + L.rnn;
+  float* q = sc + L.q;
+  float* gates = sc + L.gates;
+  float* ml = sc + L.ml;
+  ACVAE_TRY(acvae::embed_gather(word, 1, P(TP_P_EMB), V, rnn, 3 * E, N, E, st));
+  ACVAE_TRY(gemm(rnn, 3 * E, P(TP_P_ATT_W), 2 * E, nullptr, q, E, N, E, E, 0, st));
+  ACVAE_TRY(acvae_attn_fwd(q, (long)Tq * E, E, ep, mem, mem_lens, P(TP_P_ATT_V), rnn + E, (long)Tq * 3 * E, 3 * E, attw,
+                           (long)Tq * S, S, Nm, Tq, S, E, E, L.attws_bytes > 0 ? sc + L.attws : nullptr, L.attws_bytes, st, 0));
+  ACVAE_TRY(acvae::copy_rows(rnn + 2 * E, 3 * E, last_z, E, N, E, st));
+  ACVAE_TRY(gemm(rnn, 3 * E, P(TP_P_WIH), 3 * E, P(TP_P_BIH), gates, 4 * Hp, N, 4 * Hp, 3 * E, 0, st));
+  ACVAE_TRY(gemm(h_prev, Hp, P(TP_P_WHH), Hp, P(TP_P_BHH), gates, 4 * Hp, N, 4 * Hp, Hp, 1, st));
+  ACVAE_TRY(acvae::lstm_fwd(gates, 4 * Hp, c_prev, Hp, h_out, Hp, c_out, Hp, nullptr, 0, N, Hp, st));
+  ACVAE_TRY(gemm(h_out, Hp, P(TP_P_ML_W), Hp, P(TP_P_ML_B), ml, 2 * E, N, 2 * E, Hp, 0, st));
+  return acvae_reparam_fwd(ml, 2 * E, eps, E, mean, logv, z, E, nullptr, 0, N, E, st);
+}
+
+int decoder_step(const void* const* params, const int64_t* word, const float* h_prev, const float* mem,
+                 const int64_t* mem_lens, const float* ed, const float* z, float* logits, float* h_out, float* attw,
+                 float* rnn_input, float* sc, const StepLayout& L, int Nm, int Tq, int S, int E, int H, int A, int V,
+                 const Ctx& st) {
+  auto P = [&](int i) { return (const float*)params[i]; };
+  const int N = Nm * Tq;
+  float* q = sc + L.q;
+  float* gi = sc + L.gates;
+  float* gh = sc + L.gh;
+  ACVAE_TRY(acvae::embed_gather(word, 1, P(TP_DEC_EMB), V, rnn_input, 3 * E, N, E, st));
+  ACVAE_TRY(gemm(h_prev, H, P(TP_DEC_ATT_W), E + H, nullptr, q, A, N, A, H, 0, st));
+  ACVAE_TRY(acvae_attn_fwd(q, (long)Tq * A, A, ed, mem, mem_lens, P(TP_DEC_ATT_V), rnn_input + E, (long)Tq * 3 * E, 3 * E,
+                           attw, (long)Tq * S, S, Nm, Tq, S, A, E, L.attws_bytes > 0 ? sc + L.attws : nullptr, L.attws_bytes, st, 0));
+  ACVAE_TRY(acvae::copy_rows(rnn_input + 2 * E, 3 * E, z, E, N, E, st));
+  ACVAE_TRY(gemm(rnn_input, 3 * E, P(TP_DEC_WIH), 3 * E, P(TP_DEC_BIH), gi, 3 * H, N, 3 * H, 3 * E, 0, st));
+  ACVAE_TRY(gemm(h_prev, H, P(TP_DEC_WHH), H, P(TP_DEC_BHH), gh, 3 * H, N, 3 * H, H, 0, st));
+  ACVAE_TRY(acvae::gru_fwd(gi, 3 * H, gh, 3 * H, h_prev, H, h_out, H, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, N,
+                           H, st));
+  return gemm(h_out, H, P(TP_DEC_CLS_W), H, P(TP_DEC_CLS_B), logits, V, N, V, H, 0, st);
+}
+}  // namespace
+
+extern "C" int acvae_prior_step_fwd(const void* const* params, const int64_t* word, const float* mem,
+                                    const int64_t* mem_lens, const float* encproj_p, const float* h_prev,
+                                    const float* c_prev, const float* last_z, const float* eps, float* mean, float* logv,
+                                    float* z, float* h_out, float* c_out, float* attw, void* scratch_v,
+                                    int64_t scratch_bytes, int N, int S, int E, int V, void* stream) {
+  StepLayout L;
+  ACVAE_TRY(step_layout(N, S, E, E, E, V, L));
+  if (!params || !word || !mem || !mem_lens || !h_prev || !c_prev || !last_z || !eps || !mean || !logv || !z ||
+      !h_out || !c_out || !attw || !scratch_v)
+    return ACVAE_EINVAL;
+  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
+  float* sc = (float*)scratch_v;
+  Ctx st{(hipStream_t)stream, sc + L.skws};
+  ACVAE_TRY(acvae_skinny_ws_reset(st.skws, st.s));
+  ACVAE_TRY(step_attws_reset(sc, L, st.s));
+  const float* ep = encproj_p;
+  if (!ep) {
+    ACVAE_TRY(acvae_attn_precompute(params, 1, mem, sc + L.encproj, N, S, E, E, E, stream));
+    ep = sc + L.encproj;
+  }
+  return prior_step(params, word, mem, mem_lens, ep, h_prev, c_prev, last_z, eps, mean, logv, z, h_out, c_out, attw, sc,
+                    L, N, 1, S, E, V, st);
+}
+
+extern "C" int acvae_decoder_step_fwd(const void* const* params, const int64_t* word, const float* h_prev,
+                                      const float* mem, const int64_t* mem_lens, const float* encproj_d, const float* z,
+                                      float* logits, float* h_out, float* attw, float* rnn_input, void* scratch_v,
+                                      int64_t scratch_bytes, int N, int S, int E, int H, int A, int V, void* stream) {
+  StepLayout L;
+  ACVAE_TRY(step_layout(N, S, E, H, A, V, L));
+  if (!params || !word || !h_prev || !mem || !mem_lens || !z || !logits || !h_out || !attw || !rnn_input || !scratch_v)
+    return ACVAE_EINVAL;
+  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
+  float* sc = (float*)scratch_v;
+  Ctx st{(hipStream_t)stream, sc + L.skws};
+  ACVAE_TRY(acvae_skinny_ws_reset(st.skws, st.s));
+  ACVAE_TRY(step_attws_reset(sc, L, st.s));
+  const float* ed = encproj_d;
+  if (!ed) {
+    ACVAE_TRY(acvae_attn_precompute(params, 0, mem, sc + L.encproj, N, S, E, H, A, stream));
+    ed = sc + L.encproj;
+  }
+  return decoder_step(params, word, h_prev, mem, mem_lens, ed, z, logits, h_out, attw, rnn_input, sc, L, N, 1, S, E, H,
+                      A, V, st);
+}
+
+// ==========================================================================================
+// The search as ONE call, over M >= 1 members: BaseRunner._ensemble_batch / _ensemble_batch_beam_search
+// (runners/base_runner.py:562-694) carried onto Hybrid_VAEModel's step (prior step -> z -> decoder step,
+// models/vae_model.py:896-995; the reference's own ensemble code calls model.decoder without z).  All clips advance
+// together, the beams of a clip share its memory, and nothing but kernels is enqueued per step.  Every
+// member keeps its own memory, attention projections and recurrent states; all are fed the same word;
+// acvae_ensemble_mix averages their word probabilities (base_runner.py:616-618, 675-680; at M = 1 the member's own
+// log-softmax plus the running beam score, bit for bit) and the word is picked from the average:
+//   beam   - flat top-k over beam * V per clip at every step (the rows of a clip differ in z from t = 0 on, so the
+//            reference's "row 0 only at t = 0", :681-682, does not carry over), states gathered by parent once per member.
+//            Instead of re-gathering the word and attention-weight histories by prev_word_inds every step
+//            (vae_model.py:917-921, :979), each step's parent row and word (and, for the single-model entry, member 0's
+//            weights) are kept and beam 0 is traced back once at the end, which yields the same seqs[0] / attn_weights[0]
+//            (:990-995);
+//   greedy - the mix kernel's own argmax; a row that has produced end_idx keeps emitting and feeding it, and all
+//            max_length steps run without a host read-back: seqs prefilled with end_idx, as :584, 622-630 leave it.
+// Members run one after the other on the one stream.
+// ==========================================================================================
+namespace {
+struct SearchMember { const void* const* params; const float* mem; const int64_t* mem_lens; const float* eps; int S, E, H, A; };
+struct MemberLayout { StepLayout sl; long step, encd, encp, h, hp, cp, lz, mean, logv, z, h2, hp2, cp2, attp, attw, logits, rnn; };
+struct SearchLayout { MemberLayout m[ACVAE_ENSEMBLE_MAX]; long scores, topk, best, words, total; int keep_attw; };
+// keep_attw: member 0's decoder attention weights of every step, [T][R][S], for the trace-back; else [R][S], overwritten
+int search_layout(const SearchMember* mb, int M, int N, int beam, int T, int V, int keep_attw, SearchLayout& L) {
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || N <= 0 || beam <= 0 || T <= 0) return ACVAE_EINVAL;
+  const long R = (long)N * beam;
+  if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
+  L.keep_attw = keep_attw;
+  Bump b;
+  for (int m = 0; m < M; ++m) {
+    MemberLayout& o = L.m[m];
+    const long S = mb[m].S, e = mb[m].E, h = mb[m].H;
+    ACVAE_TRY(step_layout((int)R, mb[m].S, mb[m].E, mb[m].H, mb[m].A, V, o.sl));
+    o.step = b.take(o.sl.total);
+    o.encd = b.take((long)N * S * mb[m].A);
+    o.encp = b.take((long)N * S * e);
+    o.h = b.take(R * h); o.hp = b.take(R * e); o.cp = b.take(R * e); o.lz = b.take(R * e);
+    o.mean = b.take(R * e); o.logv = b.take(R * e); o.z = b.take(R * e);
+    o.h2 = b.take(R * h); o.hp2 = b.take(R * e); o.cp2 = b.take(R * e);
+    o.attp = b.take(R * S);
+    o.attw = b.take((keep_attw && m == 0 ? T : 1) * R * S);
+    o.logits = b.take(R * V);
+    o.rnn = b.take(R * 3 * e);
+  }
+  L.scores = b.take(R * V);
+  L.topk = b.take(R);
+  L.best = b.take(R);
+  L.words = b.take(2 * ((long)(3 * T + 2) * R));        // int64: word [R], argmax [R], per step idx / parent / word [T][R]
+  L.total = b.off;
+  return ACVAE_OK;
+}
+
+struct GatherJob { const float* src; float* dst; int width; };
+using GatherTable = acvae::JobTable<GatherJob, 4>;
+__global__ __launch_bounds__(256) void beam_gather_kernel(GatherTable g, const int64_t* __restrict__ parent) {
+  const GatherJob j = g.job[blockIdx.y];
+  const long r = blockIdx.x, p = parent[r];
+  for (int i = threadIdx.x; i < j.width; i += blockDim.x) j.dst[r * j.width + i] = j.src[p * j.width + i];
+}
+__global__ void fill_words_kernel(int64_t* w, int64_t v, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) w[i] = v;
+}
+// greedy bookkeeping of one step (base_runner.py:618-628): a finished row keeps end_idx
+__global__ void greedy_pick_kernel(const int64_t* __restrict__ arg, const float* __restrict__ best,
+                                   int64_t* __restrict__ seqs, float* __restrict__ logprobs, int64_t* __restrict__ word,
+                                   int64_t end_idx, int t, int T, int R) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  int64_t w = arg[r];
+  if (t > 0 && seqs[(long)r * T + t - 1] == end_idx) w = end_idx;
+  seqs[(long)r * T + t] = w;
+  logprobs[(long)r * T + t] = best[r];
+  word[r] = w;
+}
+// one workgroup per clip: follow beam 0's parents from the last step to the first.  logprobs (beam 0's final score) and
+// attw_out ([N,S,T], from the [T][R][S] history attw) may each be null.
+__global__ __launch_bounds__(256) void beam_trace_kernel(const int64_t* __restrict__ parent, const int64_t* __restrict__ word,
+                                                         const float* __restrict__ topk, const float* __restrict__ attw,
+                                                         int64_t* __restrict__ seqs, float* __restrict__ logprobs,
+                                                         float* __restrict__ attw_out, long hist_stride, int R, int beam, int T,
+                                                         int S) {
+  const int n = blockIdx.x;
+  long r = (long)n * beam;
+  if (logprobs && threadIdx.x == 0) logprobs[n] = topk[r];
+  for (int t = T - 1; t >= 0; --t) {
+    const long p = parent[t * hist_stride + r];
+    if (threadIdx.x == 0) seqs[(long)n * T + t] = word[t * hist_stride + r];
+    if (attw_out) {
+      const float* w = attw + ((long)t * R + p) * S;
+      for (int s = threadIdx.x; s < S; s += blockDim.x) attw_out[((long)n * S + s) * T + t] = w[s];
+    }
+    r = p;
+  }
+}
+
+// The driver behind both entry points; they have refused every bad argument, so nothing here fails before a launch.
+// greedy: seqs [R,T], logprobs [R,T].  Beam: seqs [N,T], logprobs [N] or null, attw_out [N,S,T] or null (not null only
+// with a layout made with keep_attw).
+int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_idx, int64_t end_idx, int greedy,
+           int64_t* seqs, float* logprobs, float* attw_out, float* sc, int N, int beam, int T, int V, hipStream_t s) {
+  const int R = N * beam;
+  // per member: the buffers that change hands from step to step (greedy swaps them, the beam search gathers by parent)
+  struct State { float *h, *hp, *cp, *lz, *h2, *hp2, *cp2, *z; } state[ACVAE_ENSEMBLE_MAX];
+  const float* logit_ptr[ACVAE_ENSEMBLE_MAX];
+  int64_t logit_ld[ACVAE_ENSEMBLE_MAX];
+  for (int m = 0; m < M; ++m) {
+    const MemberLayout& o = L.m[m];
+    const SearchMember& b = mb[m];
+    float* ssc = sc + o.step;
+    ACVAE_TRY(acvae_skinny_ws_reset(ssc + o.sl.skws, s));
+    ACVAE_TRY(step_attws_reset(ssc, o.sl, s));
+    ACVAE_TRY(acvae_attn_precompute(b.params, 0, b.mem, sc + o.encd, N, b.S, b.E, b.H, b.A, s));
+    ACVAE_TRY(acvae_attn_precompute(b.params, 1, b.mem, sc + o.encp, N, b.S, b.E, b.E, b.E, s));
+    State& x = state[m];
+    x = {sc + o.h, sc + o.hp, sc + o.cp, sc + o.lz, sc + o.h2, sc + o.hp2, sc + o.cp2, sc + o.z};
+    ACVAE_TRY(zero(x.h, (long)R * b.H, s));
+    ACVAE_TRY(zero(x.hp, (long)R * b.E, s));
+    ACVAE_TRY(zero(x.cp, (long)R * b.E, s));
+    ACVAE_TRY(zero(x.lz, (long)R * b.E, s));
+    logit_ptr[m] = sc + o.logits;
+    logit_ld[m] = V;
+  }
+  float* topk = sc + L.topk;
+  float* best = sc + L.best;
+  int64_t* word = (int64_t*)(sc + L.words);
+  int64_t* arg = word + R;
+  int64_t* hist = arg + R;                               // [T][3][R]: flat index, parent row, word (beam search)
+  ACVAE_TRY(zero(topk, R, s));
+  hipLaunchKernelGGL(fill_words_kernel, dim3((R + 255) / 256), dim3(256), 0, s, word, start_idx, R);
+  const int64_t* w_t = word;
+  for (int t = 0; t < T; ++t) {
+    int64_t* idx_t = hist + (long)t * 3 * R;
+    int64_t* par_t = idx_t + R;
+    int64_t* nxt_t = par_t + R;
+    for (int m = 0; m < M; ++m) {
+      const MemberLayout& o = L.m[m];
+      const SearchMember& b = mb[m];
+      const State& x = state[m];
+      float* ssc = sc + o.step;
+      float* attw_t = sc + o.attw + (L.keep_attw && m == 0 ? (long)t * R * b.S : 0);
+      Ctx st{s, ssc + o.sl.skws};
+      ACVAE_TRY(prior_step(b.params, w_t, b.mem, b.mem_lens, sc + o.encp, x.hp, x.cp, x.lz, b.eps + (long)t * R * b.E,
+                           sc + o.mean, sc + o.logv, x.z, x.hp2, x.cp2, sc + o.attp, ssc, o.sl, N, beam, b.S, b.E, V, st));
+      ACVAE_TRY(decoder_step(b.params, w_t, x.h, b.mem, b.mem_lens, sc + o.encd, x.z, sc + o.logits, x.h2, attw_t,
+                             sc + o.rnn, ssc, o.sl, N, beam, b.S, b.E, b.H, b.A, V, st));
+    }
+    if (greedy) {
+      ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, nullptr, 0, arg, best, 1, R, V, s));
+      hipLaunchKernelGGL(greedy_pick_kernel, dim3((R + 255) / 256), dim3(256), 0, s, arg, best, seqs, logprobs, word,
+                         end_idx, t, T, R);
+      for (int m = 0; m < M; ++m) {                      // the new states become the next step's previous ones
+        State& x = state[m];
+        std::swap(x.h, x.h2); std::swap(x.hp, x.hp2); std::swap(x.cp, x.cp2); std::swap(x.lz, x.z);
+      }
+      continue;
+    }
+    ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, topk, sc + L.scores, V, nullptr, nullptr, 0, R, V, s));
+    ACVAE_TRY(acvae_topk_flat_batched(sc + L.scores, (int64_t)beam * V, (int64_t)beam * V, beam, V, topk, idx_t, par_t,
+                                      nxt_t, N, beam, s));
+    if (t + 1 < T) {                                     // vae_model.py:961-968: next step's states follow their parents
+      for (int m = 0; m < M; ++m) {
+        const State& x = state[m];
+        GatherTable g;
+        g.add({x.h2, x.h, mb[m].H}); g.add({x.hp2, x.hp, mb[m].E}); g.add({x.cp2, x.cp, mb[m].E}); g.add({x.z, x.lz, mb[m].E});
+        hipLaunchKernelGGL(beam_gather_kernel, dim3(R, g.n), dim3(256), 0, s, g, par_t);
+      }
+      w_t = nxt_t;
+    }
+  }
+  if (!greedy)                                           // hist rows are [idx | parent | word] per step: strided views
+    hipLaunchKernelGGL(beam_trace_kernel, dim3(N), dim3(256), 0, s, hist + R, hist + 2 * R, topk, sc + L.m[0].attw, seqs,
+                       logprobs, attw_out, 3L * R, R, beam, T, mb[0].S);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+}  // namespace
+
+extern "C" int64_t acvae_beam_search_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A, int V) {
+  const SearchMember mb{nullptr, nullptr, nullptr, nullptr, S, E, H, A};
+  SearchLayout L;
+  return search_layout(&mb, 1, N, beam, max_length, V, 1, L) == ACVAE_OK ? L.total * 4 : -1;
+}
+
+extern "C" int acvae_beam_search(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
+                                 int64_t start_idx, int64_t* seqs, float* attw_out, void* scratch_v, int64_t scratch_bytes,
+                                 int N, int beam, int max_length, int S, int E, int H, int A, int V, void* stream) {
+  const SearchMember mb{params, mem, mem_lens, eps, S, E, H, A};
+  SearchLayout L;
+  ACVAE_TRY(search_layout(&mb, 1, N, beam, max_length, V, 1, L));
+  if (!params || !mem || !mem_lens || !eps || !seqs || !attw_out || !scratch_v) return ACVAE_EINVAL;
+  // the prior LSTM is E wide; acvae_topk_flat_batched selects k <= 16 and would answer a wider beam with the same code
+  if (start_idx < 0 || start_idx >= V || beam > 16 || H != E) return ACVAE_EINVAL;
+  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
+  return search(&mb, 1, L, start_idx, 0, 0, seqs, nullptr, attw_out, (float*)scratch_v, N, beam, max_length, V,
+                (hipStream_t)stream);
+}
+
+extern "C" int64_t acvae_ensemble_search_scratch_bytes(int M, int N, int beam, int max_length, const int* S, const int* E,
+                                                       const int* H, const int* A, int V) {
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A) return -1;
+  SearchMember mb[ACVAE_ENSEMBLE_MAX];
+  for (int m = 0; m < M; ++m) mb[m] = {nullptr, nullptr, nullptr, nullptr, S[m], E[m], H[m], A[m]};
+  SearchLayout L;
+  return search_layout(mb, M, N, beam, max_length, V, 0, L) == ACVAE_OK ? L.total * 4 : -1;
+}
+
+extern "C" int acvae_ensemble_search(const void* const* const* params, const float* const* mem,
+                                     const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
+                                     const int* H, const int* A, int M, int64_t start_idx, int64_t end_idx, int greedy,
+                                     int64_t* seqs, float* logprobs, void* scratch_v, int64_t scratch_bytes, int N, int beam,
+                                     int max_length, int V, void* stream) {
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !params || !mem || !mem_lens || !eps || !S || !E || !H || !A) return ACVAE_EINVAL;
+  SearchMember mb[ACVAE_ENSEMBLE_MAX];
+  for (int m = 0; m < M; ++m) {
+    if (!params[m] || !mem[m] || !mem_lens[m] || !eps[m] || H[m] != E[m]) return ACVAE_EINVAL;   // the prior LSTM is E wide
+    mb[m] = {params[m], mem[m], mem_lens[m], eps[m], S[m], E[m], H[m], A[m]};
+  }
+  if (!seqs || !logprobs || !scratch_v) return ACVAE_EINVAL;
+  if (beam > 64 || (greedy && beam != 1)) return ACVAE_EINVAL;
+  if (start_idx < 0 || start_idx >= V || end_idx < 0 || end_idx >= V) return ACVAE_EINVAL;
+  SearchLayout L;
+  ACVAE_TRY(search_layout(mb, M, N, beam, max_length, V, 0, L));
+  if (!greedy && beam > 16) return ACVAE_EUNSUPPORTED;   // acvae_topk_flat_batched selects k <= 16: refused here, not mid-call
+  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
+  return search(mb, M, L, start_idx, end_idx, greedy, seqs, logprobs, nullptr, (float*)scratch_v, N, beam, max_length, V,
+                (hipStream_t)stream);
+}

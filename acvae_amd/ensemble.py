@@ -88,21 +88,10 @@ class Ensemble(nn.Module):
             model.eval()                                                   # base_runner.py:573-574
             model._forward_token = getattr(model, "_forward_token", 0) + 1     # per-forward caches, as Hybrid_VAEModel.forward
             encoded = model.encoder(feats, copy.copy(np.asarray(feat_lens)))    # its own copy: the encoder divides it in place
-            mem = encoded["audio_embeds"].contiguous()
-            if hasattr(model, "ln"):                                       # vae_model.py:754-755, as beam_search does
-                Nn, Ss, Ee = mem.shape
-                proj = torch.empty(Nn, Ss, model.decoder.embed_size, device=dev)
-                _lib.call("acvae_gemm_nt", mem, Ee, model.ln.weight, Ee, model.ln.bias, proj, model.decoder.embed_size,
-                          Nn * Ss, model.decoder.embed_size, Ee, 0, _lib.current_stream())
-                mem = proj
+            mem = model._projected_memory(encoded)
             N, S, E = mem.shape
             H, A = model.decoder.model.hidden_size, model.decoder.attn.attn_size
-            if replay is None:
-                eps = _lib.h2d_fill((T, N, beam, E), torch.float32, dev,
-                                    lambda buf: [torch.randn(beam, E, out=buf[t, i]) for i in range(N) for t in range(T)])
-            else:
-                eps = _lib.h2d(torch.as_tensor(replay[k]).reshape(N, T, beam, E).transpose(0, 1).contiguous(), dev,
-                               torch.float32)
+            eps = model._search_noise(N, T, beam, E, dev, None if replay is None else replay[k])
             mems.append(mem)
             lens.append(torch.as_tensor(encoded["audio_embeds_lens"]).to(device=dev, dtype=torch.long).contiguous())
             epss.append(eps)

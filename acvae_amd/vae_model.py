@@ -263,35 +263,44 @@ class Hybrid_VAEModel(CaptionModel):
         self._encproj_cache[which] = (key, out, enc_mem)      # keep enc_mem alive so its address cannot be reused
         return out
 
+    def _projected_memory(self, encoded):
+        """The contiguous encoder memory [N, S, E] after the optional ``ln`` projection (vae_model.py:754-755)."""
+        mem = encoded["audio_embeds"].contiguous()
+        if hasattr(self, "ln"):
+            N, S, Eenc = mem.shape
+            E = self.decoder.embed_size
+            proj = torch.empty(N, S, E, device=mem.device)
+            _lib.call("acvae_gemm_nt", mem, Eenc, self.ln.weight, Eenc, self.ln.bias, proj, E, N * S, E, Eenc, 0,
+                      _lib.current_stream())
+            mem = proj
+        return mem
+
+    @staticmethod
+    def _search_noise(N, max_length, beam, E, dev, replay):
+        """The prior's noise of one search on the device, step-major [max_length, N, beam, E] as the library reads it.  The
+        reference walks the clips one after the other; their searches are independent, so all N x beam rows advance together
+        inside one library call.  Its noise order (clip-major: text_encoder.py:259 inside the clip loop) is kept by drawing
+        eps[clip][t] in that order on the host; ``replay`` [N, max_length, beam, E] is uploaded instead of a draw."""
+        if replay is None:
+            return _lib.h2d_fill((max_length, N, beam, E), torch.float32, dev,
+                                 lambda buf: [torch.randn(beam, E, out=buf[t, i]) for i in range(N) for t in range(max_length)])
+        return _lib.h2d(torch.as_tensor(replay).reshape(N, max_length, beam, E).transpose(0, 1).contiguous(), dev,
+                        torch.float32)
+
     @torch.no_grad()
     def beam_search(self, encoded, max_length, beam_size):
         """Validation beam search, models/vae_model.py:896-995: beams expanded over the flat beam*V log-probabilities of
         a clip, states re-gathered by prev_word_inds; returns beam 0 (the reference never fills done_beams, :986-995).
         All clips advance together; no host synchronisation inside the loop."""
-        mem_all = encoded["audio_embeds"].contiguous()
+        mem_all = self._projected_memory(encoded)
         dev = mem_all.device
-        if hasattr(self, "ln"):                              # vae_model.py:754-755
-            Nn, Ss, Ee = mem_all.shape
-            proj = torch.empty(Nn, Ss, self.decoder.embed_size, device=dev)
-            _lib.call("acvae_gemm_nt", mem_all, Ee, self.ln.weight, Ee, self.ln.bias, proj, self.decoder.embed_size,
-                      Nn * Ss, self.decoder.embed_size, Ee, 0, _lib.current_stream())
-            mem_all = proj
         lens_all = torch.as_tensor(encoded["audio_embeds_lens"]).to(device=dev, dtype=torch.long).contiguous()
         N, S, E = mem_all.shape
         V = self.vocab_size
         H, A = self.decoder.model.hidden_size, self.decoder.attn.attn_size
         replay = self.noise.get("eps_beam") if self.noise is not None else None
         self.noise = None
-        # The reference walks the clips one after the other; their searches are independent, so all N x beam rows advance
-        # together inside one library call.  Its noise order (clip-major: text_encoder.py:259 inside the clip loop) is
-        # kept by drawing eps[clip][t] in that order on the host; the library reads it step-major.
-        if replay is None:
-            eps_all = _lib.h2d_fill((max_length, N, beam_size, E), torch.float32, dev,
-                                    lambda buf: [torch.randn(beam_size, E, out=buf[t, i]) for i in range(N)
-                                                 for t in range(max_length)])
-        else:
-            eps_all = _lib.h2d(torch.as_tensor(replay).reshape(N, max_length, beam_size, E).transpose(0, 1).contiguous(),
-                               dev, torch.float32)
+        eps_all = self._search_noise(N, max_length, beam_size, E, dev, replay)
         seqs = torch.empty(N, max_length, dtype=torch.long, device=dev)
         attw = torch.empty(N, S, max_length, device=dev)
         sb = _lib.call("acvae_beam_search_scratch_bytes", N, beam_size, max_length, S, E, H, A, V)
@@ -309,14 +318,8 @@ class Hybrid_VAEModel(CaptionModel):
         Returns {"seqs": i64 [N, beam_size or group_size, max_length]}.  Host bookkeeping (sequence tables, finished
         beams) as in the reference, which also reads the chosen words back every step; prior / decoder step, the score
         transform and the flat top-k are library calls."""
-        mem_all = encoded["audio_embeds"].contiguous()
+        mem_all = self._projected_memory(encoded)
         dev = mem_all.device
-        if hasattr(self, "ln"):
-            Nn, Ss, Ee = mem_all.shape
-            proj = torch.empty(Nn, Ss, self.decoder.embed_size, device=dev)
-            _lib.call("acvae_gemm_nt", mem_all, Ee, self.ln.weight, Ee, self.ln.bias, proj, self.decoder.embed_size,
-                      Nn * Ss, self.decoder.embed_size, Ee, 0, _lib.current_stream())
-            mem_all = proj
         lens_all = torch.as_tensor(encoded["audio_embeds_lens"]).to(torch.long)
         N, S, E = mem_all.shape
         V = self.vocab_size

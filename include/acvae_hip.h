@@ -747,7 +747,11 @@ int acvae_topk_flat_batched(const float* x, int64_t n, int64_t group_stride, int
  * all N clips at once.  mem [N,S,E] (after the optional `ln` projection), mem_lens [N], eps [max_length][N*beam][E]
  * (the N(0,1) draws of PriorRNN.forward, text_encoder.py:259, step-major), start_idx = vocabulary index of <start>.
  * Outputs, as the reference keeps them (beam 0 of each clip, :990-995): seqs int64 [N,max_length],
- * attn_weights [N,S,max_length].  No host synchronisation; scratch of acvae_beam_search_scratch_bytes(). */
+ * attn_weights [N,S,max_length].  No host synchronisation; scratch of acvae_beam_search_scratch_bytes().
+ * This is the M = 1 beam case of acvae_ensemble_search (below: one driver, one acvae_ensemble_mix launch per step forms the
+ * scores) plus beam 0's attention-weight history.  Refused before any launch: a dimension <= 0 (ACVAE_EINVAL);
+ * N * beam > 2^20 (ACVAE_EUNSUPPORTED, -1 from the bytes function); a NULL pointer, start_idx outside [0, V), H != E, or
+ * beam > 16 (acvae_topk_flat_batched's limit) (ACVAE_EINVAL); scratch below the bytes function (ACVAE_EWORKSPACE). */
 int64_t acvae_beam_search_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A, int V);
 int acvae_beam_search(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
                       int64_t start_idx, int64_t* seqs, float* attn_weights, void* scratch, int64_t scratch_bytes, int N,
@@ -784,8 +788,8 @@ int acvae_dbs_scores(const float* logits, int64_t ld, float temperature, const f
  *     max_length steps run (no host read-back): seqs as :584, 622-630 leave it.  logprobs f32 [N,max_length]: the
  *     mixture's log-probability of the step's argmax.
  *   greedy == 0: beam search, flat top-k over beam * V per clip at every step, t = 0 included (as acvae_beam_search: the
- *     rows of a clip differ in z), beam 0 traced back.  logprobs f32 [N]: beam 0's final score.  With M = 1 the launches
- *     of acvae_beam_search in the same order: the same seqs bit for bit.
+ *     rows of a clip differ in z), beam 0 traced back.  logprobs f32 [N]: beam 0's final score.  With M = 1 this is
+ *     acvae_beam_search (the same driver) without the attention-weight history: the same seqs bit for bit.
  * seqs int64 [N,max_length].  Refused before any launch: M outside [1, ACVAE_ENSEMBLE_MAX], a NULL entry, H[m] != E[m],
  * beam > 64, greedy with beam != 1, start_idx / end_idx outside [0, V) (ACVAE_EINVAL); N * beam > 2^20, or beam > 16
  * without greedy (acvae_topk_flat_batched's limit) (ACVAE_EUNSUPPORTED); scratch below

@@ -194,6 +194,50 @@ def test_ensemble_search_refusal_codes():
     assert lib.acvae_ensemble_mix(ptrs, ld.ctypes.data, 2, None, 0x1000, V, None, None, 0, 4, V, None) == EINVAL
 
 
+class BeamArgs:
+    """A well-formed argument set of acvae_beam_search (fake non-null device pointers, as Args)."""
+
+    def __init__(self, N=3, beam=3):
+        self.table = (ctypes.c_void_p * 35)(*([0x1000] * 35))
+        self.params = ctypes.cast(self.table, ctypes.c_void_p).value
+        self.mem = self.mem_lens = self.eps = self.seqs = self.attn_weights = self.scratch = 0x1000
+        self.start, self.scratch_bytes = 1, 1 << 40
+        self.N, self.beam, self.T, self.S, self.E, self.H, self.A, self.V = N, beam, MAXLEN, 4, E, E, E, V
+
+    def nbytes(self):
+        return _lib.lib().acvae_beam_search_scratch_bytes(self.N, self.beam, self.T, self.S, self.E, self.H, self.A, self.V)
+
+    def call(self):
+        return _lib.lib().acvae_beam_search(self.params, self.mem, self.mem_lens, self.eps, self.start, self.seqs,
+                                            self.attn_weights, self.scratch, self.scratch_bytes, self.N, self.beam, self.T,
+                                            self.S, self.E, self.H, self.A, self.V, None)
+
+
+def test_beam_search_refusal_codes():
+    """Every case is refused before anything is launched or read on the device: with these pointers a call that got as far
+    as its first launch would not return a code at all.  Beam 17 is the case that used to be refused only mid-call, by
+    acvae_topk_flat_batched (k <= 16)."""
+    ge.build()
+    for field in ("params", "mem", "mem_lens", "eps", "seqs", "attn_weights", "scratch"):
+        a = BeamArgs()
+        setattr(a, field, None)
+        assert a.call() == EINVAL, field
+    for start in (-1, V):
+        a = BeamArgs(); a.start = start
+        assert a.call() == EINVAL, start
+    a = BeamArgs(); a.H = E + 1
+    assert a.call() == EINVAL                                       # H != E
+    for beam in (65, 17):
+        assert BeamArgs(beam=beam).call() == EINVAL, beam
+    a = BeamArgs(N=(1 << 20) // 4 + 1, beam=4)                      # N * beam > 2^20
+    assert a.call() == EUNSUPPORTED and a.nbytes() == -1
+    a = BeamArgs()
+    need = a.nbytes()
+    assert need > 0
+    a.scratch_bytes = need - 1
+    assert a.call() == EWORKSPACE
+
+
 def test_ensemble_scratch_bytes_is_host_arithmetic_and_grows_with_members():
     ge.build()
     sizes = [Args(M=M).nbytes() for M in range(1, 9)]

@@ -23,7 +23,7 @@ from acvae_amd.batch import collate_fn
 from acvae_amd.ensemble import Ensemble, ensemble_evaluate
 from acvae_amd.evaluate import Vocabulary, collect_predictions, predictions_payload
 from test_fullsize_decode_gpu import LP_TOL, MARGIN, guarded
-from test_model_gpu import build_model
+from test_model_gpu import _beam_call_vs_step_loop, build_model
 
 pytestmark = pytest.mark.gpu
 V, MAXLEN = 50, 8
@@ -132,6 +132,18 @@ def test_one_member_is_the_single_model_beam_search(beam):
         for a, b in zip(g.tolist(), want.tolist()):
             n = b.index(O.END_IDX) + 1 if O.END_IDX in b else MAXLEN
             assert a[:n] == b[:n] and a[n:] == [O.END_IDX] * (MAXLEN - n)
+
+
+def test_one_member_beam_is_the_step_api_loop():
+    """Ensemble([m]) against the reference's loop written with the sub-module step API and the two-kernel score route
+    (acvae_row_logsoftmax_argmax + acvae_logprob_add), as test_model_gpu.py builds it for the single-model entry: beam 0's
+    tokens and final score bit for bit, which pins the mix kernel's M = 1 identity end to end.  The small case: 5 ragged
+    clips x beam 3 = 15 rows, top-k over 900 scores per clip."""
+    beam, ml = 3, 12
+    loop = _beam_call_vs_step_loop(V=300, beam=beam, ml=ml, feat_lens=[160, 150, 97, 64, 33], seed=3)
+    seqs, score = run([loop["model"]], loop["feats"], loop["feat_lens"], "beam", beam, ml, [loop["eps"]])
+    assert torch.equal(seqs, loop["seqs"][0::beam].cpu())
+    assert torch.equal(score, loop["top_k"][0::beam].cpu())
 
 
 @pytest.mark.parametrize("method,beam", [("greedy", 1), ("beam", 3)])

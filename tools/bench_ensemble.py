@@ -43,6 +43,9 @@ def main():
         return
     import numpy as np
     import torch
+    from acvae_amd import _lib
+    if os.environ.get("ACVAE_DEV_LIB"):      # this TOOL's hook: time another build of the library (tools/ab_build.py)
+        _lib.use_library(os.environ["ACVAE_DEV_LIB"])
     from acvae_amd.ensemble import Ensemble
     if not torch.cuda.is_available():
         raise SystemExit("bench_ensemble.py measures on the GPU: none found")

@@ -4,6 +4,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_KERNARG_POOL_SIZE", str(32 << 20))
 import torch
+from acvae_amd import _lib
+if os.environ.get("ACVAE_DEV_LIB"):          # this TOOL's hook: time another build of the library (tools/ab_build.py)
+    _lib.use_library(os.environ["ACVAE_DEV_LIB"])
 import bench
 from acvae_amd import evaluate as EV
 B, N, T = int(sys.argv[1]) if len(sys.argv) > 1 else 32, 5, 1000
