@@ -104,7 +104,7 @@ def replicate_for_sampling(keys, feats, feat_lens, n):
     return keys, feats, feat_lens
 
 
-def forward_batch_shared_encoder(model, batch, device=None, **kwargs):
+def forward_batch_shared_encoder(model, batch, device=None, frontend=None, **kwargs):
     """Evaluation forward with N z-samples per clip that runs the encoder ONCE per clip: in evaluation mode (running
     BatchNorm statistics, no dropout) the encoder output of a replica equals that of its clip bit for bit, so the
     replicas share it and only the decode loop sees N rows per clip.  Same outputs as ``forward_batch(mode="eval")``
@@ -112,6 +112,8 @@ def forward_batch_shared_encoder(model, batch, device=None, **kwargs):
     n = kwargs["beam_size"]
     assert not model.training and n > 1 and kwargs["method"] != "dbs"
     device = device if device is not None else next(model.parameters()).device
+    if frontend is not None:                       # waveforms in, features out (see forward_batch)
+        batch[1], batch[-1] = frontend(batch[1], batch[-1], device=device)
     encoded = model.encoder(batch[1].to(device), batch[-1])
     batch[0] = [k for k in batch[0] for _ in range(n)]
     lens = torch.as_tensor(encoded["audio_embeds_lens"]).repeat_interleave(n, dim=0)
@@ -121,15 +123,24 @@ def forward_batch_shared_encoder(model, batch, device=None, **kwargs):
     return model.inference_forward(rep, **kwargs)
 
 
-def forward_batch(model, batch, mode, device=None, augment=None, clip_index=None, **kwargs):
+def forward_batch(model, batch, mode, device=None, augment=None, clip_index=None, frontend=None, **kwargs):
     """Runner._forward (pytorch_runner_vae.py:76-108).  ``batch`` is what ``collate_fn`` returned.  In evaluation mode
     with beam_size > 1 and a method other than "dbs", ``batch[0]`` (the keys) is replaced by the replicated keys, as
     the reference does in place.  In training mode the uploaded features get the training-time augmentation of
     ``augment`` (one ``AugmentParams`` per clip), or of the batch's own column when ``CaptionDataset(...,
     augment=...)`` made it (acvae_amd.augment.apply).  For a batch of ``collate_groups`` (B clips, N caption rows) pass its
-    ``clip_index=batch[-3]``: the training forward then runs the encoder once per clip."""
+    ``clip_index=batch[-3]``: the training forward then runs the encoder once per clip.  ``frontend``
+    (``acvae_amd.frontend.LogMel``): the batch holds waveforms and sample counts where it otherwise holds features and
+    frame counts; both slots are replaced by the log-mel features formed on the device and their frame counts before
+    anything else runs.  Not together with an augmentation (ValueError)."""
     assert mode in ("train", "validation", "eval")
     device = device if device is not None else next(model.parameters()).device
+    if frontend is not None:
+        from . import augment as _augment
+        from .frontend import refuse_augment
+        refuse_augment(augment if augment is not None else _augment.batch_params(batch))
+        slot, lens_slot = (0, -2) if mode == "train" else (1, -1)
+        batch[slot], batch[lens_slot] = frontend(batch[slot], batch[lens_slot], device=device)
     if mode == "train":
         feats = batch[0].to(device)
         from . import augment as _augment

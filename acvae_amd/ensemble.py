@@ -114,11 +114,13 @@ class Ensemble(nn.Module):
 
 
 def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None, dcase_format=False, zh=False,
-                      batch_size=32, **kwargs):
+                      batch_size=32, frontend=None, **kwargs):
     """The decoding half of ``BaseRunner.ensemble`` (base_runner.py:433-478): ``items`` are ``(audio_id, feature [T, F])`` as
     for ``evaluate()``, batched with ``collate_fn([1])`` (no replication); ``kwargs`` (``method``, ``beam_size``,
     ``max_length``) go to ``Ensemble.forward``.  Writes the JSON payload of ``evaluate()`` or, with ``dcase_format``, the
-    reference's two-column CSV (``file_name``, ``caption_predicted``).  Returns the payload dict; scoring stays outside."""
+    reference's two-column CSV (``file_name``, ``caption_predicted``).  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are
+    ``(audio_id, 1-D waveform)`` and the log-mel features are formed on the device, once for all members.  Returns the payload
+    dict; scoring stays outside."""
     ens = models_or_ensemble if isinstance(models_or_ensemble, Ensemble) else Ensemble(models_or_ensemble)
     device = next(ens.parameters()).device
     collate = collate_fn([1, ])
@@ -130,10 +132,14 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
             return
         batch = collate(list(pending))
         pending.clear()
+        if frontend is not None:
+            batch[1], batch[-1] = frontend(batch[1], batch[-1], device=device)
         output = ens(batch[1].to(device), batch[-1], **kwargs)
         collect_predictions(batch[0], output["seqs"].cpu().numpy(), vocabulary, zh, key2pred)
 
     for item in items:
+        if frontend is not None:                   # collate_fn pads into float32: PCM becomes the samples it stands for
+            item = (item[0], frontend.to_float(item[1]))
         pending.append(item)
         if len(pending) == batch_size:
             flush()

@@ -99,13 +99,16 @@ def predictions_payload(key2pred, zh=False):
     return {"predictions": out}
 
 
-def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size=1, device=None, **kwargs):
+def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size=1, device=None, frontend=None,
+             **kwargs):
     """Decode an evaluation set and (optionally) write the prediction file.
 
     ``items``: iterable of ``(audio_id, feature [T, F] tensor)`` in the order of the reference's ``CaptionEvalDataset``;
     they are batched with ``collate_fn([1])`` exactly as its DataLoader does.  ``kwargs`` go to the model as in
     ``evaluate(**kwargs)`` there: ``method`` ("greedy" | "beam" | "dbs"), ``beam_size`` (with "greedy": z-samples per
-    clip), ``max_length``.  Returns the payload dict."""
+    clip), ``max_length``.  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
+    or int16 PCM (``acvae_amd.frontend.read_wav``); the log-mel features are formed on the device in front of either
+    forward path.  Returns the payload dict."""
     kwargs.setdefault("method", "greedy")
     kwargs.setdefault("beam_size", 1)
     collate = collate_fn([1, ])
@@ -120,12 +123,14 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
         pending.clear()
         with torch.no_grad():
             if kwargs["beam_size"] > 1 and kwargs["method"] != "dbs":     # N samples per clip: one encoder pass per clip
-                output = forward_batch_shared_encoder(model, batch, device=device, **kwargs)
+                output = forward_batch_shared_encoder(model, batch, device=device, frontend=frontend, **kwargs)
             else:
-                output = forward_batch(model, batch, "eval", device=device, **kwargs)
+                output = forward_batch(model, batch, "eval", device=device, frontend=frontend, **kwargs)
         collect_predictions(batch[0], output["seqs"].cpu().numpy(), vocabulary, zh, key2pred)
 
     for item in items:
+        if frontend is not None:                   # collate_fn pads into float32: PCM becomes the samples it stands for
+            item = (item[0], frontend.to_float(item[1]))
         pending.append(item)
         if len(pending) == batch_size:
             flush()

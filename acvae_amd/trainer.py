@@ -295,9 +295,12 @@ class TrainStep:
             self.exchange.ready(2)
 
     # ------------------------------------------------------------------ one optimiser step
-    def forward_loss(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, kl_weight=0.5, clip_index=None):
-        """Runner._forward(mode='train') + the loss line (:315-318).  Returns (loss, parts, output).  ``clip_index``: see
-        ``step``."""
+    def forward_loss(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, kl_weight=0.5, clip_index=None,
+                     frontend=None):
+        """Runner._forward(mode='train') + the loss line (:315-318).  Returns (loss, parts, output).  ``clip_index`` and
+        ``frontend``: see ``step``."""
+        if frontend is not None:
+            feats, feat_lens = frontend(feats, feat_lens, device=self.flat_p.device)
         share = {} if clip_index is None else {"clip_index": clip_index}
         out = self.model(feats, feat_lens, caps, cap_lens, ss_ratio=ss_ratio, dis_ratio=dis_ratio, **share)
         staged = getattr(self.model, "staged", None) or {}
@@ -319,7 +322,10 @@ class TrainStep:
         that Runner._forward makes in front of every step (`feats = batch[0].to(device)`, runners/pytorch_runner_vae.py:80)
         then travels beside the step that is running instead of in front of the next encoder.  Returns the device tensor to
         hand to step(); step() makes its stream wait for the copy.  Page-locked input is copied from where it lies;
-        pageable input is staged through the package's page-locked ring first (a host memcpy).  Typical loop:
+        pageable input is staged through the package's page-locked ring first (a host memcpy).  An int16 tensor is PCM for
+        step(..., frontend=) and arrives as int16 whether it is page-locked or pageable (a pageable one used to arrive cast
+        to fp32, unlike a page-locked one; no step without frontend= accepts int16 features, so nothing relied on that
+        cast); every other dtype arrives as before.  Typical loop:
             nxt = ts.prefetch(batch0)
             for batch in batches[1:] + [None]:
                 cur, nxt = nxt, (ts.prefetch(batch) if batch is not None else None)
@@ -331,14 +337,15 @@ class TrainStep:
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(device=dev)
         with torch.cuda.stream(self._copy_stream):
-            d = t.to(dev, non_blocking=True) if t.is_pinned() else _lib.h2d(t.float(), dev)
+            # int16 is PCM for step(..., frontend=): it travels as it is (a cast would drop the kernel's 1/32768 scale)
+            d = t.to(dev, non_blocking=True) if t.is_pinned() else _lib.h2d(t if t.dtype == torch.int16 else t.float(), dev)
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
         d._acvae_ready = ev
         return d
 
     def step(self, feats, feat_lens, caps, cap_lens, ss_ratio=1.0, dis_ratio=0, kl_weight=0.5, augment=None,
-             clip_index=None):
+             clip_index=None, frontend=None):
         """One training step.  ``augment``: one ``acvae_amd.augment.AugmentParams`` per clip (a batch's column from
         ``CaptionDataset(..., augment=...)``): the rolls and masks run on the device before the encoder.
 
@@ -346,7 +353,15 @@ class TrainStep:
         ``feat_lens`` (and ``augment``) then hold the B clips, ``caps`` / ``cap_lens`` the N = B * k caption rows, and
         ``clip_index[r]`` names the clip of row r (``acvae_amd.batch.collate_groups`` builds such batches).  The loss and
         the gradients are those of the step on the batch with every clip repeated k times.  Under data parallelism nothing
-        changes: the graph has one more node between the decode loop and the encoder."""
+        changes: the graph has one more node between the decode loop and the encoder.
+
+        ``frontend`` (``acvae_amd.frontend.LogMel``): ``feats`` / ``feat_lens`` are waveforms ``[B, Lmax]`` (fp32 or int16 PCM,
+        on the host or uploaded by ``prefetch``) and their sample counts; the log-mel features are formed on the step's
+        stream in front of the encoder, with no gradient through them.  Not together with ``augment`` (ValueError: the
+        augment records are drawn per frame on host features)."""
+        if frontend is not None:                    # first: a refused call touches nothing of the step's state
+            from .frontend import refuse_augment
+            refuse_augment(augment)
         self.sync_buffers()
         ready = getattr(feats, "_acvae_ready", None)
         if ready is not None:                       # a batch uploaded by prefetch(): order this step behind its copy
@@ -362,7 +377,8 @@ class TrainStep:
         self._decode_deferred = self._projemb_seen = False
         for p in self.order:
             p.grad = None                                             # optimizer.zero_grad(set_to_none=True)
-        loss, parts, _ = self.forward_loss(feats, feat_lens, caps, cap_lens, ss_ratio, dis_ratio, kl_weight, clip_index)
+        loss, parts, _ = self.forward_loss(feats, feat_lens, caps, cap_lens, ss_ratio, dis_ratio, kl_weight, clip_index,
+                                           frontend)
         return self._backward_and_update(loss, parts)
 
     def scst_step(self, feats, feat_lens, keys, key2refs, vocabulary, scorer, sample_n=1, max_length=None, **kwargs):

@@ -686,6 +686,47 @@ int acvae_spec_augment(const float* in, float* out, const int* lens, const int* 
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Log-mel front end: waveforms -> the [T, n_mels] features every encoder of the package starts from (the PANNs front end,
+ * models/encoder.py:877-885: torchlibrosa's Spectrogram then LogmelFilterBank), one fused kernel, no workspace.
+ * For clip n of L = wave_lens[n] samples, with n = n_fft, h = hop, nb = n/2 + 1:
+ *   padding  reflect, n/2 samples on both sides of the clip's OWN length: index i < 0 -> -i, i >= L -> 2(L-1) - i;
+ *   frames   Tn = 1 + L / h frames, frame t = padded samples t*h .. t*h + n - 1;
+ *   power    P[t, f] = (sum_k x_t[k] w[k] cos(2 pi k f / n))^2 + (sum_k x_t[k] w[k] sin(2 pi k f / n))^2, f = 0 .. n/2,
+ *            w the periodic Hann window;
+ *   output   out[t, m] = 10 log10(max(sum_f P[t, f] W[f, m], amin)) - db_offset, db_offset = 10 log10(max(amin, ref)).
+ * Rows t >= Tn of `out` (and of `spec`) are written as zeros, which is what collate_fn pads features with; nothing is
+ * written outside [N, T, .].
+ *
+ * Operands (the caller owns them all; the tables are built in float64 on the host and rounded once to fp32,
+ * acvae_amd/frontend.py):
+ *   wave      [N, wave_stride] samples, fp32, or int16 PCM when wave_is_i16 (scaled by 1/32768 on load, exact in fp32);
+ *   wave_lens int32 [N] on the device.  The kernel cannot refuse a bad length, so it clamps: a length above wave_stride
+ *             counts as wave_stride, a clip shorter than n/2 + 1 has no frames (all its rows are zeros).  The caller checks
+ *             wave_lens[n] >= n/2 + 1 on the host;
+ *   basis     the windowed DFT matrix, n_fft * n_fft floats, 16-B aligned, in the order the kernel stages it:
+ *             [n_fft/128 frequency chunks][n_fft/32 K-steps][128 columns][32 k].  Column c < 64 of chunk q is the real part of
+ *             bin f = 64 q + c: w[k] cos(2 pi k f / n); column 64 + c its imaginary part -w[k] sin(2 pi k f / n) - except
+ *             column 64 of chunk 0 (the imaginary part of bin 0, identically zero), which holds the real part of the Nyquist
+ *             bin n/2, w[k] cos(pi k) (whose imaginary part is zero as well): n/2 + 1 bins in exactly n columns;
+ *   melw      [nb, n_mels] mel weights, row-major.  Row n/2 (the Nyquist bin) is added on the vector unit in the epilogue,
+ *             after the matrix-pipe sum over the other bins; LogMel's own weights there are zero (fmax <= sr/2);
+ *   out       f32 [N, T, n_mels];  spec: f32 [N, T, nb] power spectrogram, or NULL (then it never leaves the registers).
+ * A workgroup owns ACVAE_LOGMEL_FRAME_TILE consecutive frames of one clip.  Per frequency chunk it runs the DFT as a GEMM
+ * on v_mfma_f32_32x32x2_f32 (exact fp32): the frame matrix is never materialised - every K-step's [frames x 32] piece is
+ * gathered from the waveform into LDS with the reflect rule applied - squares and adds re / im in registers, multiplies the
+ * power tile by `melw` on the matrix pipe through LDS and keeps the mel sums in registers until the single store of `out`.
+ * The summation order is fixed and there are no atomics: bit-reproducible, and `spec` = NULL gives the same `out`.
+ * Limits (ACVAE_EINVAL before any HIP call): n_fft in {256, 512, 1024, 2048}; 1 <= hop <= n_fft; n_mels a multiple of 4 in
+ * [4, 128]; N, T >= 1; T = 1 + max_len / hop for the longest clip, of which (T - 1) * hop <= wave_stride is checked;
+ * n_fft/2 + 1 <= wave_stride <= 2^30; N * T * nb < 2^31; amin > 0; wave_is_i16 0 or 1; a NULL pointer other than
+ * `spec`.  `basis` not 16-B aligned -> ACVAE_EALIGN.
+ * ------------------------------------------------------------------------------------------- */
+#define ACVAE_LOGMEL_FRAME_TILE 64
+int acvae_logmel_fwd(const void* wave, int wave_is_i16, int64_t wave_stride, const int* wave_lens, const float* basis,
+                     const float* melw, float* out, float* spec, int N, int T, int n_fft, int hop, int n_mels, float amin,
+                     float db_offset, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Rows of a [*, R] matrix gathered by an index, and the adjoint: rows folded into the row they came from.  The training
  * step with several captions per clip (Hybrid_VAEModel.forward(..., clip_index=)) runs the encoder once over the B clips
  * and gathers its memory [B, R = S * C] into the N caption rows; the backward folds the N rows' gradients into the B clips'.
