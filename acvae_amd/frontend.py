@@ -14,6 +14,22 @@ definition, restated from torchlibrosa / librosa, for one clip ``x`` of ``L`` sa
 The split is the package's usual one (``acvae_amd.augment``): the tables are made on the host, in float64, rounded once to
 fp32 and uploaded once per device; the arithmetic is one HIP kernel (``acvae_logmel_fwd``, include/acvae_hip.h) on the
 current stream.  There is no CPU code path, and no gradient flows through the front end.
+
+Audio at another rate (Clotho is 44.1 kHz, AudioCaps and field recordings 44.1 or 48 kHz) is resampled on the device in
+front of it: ``Resample`` (``acvae_resample_fwd``), and ``Resampled(resample, logmel)`` / ``LogMel.at_input_rate(rate)``
+for the pair.  The definition, for rates ``orig -> new`` with ``g = gcd``, ``U = new / g``, ``D = orig / g``, ``Z`` zero
+crossings and ``c = rolloff * min(1, U / D)``:
+
+  * kernel function, ``tau`` in input samples: ``g(tau) = c sinc(c tau) I0(beta sqrt(1 - (c tau / Z)^2)) / I0(beta)`` for
+    ``|c tau| < Z`` and 0 otherwise, ``sinc(u) = sin(pi u) / (pi u)``;
+  * output ``y[m] = sum_n x[n] g(m D / U - n)``, the argument formed exactly as ``(m D - n U) / U`` from integers, ``x`` zero
+    outside ``[0, L)``; ``L_out = ceil(L U / D)``; the columns of an output row behind ``L_out`` are zeros;
+  * ``kaiser_best``: ``Z = 64, rolloff = 0.9475937167399596, beta = 14.769656459379492``; ``kaiser_fast``: ``Z = 16,
+    rolloff = 0.85, beta = 8.555504641634386`` (the settings librosa / resampy publish under these names).
+
+This is the closed form: resampy's interpolated table and soxr are not reproduced bit for bit.  Not supported: clips of
+different rates in one batch, a gradient through the resampler, the resampler fused into the log-mel kernel's gather, and
+``frontend=`` together with ``augment=``.
 """
 import math
 import wave as _wave
@@ -26,6 +42,10 @@ from . import _lib
 FRAME_TILE = int(_lib._defs["ACVAE_LOGMEL_FRAME_TILE"])
 N_FFTS = (256, 512, 1024, 2048)
 _CHUNK, _BK = 64, 32                     # frequencies per chunk and k per K-step of the kernel's basis layout
+BLOCK_TILE = int(_lib._defs["ACVAE_RESAMPLE_BLOCK_TILE"])
+MAX_RATIO = int(_lib._defs["ACVAE_RESAMPLE_MAX_RATIO"])
+MAX_TAPS = int(_lib._defs["ACVAE_RESAMPLE_MAX_TAPS"])
+_PT = 32                                 # phases per tile of the resampler's filter bank
 
 
 def hz_to_mel(f):
@@ -74,6 +94,13 @@ class LogMel:
     def panns_16k(cls):
         """The ``Cnn14_16k`` family."""
         return cls(16000, 512, 160, n_mels=64, fmin=50.0, fmax=8000.0)
+
+    def at_input_rate(self, rate, **resample_args):
+        """The front end for audio at ``rate``: ``self`` at the front end's own rate, otherwise ``Resampled(Resample(rate,
+        sample_rate, **resample_args), self)`` (``kaiser_best`` unless told otherwise)."""
+        if rate == self.sample_rate:
+            return self
+        return Resampled(Resample(rate, self.sample_rate, **resample_args), self)
 
     def n_frames(self, L):
         """Frames of a clip (or an array of clips) of ``L`` samples: ``1 + L // hop_length``."""
@@ -176,6 +203,213 @@ class LogMel:
                   self.n_fft, self.hop_length, self.n_mels, self.amin, self.db_offset, _lib.current_stream())
         feat_lens = self.n_frames(lens)
         return (feats, feat_lens, spec) if spectrogram else (feats, feat_lens)
+
+
+def _batch(waves, wave_lens):
+    """The checks every front end makes of a batch's form -> (waves as a tensor, lens int64 [N])."""
+    if isinstance(waves, np.ndarray):
+        waves = torch.from_numpy(waves)
+    if not isinstance(waves, torch.Tensor) or waves.dim() != 2:
+        raise ValueError("waves must be a [N, Lmax] tensor")
+    if waves.dtype not in (torch.float32, torch.int16):
+        raise ValueError(f"waves must be float32 or int16 PCM, got {waves.dtype}")
+    lens = np.asarray(wave_lens).reshape(-1)
+    if not np.issubdtype(lens.dtype, np.integer):
+        if not np.all(lens == np.floor(lens)):
+            raise ValueError("wave_lens must be whole numbers of samples")
+    lens = lens.astype(np.int64)
+    N, Lmax = waves.shape
+    if N == 0 or len(lens) != N:
+        raise ValueError(f"{len(lens)} lengths for a batch of {N} clips")
+    if lens.max() > Lmax:
+        raise ValueError(f"clip {int(lens.argmax())}: length {int(lens.max())} beyond the batch's {Lmax} samples")
+    if Lmax > 1 << 30:
+        raise ValueError(f"clips of {Lmax} samples: the kernel indexes a clip with 32-bit integers")
+    return waves, lens
+
+
+class Resample:
+    """``Resample(orig_rate, new_rate, zeros=64, rolloff=0.9475937167399596, beta=14.769656459379492)``: band-limited
+    sample-rate conversion by the module docstring's definition; ``Resample.kaiser_best(o, n)`` (the defaults) and
+    ``Resample.kaiser_fast(o, n)`` are the two published settings.  Limits (the kernel's): after the grouping of blocks for a
+    small ``U`` (``kernel_up = s U >= 32``, ``kernel_down = s D``) both at most 1024, at most 2048 taps per output, and
+    ``orig_rate != new_rate``."""
+    BEST = dict(zeros=64, rolloff=0.9475937167399596, beta=14.769656459379492)
+    FAST = dict(zeros=16, rolloff=0.85, beta=8.555504641634386)
+
+    def __init__(self, orig_rate, new_rate, zeros=64, rolloff=0.9475937167399596, beta=14.769656459379492):
+        for name, r in (("orig_rate", orig_rate), ("new_rate", new_rate)):
+            if isinstance(r, bool) or int(r) != r or r < 1:
+                raise ValueError(f"{name}={r}: rates are positive whole numbers of Hz")
+        if int(orig_rate) == int(new_rate):
+            raise ValueError(f"orig_rate = new_rate = {int(new_rate)}: nothing to resample")
+        if isinstance(zeros, bool) or int(zeros) != zeros or zeros < 1:
+            raise ValueError(f"zeros={zeros}: must be a whole number >= 1")
+        if not 0.0 < rolloff <= 1.0:
+            raise ValueError(f"rolloff={rolloff}: must lie in (0, 1]")
+        if not (beta >= 0.0 and math.isfinite(beta)):
+            raise ValueError(f"beta={beta}: must be finite and >= 0")
+        self.orig_rate, self.new_rate = int(orig_rate), int(new_rate)
+        self.zeros, self.rolloff, self.beta = int(zeros), float(rolloff), float(beta)
+        g = math.gcd(self.orig_rate, self.new_rate)
+        self.up, self.down = self.new_rate // g, self.orig_rate // g
+        self.cutoff = self.rolloff * min(1.0, self.up / self.down)                       # c
+        self.half_width = int(math.ceil(self.zeros / self.cutoff)) + 1                   # W
+        self.group = 1 if self.up >= _PT else -(-_PT // self.up)                         # s: blocks per kernel block
+        self.kernel_up, self.kernel_down = self.group * self.up, self.group * self.down  # U', D'
+        if max(self.kernel_up, self.kernel_down) > MAX_RATIO:
+            raise ValueError(f"{self.orig_rate} -> {self.new_rate} Hz is {self.down} -> {self.up} in lowest terms: the kernel "
+                             f"takes ratios up to {MAX_RATIO}")
+        if 2 * self.half_width > MAX_TAPS:
+            raise ValueError(f"{2 * self.half_width} taps per output (zeros / (rolloff min(1, U / D)) = "
+                             f"{self.zeros / self.cutoff:.1f}): the kernel takes up to {MAX_TAPS}")
+        self.n_rows = 2 * self.half_width + self.kernel_down                             # rows k of H
+        self._device_tables = {}
+        self._kernel_tables = None
+
+    @classmethod
+    def kaiser_best(cls, orig_rate, new_rate):
+        return cls(orig_rate, new_rate, **cls.BEST)
+
+    @classmethod
+    def kaiser_fast(cls, orig_rate, new_rate):
+        return cls(orig_rate, new_rate, **cls.FAST)
+
+    def out_len(self, L):
+        """Output samples of a clip (or an array of clips) of ``L`` samples: ``ceil(L U / D)`` in exact integers."""
+        return (np.asarray(L, dtype=np.int64) * self.up + self.down - 1) // self.down
+
+    # ------------------------------------------------------------------ tables (the only definition in the product)
+    def tables(self):
+        """Host float64 ``H [2 W + D', U']``: ``H[k, i] = g(i D' / U' - (k - W))``, the kernel's view (block ``j``, phase
+        ``i < U'``: ``y[j U' + i] = sum_k x[j D' + k - W] H[k, i]``).  The argument of every entry is the integer
+        ``i D' - (k - W) U'`` with the common factor ``s`` taken out, over ``U``."""
+        i = np.arange(self.kernel_up, dtype=np.int64)[None, :]
+        k = np.arange(self.n_rows, dtype=np.int64)[:, None] - self.half_width
+        num = (i * self.kernel_down - k * self.kernel_up) // self.group                  # exact: both terms carry s
+        u = self.cutoff * num.astype(np.float64) / self.up                               # c tau
+        inside = np.abs(u) < self.zeros
+        r = np.where(inside, u / self.zeros, 0.0)
+        win = np.i0(self.beta * np.sqrt(1.0 - r * r)) / np.i0(self.beta)
+        return np.where(inside, self.cutoff * np.sinc(u) * win, 0.0)
+
+    def kernel_tables(self):
+        """The fp32 table in the kernel's layout (include/acvae_hip.h) and its index: ``bank [phase tiles][K-steps][32 phases]
+        [32 k]``, entry ``(t, s, p, q) = H[first_k(t) + 32 s + q, 32 t + p]`` with zeros for phases ``>= U'``, rows outside
+        ``H`` and K-steps behind the tile's own; ``index`` int32 ``[phase tiles, 2]``: ``first_k``, the first row of ``H`` with
+        a non-zero tap in the tile, and the tile's number of K-steps (enough for its last such row).  Every tile has the
+        K-steps of the widest one (``bank.shape[1]``, the kernel's ``ksteps``)."""
+        if self._kernel_tables is None:
+            H = self.tables()
+            nt = -(-self.kernel_up // _PT)
+            Hp = np.zeros((self.n_rows, nt * _PT))
+            Hp[:, :self.kernel_up] = H
+            index = np.zeros((nt, 2), dtype=np.int32)
+            for t in range(nt):
+                rows = np.nonzero(Hp[:, t * _PT:(t + 1) * _PT].any(axis=1))[0]
+                index[t] = rows[0], -(-(rows[-1] - rows[0] + 1) // _BK)
+            ks = int(index[:, 1].max())
+            bank = np.zeros((nt, ks, _PT, _BK), dtype=np.float32)
+            for t in range(nt):
+                first, n = int(index[t, 0]), int(index[t, 1])
+                band = np.zeros((n * _BK, _PT))
+                stop = min(self.n_rows, first + n * _BK)
+                band[:stop - first] = Hp[first:stop, t * _PT:(t + 1) * _PT]
+                bank[t, :n] = band.reshape(n, _BK, _PT).transpose(0, 2, 1)
+            self._kernel_tables = (bank, index)
+        return self._kernel_tables
+
+    def _tables_on(self, dev):
+        key = dev.index if dev.index is not None else torch.cuda.current_device()
+        t = self._device_tables.get(key)
+        if t is None:
+            bank, index = self.kernel_tables()
+            t = self._device_tables[key] = (torch.from_numpy(bank).to(dev), torch.from_numpy(index).to(dev))
+        return t
+
+    # ------------------------------------------------------------------ the device half
+    def check(self, waves, wave_lens):
+        """Validate a batch on the host (ValueError, before any launch) -> (waves as a tensor, lens int64 [N])."""
+        waves, lens = _batch(waves, wave_lens)
+        if lens.min() < 1:
+            raise ValueError(f"clip {int(lens.argmin())}: {int(lens.min())} samples")
+        if len(lens) * int(self.out_len(lens.max())) >= 1 << 31:
+            raise ValueError(f"batch of {len(lens)} x {int(self.out_len(lens.max()))} output samples: the kernel indexes the "
+                             "batch with 32-bit integers")
+        return waves, lens
+
+    def __call__(self, waves, wave_lens, device=None):
+        """``waves`` [N, Lmax] fp32 or int16 PCM at ``orig_rate``, on the device or on the host (then uploaded, to ``device`` or
+        the current GPU); ``wave_lens`` the N sample counts (host).  -> ``(out f32 [N, max L_out] on the device at ``new_rate``,
+        out_lens np.int64 [N])``; the columns behind a clip's own ``L_out`` are zeros."""
+        waves, lens = self.check(waves, wave_lens)
+        if not waves.is_cuda:
+            if device is None:
+                if not torch.cuda.is_available():
+                    raise RuntimeError("acvae_amd: the HIP path needs a GPU device (no CPU fallback)")
+                device = torch.device("cuda", torch.cuda.current_device())
+            waves = _lib.h2d(waves, device)
+        waves = waves.contiguous()
+        dev = waves.device
+        N, Lmax = waves.shape
+        out_lens = self.out_len(lens)
+        bank, index = self._tables_on(dev)
+        lens_d = _lib.h2d(lens.astype(np.int32), dev)
+        with torch.no_grad():
+            out = torch.empty(N, int(out_lens.max()), device=dev)
+        _lib.call("acvae_resample_fwd", waves, int(waves.dtype == torch.int16), Lmax, lens_d, bank, index, out, out.shape[1], N,
+                  self.kernel_up, self.kernel_down, self.half_width, bank.shape[1], _lib.current_stream())
+        return out, out_lens
+
+
+class Resampled:
+    """``Resampled(resample, logmel)``: audio at ``resample.orig_rate`` -> features, a front end wherever ``frontend=`` takes
+    a ``LogMel``: both kernels on the current stream, the resampled batch the one tensor between them."""
+    to_float = LogMel.to_float
+
+    def __init__(self, resample, logmel):
+        if resample.new_rate != logmel.sample_rate:
+            raise ValueError(f"the resampler ends at {resample.new_rate} Hz, the log-mel front end starts from "
+                             f"{logmel.sample_rate} Hz")
+        self.resample, self.logmel = resample, logmel
+        self.sample_rate = resample.orig_rate
+
+    def n_frames(self, L):
+        """Frames of a clip (or an array of clips) of ``L`` samples at the input rate."""
+        return self.logmel.n_frames(self.resample.out_len(L))
+
+    def check(self, waves, wave_lens):
+        """Validate a batch for both halves on the host (ValueError, before any launch)."""
+        waves, lens = self.resample.check(waves, wave_lens)
+        short = self.resample.out_len(lens)
+        if short.min() < self.logmel.n_bins:
+            raise ValueError(f"clip {int(short.argmin())}: {int(lens[short.argmin()])} samples are {int(short.min())} at "
+                             f"{self.logmel.sample_rate} Hz, reflect padding needs at least n_fft/2 + 1 = {self.logmel.n_bins}")
+        T = 1 + int(short.max()) // self.logmel.hop_length
+        if len(lens) * T * self.logmel.n_bins >= 1 << 31:
+            raise ValueError(f"batch of {len(lens)} x {T} frames x {self.logmel.n_bins} bins: the kernel indexes the batch with "
+                             "32-bit integers")
+        return waves, lens
+
+    def __call__(self, waves, wave_lens, spectrogram=False, device=None):
+        """As ``LogMel.__call__``, from waveforms at the resampler's input rate."""
+        waves, lens = self.check(waves, wave_lens)
+        mid, mid_lens = self.resample(waves, lens, device=device)
+        return self.logmel(mid, mid_lens, spectrogram=spectrogram)
+
+
+def read_wav_any(path):
+    """A 16-bit PCM ``.wav`` file at whatever rate -> ``(int16 tensor [L], rate)``, channels averaged as ``read_wav`` does;
+    ``LogMel.at_input_rate(rate)`` is the front end for it."""
+    with _wave.open(str(path), "rb") as fh:
+        rate, width, ch, frames = fh.getframerate(), fh.getsampwidth(), fh.getnchannels(), fh.getnframes()
+        if width != 2:
+            raise ValueError(f"{path}: {8 * width}-bit samples, only 16-bit PCM is read")
+        data = np.frombuffer(fh.readframes(frames), dtype="<i2").reshape(-1, ch)
+    if ch == 1:
+        return torch.from_numpy(data[:, 0].astype(np.int16)), rate
+    total = data.astype(np.int32).sum(axis=1)
+    return torch.from_numpy(((2 * total + ch) // (2 * ch)).astype(np.int16)), rate
 
 
 def read_wav(path, sample_rate):

@@ -727,6 +727,48 @@ int acvae_logmel_fwd(const void* wave, int wave_is_i16, int64_t wave_stride, con
                      float db_offset, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sample-rate conversion in front of the log-mel front end: band-limited interpolation with a Kaiser-windowed sinc
+ * (the closed form behind librosa / resampy's "kaiser_best" and "kaiser_fast" settings; their interpolated tables and
+ * soxr are NOT reproduced bit for bit), one kernel, no workspace.  Rates orig -> new, g = gcd, U = new / g, D = orig / g,
+ * c = rolloff * min(1, U / D), Z zero crossings:
+ *   kernel   g(tau) = c sinc(c tau) I0(beta sqrt(1 - (c tau / Z)^2)) / I0(beta) for |c tau| < Z, else 0 (tau in input samples);
+ *   output   y[m] = sum_n x[n] g(m D / U - n), x zero outside [0, L);  L_out = ceil(L U / D) outputs for a clip of L samples.
+ * Columns L_out .. out_stride - 1 of a clip's row of `out` are written as zeros; nothing is written outside
+ * [N, out_stride].
+ *
+ * The kernel runs it as the product Y[j, i] = sum_k X[j, k] H[k, i] with m = j U + i (block j, phase i < U),
+ * X[j, k] = x[j D + k - W] and H[k, i] = g(i D / U - (k - W)), W = ceil(Z / c) + 1, on v_mfma_f32_32x32x2_f32 (exact fp32);
+ * X is never materialised - every K-step's [blocks x 32] piece is gathered from the waveform into LDS with the zero rule
+ * applied.  U and D need not be coprime: for a small U the host groups s blocks into one (U' = s U >= 32, D' = s D) and
+ * hands in U', D'; the kernel knows nothing of s.
+ *
+ * Operands (the caller owns them all; the tables are built in float64 on the host and rounded once to fp32,
+ * acvae_amd/frontend.py):
+ *   wave       [N, wave_stride] samples, fp32, or int16 PCM when wave_is_i16 (scaled by 1/32768 on load, exact in fp32);
+ *   wave_lens  int32 [N] on the device.  The kernel cannot refuse a bad length, so it clamps it to [0, wave_stride];
+ *   bank       the filter table compacted per tile of 32 phases, 16-B aligned:
+ *              [ceil(U / 32) phase tiles][ksteps K-steps][32 phases][32 k] floats.  Entry (t, s, p, q) is
+ *              H[first_k(t) + 32 s + q, 32 t + p]; phases >= U, K-steps behind the tile's own and rows outside H are zeros;
+ *   bank_index int32 [ceil(U / 32), 2] on the device: per phase tile its first k and its number of K-steps (clamped to
+ *              [0, ksteps] by the kernel).  A tile's taps are non-zero only over a band of about 2 Z / c + 31 D / U values
+ *              of k, and the kernel visits only the K-steps of that band;
+ *   out        f32 [N, out_stride], out_stride >= the longest L_out the caller wants to keep (outputs behind out_stride
+ *              are dropped).
+ * A workgroup owns ACVAE_RESAMPLE_BLOCK_TILE consecutive blocks of one clip times one phase tile.  The summation order is
+ * fixed, there are no atomics and every output is stored once: bit-reproducible.
+ * Limits (ACVAE_EINVAL before any HIP call): U, D in [1, ACVAE_RESAMPLE_MAX_RATIO] and U != D; W >= 1 and the taps per
+ * output 2 W <= ACVAE_RESAMPLE_MAX_TAPS; ksteps in [1, ACVAE_RESAMPLE_MAX_KSTEPS]; N >= 1; 1 <= wave_stride <= 2^30;
+ * out_stride >= 1 and N * out_stride < 2^31; wave_is_i16 0 or 1; a NULL pointer.  `bank` not 16-B aligned -> ACVAE_EALIGN.
+ * ------------------------------------------------------------------------------------------- */
+#define ACVAE_RESAMPLE_BLOCK_TILE 64
+#define ACVAE_RESAMPLE_MAX_RATIO 1024
+#define ACVAE_RESAMPLE_MAX_TAPS 2048
+#define ACVAE_RESAMPLE_MAX_KSTEPS 98    /* (MAX_TAPS + MAX_RATIO) / 32 + 2: the widest band of a phase tile */
+int acvae_resample_fwd(const void* wave, int wave_is_i16, int64_t wave_stride, const int* wave_lens, const float* bank,
+                       const int* bank_index, float* out, int64_t out_stride, int N, int U, int D, int W, int ksteps,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Rows of a [*, R] matrix gathered by an index, and the adjoint: rows folded into the row they came from.  The training
  * step with several captions per clip (Hybrid_VAEModel.forward(..., clip_index=)) runs the encoder once over the B clips
  * and gathers its memory [B, R = S * C] into the N caption rows; the backward folds the N rows' gradients into the B clips'.
