@@ -1,11 +1,17 @@
-// decode_persist.hip: the teacher-forced decode loop as one persistent launch (internal C++ interface; the C ABI entry is
-// acvae_decode_fwd, which takes this path when acvae::decode_persist_ok says so: the shape is one the kernel takes AND its
-// whole grid is resident on the current device at once; `flags`: ACVAE_FLAG_* of include/acvae_hip.h).
+// decode_persist.hip: the teacher-forced decode loop, its backward through time and the posterior's BiGRU as persistent
+// launches (internal C++ interface of the C ABI entries of decoder.hip; `flags`: ACVAE_FLAG_* of include/acvae_hip.h).
+// Per launch a caller
+//   1. makes the PLAN from the dims (persist_plan.h: pure - role counts, grid, LDS, counters, scratch; the workspace layouts
+//      read the same plans),
+//   2. asks *_resident() whether the kernel takes the shape AND the plan's whole grid is resident on the current device at
+//      once - the only place that talks to the occupancy calculator, its answers cached per device - and takes the per-step
+//      path if not,
+//   3. fills the parameter struct's pointers and launches with the plan: the launcher copies the plan's dims and counts into
+//      the struct, derives nothing and queries nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
-
-enum { PD_C_D1Q, PD_C_D1H, PD_C_D2, PD_C_D3, PD_C_P1, PD_C_P2, PD_C_COUNT };   // arrival counters: [role][step]
+#include "persist_plan.h"
 
 struct PdParams {
   // decoder (models/decoder.py:175-203): attention h2attn [A, H + E] (query half = columns 0..H), GRU weight_hh [3H, H] /
@@ -22,15 +28,14 @@ struct PdParams {
   // written by the launch ([N, Tc, .] batch-major like the reference's outputs)
   float *qd, *gh, *rnn_d, *attn_w, *outputs, *gru_save, *hprev_d;
   float *rnn_p, *hp_all, *c_all, *lstm_save, *p_means, *p_logs, *p_z;
-  unsigned* cnt;                   // decode_persist_counter_words(Tc) words, zeroed by the launcher
-  unsigned* abort_word;            // set by the launcher (last counter word)
-  unsigned spin_limit;             // set by the launcher: polls after which a wait gives up and raises abort_word
+  unsigned* cnt;                   // PdPlan::counter_words words, zeroed by the launcher
+  // everything below is set by the launcher, from the plan
+  unsigned* abort_word;            // cnt + PdPlan::abort_index
+  unsigned spin_limit;             // polls after which a wait gives up and raises abort_word
   int N, Tc, S, E, H, A;
-  int n_d1, n_d3, n_p1, n_p2;      // set by the launcher
-  int att_resident;                // set by the launcher: the attention keeps its clip's memory on the CU
+  int n_d1, n_d3, n_p1, n_p2;
+  int att_resident;                // the attention keeps its clip's memory on the CU
 };
-
-enum { PB_C_RA, PB_C_RB, PB_C_RC, PB_C_PA, PB_C_PB, PB_C_COUNT };
 
 // backward through time of the same loop (acvae_decode_bwd)
 struct PbParams {
@@ -45,33 +50,33 @@ struct PbParams {
   // written by the launch (dctx: [N, Tc, E], one slot per step)
   float *dgi, *dgh, *dqd, *dctx, *dencproj, *dmem, *dvpart, *dgates, *dml_all, *dhp;
   // clips of more than 64 frames: the attention role runs as rc_splits workgroups per clip (set by the launcher); their shares
-  // of d qd [rc_splits][N][Tc][A] (RA adds them and writes the sum to dqd) and the forward's rnn_d ([N][Tc][3E]: ctx = columns E..2E)
+  // of d qd [rc_splits][N][Tc][A] (PbPlan::dqd_part_floats; RA adds them and writes the sum to dqd) and the forward's rnn_d
+  // ([N][Tc][3E]: ctx = columns E..2E)
   float* dqd_part;
   const float* ctx;
   int rc_splits;
-  // K-split partials handed over inside the launch (scratch, decode_persist_bwd_part_floats): dctx [ks_rb][N][E],
-  // dhp [ks_pa][N][Hp], dml [ks_pa][N][2E]
+  // K-split partials handed over inside the launch: dctx [ks_rb][N][E], dhp [ks_pa][N][Hp], dml [ks_pa][N][2E], at
+  // PbPlan::*_part_off of one scratch region of PbPlan::part_floats
   float *dctx_part, *dhp_part, *dml_part;
-  unsigned* cnt;
+  unsigned* cnt;                   // PbPlan::counter_words words
+  // set by the launcher, from the plan
   unsigned* abort_word;
   unsigned spin_limit;
   int N, Tc, S, E, H, A;
   int n_ra, n_rb, n_pa, n_pb;
-  int ks_rb, ks_pa;                // K-splits of the RB / PA products (set by the launcher)
+  int ks_rb, ks_pa;                // K-splits of the RB / PA products
 };
 
 namespace acvae {
-bool decode_persist_bwd_ok(int N, int Tc, int S, int E, int H, int A);
 // internal flag beside the public ACVAE_FLAG_* of a launch: the caller has zeroed p.cnt in this stream (with its other tickets,
 // one launch: rnn.h ZeroBatch) - the launcher skips its own memset
 #define ACVAE_FLAG_INT_CNT_ZEROED (1 << 16)
-long decode_persist_bwd_counter_words(int Tc);
-int decode_persist_bwd_rc_splits(int S);     // attention workgroups per clip (64 frames each)
-int decode_persist_bwd(PbParams p, hipStream_t st, int flags);
-long decode_persist_bwd_part_floats(int N, int E, int H);
-bool decode_persist_ok(int N, int Tc, int S, int E, int H, int A);
-long decode_persist_counter_words(int Tc);
-int decode_persist_fwd(PdParams p, hipStream_t st, int flags);
+// The plan whose grid is resident on the current device: with the attention's memory on the CU where the shape has that form
+// and it fits, else streamed.  false: the kernel does not take the shape, or neither form fits.
+bool decode_fwd_resident(int N, int Tc, int S, int E, int H, int A, PdPlan& plan);
+int decode_persist_fwd(PdParams p, const PdPlan& plan, hipStream_t st, int flags);
+bool decode_bwd_resident(const PbPlan& plan);
+int decode_persist_bwd(PbParams p, const PbPlan& plan, hipStream_t st, int flags);   // p.dqd_part / p.ctx: needed when plan.rc_splits > 1
 }  // namespace acvae
 
 
@@ -90,9 +95,9 @@ struct PqParams {
   float* save[2];              // [N][Tc][4Hq] = r | z | n | gh_n
   float* hprev[2];             // [N][Tc][Hq]
   float* hbuf;                 // [2 directions][2 step parities][N][Hq]: the state in flight, ZEROED by the caller (step 0 reads parity 1)
-  unsigned* cnt;               // posterior_persist_counter_words(Tc), zeroed by the launcher
-  unsigned* abort_word;        // set by the launcher
-  unsigned spin_limit;         // set by the launcher
+  unsigned* cnt;               // PqPlan::counter_words words, zeroed by the launcher
+  unsigned* abort_word;        // set by the launcher, as are the fields below
+  unsigned spin_limit;
   int N, Tc, Hq;
 };
 struct PqbParams {
@@ -109,8 +114,7 @@ struct PqbParams {
   int N, Tc, Hq;
 };
 namespace acvae {
-bool posterior_persist_ok(int N, int Tc, int Hq);
-long posterior_persist_counter_words(int Tc);
-int posterior_persist_fwd(PqParams p, hipStream_t st, int flags);
-int posterior_persist_bwd(PqbParams p, hipStream_t st, int flags);
+bool posterior_resident(const PqPlan& plan);     // both passes: a forward on the persistent path is followed by such a backward
+int posterior_persist_fwd(PqParams p, const PqPlan& plan, hipStream_t st, int flags);
+int posterior_persist_bwd(PqbParams p, const PqPlan& plan, hipStream_t st, int flags);
 }  // namespace acvae

@@ -21,8 +21,9 @@
 // no other CU's store ever refreshes); every storing wave drains its stores (s_waitcnt vmcnt(0)), the workgroup meets at
 // a barrier, ONE lane adds to the step's arrival counter; the consumer's lane 0 polls that ONE word relaxed with s_sleep,
 // then the workgroup's barrier.  No fence anywhere.  Counters are per (role, step), zeroed by the launcher's memset:
-// nothing is ever reset or reused inside the launch.  All workgroups (160 + N + ...) fit the chip at once (512 threads,
-// 34 KB of LDS: two per CU would fit); every spin is bounded and raises an abort word that ends all roles.
+// nothing is ever reset or reused inside the launch.  All workgroups (A/32 + 3H/32 + N + H/16 + E/8 + E/16: 192 + N at 512,
+// PdPlan::grid of persist_plan.h) must be on the chip at once (512 threads, 37 KB of LDS, or up to 150 KB where the attention
+// keeps its clip's memory: the launchers below check it); every spin is bounded and raises an abort word that ends all roles.
 //
 // Also in this file: the backward through time of the same loop (decode_persist_bwd_kernel: roles RA / RB / RC / PA / PB, K-splits
 // with the combine on the reader's side) and the posterior's bidirectional GRU, forward and backward, as one launch per pass
@@ -38,7 +39,9 @@
 namespace {
 using namespace mfma;
 
-constexpr int PD_THREADS = 512;          // 8 wavefronts, as gemm_skinny_kernel
+using acvae::PD_THREADS;                 // 8 wavefronts, as gemm_skinny_kernel (persist_plan.h)
+using acvae::PD_U;
+static_assert(acvae::PD_WAVES == SK_WAVES, "the plans count the reduction tiles of SK_WAVES wavefronts");
 constexpr unsigned PD_SPIN_LIMIT = 1u << 24;   // polls x ~150 ns: seconds; never reached unless part of the grid is not resident
 
 #define PD_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
@@ -91,7 +94,6 @@ __device__ __forceinline__ void pd_arrive(unsigned* cnt) {
 // the L2s: the load goes to the memory side), so the loads are split by what they depend on: the weight fragments of the
 // first PD_U groups are fetched BEFORE the role waits for its input (pd_fetch_b), the input fragments in ONE batch behind
 // the wait (hipcc, left alone, waits for the first two groups, starts the MFMAs and fetches the rest behind a second wait).
-constexpr int PD_U = 8;
 struct PdFrag { float4 b[PD_U]; };
 __device__ __forceinline__ void pd_fetch_b(PdFrag& f, const float* bp, int K, int wave) {
   const int Gfull = K / 8;
@@ -178,6 +180,7 @@ struct PdSmem {
   float keep[32][33];              // D3: the first tile's sums while the second is reduced
   int flag;
 };
+static_assert(sizeof(PdSmem) == acvae::PD_SMEM_BYTES, "persist_plan.h sizes the launch's LDS");
 
 // What a role can fetch without its input - its weight fragments (for K <= 512 a wave's whole share: 8 groups = 32 registers,
 // fetched ONCE and kept for all Tc steps), biases, the hoisted projections of the step - is fetched before the role waits;
@@ -226,10 +229,10 @@ __device__ void role_d1(const PdParams& p, int tile, PdSmem& sm) {
 template <bool RES>
 __device__ void role_d2(const PdParams& p, int n, float* smem, int* s_flag) {
   const int S = p.S, A = p.A, E = p.E;
-  float* sc = smem;
+  float* sc = smem;                                         // the role's LDS area: persist_plan.h, pd_att_floats
   float* red = smem + S;
-  float* part = smem + ((S + 16 + 3) & ~3);
-  float* Pl = part + 4096;                                  // RES: [S][A]
+  float* part = smem + acvae::pd_att_part_off(S);
+  float* Pl = part + acvae::PD_ATT_PART_FLOATS;             // RES: [S][A]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* Pg = p.encproj + (long)n * S * A;
   const float* Hn = p.mem + (long)n * S * E;
@@ -525,7 +528,7 @@ __global__ __launch_bounds__(PD_THREADS) void decode_persist_kernel(PdParams p) 
   if (b < p.n_d1) { role_d1(p, b, sm); return; }
   b -= p.n_d1;
   if (b < p.N) {
-    float* sm2 = reinterpret_cast<float*>(pd_smem_raw) + 4;
+    float* sm2 = reinterpret_cast<float*>(pd_smem_raw) + acvae::ATT_LDS_HEAD;
     int* fl = reinterpret_cast<int*>(pd_smem_raw);
     if (p.att_resident) role_d2<true>(p, b, sm2, fl); else role_d2<false>(p, b, sm2, fl);
     return;
@@ -555,12 +558,12 @@ __global__ __launch_bounds__(PD_THREADS) void decode_persist_kernel(PdParams p) 
 // step.  Same hand-off protocol as the forward launch.  Products are summed over 8 wave shares (one pass) instead of the per-step
 // path's split-K slabs and the attention sums its frames in one sweep, so results agree with that path to rounding (not
 // bit for bit); the parity test bounds the difference.
-constexpr int PB_THREADS = 512, PB_WAVES = 8;
-
 struct PbSmem {
-  float red[PB_WAVES][32][33];
+  float red[SK_WAVES][32][33];
   int flag;
 };
+static_assert(sizeof(PbSmem) == acvae::PB_SMEM_BYTES, "persist_plan.h sizes the launch's LDS");
+// (the same two functions as pd_stash / pd_sum: with one pair for both launches hipcc schedules the BPTT kernel differently)
 __device__ __forceinline__ void pb_stash(float (*red)[32][33], const f32x16& acc, int wave, int li, int lh) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) red[wave][(r & 3) + 8 * (r >> 2) + 4 * lh][li] = acc[r];
@@ -568,7 +571,7 @@ __device__ __forceinline__ void pb_stash(float (*red)[32][33], const f32x16& acc
 __device__ __forceinline__ float pb_sum(float (*red)[32][33], int mm, int nn) {
   float v = 0.f;
 #pragma unroll
-  for (int w = 0; w < PB_WAVES; ++w) v += red[w][mm][nn];
+  for (int w = 0; w < SK_WAVES; ++w) v += red[w][mm][nn];
   return v;
 }
 // acc += A[32 rows][K] . B[32 rows][K]^T, this wave's K-groups (wave, wave + 8, ..) in batches of eight, software-pipelined by
@@ -587,8 +590,8 @@ __device__ __forceinline__ void pb_load(PbBatch& f, const float* abase, long aid
   const float* bq = bp + (long)g * 8;
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
-    f.b[u] = *reinterpret_cast<const float4*>(bq + u * PB_WAVES * 8);
-    const pd_v4u v = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, u * PB_WAVES * 32, 16 /* sc1 */);
+    f.b[u] = *reinterpret_cast<const float4*>(bq + u * SK_WAVES * 8);
+    const pd_v4u v = __builtin_amdgcn_raw_buffer_load_b128(ars, vo, u * SK_WAVES * 32, 16 /* sc1 */);
     f.a[u] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
   }
 }
@@ -604,7 +607,7 @@ __device__ __forceinline__ void pb_mfma(f32x16& acc, const PbBatch& f) {
 // any K (a multiple of 8): this wave's groups wave, wave + 8, .. one at a time
 __device__ __forceinline__ void pb_gemm_tail(f32x16& acc, const float* abase, long aidx, const float* bp, int G, int wave) {
 #pragma clang loop unroll(disable)
-  for (int g = wave; g < G; g += PB_WAVES) {
+  for (int g = wave; g < G; g += SK_WAVES) {
     const float4 b = *reinterpret_cast<const float4*>(bp + (long)g * 8);
     const float4 a = ld_sc1_4(abase, aidx + (long)g * 8);
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
@@ -616,7 +619,7 @@ __device__ __forceinline__ void pb_gemm_tail(f32x16& acc, const float* abase, lo
 // K <= 512: the wave's whole share is one batch
 __device__ __forceinline__ void pb_gemm1(f32x16& acc, const float* abase, long aidx, const float* bp, int K, int wave) {
   const int G = K / 8;
-  if (G == 8 * PB_WAVES) {
+  if (G == 8 * SK_WAVES) {
     PbBatch f;
     pb_load(f, abase, aidx, bp, wave);
     __builtin_amdgcn_sched_barrier(0);
@@ -631,7 +634,7 @@ __device__ __forceinline__ void pb_gemm1(f32x16& acc, const float* abase, long a
 __device__ __forceinline__ void pb_gemm1_shares(f32x16& acc, const float* abase, long aidx, long sstride, int ns, const float* bp,
                                                 int K, int wave, float* keep) {
   const int G = K / 8;
-  if (G == 8 * PB_WAVES) {
+  if (G == 8 * SK_WAVES) {
     const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(abase), 0, 0x7fffffff, 0x00020000);
     const int vo = (int)((aidx + (long)wave * 8) * 4);
     const float* bq = bp + (long)wave * 8;
@@ -639,10 +642,10 @@ __device__ __forceinline__ void pb_gemm1_shares(f32x16& acc, const float* abase,
     float4 b[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      b[u] = *reinterpret_cast<const float4*>(bq + u * PB_WAVES * 8);
+      b[u] = *reinterpret_cast<const float4*>(bq + u * SK_WAVES * 8);
 #pragma unroll
       for (int q = 0; q < 3; ++q)
-        r[q][u] = __builtin_amdgcn_raw_buffer_load_b128(ars, vo + (int)((q < ns ? q : 0) * sstride * 4), u * PB_WAVES * 32, 16 /* sc1 */);
+        r[q][u] = __builtin_amdgcn_raw_buffer_load_b128(ars, vo + (int)((q < ns ? q : 0) * sstride * 4), u * SK_WAVES * 32, 16 /* sc1 */);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -654,7 +657,7 @@ __device__ __forceinline__ void pb_gemm1_shares(f32x16& acc, const float* abase,
           v.x += __uint_as_float(r[q][u].x); v.y += __uint_as_float(r[q][u].y);
           v.z += __uint_as_float(r[q][u].z); v.w += __uint_as_float(r[q][u].w);
         }
-      if (keep) *reinterpret_cast<float4*>(keep + (wave + u * PB_WAVES) * 8) = v;
+      if (keep) *reinterpret_cast<float4*>(keep + (wave + u * SK_WAVES) * 8) = v;
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(v.x, b[u].x, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(v.y, b[u].y, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(v.z, b[u].z, acc, 0, 0, 0);
@@ -662,7 +665,7 @@ __device__ __forceinline__ void pb_gemm1_shares(f32x16& acc, const float* abase,
     }
   } else {
 #pragma clang loop unroll(disable)
-    for (int g = wave; g < G; g += PB_WAVES) {
+    for (int g = wave; g < G; g += SK_WAVES) {
       const float4 b = *reinterpret_cast<const float4*>(bp + (long)g * 8);
       float4 v = ld_sc1_4(abase, aidx + (long)g * 8);
       for (int q = 1; q < ns; ++q) {
@@ -679,7 +682,7 @@ __device__ __forceinline__ void pb_gemm1_shares(f32x16& acc, const float* abase,
 }
 __device__ __forceinline__ void pb_gemm(f32x16& acc, const float* abase, long aidx, const float* bp, int K, int wave) {
   const int G = K / 8;
-  constexpr int STEP = 8 * PB_WAVES;
+  constexpr int STEP = 8 * SK_WAVES;
   if (G % STEP != 0) { pb_gemm_tail(acc, abase, aidx, bp, G, wave); return; }
   PbBatch f0, f1;
   pb_load(f0, abase, aidx, bp, wave);
@@ -705,7 +708,7 @@ template <int NB, int NP = 1>
 __device__ __forceinline__ void pb_gemm_apre(f32x16& acc, const float* abase, long aidx, const float* bp, int wave, long pstride = 0,
                                              float* keep = nullptr, int keep_mod = 1, int keep_rem = 0) {
   // K = 512 NB exactly: every K-group exists, all offsets are a per-wave base plus constants
-  constexpr int STEP = 8 * PB_WAVES;
+  constexpr int STEP = 8 * SK_WAVES;
   const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(abase), 0, 0x7fffffff, 0x00020000);
   const int vbase = (int)((aidx + (long)wave * 8) * 4);
   const float* bw = bp + wave * 8;
@@ -718,7 +721,7 @@ __device__ __forceinline__ void pb_gemm_apre(f32x16& acc, const float* abase, lo
       for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-          r[q][nb][u] = __builtin_amdgcn_raw_buffer_load_b128(ars, vbase + (int)(q * pstride * 4), (nb * STEP + u * PB_WAVES) * 32, 16 /* sc1 */);
+          r[q][nb][u] = __builtin_amdgcn_raw_buffer_load_b128(ars, vbase + (int)(q * pstride * 4), (nb * STEP + u * SK_WAVES) * 32, 16 /* sc1 */);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -731,13 +734,13 @@ __device__ __forceinline__ void pb_gemm_apre(f32x16& acc, const float* abase, lo
           v.z += __uint_as_float(r[q][nb][u].z); v.w += __uint_as_float(r[q][nb][u].w);
         }
         a[nb][u] = v;
-        if (keep && (nb * 8 + u) % keep_mod == keep_rem) *reinterpret_cast<float4*>(keep + (wave + nb * STEP + u * PB_WAVES) * 8) = v;
+        if (keep && (nb * 8 + u) % keep_mod == keep_rem) *reinterpret_cast<float4*>(keep + (wave + nb * STEP + u * SK_WAVES) * 8) = v;
       }
   }
   float4 b0[8], b1[8];
   auto load_b = [&](float4 (&b)[8], int nb) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) b[u] = *reinterpret_cast<const float4*>(bw + (nb * STEP + u * PB_WAVES) * 8);
+    for (int u = 0; u < 8; ++u) b[u] = *reinterpret_cast<const float4*>(bw + (nb * STEP + u * SK_WAVES) * 8);
   };
   auto mfma = [&](const float4 (&av)[8], const float4 (&b)[8]) {
 #pragma unroll
@@ -882,15 +885,16 @@ __device__ void role_rc(const PbParams& p, int n, int share, float* smem, int* s
   const int A = p.A, E = p.E;
   const int s0 = share * 64, S = min(64, p.S - s0);          // this workgroup's frames: s0 .. s0 + S - 1
   const bool split = p.rc_splits > 1;
-  float* w_s = smem;                  // [64]
-  float* ds_s = smem + 64;            // [64]
-  float* dwred = smem + 128;          // [8][64]
-  float* dc_s = smem + 128 + 512;     // [512]
-  float* Pl = smem + 128 + 512 + 512; // [S][A]
+  constexpr acvae::PbAttLds map = acvae::PB_ATT_LDS;
+  float* w_s = smem + map.w;          // [64]
+  float* ds_s = smem + map.ds;        // [64]
+  float* dwred = smem + map.dwred;    // [8][64]
+  float* dc_s = smem + map.dc;        // [512]
+  float* Pl = smem + map.pl;          // [S][A]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int a = threadIdx.x;
   const int len = (int)p.mem_lens[n];
-  for (int i = threadIdx.x * 4; i < S * A; i += PB_THREADS * 4)
+  for (int i = threadIdx.x * 4; i < S * A; i += PD_THREADS * 4)
     *reinterpret_cast<float4*>(Pl + i) = *reinterpret_cast<const float4*>(p.encproj + ((long)n * p.S + s0) * A + i);
   // dw[s] = dctx . mem[s] with lanes over the frames: thread (wave w, lane s) holds mem[s][64 w .. 64 w + 63] and sums its 64
   // products in registers - no cross-lane reduction (62 wave-wide shuffle reductions per step cost 8 us here); the eight
@@ -1081,7 +1085,7 @@ __device__ void role_pb(const PbParams& p, int slice, PbSmem& sm) {
       else {                     // other widths: one share (ks_pa = 1), the streaming product, the step's row copied by slice 0
         pb_gemm(acc, p.dml_part, aidx, bp, 2 * E, wave);
         if (slice == 0)
-          for (int i = threadIdx.x; i < p.N * 2 * E; i += PB_THREADS) {
+          for (int i = threadIdx.x; i < p.N * 2 * E; i += PD_THREADS) {
             const int n_ = i / (2 * E), c_ = i - n_ * 2 * E;
             p.dml_all[(long)n_ * p.Tc * 2 * E + (long)t * 2 * E + c_] = ld_sc1(p.dml_part + i);
           }
@@ -1120,7 +1124,7 @@ __global__ void attn_dmem_kernel(const float* __restrict__ w, const float* __res
   }
 }
 
-__global__ __launch_bounds__(PB_THREADS) void decode_persist_bwd_kernel(PbParams p) {
+__global__ __launch_bounds__(PD_THREADS) void decode_persist_bwd_kernel(PbParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pb_smem_raw[];
   PbSmem& sm = *reinterpret_cast<PbSmem*>(pb_smem_raw);
   int b = blockIdx.x;
@@ -1129,7 +1133,8 @@ __global__ __launch_bounds__(PB_THREADS) void decode_persist_bwd_kernel(PbParams
   if (b < p.n_rb) { role_rb(p, b, sm); return; }
   b -= p.n_rb;
   if (b < p.N * p.rc_splits) {
-    role_rc(p, b / p.rc_splits, b % p.rc_splits, reinterpret_cast<float*>(pb_smem_raw) + 4, reinterpret_cast<int*>(pb_smem_raw));
+    role_rc(p, b / p.rc_splits, b % p.rc_splits, reinterpret_cast<float*>(pb_smem_raw) + acvae::ATT_LDS_HEAD,
+            reinterpret_cast<int*>(pb_smem_raw));
     return;
   }
   b -= p.N * p.rc_splits;
@@ -1149,6 +1154,7 @@ struct PqSmem {
   float red[SK_WAVES][32][33];
   int flag;
 };
+static_assert(sizeof(PqSmem) == acvae::PQ_SMEM_BYTES, "persist_plan.h sizes the launch's LDS");
 
 __global__ __launch_bounds__(PD_THREADS) void posterior_persist_fwd_kernel(PqParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pq_smem_raw[];
@@ -1291,27 +1297,37 @@ __global__ __launch_bounds__(PD_THREADS) void posterior_persist_bwd_kernel(PqbPa
 
 // =====================================================================================================================
 // Launchers.  A persistent launch only makes progress while ALL of its workgroups are resident (every role spins on what
-// another role produces), so a launcher
-//   (1) asks the occupancy calculator whether the whole grid fits the device with the launch's LDS and registers, and
-//       reports "does not fit" to its caller BEFORE anything is queued (the per-step path of decoder.hip runs instead);
-//   (2) chains the device's persistent launches behind each other (one event per device, recorded after every such launch
+// another role produces).  What a launch looks like - role counts, grid, LDS, counter words, scratch - is its PLAN, a pure
+// function of the dims (persist_plan.h); this file adds the two things that need the device:
+//   *_resident(plan): does the kernel take the shape, and does the plan's whole grid fit the current device at once with
+//       its LDS and registers?  The only place that asks the occupancy calculator (and raises the dynamic-LDS attribute); the
+//       answer for a (kernel, LDS size) does not change within a process and is kept in the device's slot, so a training
+//       step asks the driver nothing after its first.  "No": nothing is queued, the caller runs the per-step path of decoder.hip.
+//   *_persist_*(params, plan, ..): copies the plan's dims and counts into the parameter struct and launches the plan's grid;
+//       derives nothing, queries nothing.  It
+//   (1) chains the device's persistent launches behind each other (one event per device, recorded after every such launch
 //       and waited for by the next one, whatever stream or host thread it comes from): two spin-wait grids of one process
 //       never share the chip;
-//   (3) queues a one-workgroup tail kernel behind the launch that reads the launch's abort word - set when a bounded wait ran
+//   (2) queues a one-workgroup tail kernel behind the launch that reads the launch's abort word - set when a bounded wait ran
 //       out all the same (another PROCESS holds the CUs, a CU mask the occupancy query does not see) - and, if it is set,
 //       overwrites the launch's outputs with NaN and raises the device's status word (acvae_persist_status_register):
 //       an aborted launch can neither be trained on nor go unnoticed.
-// The slot below (event, status pointer, CU count) is the library's per-device mutable state, listed in acvae_hip.h.
+// The slot below (event, status pointer, CU count and, of a kind with it, workgroups per CU) is the library's per-device
+// mutable state, listed in acvae_hip.h.
 // =====================================================================================================================
 namespace {
 constexpr int PERSIST_MAX_DEV = 64;
 enum { PK_DECODE_FWD, PK_DECODE_BWD, PK_POST_FWD, PK_POST_BWD, PK_COUNT };
 struct PersistSlot {
-  std::mutex mu;
+  std::mutex mu;                                  // guards everything but `status`
   hipEvent_t done = nullptr;                      // completion of the device's latest persistent launch
   std::atomic<unsigned*> status{nullptr};         // registered status words (device-visible), or null
-  std::atomic<int> cus{0};
-  std::atomic<bool> raised[PK_COUNT];             // dynamic-LDS attribute of kernel k raised on this device
+  int cus = 0;
+  bool raised[PK_COUNT] = {};                     // dynamic-LDS attribute of kernel k raised on this device
+  // workgroups of kernel `kid` with `shm` bytes of LDS that one CU holds: a handful of (kid, shm) pairs occur in a process
+  // (a full table only means that further pairs are asked for every time)
+  struct Fit { int kid; size_t shm; int per_cu; } fit[16];
+  int n_fit = 0;
 };
 PersistSlot g_slot[PERSIST_MAX_DEV];
 
@@ -1334,40 +1350,48 @@ int persist_device(int& dev) {
   if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
   return (dev < 0 || dev >= PERSIST_MAX_DEV) ? ACVAE_EUNSUPPORTED : ACVAE_OK;
 }
-// does a grid of `grid` workgroups of 512 threads with `shm` bytes of dynamic LDS fit the current device all at once?
+// does a grid of `grid` workgroups of PD_THREADS threads with `shm` bytes of dynamic LDS fit the current device all at once?
 template <class K>
 bool persist_fits(K kernel, int kid, int grid, size_t shm) {
   int dev = 0;
   if (persist_device(dev) != ACVAE_OK) return false;
   PersistSlot& sl = g_slot[dev];
-  if (shm > 64 * 1024 && !sl.raised[kid].load()) {       // more than 64 KB of dynamic LDS needs the attribute, once per device
+  std::lock_guard<std::mutex> lock(sl.mu);
+  for (int k = 0; k < sl.n_fit; ++k)
+    if (sl.fit[k].kid == kid && sl.fit[k].shm == shm) return (long)sl.fit[k].per_cu * sl.cus >= grid;
+  if (shm > 64 * 1024 && !sl.raised[kid]) {       // more than 64 KB of dynamic LDS needs the attribute, once per device
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
         hipSuccess) {
       (void)hipGetLastError();
       return false;
     }
-    sl.raised[kid].store(true);
+    sl.raised[kid] = true;
   }
-  int cus = sl.cus.load();
-  if (cus == 0) {
+  if (sl.cus == 0) {
+    int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
       (void)hipGetLastError();
       return false;
     }
-    sl.cus.store(cus);
+    sl.cus = cus;
   }
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, PD_THREADS, shm) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
-  return (long)per_cu * cus >= grid;
+  if (sl.n_fit < (int)(sizeof(sl.fit) / sizeof(sl.fit[0]))) sl.fit[sl.n_fit++] = {kid, shm, per_cu};
+  return (long)per_cu * sl.cus >= grid;
 }
-// memset of the counters, the launch and its tail, chained behind the device's previous persistent launch
-template <class K, class P>
-int persist_launch(K kernel, int kid, const P& p, int grid, size_t shm, long counter_words, const PoisonList& poison, hipStream_t st,
-                   bool zeroed = false) {
+// memset of the counters, the launch and its tail, chained behind the device's previous persistent launch.
+// ACVAE_FLAG_TEST_STALL: one workgroup short and a short spin limit - the roles that wait for the missing workgroup run into
+// their bound, exactly as when part of a grid is not resident (tests/test_decode_persist_gpu.py)
+template <class K, class P, class Plan>
+int persist_launch(K kernel, int kid, P& p, const Plan& plan, const PoisonList& poison, hipStream_t st, int flags) {
   if (!poison.ok()) return ACVAE_EINVAL;
+  const bool stall = (flags & ACVAE_FLAG_TEST_STALL) != 0;
+  p.abort_word = p.cnt + plan.abort_index;
+  p.spin_limit = stall ? 1u << 12 : PD_SPIN_LIMIT;
   int dev = 0;
   ACVAE_TRY(persist_device(dev));
   PersistSlot& sl = g_slot[dev];
@@ -1377,18 +1401,14 @@ int persist_launch(K kernel, int kid, const P& p, int grid, size_t shm, long cou
   } else if (hipStreamWaitEvent(st, sl.done, 0) != hipSuccess) {
     return (int)hipGetLastError();
   }
-  if (!zeroed && hipMemsetAsync(p.cnt, 0, (size_t)counter_words * sizeof(unsigned), st) != hipSuccess) return (int)hipGetLastError();
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(PD_THREADS), shm, st, p);
+  if (!(flags & ACVAE_FLAG_INT_CNT_ZEROED) &&
+      hipMemsetAsync(p.cnt, 0, (size_t)plan.counter_words * sizeof(unsigned), st) != hipSuccess)
+    return (int)hipGetLastError();
+  hipLaunchKernelGGL(kernel, dim3(plan.grid - (stall ? 1 : 0)), dim3(PD_THREADS), plan.shm, st, p);
   hipLaunchKernelGGL(persist_tail_kernel, dim3(1), dim3(1024), 0, st, p.abort_word, sl.status.load(), kid, poison);
   ACVAE_LAUNCH_CHECK();
   if (hipEventRecord(sl.done, st) != hipSuccess) return (int)hipGetLastError();
   return ACVAE_OK;
-}
-// ACVAE_FLAG_TEST_STALL: one workgroup short and a short spin limit - the roles that wait for the missing workgroup run into
-// their bound, exactly as when part of a grid is not resident (tests/test_decode_persist_gpu.py)
-inline void persist_test_stall(int flags, int& grid, unsigned& spin_limit) {
-  spin_limit = PD_SPIN_LIMIT;
-  if (flags & ACVAE_FLAG_TEST_STALL) { grid -= 1; spin_limit = 1u << 12; }
 }
 }  // namespace
 
@@ -1407,98 +1427,43 @@ extern "C" int acvae_persist_status_register(int device, void* status_words_host
 namespace acvae {
 
 // ---- decode forward
-static void decode_fwd_geometry(int N, int S, int E, int H, int A, bool resident, int& grid, size_t& shm, int& att_resident) {
-  grid = (A / 32 + 3 * H / 32) + N + H / 16 + E / 8 + E / 16;
-  shm = sizeof(PdSmem);
-  size_t att = (size_t)(4 + ((S + 16 + 3) & ~3) + 4096) * sizeof(float);      // context partials: (1024 / (E/4)) x E
-  // the clip's projected memory in LDS and its memory rows in registers (8 frames for each of a thread's 2 context groups)
-  const int GV = 1024 / (E / 4);
-  att_resident = (resident && S <= 8 * GV && att + (size_t)S * A * sizeof(float) <= 150 * 1024) ? 1 : 0;
-  if (att_resident) att += (size_t)S * A * sizeof(float);
-  if (att > shm) shm = att;
-}
-static bool decode_fwd_shape_ok(int N, int Tc, int S, int E, int H, int A) {
-  // one 32-row tile of clips; whole 32 / 16 / 8-wide slices and K-groups of 8; one score per thread in the softmax; E a
-  // power of two so that the context groups of the per-step attention kernel (1024 / (E / 4)) can be replayed exactly
-  return N >= 1 && N <= 32 && Tc >= 1 && S >= 1 && S <= PD_THREADS && E >= 32 && E <= 2048 && (E & (E - 1)) == 0 &&
-         H % 32 == 0 && A % 32 == 0;
-}
-// picks the attention form (memory resident on the CU or streamed) whose grid fits the device; false: neither does
-static bool decode_fwd_plan(int N, int Tc, int S, int E, int H, int A, int& grid, size_t& shm, int& att_resident) {
-  if (!decode_fwd_shape_ok(N, Tc, S, E, H, A)) return false;
+bool decode_fwd_resident(int N, int Tc, int S, int E, int H, int A, PdPlan& plan) {
   for (int resident = 1; resident >= 0; --resident) {
-    decode_fwd_geometry(N, S, E, H, A, resident != 0, grid, shm, att_resident);
-    if (resident && !att_resident) continue;
-    if (persist_fits(decode_persist_kernel, PK_DECODE_FWD, grid, shm)) return true;
+    plan = decode_fwd_plan(N, Tc, S, E, H, A, resident != 0);
+    if (!plan.shape_ok) return false;
+    if (resident && !plan.att_resident) continue;          // the shape has no memory-resident form
+    if (persist_fits(decode_persist_kernel, PK_DECODE_FWD, plan.grid, plan.shm)) return true;
   }
   return false;
 }
-bool decode_persist_ok(int N, int Tc, int S, int E, int H, int A) {
-  int grid, res; size_t shm;
-  return decode_fwd_plan(N, Tc, S, E, H, A, grid, shm, res);
-}
-long decode_persist_counter_words(int Tc) { return ((long)PD_C_COUNT * Tc + 1 + 3) & ~3L; }
-
-int decode_persist_fwd(PdParams p, hipStream_t st, int flags) {
-  int grid; size_t shm;
-  if (!decode_fwd_plan(p.N, p.Tc, p.S, p.E, p.H, p.A, grid, shm, p.att_resident)) return ACVAE_EUNSUPPORTED;
-  p.n_d1 = p.A / 32 + 3 * p.H / 32;
-  p.n_d3 = p.H / 16;
-  p.n_p1 = p.E / 8;
-  p.n_p2 = p.E / 16;
-  const long words = decode_persist_counter_words(p.Tc);
-  p.abort_word = p.cnt + (long)PD_C_COUNT * p.Tc;
-  persist_test_stall(flags, grid, p.spin_limit);
+int decode_persist_fwd(PdParams p, const PdPlan& plan, hipStream_t st, int flags) {
+  if (!plan.shape_ok) return ACVAE_EUNSUPPORTED;
+  p.N = plan.N; p.Tc = plan.Tc; p.S = plan.S; p.E = plan.E; p.H = plan.H; p.A = plan.A;
+  p.n_d1 = plan.n_d1; p.n_d3 = plan.n_d3; p.n_p1 = plan.n_p1; p.n_p2 = plan.n_p2;
+  p.att_resident = plan.att_resident;
   const long R = (long)p.N * p.Tc;
   PoisonList poison;
   poison.add(p.outputs, R * p.H); poison.add(p.p_means, R * p.E); poison.add(p.p_logs, R * p.E);
   poison.add(p.p_z, R * p.E); poison.add(p.attn_w, R * p.S);
-  return persist_launch(decode_persist_kernel, PK_DECODE_FWD, p, grid, shm, words, poison, st, (flags & ACVAE_FLAG_INT_CNT_ZEROED) != 0);
+  return persist_launch(decode_persist_kernel, PK_DECODE_FWD, p, plan, poison, st, flags);
 }
 
 // ---- decode backward
-static size_t decode_bwd_shm(int S, int A) {
-  size_t shm = sizeof(PbSmem);
-  const size_t att = (size_t)(4 + 128 + 512 + 512 + (long)(S < 64 ? S : 64) * A) * sizeof(float);   // 64 frames per attention workgroup
-  return att > shm ? att : shm;
+bool decode_bwd_resident(const PbPlan& plan) {
+  return plan.shape_ok && persist_fits(decode_persist_bwd_kernel, PK_DECODE_BWD, plan.grid, plan.shm);
 }
-int decode_persist_bwd_rc_splits(int S) { return (S + 63) / 64; }
-static void decode_bwd_splits(int E, int H, int& ks_rb, int& ks_pa) {
-  // K-splits: one resident batch (K <= 512) per workgroup where the K of the product divides that way, at most 4
-  ks_rb = (3 * H) % 512 == 0 && 3 * H / 512 <= 4 ? 3 * H / 512 : 1;
-  ks_pa = E == 512 ? 2 : 1;               // K = 4Hp = 2048 = 2 x 1024 and 2E = 1024: the shapes the split products are written for
-}
-bool decode_persist_bwd_ok(int N, int Tc, int S, int E, int H, int A) {
-  // an attention workgroup keeps 64 frames in 2 x 32 register slots and its channels in 512 thread columns; a clip takes up to
-  // three of them (S <= 192: BASELINE configs[3] has 187)
-  if (!(decode_fwd_shape_ok(N, Tc, S, E, H, A) && S <= 192 && E <= 512 && A <= 512 && H % 32 == 0 && H == E &&
-        decode_bwd_shm(S, A) <= 150 * 1024))
-    return false;
-  int ks_rb, ks_pa;
-  decode_bwd_splits(E, H, ks_rb, ks_pa);
-  const int grid = H / 32 + (E / 32) * ks_rb + N * decode_persist_bwd_rc_splits(S) + (E / 16) * ks_pa + E / 32;
-  return persist_fits(decode_persist_bwd_kernel, PK_DECODE_BWD, grid, decode_bwd_shm(S, A));
-}
-long decode_persist_bwd_counter_words(int Tc) { return ((long)PB_C_COUNT * Tc + 1 + 3) & ~3L; }
-long decode_persist_bwd_part_floats(int N, int E, int H) { return 4L * N * E + 4L * N * E + 4L * N * 2 * E; }
-
-int decode_persist_bwd(PbParams p, hipStream_t st, int flags) {
-  if (!decode_persist_bwd_ok(p.N, p.Tc, p.S, p.E, p.H, p.A)) return ACVAE_EUNSUPPORTED;
-  decode_bwd_splits(p.E, p.H, p.ks_rb, p.ks_pa);
-  p.n_ra = p.H / 32; p.n_rb = (p.E / 32) * p.ks_rb; p.n_pa = (p.E / 16) * p.ks_pa; p.n_pb = p.E / 32;
-  p.rc_splits = decode_persist_bwd_rc_splits(p.S);
+int decode_persist_bwd(PbParams p, const PbPlan& plan, hipStream_t st, int flags) {
+  if (!plan.shape_ok) return ACVAE_EUNSUPPORTED;
+  p.N = plan.N; p.Tc = plan.Tc; p.S = plan.S; p.E = plan.E; p.H = plan.H; p.A = plan.A;
+  p.n_ra = plan.n_ra; p.n_rb = plan.n_rb; p.n_pa = plan.n_pa; p.n_pb = plan.n_pb;
+  p.ks_rb = plan.ks_rb; p.ks_pa = plan.ks_pa; p.rc_splits = plan.rc_splits;
   if (p.rc_splits > 1 && (!p.dqd_part || !p.ctx)) return ACVAE_EINVAL;
-  const long words = decode_persist_bwd_counter_words(p.Tc);
-  p.abort_word = p.cnt + (long)PB_C_COUNT * p.Tc;
-  int grid = p.n_ra + p.n_rb + p.N * p.rc_splits + p.n_pa + p.n_pb;
-  persist_test_stall(flags, grid, p.spin_limit);
   const long R = (long)p.N * p.Tc;
   PoisonList poison;
   poison.add(p.dgi, R * 3 * p.H); poison.add(p.dgh, R * 3 * p.H); poison.add(p.dgates, R * 4 * p.E);
   poison.add(p.dml_all, R * 2 * p.E); poison.add(p.dctx, R * p.E); poison.add(p.dqd, R * p.A);
   poison.add(p.dencproj, (long)p.N * p.S * p.A);
-  ACVAE_TRY(persist_launch(decode_persist_bwd_kernel, PK_DECODE_BWD, p, grid, decode_bwd_shm(p.S, p.A), words, poison, st,
-                           (flags & ACVAE_FLAG_INT_CNT_ZEROED) != 0));
+  ACVAE_TRY(persist_launch(decode_persist_bwd_kernel, PK_DECODE_BWD, p, plan, poison, st, flags));
   // (dctx poisoned = NaN in dmem: attn_dmem_kernel forms it from dctx behind the tail)
   hipLaunchKernelGGL(attn_dmem_kernel, dim3(p.N * p.S), dim3(256), 0, st, p.attn_w, p.dctx, p.dmem, p.Tc, p.S, p.E);
   ACVAE_LAUNCH_CHECK();
@@ -1506,35 +1471,25 @@ int decode_persist_bwd(PbParams p, hipStream_t st, int flags) {
 }
 
 // ---- posterior
-bool posterior_persist_ok(int N, int Tc, int Hq) {
-  // one 32-row tile of clips; 32 hidden units per workgroup; a wavefront's share of K = Hq is one resident batch
-  if (!(N >= 1 && N <= 32 && Tc >= 1 && Hq >= 32 && Hq <= 64 * PD_U && Hq % 32 == 0)) return false;
-  return persist_fits(posterior_persist_fwd_kernel, PK_POST_FWD, 2 * (Hq / 32), sizeof(PqSmem)) &&
-         persist_fits(posterior_persist_bwd_kernel, PK_POST_BWD, 2 * (Hq / 32), sizeof(PqSmem));
+bool posterior_resident(const PqPlan& plan) {
+  return plan.shape_ok && persist_fits(posterior_persist_fwd_kernel, PK_POST_FWD, plan.grid, plan.shm) &&
+         persist_fits(posterior_persist_bwd_kernel, PK_POST_BWD, plan.grid, plan.shm);
 }
-long posterior_persist_counter_words(int Tc) { return (2L * Tc + 1 + 3) & ~3L; }
-
-int posterior_persist_fwd(PqParams p, hipStream_t st, int flags) {
-  if (!posterior_persist_ok(p.N, p.Tc, p.Hq)) return ACVAE_EUNSUPPORTED;
-  p.abort_word = p.cnt + 2L * p.Tc;
-  int grid = 2 * (p.Hq / 32);
-  persist_test_stall(flags, grid, p.spin_limit);
+int posterior_persist_fwd(PqParams p, const PqPlan& plan, hipStream_t st, int flags) {
+  if (!plan.shape_ok) return ACVAE_EUNSUPPORTED;
+  p.N = plan.N; p.Tc = plan.Tc; p.Hq = plan.Hq;
   PoisonList poison;
   poison.add(p.hid, (long)p.N * p.Tc * 2 * p.Hq);
-  return persist_launch(posterior_persist_fwd_kernel, PK_POST_FWD, p, grid, sizeof(PqSmem), posterior_persist_counter_words(p.Tc),
-                        poison, st, (flags & ACVAE_FLAG_INT_CNT_ZEROED) != 0);
+  return persist_launch(posterior_persist_fwd_kernel, PK_POST_FWD, p, plan, poison, st, flags);
 }
-int posterior_persist_bwd(PqbParams p, hipStream_t st, int flags) {
-  if (!posterior_persist_ok(p.N, p.Tc, p.Hq)) return ACVAE_EUNSUPPORTED;
-  p.abort_word = p.cnt + 2L * p.Tc;
-  int grid = 2 * (p.Hq / 32);
-  persist_test_stall(flags, grid, p.spin_limit);
+int posterior_persist_bwd(PqbParams p, const PqPlan& plan, hipStream_t st, int flags) {
+  if (!plan.shape_ok) return ACVAE_EUNSUPPORTED;
+  p.N = plan.N; p.Tc = plan.Tc; p.Hq = plan.Hq;
   PoisonList poison;
   for (int dir = 0; dir < 2; ++dir) {
     poison.add(p.dgi[dir], (long)p.N * p.Tc * 3 * p.Hq);
     poison.add(p.dgh[dir], (long)p.N * p.Tc * 3 * p.Hq);
   }
-  return persist_launch(posterior_persist_bwd_kernel, PK_POST_BWD, p, grid, sizeof(PqSmem), posterior_persist_counter_words(p.Tc),
-                        poison, st, (flags & ACVAE_FLAG_INT_CNT_ZEROED) != 0);
+  return persist_launch(posterior_persist_bwd_kernel, PK_POST_BWD, p, plan, poison, st, flags);
 }
 }  // namespace acvae

@@ -110,7 +110,7 @@ struct PostLayout {
   // scratch
   long gi_f, gi_r, gh, hf, ml, dml, dhid, dgi_f, dgi_r, dgh_f, dgh_r, dh_a, dh_b, dx, wt, wt2, wt_ih0, wt_ih1, wt_ml, pq_hbuf, pq_cnt, tn, dpart, skws,
        dhid2, wtu_hh0, wtu_hh1, wtu_ih0, wtu_ih1, scratch_total;
-  long tn_floats, dpart_doubles, pq_cnt_words;
+  long tn_floats, dpart_doubles;
 };
 int post_layout(int N, int Tc, int E, int Hq, int V, int NL, PostLayout& L) {
   if (N <= 0 || Tc <= 0 || E <= 0 || Hq <= 0 || V <= 0 || NL < 1 || NL > POST_MAX_LAYERS) return ACVAE_EINVAL;
@@ -139,9 +139,9 @@ int post_layout(int N, int Tc, int E, int Hq, int V, int NL, PostLayout& L) {
   L.wt2 = c.take((long)3 * Hq * Hq);                        // persistent BPTT: both directions' transposed weight_hh at once
   // the backward's other transposed weights (round 4: all five transposes of the call in one launch in front of it)
   L.wt_ih0 = c.take((long)3 * Hq * E); L.wt_ih1 = c.take((long)3 * Hq * E); L.wt_ml = c.take((long)2 * E * 2 * Hq);
-  L.pq_hbuf = c.take((long)NL * 4 * N * Hq);                // persistent forward: h in flight, [layer][direction][parity][N][Hq]
-  L.pq_cnt_words = acvae::posterior_persist_counter_words(Tc);
-  L.pq_cnt = c.take(NL * L.pq_cnt_words);                   // one set of arrival counters per layer, all zeroed at the entry
+  const acvae::PqPlan pq = acvae::posterior_plan(N, Tc, Hq);   // the persistent launches: sizes only, whatever the device says
+  L.pq_hbuf = c.take(NL * pq.hbuf_floats);                  // forward: h in flight, per layer
+  L.pq_cnt = c.take(NL * pq.counter_words);                 // one set of arrival counters per layer, all zeroed at the entry
   long tn = tn_ws_floats(2 * E, 2 * Hq, (int)R);
   long t2 = tn_ws_floats(3 * Hq, E, (int)R); if (t2 > tn) tn = t2;
   t2 = tn_ws_floats(3 * Hq, Hq, (int)R); if (t2 > tn) tn = t2;
@@ -209,7 +209,7 @@ int dec_layout(int N, int Tc, int S, int E, int H, int A, int V, int Eenc, DecLa
   L.skws_p = f.take(acvae_skinny_ws_floats());
   L.gi_d = f.take(R * 3 * H); L.gh_d = f.take((long)N * 3 * H); L.gates_p = f.take(R * 4 * Hp);
   L.ml = f.take((long)N * 2 * E); L.h0 = f.take((long)N * (H > Hp ? H : Hp));
-  L.pd_cnt = f.take(acvae::decode_persist_counter_words(Tc));      // arrival counters of the persistent decode loop
+  L.pd_cnt = f.take(acvae::decode_fwd_plan(N, Tc, S, E, H, A, false).counter_words);   // arrival counters of the persistent decode loop
   // per-step path: workspaces of the split-over-frames attention, one per chain (the chains may run on two streams)
   L.attfws_bytes = acvae_attn_fwd_workspace_bytes(N, 1, S, A, E);
   { const long w2 = acvae_attn_fwd_workspace_bytes(N, 1, S, E, E); if (w2 > L.attfws_bytes) L.attfws_bytes = w2; }
@@ -221,7 +221,8 @@ int dec_layout(int N, int Tc, int S, int E, int H, int A, int V, int Eenc, DecLa
   L.wt_ln = b.take((long)Eenc * E);
   L.d_out = b.take(R * H); L.dgi = b.take(R * 3 * H); L.dgh = b.take(R * 3 * H); L.dqd = b.take(R * A);
   L.dencproj = b.take((long)N * S * (A > E ? A : E));
-  L.dvpart = b.take((long)3 * N * (A > E ? A : E));             // up to three frame shares per clip (persistent BPTT, S > 64)
+  const acvae::PbPlan pb = acvae::decode_bwd_plan(N, Tc, S, E, H, A);   // the persistent BPTT: sizes only, whatever the device says
+  L.dvpart = b.take((long)pb.dv_rows_max * (A > E ? A : E));    // one row per clip and frame share of its attention role
   L.dctx = b.take((long)N * E); L.dh_a = b.take((long)N * H); L.dh_b = b.take((long)N * H);
   L.dgates = b.take(R * 4 * Hp); L.dml_all = b.take(R * 2 * E); L.dml = b.take((long)N * 2 * E);
   L.dhp_a = b.take((long)N * Hp); L.dhp_b = b.take((long)N * Hp); L.dc_a = b.take((long)N * Hp);
@@ -263,9 +264,9 @@ int dec_layout(int N, int Tc, int S, int E, int H, int A, int V, int Eenc, DecLa
     int w = V; if (4 * Hp > w) w = 4 * Hp; if (3 * H > w) w = 3 * H; if (2 * E > w) w = 2 * E; if (A > w) w = A;
     L.dpart_p = b.take(2 * acvae::colsum_scratch_doubles(w));
   }
-  L.pd_cnt_b = b.take(acvae::decode_persist_bwd_counter_words(Tc));   // arrival counters of the persistent BPTT launch
-  L.pd_part = b.take(acvae::decode_persist_bwd_part_floats(N, E, H));  // its K-split partial tiles
-  L.pd_dqd = b.take(S > 64 && S <= 192 ? (long)acvae::decode_persist_bwd_rc_splits(S) * R * A : 0);   // d qd shares of the split attention role
+  L.pd_cnt_b = b.take(pb.counter_words);      // arrival counters of the persistent BPTT launch
+  L.pd_part = b.take(pb.part_floats);         // its K-split partial tiles
+  L.pd_dqd = b.take(pb.dqd_part_floats);      // d qd shares of the split attention role
   L.scratch_bwd = b.off;
   return ACVAE_OK;
 }
@@ -319,13 +320,14 @@ extern "C" int acvae_posterior_stack_fwd(const void* const* params, const void* 
   float* sv = (float*)saved_v;
   float* sc = (float*)scratch_v;
   Ctx st{(hipStream_t)stream, sc + L.skws};
-  const bool persist_q = !(flags & ACVAE_FLAG_NO_PERSIST) && acvae::posterior_persist_ok(N, Tc, Hq);
+  const acvae::PqPlan pq_plan = acvae::posterior_plan(N, Tc, Hq);       // one plan for all layers
+  const bool persist_q = !(flags & ACVAE_FLAG_NO_PERSIST) && acvae::posterior_resident(pq_plan);
   {
     acvae::ZeroBatch zb;
     zb_skinny(zb, st.skws);
     if (persist_q) {
-      zb.add(sc + L.pq_cnt, num_layers * L.pq_cnt_words);
-      zb.add(sc + L.pq_hbuf, (long)num_layers * 4 * N * Hq);
+      zb.add(sc + L.pq_cnt, num_layers * pq_plan.counter_words);
+      zb.add(sc + L.pq_hbuf, num_layers * pq_plan.hbuf_floats);
       flags |= ACVAE_FLAG_INT_CNT_ZEROED;
     }
     ACVAE_TRY(acvae::zero_batch(zb, st.s));
@@ -352,10 +354,9 @@ extern "C" int acvae_posterior_stack_fwd(const void* const* params, const void* 
         pq.save[dir] = sv + (dir ? L.save_r[layer] : L.save_f[layer]);
         pq.hprev[dir] = sv + (dir ? L.hprev_r[layer] : L.hprev_f[layer]);
       }
-      pq.lens1 = lens1; pq.hid = hid; pq.hbuf = sc + L.pq_hbuf + (long)layer * 4 * N * Hq;
-      pq.cnt = (unsigned*)(sc + L.pq_cnt + layer * L.pq_cnt_words);
-      pq.N = N; pq.Tc = Tc; pq.Hq = Hq;
-      ACVAE_TRY(acvae::posterior_persist_fwd(pq, st.s, flags));          // hbuf and the counters: zeroed at the entry
+      pq.lens1 = lens1; pq.hid = hid; pq.hbuf = sc + L.pq_hbuf + layer * pq_plan.hbuf_floats;
+      pq.cnt = (unsigned*)(sc + L.pq_cnt + layer * pq_plan.counter_words);
+      ACVAE_TRY(acvae::posterior_persist_fwd(pq, pq_plan, st.s, flags));          // hbuf and the counters: zeroed at the entry
     } else
     for (int dir = 0; dir < 2; ++dir) {
       float* gi = sc + (dir ? L.gi_r : L.gi_f);
@@ -416,11 +417,12 @@ extern "C" int acvae_posterior_stack_bwd(const void* const* params, void* const*
   const int R = N * Tc;
   TnWs tn{sc + L.tn, L.tn_floats * 4};
   double* dpart = (double*)(sc + L.dpart);
-  const bool persist = !(flags & ACVAE_FLAG_NO_PERSIST) && acvae::posterior_persist_ok(N, Tc, Hq);
+  const acvae::PqPlan pq_plan = acvae::posterior_plan(N, Tc, Hq);       // one plan for all layers
+  const bool persist = !(flags & ACVAE_FLAG_NO_PERSIST) && acvae::posterior_resident(pq_plan);
   {
     acvae::ZeroBatch zb;
     zb_skinny(zb, st.skws); zb_colsum(zb, dpart); zb_tn(zb, tn);
-    if (persist) { zb.add(sc + L.pq_cnt, num_layers * L.pq_cnt_words); flags |= ACVAE_FLAG_INT_CNT_ZEROED; }
+    if (persist) { zb.add(sc + L.pq_cnt, num_layers * pq_plan.counter_words); flags |= ACVAE_FLAG_INT_CNT_ZEROED; }
     zb.add(G(TP_Q_EMB), (long)V * E);          // the embedding-table gradient starts from zero (embed_scatter adds rows)
     ACVAE_TRY(acvae::zero_batch(zb, st.s));
   }
@@ -480,9 +482,8 @@ extern "C" int acvae_posterior_stack_bwd(const void* const* params, void* const*
       pb.dgi[dir] = sc + (dir ? L.dgi_r : L.dgi_f);
       pb.dgh[dir] = sc + (dir ? L.dgh_r : L.dgh_f);
     }
-    pb.dhid = dhid; pb.lens1 = lens1; pb.cnt = (unsigned*)(sc + L.pq_cnt + layer * L.pq_cnt_words);
-    pb.N = N; pb.Tc = Tc; pb.Hq = Hq;
-    return acvae::posterior_persist_bwd(pb, st.s, flags);
+    pb.dhid = dhid; pb.lens1 = lens1; pb.cnt = (unsigned*)(sc + L.pq_cnt + layer * pq_plan.counter_words);
+    return acvae::posterior_persist_bwd(pb, pq_plan, st.s, flags);
   };
   // the upper layers, top-down: BPTT, their parameter products, and dX = dgi_f . W_ih_f + dgi_r . W_ih_r through the
   // inter-layer dropout into the gradient of the output of the layer below (the other half of the dhid ping-pong)
@@ -637,14 +638,15 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
   Ctx sp{fork.aux, sc + L.skws_p};
   // the step-by-step paths may use the split-over-frames attention: its arrival counters start at zero (ordered in front of
   // the fork); the persistent launch has its own attention
+  acvae::PdPlan pd_plan{};                 // (filled, and resident on this device, when persist_fwd)
   const bool persist_fwd = teacher && !prior_feeds_decoder && !(flags & ACVAE_FLAG_NO_PERSIST) && H == E &&
-                           acvae::decode_persist_ok(N, Tc, S, E, H, A);
+                           acvae::decode_fwd_resident(N, Tc, S, E, H, A, pd_plan);
   const bool attws_ready = !persist_fwd && L.attfws_bytes > 0;
   {   // every ticket / counter of the call in one launch, in front of the fork
     acvae::ZeroBatch zb;
     zb_skinny(zb, st.skws); zb_skinny(zb, sp.skws);
     if (attws_ready) { zb.add(sc + L.attfws_d, 256); zb.add(sc + L.attfws_p, 256); }
-    if (persist_fwd) { zb.add(sc + L.pd_cnt, acvae::decode_persist_counter_words(Tc)); flags |= ACVAE_FLAG_INT_CNT_ZEROED; }
+    if (persist_fwd) { zb.add(sc + L.pd_cnt, pd_plan.counter_words); flags |= ACVAE_FLAG_INT_CNT_ZEROED; }
     // h_{-1} of both chains: read by the first step on either stream, so it is zeroed here, in front of the fork
     zb.add(sc + L.h0, (long)N * (H > Hp ? H : Hp));
     ACVAE_TRY(acvae::zero_batch(zb, st.s));
@@ -825,8 +827,7 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
       pd.hprev_d = sv + L.hprev_d; pd.rnn_p = rnn_p; pd.hp_all = sv + L.hp_all; pd.c_all = sv + L.c_all;
       pd.lstm_save = sv + L.lstm_save; pd.p_means = p_means; pd.p_logs = p_logs; pd.p_z = p_z;
       pd.cnt = (unsigned*)(sc + L.pd_cnt);
-      pd.N = N; pd.Tc = Tc; pd.S = S; pd.E = E; pd.H = H; pd.A = A;
-      ACVAE_TRY(acvae::decode_persist_fwd(pd, st.s, flags));
+      ACVAE_TRY(acvae::decode_persist_fwd(pd, pd_plan, st.s, flags));
     } else {                              // independent chains: feed both queues step by step
       ACVAE_TRY(dec_pre(0, Tc));
       for (int t = 0; t < Tc; ++t) {
@@ -929,13 +930,14 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
   TnWs tn_p{sc + L.tn_p, L.tn_p_floats * 4};
   double* dpart = (double*)(sc + L.dpart);
   double* dpart_p = (double*)(sc + L.dpart_p);
-  const bool persist_bwd = !prior_feeds_decoder && !(flags & ACVAE_FLAG_NO_PERSIST) && acvae::decode_persist_bwd_ok(N, Tc, S, E, H, A);
+  const acvae::PbPlan pb_plan = acvae::decode_bwd_plan(N, Tc, S, E, H, A);
+  const bool persist_bwd = !prior_feeds_decoder && !(flags & ACVAE_FLAG_NO_PERSIST) && acvae::decode_bwd_resident(pb_plan);
   {   // in front of the fork: both chains' tickets (skinny split-K, column sums, gemm_tn tiles), the persistent launch's arrival
       // counters and the prior attention's memory gradient - one launch instead of eight memsets
     acvae::ZeroBatch zb;
     zb_skinny(zb, st.skws); zb_skinny(zb, sp.skws); zb_colsum(zb, dpart); zb_colsum(zb, dpart_p); zb_tn(zb, tn); zb_tn(zb, tn_p);
     if (persist_bwd) {
-      zb.add(sc + L.pd_cnt_b, acvae::decode_persist_bwd_counter_words(Tc));
+      zb.add(sc + L.pd_cnt_b, pb_plan.counter_words);
       zb.add(sc + L.dmem_p, (long)N * S * E);
       flags |= ACVAE_FLAG_INT_CNT_ZEROED;
     }
@@ -1202,12 +1204,12 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     pb.d_out = d_out; pb.d_p_z = d_p_z; pb.d_p_means = d_p_means; pb.d_p_logs = d_p_logs;
     pb.dgi = dgi; pb.dgh = dgh; pb.dqd = dqd; pb.dctx = drnn;      // [N, Tc, E] slots in the (later) d rnn_input buffer
     pb.dencproj = dencproj; pb.dmem = dmem; pb.dvpart = dvpart; pb.dgates = dgates; pb.dml_all = dml_all; pb.dhp = dhp;
-    pb.dctx_part = sc + L.pd_part; pb.dhp_part = pb.dctx_part + 4L * N * E; pb.dml_part = pb.dhp_part + 4L * N * E;
+    float* part = sc + L.pd_part;
+    pb.dctx_part = part + pb_plan.dctx_part_off; pb.dhp_part = part + pb_plan.dhp_part_off; pb.dml_part = part + pb_plan.dml_part_off;
     pb.cnt = (unsigned*)(sc + L.pd_cnt_b);
     pb.dqd_part = sc + L.pd_dqd; pb.ctx = rnn_d + E;
-    pb.N = N; pb.Tc = Tc; pb.S = S; pb.E = E; pb.H = H; pb.A = A;
-    ACVAE_TRY(acvae::decode_persist_bwd(pb, st.s, flags));
-    dv_rows = N * acvae::decode_persist_bwd_rc_splits(S);
+    ACVAE_TRY(acvae::decode_persist_bwd(pb, pb_plan, st.s, flags));
+    dv_rows = pb_plan.dv_rows;
     ACVAE_TRY(dec_memgrad());
     if (fork.on()) ACVAE_TRY(Fork::edge(st.s, sp.s));     // the prior's batched work reads what the launch wrote
     ACVAE_TRY(prior_memgrad());

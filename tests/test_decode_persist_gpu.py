@@ -88,6 +88,35 @@ def test_persistent_decode_is_bit_identical_to_the_per_step_path(B, T, V, E, L):
     assert bool(torch.isfinite(ref_out["logits"]).all())
 
 
+def test_plans_and_the_cached_fit_follow_the_shape_from_call_to_call():
+    """One process, one model, three training steps whose clips are 1024, 1056 and 1024 frames long: S = 64 (the attention keeps
+    its memory on the CU: 148 KB of LDS; one backward attention share per clip), S = 66 (streamed attention: 37 KB; two shares
+    per clip, their d qd parts in use), S = 64 again.  The launchers keep the occupancy calculator's answer per kernel AND LDS
+    size and take grid, LDS, counters and scratch from the plan of each call (csrc/persist_plan.h): an answer or a plan carried
+    over from the call before would launch the wrong grid or the wrong attention form."""
+    V, E, B, L = 50, 512, 2, 5
+    model = build(V, E)
+    g = torch.Generator().manual_seed(1)
+    eps_q = torch.randn(B, L - 1, E, generator=g); eps_p = torch.randn(L - 1, B, E, generator=g)
+    for T in (1024, 1056, 1024):
+        feats, caps, fl, cl = batch(B, T, V, L, seed=B + T)
+        f = feats.cuda()
+        ref_out, ref_grads = run(model, V, E, f, caps, fl, cl, eps_q, eps_p, persist=False)
+        out, grads = run(model, V, E, f, caps, fl, cl, eps_q, eps_p, persist=True)
+        assert ref_out["attn_weights"].shape[1] == T // 16            # [N, S, Tc]
+        for k in ref_out:
+            a, b = ref_out[k], out[k]
+            if isinstance(a, (tuple, list)):
+                a, b = torch.cat([x.reshape(-1) for x in a]), torch.cat([x.reshape(-1) for x in b])
+            assert torch.equal(a, b), (T, k, float((a.double() - b.double()).abs().max()))
+        assert set(grads) == set(ref_grads)
+        for k in ref_grads:
+            a, b = ref_grads[k].double(), grads[k].double()
+            tol = 2e-5 * float(a.abs().max()) + 1e-9
+            assert float((a - b).abs().max()) <= tol, (T, k, float((a - b).abs().max()), float(a.abs().max()))
+    _lib.check_persist_status("cuda")
+
+
 def test_persistent_decode_under_a_busy_gpu():
     """Uneven load: a long convolution-heavy stream runs beside the decode (the posterior and the encoder of the NEXT batch
     on another stream in a real step); the hand-offs must not depend on timing or placement."""
