@@ -10,6 +10,8 @@ from typing import List
 import numpy as np
 import torch
 
+from .frontend import refuse_augmented
+
 
 def _pad_stack(seqs):
     """Zero-pad tensors that differ in their first dimension into one float32 [n, max...] tensor (captions therefore
@@ -109,6 +111,7 @@ def forward_batch_shared_encoder(model, batch, device=None, frontend=None, **kwa
     BatchNorm statistics, no dropout) the encoder output of a replica equals that of its clip bit for bit, so the
     replicas share it and only the decode loop sees N rows per clip.  Same outputs as ``forward_batch(mode="eval")``
     with the clip-major replication; ``batch[0]`` is replaced by the replicated keys likewise."""
+    refuse_augmented(frontend, "forward_batch_shared_encoder")
     n = kwargs["beam_size"]
     assert not model.training and n > 1 and kwargs["method"] != "dbs"
     device = device if device is not None else next(model.parameters()).device
@@ -132,8 +135,11 @@ def forward_batch(model, batch, mode, device=None, augment=None, clip_index=None
     ``clip_index=batch[-3]``: the training forward then runs the encoder once per clip.  ``frontend``
     (``acvae_amd.frontend.LogMel``): the batch holds waveforms and sample counts where it otherwise holds features and
     frame counts; both slots are replaced by the log-mel features formed on the device and their frame counts before
-    anything else runs.  Not together with an augmentation (ValueError)."""
+    anything else runs.  Not together with an augmentation (ValueError); in training mode an
+    ``acvae_amd.frontend.Augmented`` front end augments such a batch, in the other modes it is refused (ValueError)."""
     assert mode in ("train", "validation", "eval")
+    if mode != "train":
+        refuse_augmented(frontend, f"forward_batch(mode={mode!r})")
     device = device if device is not None else next(model.parameters()).device
     if frontend is not None:
         from . import augment as _augment

@@ -8,6 +8,11 @@
 // where the current value of a cell in region k is the fill of the latest earlier mask that covers it, else the rolled
 // input.  Every pass reads only `in`, never what the kernel wrote.  Sums are fp64 in a fixed order (per-thread strided
 // partials, butterfly, then waves in order): bit-reproducible run to run.
+//
+// acvae_augment_window is the same body with a crop in front: the clip the rolls and masks see is a chain of (circular)
+// windows cut out of a longer input clip, as Augment.draw_shape planned them.  Only the row a cell is read from changes:
+// every pass walks the cells of the OUTPUT clip in the order spec_augment_kernel walks them, so the sums - and with them
+// the fills - are bit for bit those of acvae_spec_augment run on the host-cropped clip.
 #include "common.h"
 #include "../../include/acvae_hip.h"
 
@@ -41,6 +46,26 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // Input row of output row i under the roll by s (0 <= i < L, 0 <= s < L).
 __device__ __forceinline__ int src_row(int i, int s, int L) { return i >= s ? i - s : i - s + L; }
 
+// The crops of one clip, last first: row j of the clip behind a window is row (j + add) mod len of the clip in front of
+// it, add = (start - shift) mod len.  j < len holds at every step (each window is no longer than the clip it is cut
+// from), so one conditional subtraction is the modulo.  Unused steps are add = 0, len = INT32_MAX: no-ops; a clip
+// without crops (n == 0, the same for the whole workgroup) skips them.
+struct Windows {
+  int add[ACVAE_AUG_MAX_WINDOWS], len[ACVAE_AUG_MAX_WINDOWS];
+  int n;
+};
+template <bool WIN>
+__device__ __forceinline__ int win_row(int j, const Windows& W) {
+  if (WIN && W.n > 0) {
+#pragma unroll
+    for (int w = 0; w < ACVAE_AUG_MAX_WINDOWS; ++w) {
+      j += W.add[w];
+      if (j >= W.len[w]) j -= W.len[w];
+    }
+  }
+  return j;
+}
+
 // Latest time mask with index < kend that covers row i, or -1.  A fixed-length loop without early exit: its LDS reads
 // issue together instead of one dependent read per mask.
 __device__ __forceinline__ int time_cover(const Masks& M, int i, int kend) {
@@ -51,22 +76,45 @@ __device__ __forceinline__ int time_cover(const Masks& M, int i, int kend) {
   return best;
 }
 
-__global__ __launch_bounds__(TH) void spec_augment_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                          const int* __restrict__ lens, const int* __restrict__ params,
-                                                          int T, int F) {
+// The body of both kernels.  WIN = false: acvae_spec_augment (`lens` the clips' lengths, To == T, rows >= L copied).
+// WIN = true: acvae_augment_window (`lens` the lengths of the input clips, rows of K = ACVAE_AUG_WINDOW_TABLE_WIDTH
+// entries, the output clip To rows long, rows >= L zeros).
+template <bool WIN>
+__device__ __forceinline__ void augment_body(const float* __restrict__ in, float* __restrict__ out,
+                                             const int* __restrict__ lens, const int* __restrict__ params, int T, int To,
+                                             int F) {
   __shared__ Masks M;
   __shared__ double red[NW];
   __shared__ double S;
   __shared__ int L_s, shift_s;
+  __shared__ Windows W_s;
   const int n = blockIdx.x;
   const int F4 = F >> 2;
   const long base = (long)n * T * F;
   const float4* in4 = reinterpret_cast<const float4*>(in + base);
-  float4* out4 = reinterpret_cast<float4*>(out + base);
+  float4* out4 = reinterpret_cast<float4*>(out + (WIN ? (long)n * To * F : base));
 
   if (threadIdx.x == 0) {
-    const int* row = params + (long)n * ACVAE_AUG_TABLE_WIDTH;
-    const int L = clampi(lens[n], 0, T);
+    const int* row = params + (long)n * (WIN ? ACVAE_AUG_WINDOW_TABLE_WIDTH : ACVAE_AUG_TABLE_WIDTH);
+    int L = clampi(lens[n], 0, T);
+    if (WIN) {                                   // the crops: each length clamped into [1, the size in front of it]
+      const int* win = row + ACVAE_AUG_TABLE_WIDTH + 2;
+      const int nw = L > 0 ? clampi(row[ACVAE_AUG_TABLE_WIDTH + 1], 0, ACVAE_AUG_MAX_WINDOWS) : 0;
+      for (int w = 0; w < ACVAE_AUG_MAX_WINDOWS; ++w) {
+        const int k = nw - 1 - w;                // stored last window first, the order win_row applies them in
+        int add = 0, len = INT32_MAX;
+        if (w < nw) {
+          len = L = clampi(win[3 * w + 2], 1, L);
+          add = (clampi(win[3 * w], 0, len - 1) - win[3 * w + 1] % len) % len;
+          if (add < 0) add += len;
+          W_s.add[k] = add; W_s.len[k] = len;
+        } else {
+          W_s.add[w] = add; W_s.len[w] = len;
+        }
+      }
+      W_s.n = nw;
+      L = clampi(row[ACVAE_AUG_TABLE_WIDTH], 0, L < To ? L : To);
+    }
     int s = 0;
     if (L > 0) {
       s = row[0] % L;
@@ -91,6 +139,11 @@ __global__ __launch_bounds__(TH) void spec_augment_kernel(const float* __restric
   __syncthreads();
   const int L = L_s, s = shift_s, nm = M.m, nt = M.nt;
   const int n4 = L * F4;            // in-clip indices are int: T * F < 2^31
+  Windows W;
+  if (WIN) {
+    W = W_s;
+    W.n = __builtin_amdgcn_readfirstlane(W.n);
+  }
 
   if (nm > 0) {
     // pass 1: the clip's sum (the roll does not change it)
@@ -99,8 +152,8 @@ __global__ __launch_bounds__(TH) void spec_augment_kernel(const float* __restric
       float4 v[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {                  // loads first, from in-bounds addresses: U in flight per lane
-        const int q = q0 + u * TH;
-        v[u] = in4[q < n4 ? q : q0];
+        const int q = q0 + u * TH < n4 ? q0 + u * TH : q0;
+        v[u] = in4[WIN && W.n > 0 ? win_row<WIN>(q / F4, W) * F4 + q % F4 : q];
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
@@ -125,7 +178,7 @@ __global__ __launch_bounds__(TH) void spec_augment_kernel(const float* __restric
           for (int u = 0; u < U; ++u) {
             const int q = q0 + u * TH < cnt ? q0 + u * TH : q0;
             i[u] = r0 + q / F4;
-            v[u] = in4[src_row(i[u], s, L) * F4 + q % F4];
+            v[u] = in4[win_row<WIN>(src_row(i[u], s, L), W) * F4 + q % F4];
           }
 #pragma unroll
           for (int u = 0; u < U; ++u) {
@@ -150,7 +203,7 @@ __global__ __launch_bounds__(TH) void spec_augment_kernel(const float* __restric
             const int q = q0 + u * TH < cnt ? q0 + u * TH : q0;
             i[u] = r0 + q / w;
             j[u] = c0 + q % w;
-            v[u] = inr[src_row(i[u], s, L) * F + j[u]];
+            v[u] = inr[win_row<WIN>(src_row(i[u], s, L), W) * F + j[u]];
           }
 #pragma unroll
           for (int u = 0; u < U; ++u) {
@@ -180,7 +233,7 @@ __global__ __launch_bounds__(TH) void spec_augment_kernel(const float* __restric
     for (int u = 0; u < U; ++u) {
       const int q = q0 + u * TH < n4 ? q0 + u * TH : q0;
       row[u] = q / F4;
-      v[u] = in4[src_row(row[u], s, L) * F4 + q % F4];
+      v[u] = in4[win_row<WIN>(src_row(row[u], s, L), W) * F4 + q % F4];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -200,6 +253,11 @@ __global__ __launch_bounds__(TH) void spec_augment_kernel(const float* __restric
       out4[q] = v[u];
     }
   }
+  if (WIN) {                         // rows >= L of the output clip: zeros, what collate_fn pads with
+    const int t4 = To * F4;
+    for (int q = n4 + threadIdx.x; q < t4; q += TH) out4[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
   // rows >= L: copied unchanged
   const int t4 = T * F4;
   for (int q0 = n4 + threadIdx.x; q0 < t4; q0 += U * TH) {
@@ -216,6 +274,18 @@ __global__ __launch_bounds__(TH) void spec_augment_kernel(const float* __restric
     }
   }
 }
+
+__global__ __launch_bounds__(TH) void spec_augment_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                          const int* __restrict__ lens, const int* __restrict__ params,
+                                                          int T, int F) {
+  augment_body<false>(in, out, lens, params, T, T, F);
+}
+
+__global__ __launch_bounds__(TH) void augment_window_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                            const int* __restrict__ src_lens,
+                                                            const int* __restrict__ table, int T, int To, int F) {
+  augment_body<true>(in, out, src_lens, table, T, To, F);
+}
 }  // namespace
 
 extern "C" int acvae_spec_augment(const float* in, float* out, const int* lens, const int* params, int N, int T, int F,
@@ -225,6 +295,17 @@ extern "C" int acvae_spec_augment(const float* in, float* out, const int* lens, 
     return ACVAE_EINVAL;
   if (!aligned16(in) || !aligned16(out)) return ACVAE_EALIGN;
   hipLaunchKernelGGL(spec_augment_kernel, dim3(N), dim3(TH), 0, (hipStream_t)stream, in, out, lens, params, T, F);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_augment_window(const float* in, float* out, const int* src_lens, const int* table, int N, int T,
+                                    int To, int F, int K, void* stream) {
+  if (!in || !out || !src_lens || !table || N <= 0 || T <= 0 || To <= 0 || To > T || F <= 0 || (F & 3) != 0 ||
+      F > ACVAE_AUG_MAX_F || (int64_t)T * F > INT32_MAX || K != ACVAE_AUG_WINDOW_TABLE_WIDTH)
+    return ACVAE_EINVAL;
+  if (!aligned16(in) || !aligned16(out)) return ACVAE_EALIGN;
+  hipLaunchKernelGGL(augment_window_kernel, dim3(N), dim3(TH), 0, (hipStream_t)stream, in, out, src_lens, table, T, To, F);
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }

@@ -28,6 +28,7 @@ from . import _lib
 from .batch import collate_fn
 from .encoder import ptr_table, scratch_buffer
 from .evaluate import collect_predictions, predictions_payload
+from .frontend import refuse_augmented
 from .seq_train_model import ScstWrapper
 from .vae_model import Hybrid_VAEModel
 
@@ -121,6 +122,7 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
     reference's two-column CSV (``file_name``, ``caption_predicted``).  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are
     ``(audio_id, 1-D waveform)`` and the log-mel features are formed on the device, once for all members.  Returns the payload
     dict; scoring stays outside."""
+    refuse_augmented(frontend, "ensemble_evaluate")
     ens = models_or_ensemble if isinstance(models_or_ensemble, Ensemble) else Ensemble(models_or_ensemble)
     device = next(ens.parameters()).device
     collate = collate_fn([1, ])

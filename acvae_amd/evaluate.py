@@ -17,6 +17,7 @@ from pathlib import Path
 import torch
 
 from .batch import collate_fn, forward_batch, forward_batch_shared_encoder
+from .frontend import refuse_augmented
 
 
 class Vocabulary(object):
@@ -109,6 +110,7 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
     clip), ``max_length``.  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
     or int16 PCM (``acvae_amd.frontend.read_wav``); the log-mel features are formed on the device in front of either
     forward path.  Returns the payload dict."""
+    refuse_augmented(frontend, "evaluate")
     kwargs.setdefault("method", "greedy")
     kwargs.setdefault("beam_size", 1)
     collate = collate_fn([1, ])

@@ -28,8 +28,11 @@ crossings and ``c = rolloff * min(1, U / D)``:
     rolloff = 0.85, beta = 8.555504641634386`` (the settings librosa / resampy publish under these names).
 
 This is the closed form: resampy's interpolated table and soxr are not reproduced bit for bit.  Not supported: clips of
-different rates in one batch, a gradient through the resampler, the resampler fused into the log-mel kernel's gather, and
-``frontend=`` together with ``augment=``.
+different rates in one batch, a gradient through the resampler, and the resampler fused into the log-mel kernel's gather.
+
+Training-time augmentation of such batches: ``Augmented(frontend, augment)`` / ``fe.augmented(augment)``, a front end for
+the training calls that draws the config's ``augments`` per batch and applies them on the device
+(``acvae_amd.augment.apply_plans``).  ``frontend=`` together with ``augment=`` stays refused.
 """
 import math
 import wave as _wave
@@ -101,6 +104,10 @@ class LogMel:
         if rate == self.sample_rate:
             return self
         return Resampled(Resample(rate, self.sample_rate, **resample_args), self)
+
+    def augmented(self, augment):
+        """``Augmented(self, augment)``: this front end with the training-time augmentation behind it."""
+        return Augmented(self, augment)
 
     def n_frames(self, L):
         """Frames of a clip (or an array of clips) of ``L`` samples: ``1 + L // hop_length``."""
@@ -374,6 +381,8 @@ class Resampled:
         self.resample, self.logmel = resample, logmel
         self.sample_rate = resample.orig_rate
 
+    augmented = LogMel.augmented
+
     def n_frames(self, L):
         """Frames of a clip (or an array of clips) of ``L`` samples at the input rate."""
         return self.logmel.n_frames(self.resample.out_len(L))
@@ -396,6 +405,43 @@ class Resampled:
         waves, lens = self.check(waves, wave_lens)
         mid, mid_lens = self.resample(waves, lens, device=device)
         return self.logmel(mid, mid_lens, spectrogram=spectrogram)
+
+
+class Augmented:
+    """``Augmented(frontend, augment)``: waveforms -> features with the training-time augmentation of ``augment``
+    (``acvae_amd.augment.Augment``, e.g. ``parse_augments(config["augments"])``) applied, a front end wherever ``frontend=``
+    goes in training (``TrainStep.step`` / ``forward_loss``, ``forward_batch(mode="train")``).  The inner front end runs,
+    the host draws ``augment.draw_shape(L_n, F)`` for the clips in batch order while the GPU works (every draw depends on
+    the clip's shape alone, and ``L_n`` is known from the sample count), and ``apply_plans`` crops, rolls and masks on the
+    same stream.  The lengths returned are those after the crop; ``last_plans`` keeps the plans of the latest batch.
+    The draws are the reference's, made per batch at step time instead of per item in loader workers.  Evaluation never
+    augments: the evaluation calls refuse an ``Augmented``."""
+
+    def __init__(self, frontend, augment):
+        if isinstance(frontend, Augmented):
+            raise ValueError("the front end is already augmented")
+        if not hasattr(augment, "draw_shape"):
+            raise ValueError(f"augment must be an acvae_amd.augment.Augment, got {type(augment).__name__}")
+        self.frontend, self.augment = frontend, augment
+        self.sample_rate = frontend.sample_rate
+        self.last_plans = None
+
+    def check(self, waves, wave_lens):
+        return self.frontend.check(waves, wave_lens)
+
+    def to_float(self, wave):
+        return self.frontend.to_float(wave)
+
+    def __call__(self, waves, wave_lens, spectrogram=False, device=None):
+        """As ``LogMel.__call__``; ``feat_lens`` are the clips' lengths after the crop and the batch is as long as the
+        longest of them.  ``spectrogram=True`` raises ValueError: the power spectrogram is not augmented."""
+        if spectrogram:
+            raise ValueError("an Augmented front end returns no spectrogram (the augmentation acts on the features)")
+        from . import augment as _augment
+        feats, lens = self.frontend(waves, wave_lens, device=device)
+        F = feats.shape[2]
+        self.last_plans = plans = [self.augment.draw_shape(int(L), F) for L in lens]
+        return _augment.apply_plans(feats, lens, plans)
 
 
 def read_wav_any(path):
@@ -431,4 +477,9 @@ def read_wav(path, sample_rate):
 def refuse_augment(augment):
     if augment is not None:
         raise ValueError("frontend= together with augment=: the augment records are drawn per frame on host features; "
-                         "drawing them for waveforms is not supported yet")
+                         "to augment a batch of waveforms hand the step frontend=fe.augmented(...) instead")
+
+
+def refuse_augmented(frontend, where):
+    if isinstance(frontend, Augmented):
+        raise ValueError(f"{where}: evaluation never augments, hand it the plain front end (frontend.frontend)")

@@ -358,7 +358,7 @@ class TrainStep:
         ``frontend`` (``acvae_amd.frontend.LogMel``): ``feats`` / ``feat_lens`` are waveforms ``[B, Lmax]`` (fp32 or int16 PCM,
         on the host or uploaded by ``prefetch``) and their sample counts; the log-mel features are formed on the step's
         stream in front of the encoder, with no gradient through them.  Not together with ``augment`` (ValueError: the
-        augment records are drawn per frame on host features)."""
+        augment records are drawn per frame on host features); ``frontend=fe.augmented(...)`` augments such a batch."""
         if frontend is not None:                    # first: a refused call touches nothing of the step's state
             from .frontend import refuse_augment
             refuse_augment(augment)

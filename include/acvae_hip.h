@@ -685,6 +685,27 @@ int acvae_sgd_step(float* params, const float* grads, float* momentum_buffer, in
 int acvae_spec_augment(const float* in, float* out, const int* lens, const int* params, int N, int T, int F, int K,
                        void* stream);
 
+/* The same with datasets/augment.py:random_crop in front, for clips that exist only on the device (features formed there
+ * from waveforms): `in` [N, T, F] holds the uncropped clips of src_lens[n] rows, `out` [N, To, F] (To <= T, never
+ * aliasing `in`) the cropped, rolled and masked ones.  `table` is int32 [N, K], K = ACVAE_AUG_WINDOW_TABLE_WIDTH, one
+ * row per clip:
+ *   [the ACVAE_AUG_TABLE_WIDTH columns above, out_len, n_windows, (start, shift, length) x ACVAE_AUG_MAX_WINDOWS]
+ * The windows are the crops that fired, in the order they were applied: `length` is the clip's length in front of the
+ * crop, `shift` the roll pending in front of it, and the crop keeps rows [start, start + size) of the rolled clip
+ * (circularly), `size` being the next window's `length`, or out_len behind the last one.  Row i < out_len of the clip the
+ * first ACVAE_AUG_TABLE_WIDTH columns apply to is input row j, from j = i and, for the windows from last to first,
+ * j = (start + j - shift) mod length; the roll and the masks then act on that clip of L = out_len rows exactly as above:
+ * the same arithmetic in the same order, so the result equals acvae_spec_augment on the host-cropped clip bit for bit.
+ * Rows >= out_len of `out` are written as zeros, which is what collate_fn pads with.  Each window's length is clamped
+ * into [1, the size in front of it], start into the window's clip, out_len into [0, min(last size, To)]: a bad table
+ * cannot reach outside the clip.  One workgroup per clip, no workspace.  N <= 0, T <= 0, To <= 0, To > T, F % 4 != 0,
+ * F > ACVAE_AUG_MAX_F, T * F > INT32_MAX, a NULL pointer or K != ACVAE_AUG_WINDOW_TABLE_WIDTH -> ACVAE_EINVAL before any
+ * HIP call; `in` / `out` not 16-B aligned -> ACVAE_EALIGN. */
+#define ACVAE_AUG_MAX_WINDOWS 4
+#define ACVAE_AUG_WINDOW_TABLE_WIDTH 49 /* ACVAE_AUG_TABLE_WIDTH + 2 + 3 * ACVAE_AUG_MAX_WINDOWS */
+int acvae_augment_window(const float* in, float* out, const int* src_lens, const int* table, int N, int T, int To, int F,
+                         int K, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Log-mel front end: waveforms -> the [T, n_mels] features every encoder of the package starts from (the PANNs front end,
  * models/encoder.py:877-885: torchlibrosa's Spectrogram then LogmelFilterBank), one fused kernel, no workspace.
