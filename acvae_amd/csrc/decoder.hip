@@ -594,16 +594,22 @@ extern "C" int acvae_decode_fwd(const void* const* params, const float* mem_in, 
                                   ACVAE_SAMPLE_GREEDY, 1.f, nullptr, nullptr, 0.f, flags);
 }
 
-extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* mem_in, const int64_t* mem_lens,
-                                        const int64_t* caps, int64_t ld_caps, const int64_t* lens1, const float* q_z,
-                                        const float* eps_p, const int* ss_flags_host, const int* dis_flags_host,
-                                        float* logits, float* outputs, int64_t* seqs, float* sampled_logprobs,
-                                        float* attn_w, float* p_means, float* p_logs, float* p_z, float* p_means_utt,
-                                        float* h_final, float* hp_final, float* cp_final, void* saved_v,
-                                        int64_t saved_bytes, void* scratch_v, int64_t scratch_bytes, int N, int Tc, int S,
-                                        int E, int H, int A, int V, int Eenc, int start_idx, int end_idx, void* stream,
-                                        void* aux_stream, int sample_method, float temp, const float* sample_noise,
-                                        const uint8_t* emb_keep, float emb_drop_p, int flags) {
+// The decode forward behind acvae_decode_fwd_sampled (top_k = 0, top_p = 1, kept = NULL: the untruncated kernel, and
+// nothing else differs) and acvae_decode_fwd_truncated.
+static int decode_fwd_driver(const void* const* params, const float* mem_in, const int64_t* mem_lens,
+                             const int64_t* caps, int64_t ld_caps, const int64_t* lens1, const float* q_z,
+                             const float* eps_p, const int* ss_flags_host, const int* dis_flags_host,
+                             float* logits, float* outputs, int64_t* seqs, float* sampled_logprobs,
+                             float* attn_w, float* p_means, float* p_logs, float* p_z, float* p_means_utt,
+                             float* h_final, float* hp_final, float* cp_final, void* saved_v,
+                             int64_t saved_bytes, void* scratch_v, int64_t scratch_bytes, int N, int Tc, int S,
+                             int E, int H, int A, int V, int Eenc, int start_idx, int end_idx, void* stream,
+                             void* aux_stream, int sample_method, float temp, const float* sample_noise,
+                             const uint8_t* emb_keep, float emb_drop_p, int flags, int top_k, float top_p,
+                             int32_t* kept) {
+  if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) return ACVAE_EINVAL;          // (a NaN top_p fails both comparisons)
+  const bool truncate = top_k > 0 || top_p < 1.f;
+  if (truncate && (sample_method == ACVAE_SAMPLE_GREEDY || (flags & ACVAE_FLAG_ROLLOUT_GRAD))) return ACVAE_EINVAL;
   if (emb_keep && !(emb_drop_p > 0.f && emb_drop_p <= 1.f)) return ACVAE_EINVAL;   // p = 1: nn.Dropout zeroes everything
   if (sample_method != ACVAE_SAMPLE_GREEDY &&
       ((sample_method != ACVAE_SAMPLE_GUMBEL && sample_method != ACVAE_SAMPLE_MULTINOMIAL) || !sample_noise ||
@@ -793,7 +799,11 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
                    ldof(cnt, V), M, V, H, 0, st));
     ACVAE_TRY(acvae_row_logsoftmax_argmax(logits + (long)t0 * V, (long)Tc * V, V, seqs + t0, sampled_logprobs + t0,
                                           lse + t0, Tc, 1, N, cnt, V, st));
-    if (sample_method != ACVAE_SAMPLE_GREEDY)      // word_model.py:188-203 overwrite the greedy choice
+    if (truncate)                                  // the same draw over the top-k / nucleus prefix of each row
+      ACVAE_TRY(acvae_sample_next_word_truncated(logits + (long)t0 * V, (long)Tc * V, V, sample_noise + (long)t0 * N * V,
+                                                 V, (long)N * V, sample_method, temp, seqs + t0, sampled_logprobs + t0,
+                                                 Tc, 1, N, cnt, V, top_k, top_p, kept ? kept + t0 : nullptr, st));
+    else if (sample_method != ACVAE_SAMPLE_GREEDY) // word_model.py:188-203 overwrite the greedy choice
       ACVAE_TRY(acvae_sample_next_word(logits + (long)t0 * V, (long)Tc * V, V, sample_noise + (long)t0 * N * V, V,
                                        (long)N * V, sample_method, temp, seqs + t0, sampled_logprobs + t0, Tc, 1, N, cnt,
                                        V, st));
@@ -868,6 +878,41 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
     ACVAE_TRY(gemm(hidp, H, P(TP_MLO_W), H, P(TP_MLO_B), p_means_utt, 2 * E, N, 2 * E, H, 0, st));
   }
   return ACVAE_OK;
+}
+
+extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* mem_in, const int64_t* mem_lens,
+                                        const int64_t* caps, int64_t ld_caps, const int64_t* lens1, const float* q_z,
+                                        const float* eps_p, const int* ss_flags_host, const int* dis_flags_host,
+                                        float* logits, float* outputs, int64_t* seqs, float* sampled_logprobs,
+                                        float* attn_w, float* p_means, float* p_logs, float* p_z, float* p_means_utt,
+                                        float* h_final, float* hp_final, float* cp_final, void* saved_v,
+                                        int64_t saved_bytes, void* scratch_v, int64_t scratch_bytes, int N, int Tc, int S,
+                                        int E, int H, int A, int V, int Eenc, int start_idx, int end_idx, void* stream,
+                                        void* aux_stream, int sample_method, float temp, const float* sample_noise,
+                                        const uint8_t* emb_keep, float emb_drop_p, int flags) {
+  return decode_fwd_driver(params, mem_in, mem_lens, caps, ld_caps, lens1, q_z, eps_p, ss_flags_host, dis_flags_host, logits,
+                           outputs, seqs, sampled_logprobs, attn_w, p_means, p_logs, p_z, p_means_utt, h_final, hp_final,
+                           cp_final, saved_v, saved_bytes, scratch_v, scratch_bytes, N, Tc, S, E, H, A, V, Eenc, start_idx,
+                           end_idx, stream, aux_stream, sample_method, temp, sample_noise, emb_keep, emb_drop_p, flags, 0,
+                           1.f, nullptr);
+}
+
+extern "C" int acvae_decode_fwd_truncated(const void* const* params, const float* mem_in, const int64_t* mem_lens,
+                                          const int64_t* caps, int64_t ld_caps, const int64_t* lens1, const float* q_z,
+                                          const float* eps_p, const int* ss_flags_host, const int* dis_flags_host,
+                                          float* logits, float* outputs, int64_t* seqs, float* sampled_logprobs,
+                                          float* attn_w, float* p_means, float* p_logs, float* p_z, float* p_means_utt,
+                                          float* h_final, float* hp_final, float* cp_final, void* saved_v,
+                                          int64_t saved_bytes, void* scratch_v, int64_t scratch_bytes, int N, int Tc,
+                                          int S, int E, int H, int A, int V, int Eenc, int start_idx, int end_idx,
+                                          void* stream, void* aux_stream, int sample_method, float temp,
+                                          const float* sample_noise, const uint8_t* emb_keep, float emb_drop_p, int flags,
+                                          int top_k, float top_p, int32_t* kept) {
+  return decode_fwd_driver(params, mem_in, mem_lens, caps, ld_caps, lens1, q_z, eps_p, ss_flags_host, dis_flags_host, logits,
+                           outputs, seqs, sampled_logprobs, attn_w, p_means, p_logs, p_z, p_means_utt, h_final, hp_final,
+                           cp_final, saved_v, saved_bytes, scratch_v, scratch_bytes, N, Tc, S, E, H, A, V, Eenc, start_idx,
+                           end_idx, stream, aux_stream, sample_method, temp, sample_noise, emb_keep, emb_drop_p, flags,
+                           top_k, top_p, kept);
 }
 
 extern "C" int acvae_decode_bwd_defers(const int* dis_flags_host, int Tc, void* stream, void* aux_stream, int flags) {

@@ -223,6 +223,195 @@ __global__ __launch_bounds__(EW_THREADS) void sample_rows_kernel(const float* __
   }
 }
 
+// ------------------------------------------------------------------ sample_next_word, truncated: top-k and nucleus (top-p)
+// The same draw over a prefix of the row's words in the order (logit descending, equal logits by lower index): the first
+// min(top_k, V) of them (top_k > 0) and those whose preceding mass is < top_p of the total (top_p < 1; rank 0 always), the
+// shorter prefix when both are given.  The mass is that of the distribution the method samples from: softmax(x / temp)
+// for method 2; softmax(x) for method 1, whose temp divides every score alike and moves no argmax.  The noise is the
+// untruncated kernel's (one value per word, kept or not), the score is its score, the winner its first-index argmax
+// over the kept words; logprob stays log_softmax(x)[w] of the full row.
+//
+// The cut is a key c and an index i: kept = {key > c} + {key == c, index <= i}; `key` is the logit's bits mapped to an
+// unsigned integer of the same order (-0 as +0).  Neither sort nor atomics: c is the smallest 32-bit value at which
+// "the words with a larger key are fewer than k and their mass is < top_p * Z" still holds - 32 probes from the top bit
+// down, each one block-wide count and one block-wide sum.  Every sum, Z included, is formed in one fixed order: a lane's
+// words in stride order, a butterfly over each row of 16 lanes, the four rows of a wavefront in sequence, the wavefronts
+// in sequence.  A sum of non-negative terms in a fixed order is monotone in the set summed, so the probes bisect.  Where
+// several words share the key c, i is found the same way among them, over the bits of V - 1.
+// No loop runs until something converges: the trip counts are 32 and bits(V - 1), and the second loop is skipped on a
+// workgroup-uniform integer count - a row with a NaN walks through the same probes (its word is unspecified, and clamped
+// into the row as the untruncated kernel's is).  One barrier per probe: the partials alternate between two LDS slots, and
+// a wavefront reaches a slot's next use only behind a barrier that every reader of this use has passed.  The counts are
+// popcounts of the lanes' votes (scalar unit), the sums stay on the vector unit (DPP, readlane): no LDS traffic but the
+// four partials of a probe.
+//
+// VPT > 0: the row lives in registers - key, mass and score of VPT words per lane, row and noise read once - for
+// V <= VPT * 256 (4: V <= 1024; 20: the vocabulary of 5000; 32: V <= TRUNC_REG_V = 8192).  VPT == 0, above that: every
+// probe re-reads the row (from L2) and re-forms key and mass from it; the arithmetic, and so every result, is the same.
+// Resources (hipcc's remarks) for VPT 4 / 20 / 32 / 0: 34 / 114 / 151 / 32 VGPRs; 192 B of LDS and no scratch in each.
+#define TRUNC_REG_V (32 * EW_THREADS)
+__device__ __forceinline__ unsigned trunc_key(float v) {
+  const unsigned u = v == 0.f ? 0u : __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float lane_of(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+__device__ __forceinline__ int votes(bool p) { return __popcll(__ballot(p)); }   // of the wavefront's active lanes
+template <int VPT>
+__global__ __launch_bounds__(EW_THREADS) void sample_trunc_rows_kernel(
+    const float* __restrict__ logits, long ld_n, long ld_t, const float* __restrict__ noise, long nz_sn, long nz_st,
+    int method, float temp, int top_k, float top_p, int64_t* __restrict__ w_out, float* __restrict__ lp_out,
+    int* __restrict__ kept_out, long o_sn, long o_st, int T, int V) {
+  constexpr bool REG = VPT > 0;
+  constexpr int NR = REG ? VPT : 1;
+  __shared__ float red[16];
+  __shared__ int redi[16];
+  __shared__ float pf[2][EW_THREADS / 64];
+  __shared__ int pi[2][EW_THREADS / 64];
+  const int n = blockIdx.x / T, t = blockIdx.x % T;
+  const float* x = logits + n * ld_n + t * ld_t;
+  const float* z = noise + n * nz_sn + t * nz_st;
+  const int tid = threadIdx.x;
+  const float te = method == 1 ? 1.f : temp;      // the temperature of the distribution sampled from
+  // m, s and ls exactly as sample_rows_kernel forms them
+  [[maybe_unused]] float xr[NR];
+  float m = -INFINITY;
+  if constexpr (REG) {
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+      const int c = tid + i * EW_THREADS;
+      xr[i] = c < V ? x[c] : -INFINITY;
+      m = fmaxf(m, xr[i]);
+    }
+  } else {
+    for (int c = tid; c < V; c += EW_THREADS) m = fmaxf(m, x[c]);
+  }
+  m = block_max(m, red);
+  float s = 0.f;
+  if constexpr (REG) {
+#pragma unroll
+    for (int i = 0; i < VPT; ++i)
+      if (tid + i * EW_THREADS < V) s += expf(xr[i] - m);
+  } else {
+    for (int c = tid; c < V; c += EW_THREADS) s += expf(x[c] - m);
+  }
+  s = block_sum(s, red);
+  const float ls = logf(s);
+  auto score = [&](float xv, float zv) {
+    const float lp = (xv - m) - ls;
+    return method == 1 ? (lp + zv) / temp : expf(lp / temp) / zv;
+  };
+  // slots past the row: key 0 and mass 0 - never above a probe, and behind every index a probe asks about
+  [[maybe_unused]] unsigned key[NR];
+  [[maybe_unused]] float e[NR], sc[NR];
+  if constexpr (REG) {
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+      const int c = tid + i * EW_THREADS;
+      const bool in = c < V;
+      key[i] = in ? trunc_key(xr[i]) : 0u;
+      e[i] = in ? expf((xr[i] - m) / te) : 0.f;
+      sc[i] = in ? score(xr[i], z[c]) : 0.f;
+    }
+  }
+  // count and mass of the words `pred(key, index)` holds for
+  int par = 0;
+  auto probe = [&](auto pred, int& cnt, float& mass) {
+    int cn = 0;                        // (wavefront-uniform)
+    float ms = 0.f;
+    if constexpr (REG) {
+#pragma unroll
+      for (int i = 0; i < VPT; ++i) {
+        const bool in = pred(key[i], tid + i * EW_THREADS);
+        cn += votes(in);
+        ms += in ? e[i] : 0.f;
+      }
+    } else {
+      for (int c = tid; c < V; c += EW_THREADS) {
+        const float xv = x[c];
+        const bool in = pred(trunc_key(xv), c);
+        cn += votes(in);
+        ms += in ? expf((xv - m) / te) : 0.f;
+      }
+    }
+    ms = row16_sum(ms);
+    float wm = lane_of(ms, 0);
+    wm += lane_of(ms, 16);
+    wm += lane_of(ms, 32);
+    wm += lane_of(ms, 48);
+    if ((tid & 63) == 0) { pf[par][tid >> 6] = wm; pi[par][tid >> 6] = cn; }
+    __syncthreads();
+    cnt = 0; mass = 0.f;
+    for (int i = 0; i < EW_THREADS / 64; ++i) { cnt += pi[par][i]; mass += pf[par][i]; }
+    par ^= 1;
+  };
+  const int k_eff = top_k > 0 && top_k < V ? top_k : V;
+  const bool p_on = top_p < 1.f;
+  unsigned cut = 0u;
+  int cut_i = 0x7fffffff;              // truncation off: everything is kept
+  if (k_eff < V || p_on) {
+    int cnt; float mass, pz = 0.f;
+    if (p_on) {
+      probe([](unsigned, int) { return true; }, cnt, mass);
+      pz = top_p * mass;
+    }
+    auto holds = [&]() { return cnt < k_eff && (!p_on || mass < pz || cnt == 0); };
+    cut = 0xffffffffu;
+    for (int b = 31; b >= 0; --b) {
+      const unsigned tc = cut & ~(1u << b);
+      probe([tc](unsigned k, int) { return k > tc; }, cnt, mass);
+      if (holds()) cut = tc;
+    }
+    probe([cut](unsigned k, int) { return k == cut; }, cnt, mass);
+    if (cnt > 1) {                      // (uniform) several words at the cut: the lowest indices first
+      cut_i = 0;
+      for (int b = 31 - __clz((V - 1) | 1); b >= 0; --b) {
+        const int ti = cut_i | (1 << b);
+        if (ti >= V) continue;          // (uniform)
+        probe([cut, ti](unsigned k, int c) { return k > cut || (k == cut && c < ti); }, cnt, mass);
+        if (holds()) cut_i = ti;
+      }
+    }
+  }
+  float best = -INFINITY;
+  int bi = 0x7fffffff, nk = 0;         // (nk: wavefront-uniform)
+  auto take = [&](unsigned k, int c, float v) {
+    const bool in = k > cut || (k == cut && c <= cut_i);
+    nk += votes(in);
+    if (in && (v > best || bi == 0x7fffffff)) { best = v; bi = c; }   // strict '>': first maximum within the stride
+  };
+  if constexpr (REG) {
+#pragma unroll
+    for (int i = 0; i < VPT; ++i)
+      if (tid + i * EW_THREADS < V) take(key[i], tid + i * EW_THREADS, sc[i]);
+  } else {
+    for (int c = tid; c < V; c += EW_THREADS) take(trunc_key(x[c]), c, score(x[c], z[c]));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+  __syncthreads();
+  const int w = tid >> 6;
+  if ((tid & 63) == 0) { red[w] = best; redi[w] = bi; pi[0][w] = nk; }
+  __syncthreads();
+  if (tid == 0) {
+    best = red[0]; bi = redi[0]; nk = pi[0][0];
+    for (int i = 1; i < EW_THREADS / 64; ++i) {
+      if (red[i] > best || (red[i] == best && redi[i] < bi)) { best = red[i]; bi = redi[i]; }
+      nk += pi[0][i];
+    }
+    if (bi < 0 || bi >= V) bi = 0;                        // every kept score NaN, or a NaN row's empty cut
+    const long o = n * o_sn + t * o_st;
+    w_out[o] = bi;
+    if (lp_out) lp_out[o] = (x[bi] - m) - ls;
+    if (kept_out) kept_out[o] = nk;
+  }
+}
+
 // ------------------------------------------------------------------ label-smoothed CE
 // loss_row = -[(1-s) * lp_tgt + s/(V-1) * (sum_c lp_c - lp_tgt)],  lp_c = x_c - lse.
 __global__ __launch_bounds__(EW_THREADS) void ce_rows_kernel(const float* __restrict__ logits, long ld_n, long ld_t,
@@ -611,6 +800,25 @@ extern "C" int acvae_sample_next_word(const float* logits, int64_t ld_n, int64_t
   if ((method != ACVAE_SAMPLE_GUMBEL && method != ACVAE_SAMPLE_MULTINOMIAL) || !(temp > 0.f)) return ACVAE_EINVAL;
   hipLaunchKernelGGL(sample_rows_kernel, dim3(N * T), dim3(EW_THREADS), 0, (hipStream_t)stream, logits, ld_n, ld_t, noise,
                      nz_sn, nz_st, method, temp, w_out, logprob_out, o_sn, o_st, T, V);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_sample_next_word_truncated(const float* logits, int64_t ld_n, int64_t ld_t, const float* noise,
+                                                int64_t nz_sn, int64_t nz_st, int method, float temp, int64_t* w_out,
+                                                float* logprob_out, int64_t o_sn, int64_t o_st, int N, int T, int V,
+                                                int top_k, float top_p, int32_t* kept_out, void* stream) {
+  if (!logits || !noise || !w_out || N <= 0 || T <= 0 || V <= 0) return ACVAE_EINVAL;
+  if ((method != ACVAE_SAMPLE_GUMBEL && method != ACVAE_SAMPLE_MULTINOMIAL) || !(temp > 0.f)) return ACVAE_EINVAL;
+  if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) return ACVAE_EINVAL;      // (a NaN top_p fails both comparisons)
+#define ACVAE_TRUNC_LAUNCH(VPT)                                                                                        \
+  hipLaunchKernelGGL(sample_trunc_rows_kernel<VPT>, dim3(N * T), dim3(EW_THREADS), 0, (hipStream_t)stream, logits, ld_n, \
+                     ld_t, noise, nz_sn, nz_st, method, temp, top_k, top_p, w_out, logprob_out, kept_out, o_sn, o_st, T, V)
+  if (V <= 4 * EW_THREADS) ACVAE_TRUNC_LAUNCH(4);
+  else if (V <= 20 * EW_THREADS) ACVAE_TRUNC_LAUNCH(20);
+  else if (V <= TRUNC_REG_V) ACVAE_TRUNC_LAUNCH(32);
+  else ACVAE_TRUNC_LAUNCH(0);
+#undef ACVAE_TRUNC_LAUNCH
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }

@@ -107,7 +107,11 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
     ``items``: iterable of ``(audio_id, feature [T, F] tensor)`` in the order of the reference's ``CaptionEvalDataset``;
     they are batched with ``collate_fn([1])`` exactly as its DataLoader does.  ``kwargs`` go to the model as in
     ``evaluate(**kwargs)`` there: ``method`` ("greedy" | "beam" | "dbs"), ``beam_size`` (with "greedy": z-samples per
-    clip), ``max_length``.  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
+    clip), ``max_length``.  Sampled decoding, which the reference's evaluation does not offer: ``method="sample"`` (or
+    ``"gumbel"``) with ``temp``, ``rng`` ("host" | "device") and the truncation keywords ``top_k`` (the k most probable
+    words of each step, 0 = off) and ``top_p`` (the nucleus of that mass, 1.0 = off), e.g. ``method="sample", beam_size=5,
+    top_p=0.9, rng="device"`` for five sampled captions per clip; ``top_k`` / ``top_p`` with any other method are a
+    ValueError (``Hybrid_VAEModel._truncation``).  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
     or int16 PCM (``acvae_amd.frontend.read_wav``); the log-mel features are formed on the device in front of either
     forward path.  Returns the payload dict."""
     refuse_augmented(frontend, "evaluate")

@@ -59,12 +59,16 @@ class _DecodeFn(torch.autograd.Function):
         keep, drop_p = sampling["emb_keep"] if sampling and sampling.get("emb_keep") else (None, 0.0)
         # a rollout whose graph is recorded (self-critical training): the call keeps what acvae_decode_bwd reads
         rollout = bool(not train and sampling and sampling.get("rollout_grad"))
+        # top-k / nucleus truncation of the sampled steps: its own entry, and the size of every kept prefix beside the words
+        truncate = sampling.get("truncate") if sampling else None
+        kept = torch.empty(N, Tc, dtype=torch.int32, device=dev) if truncate else None
         _lib.persist_status(dev)                 # the device's status words are registered before the first persistent launch
-        _lib.call("acvae_decode_fwd_sampled", ptr_table(params), mem, mem_lens_d, caps_d,
-                  caps_d.stride(0) if train else 0, lens1_d, q_z, eps_p, ss_arr, dis_arr, logits, outputs, seqs, slp,
-                  attw, pm, pl, pz, putt, hfin, hp, cp, saved, saved_b, scratch, scratch_b, *dims, model.start_idx,
+        _lib.call("acvae_decode_fwd_truncated" if truncate else "acvae_decode_fwd_sampled", ptr_table(params), mem,
+                  mem_lens_d, caps_d, caps_d.stride(0) if train else 0, lens1_d, q_z, eps_p, ss_arr, dis_arr, logits,
+                  outputs, seqs, slp, attw, pm, pl, pz, putt, hfin, hp, cp, saved, saved_b, scratch, scratch_b, *dims, model.start_idx,
                   model.end_idx, _lib.current_stream(), model._aux_stream(), int(method), float(temp), noise, keep,
-                  float(drop_p), _lib.call_flags() | (_lib.FLAG_ROLLOUT_GRAD if rollout else 0))
+                  float(drop_p), _lib.call_flags() | (_lib.FLAG_ROLLOUT_GRAD if rollout else 0),
+                  *((int(truncate[0]), float(truncate[1]), kept) if truncate else ()))
         ctx.set_materialize_grads(False)         # outputs the loss does not use (outputs, p_z, ..) arrive as None, not as zero tensors
         ctx.model, ctx.saved, ctx.dims, ctx.dis_arr = model, saved, dims, dis_arr
         ctx.emb_keep, ctx.emb_p, ctx.rollout = keep, float(drop_p), rollout
@@ -74,6 +78,9 @@ class _DecodeFn(torch.autograd.Function):
         if not train:
             putt = torch.zeros(0, device=dev)
             ctx.mark_non_differentiable(putt)
+        if kept is not None:
+            ctx.mark_non_differentiable(kept)
+            return logits, outputs, seqs, slp, attw, pm, pl, pz, putt, hfin, hp, cp, kept
         return logits, outputs, seqs, slp, attw, pm, pl, pz, putt, hfin, hp, cp
 
     @staticmethod
@@ -430,6 +437,7 @@ class Hybrid_VAEModel(CaptionModel):
     def inference_forward(self, encoded, **kwargs):
         method = kwargs.get("method", "greedy")
         max_length = kwargs.get("max_length", self.max_length)
+        self._truncation(kwargs, rollout=True)
         if method == "beam":                                              # vae_model.py:884-886
             return self.beam_search(encoded, max_length, kwargs.get("beam_size", 3))
         if method == "dbs":                                               # vae_model.py:887-893
@@ -447,7 +455,12 @@ class Hybrid_VAEModel(CaptionModel):
         row r, in any order (``acvae_amd.batch.collate_groups`` sorts the rows by caption length).  Every output has N rows.
         The loss and every parameter gradient are those of the forward on ``feats[clip_index]``; see ``_share_rows`` for why
         and for the two departures (shared dropout masks, ``running_var``'s Bessel factor).  ``clip_rows`` says what is
-        refused (ValueError)."""
+        refused (ValueError).
+
+        ``top_k`` (default 0 = off) / ``top_p`` (default 1.0 = off) with ``method="sample"`` or ``"gumbel"``: every sampled
+        word is drawn among the ``top_k`` most probable words and / or the nucleus of mass ``top_p`` only (see
+        ``_truncation``); the output dict then also holds ``"kept"``, int32 [N, Tc], the number of words each draw chose from."""
+        self._truncation(kwargs, rollout=len(input) == 2)      # (refusals come in front of the encoder's launches)
         self._forward_token = getattr(self, "_forward_token", 0) + 1     # per-forward caches (decoder.embedding_table)
         clip_index = kwargs.pop("clip_index", None)
         if clip_index is not None and len(input) != 4:
@@ -537,6 +550,7 @@ class Hybrid_VAEModel(CaptionModel):
         repeated on the device, clip-major (row ``n * sample_n + j``), and autograd folds the rows' memory gradients back
         into the clip's.  In train() the replicas of a clip therefore share the encoder's dropout masks and the BatchNorm
         statistics are those of the clips, not of the repeated batch."""
+        self._truncation(kwargs, rollout=True)
         self._forward_token = getattr(self, "_forward_token", 0) + 1
         encoded = self.encoder(feats, feat_lens)
         n = int(sample_n)
@@ -545,6 +559,50 @@ class Hybrid_VAEModel(CaptionModel):
                "audio_embeds_pooled": encoded["audio_embeds_pooled"].repeat_interleave(n, dim=0),
                "audio_embeds_lens": lens, "state": None}
         return self.inference_forward(rep, **kwargs)
+
+    def _records_rollout(self):
+        """A 2-input forward records a graph (self-critical training) only in train() with gradients enabled and something
+        to train; every other 2-input forward is the inference path."""
+        return torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
+
+    def _truncation(self, kwargs, rollout=False):
+        """The ``top_k`` / ``top_p`` keywords of a forward -> (top_k, top_p), (0, 1.0) when both are off.
+
+        ``top_k`` (int >= 0, 0 = off) keeps the k most probable words of a step; ``top_p`` (in (0, 1], exactly 1.0 = off) keeps
+        the nucleus: the shortest prefix of the words, most probable first, whose mass reaches ``top_p``.  With both, the
+        shorter prefix.  Equal logits rank by lower index.  The mass is that of the distribution the method samples from:
+        softmax(logits / temp) for ``method="sample"``; softmax(logits) for ``"gumbel"``, where ``temp`` changes no word
+        (it divides every score alike - in the reference too).  The draw is the untruncated one restricted to the kept
+        words, on the same noise: the host's draws on the CPU generator and the device generator's counters do not depend
+        on the keywords.  ``sampled_logprobs`` stays the log-probability under the FULL distribution.
+
+        ValueError: a value out of range; truncation together with ``method="greedy"``, ``"beam"`` or ``"dbs"`` (nothing
+        is sampled there); truncation in a forward that records a differentiable rollout (``rollout``: a 2-input forward),
+        where ``sampled_logprobs`` would not be the log-probability of the distribution sampled from."""
+        top_k, top_p = kwargs.get("top_k", 0), kwargs.get("top_p", 1.0)
+        top_k = 0 if top_k is None else top_k
+        top_p = 1.0 if top_p is None else top_p
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0 or top_k > 0x7fffffff:
+            raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {top_k!r}")
+        try:
+            p32 = float(np.float32(top_p))               # the value the kernel compares with
+        except (TypeError, ValueError):
+            raise ValueError(f"top_p must be a number in (0, 1] (1.0 = off), got {top_p!r}") from None
+        if isinstance(top_p, bool) or not (0.0 < p32 <= 1.0):
+            raise ValueError(f"top_p must lie in (0, 1] (1.0 = off), got {top_p!r}")
+        top_k = int(top_k)
+        if top_k == 0 and p32 == 1.0:
+            return 0, 1.0
+        given = " / ".join(f"{n}={v!r}" for n, v, on in (("top_k", top_k, top_k > 0), ("top_p", top_p, p32 < 1.0)) if on)
+        method = kwargs.get("method", "greedy")
+        if method in ("greedy", "beam", "dbs"):
+            raise ValueError(f"{given} truncates sampled decoding (method='sample' or 'gumbel'): method={method!r} samples "
+                             "nothing")
+        if rollout and self._records_rollout():
+            raise ValueError(f"{given} in a forward that records a differentiable rollout (train() with gradients enabled): "
+                             "sampled_logprobs is the log-probability under the full distribution, not under the truncated "
+                             "one the words are drawn from; use torch.no_grad() or eval()")
+        return top_k, p32
 
     def _host_prepare(self, N, dev, caps, cap_lens, kwargs):
         """The decode loop's host-side random decisions, in the reference's per-step order (scheduled-sampling coin
@@ -570,6 +628,7 @@ class Hybrid_VAEModel(CaptionModel):
         temp = float(kwargs.get("temp", 1))
         V = self.vocab_size
         code = 0 if method == "greedy" else (1 if method == "gumbel" else 2)
+        top_k, top_p = self._truncation(kwargs, rollout=not train)
         # rng="device" (or model.sample_rng = "device") - opt-in, not the reference's stream: ONE draw on the CPU generator
         # seeds a counter-based generator on the device that fills the [Tc,N,V] noise (acvae_sample_noise); same
         # distributions, so the captions are samples of the same model, but not the words the reference would draw from
@@ -625,6 +684,8 @@ class Hybrid_VAEModel(CaptionModel):
             if sample_noise is None:
                 sample_noise = torch.as_tensor(replay["sample_noise"])[:Tc]
             sampling["sample"] = (code, temp, _lib.h2d(sample_noise, dev, torch.float32).contiguous())
+        if top_k > 0 or top_p < 1.0:
+            sampling["truncate"] = (top_k, top_p)
         if drop_p > 0.0:
             if dec_keep is None:
                 dec_keep = torch.as_tensor(replay["dec_keep"])[:Tc]
@@ -646,7 +707,7 @@ class Hybrid_VAEModel(CaptionModel):
         prep = encoded.pop("_prep", None) or self._host_prepare(N, dev, caps, cap_lens, kwargs)
         # A rollout records a graph (self-critical training: sampled_logprobs differentiable, the words constants) only in
         # train() with gradients enabled and something to train; every other 2-input forward is the inference path as before.
-        record = train or (torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()))
+        record = train or self._records_rollout()
         if record and not train:
             prep["sampling"] = dict(prep.get("sampling") or {}, rollout_grad=True)
         Tc, ss_flags, dis_flags, eps_p = prep["Tc"], prep["ss_flags"], prep["dis_flags"], prep["eps_p"]
@@ -656,10 +717,12 @@ class Hybrid_VAEModel(CaptionModel):
         with contextlib.nullcontext() if record else torch.no_grad():
             outs = _DecodeFn.apply(self, mem, mem_lens_d, caps_d, lens1_d, q_z, eps_p, ss_flags, dis_flags, Tc,
                                    prep.get("sampling"), *self._decode_weights())
-        logits, outputs, seqs, slp, attw, pm, pl, pz, putt, hfin, hp, cp = outs
+        logits, outputs, seqs, slp, attw, pm, pl, pz, putt, hfin, hp, cp = outs[:12]
         output = {"seqs": seqs, "logits": logits, "outputs": outputs, "sampled_logprobs": slp,
                   "attn_weights": attw.transpose(1, 2), "p_means": pm, "p_logs": pl, "p_z": pz,
                   "state": hfin.unsqueeze(0), "hiddens_state": (hp.unsqueeze(0), cp.unsqueeze(0)), "last_z": pz[:, -1]}
+        if len(outs) > 12:                        # top_k / top_p: the number of words every draw chose from
+            output["kept"] = outs[12]
         if train:
             for k in ("q_means", "q_logs", "q_z", "q_means_utt", "q_logs_utt"):
                 output[k] = encoded[k]

@@ -206,6 +206,29 @@ int acvae_sample_noise(float* noise, int64_t n, int method, uint64_t seed, void*
 int acvae_sample_next_word(const float* logits, int64_t ld_n, int64_t ld_t, const float* noise, int64_t nz_sn,
                            int64_t nz_st, int method, float temp, int64_t* w_out, float* logprob_out, int64_t o_sn,
                            int64_t o_st, int N, int T, int V, void* stream);
+/* The same draw restricted to a prefix of the row's words: top-k and nucleus (top-p) sampling.  No counterpart in the
+ * reference.  Per row of V logits x:
+ *   order      x descending, equal values by lower index (a stable sort on -x);
+ *   pi         the distribution the method samples from: softmax(x / temp) for ACVAE_SAMPLE_MULTINOMIAL; softmax(x) for
+ *              ACVAE_SAMPLE_GUMBEL, where `temp` divides every score (lp + g) / temp alike and so moves no argmax - in the
+ *              reference's Gumbel branch temp has no effect on the word, and it has none on the nucleus here;
+ *   top_k      >= 0, 0 = off: keep the first min(top_k, V) words of the order;
+ *   top_p      in (0, 1], exactly 1 = off: keep the word at rank r iff the mass of the ranks before it is < top_p (the
+ *              shortest prefix whose mass reaches top_p; rank 0 is always kept).  The masses are fp32 sums in a fixed
+ *              order (bit-reproducible), so against exact arithmetic the cut may sit a few words off where the prefix
+ *              mass passes top_p within ~1e-5;
+ *   both       the shorter of the two prefixes.
+ * w is the first-index argmax over the kept words of acvae_sample_next_word's score, with the same noise: one value per
+ * word of the row is consumed, kept or not, so a seeded run uses the same random stream with and without truncation.
+ * logprob_out stays log_softmax(x)[w] of the FULL row (the reference's sampled_logprobs), which is NOT the log-probability
+ * of w under the truncated distribution.  kept_out (may be NULL): int32, the size of the kept prefix, strided by
+ * o_sn / o_st as the other outputs.  With both knobs off this is acvae_sample_next_word bit for bit, and kept = V.
+ * -inf logits are words of mass 0; a row with a NaN terminates and touches nothing out of range, its word is unspecified.
+ * No workspace.  ACVAE_EINVAL for top_k < 0, top_p outside (0, 1] or NaN, and for what acvae_sample_next_word refuses. */
+int acvae_sample_next_word_truncated(const float* logits, int64_t ld_n, int64_t ld_t, const float* noise, int64_t nz_sn,
+                                     int64_t nz_st, int method, float temp, int64_t* w_out, float* logprob_out,
+                                     int64_t o_sn, int64_t o_st, int N, int T, int V, int top_k, float top_p,
+                                     int32_t* kept_out, void* stream);
 /* reduction: 0 none (writes loss_rows only), 1 mean over valid rows, 2 sum.  loss_rows [N,T] (0 at invalid rows). */
 int acvae_ls_ce_fwd(const float* logits, int64_t ld_n, int64_t ld_t, const int64_t* targets, int64_t tg_sn,
                     const int64_t* lens1, const float* lse, float smoothing, int reduction, float* loss_rows,
@@ -607,6 +630,22 @@ int acvae_decode_fwd_sampled(const void* const* params, const float* mem_in, con
                              int N, int Tc, int S, int E, int H, int A, int V, int Eenc, int start_idx, int end_idx,
                              void* stream, void* aux_stream, int sample_method, float temp, const float* sample_noise,
                              const uint8_t* emb_keep, float emb_drop_p, int flags);
+/* The same with every sampled step drawn by acvae_sample_next_word_truncated(top_k, top_p) (see there); `kept` (may be
+ * NULL): int32 [N,Tc], the size of the kept prefix of every row and step.  acvae_decode_fwd_sampled is the
+ * (0, 1.0f, NULL) case of this call: with both knobs off the untruncated kernel runs and `kept` is not written.
+ * ACVAE_EINVAL, before anything is launched: top_k < 0; top_p outside (0, 1] or NaN; truncation (top_k > 0 or
+ * top_p < 1) together with ACVAE_SAMPLE_GREEDY, or together with ACVAE_FLAG_ROLLOUT_GRAD - sampled_logprobs is the
+ * log-probability under the full distribution, not the one sampled from, so it is not what a policy gradient needs. */
+int acvae_decode_fwd_truncated(const void* const* params, const float* mem_in, const int64_t* mem_lens,
+                               const int64_t* caps, int64_t ld_caps, const int64_t* lens1, const float* q_z,
+                               const float* eps_p, const int* ss_flags_host, const int* dis_flags_host, float* logits,
+                               float* outputs, int64_t* seqs, float* sampled_logprobs, float* attn_w, float* p_means,
+                               float* p_logs, float* p_z, float* p_means_utt, float* h_final, float* hp_final,
+                               float* cp_final, void* saved, int64_t saved_bytes, void* scratch, int64_t scratch_bytes,
+                               int N, int Tc, int S, int E, int H, int A, int V, int Eenc, int start_idx, int end_idx,
+                               void* stream, void* aux_stream, int sample_method, float temp, const float* sample_noise,
+                               const uint8_t* emb_keep, float emb_drop_p, int flags, int top_k, float top_p,
+                               int32_t* kept);
 /* Backward for upstream gradients of logits / outputs / p_means / p_logs / p_z / p_means_utt (each may be
  * NULL).  Writes every decoder / pnet / mean_log_out / ln gradient, d_mem_in [N,S,Eenc] and d_q_z [N,Tc,E].
  * Stream contract: d_mem_in and d_q_z are ordered on `stream` when the call returns.  With ACVAE_FLAG_DEFER_PARAM_GRADS, when
