@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <vector>
 #include "common.h"
+#include "constrain.h"
 #include "conv.h"
 #include "rnn.h"
 #include "decode_persist.h"
@@ -595,7 +596,7 @@ extern "C" int acvae_decode_fwd(const void* const* params, const float* mem_in, 
 }
 
 // The decode forward behind acvae_decode_fwd_sampled (top_k = 0, top_p = 1, kept = NULL: the untruncated kernel, and
-// nothing else differs) and acvae_decode_fwd_truncated.
+// nothing else differs), acvae_decode_fwd_truncated (no constraint: no launch added) and acvae_decode_fwd_constrained.
 static int decode_fwd_driver(const void* const* params, const float* mem_in, const int64_t* mem_lens,
                              const int64_t* caps, int64_t ld_caps, const int64_t* lens1, const float* q_z,
                              const float* eps_p, const int* ss_flags_host, const int* dis_flags_host,
@@ -606,7 +607,11 @@ static int decode_fwd_driver(const void* const* params, const float* mem_in, con
                              int E, int H, int A, int V, int Eenc, int start_idx, int end_idx, void* stream,
                              void* aux_stream, int sample_method, float temp, const float* sample_noise,
                              const uint8_t* emb_keep, float emb_drop_p, int flags, int top_k, float top_p,
-                             int32_t* kept) {
+                             int32_t* kept, const acvae::Constraints& con) {
+  // constrained decoding (constrain.hip) belongs to the free-running loop: a teacher-forced row has no history of its own,
+  // and the backward of a recorded rollout does not know the penalty's factor
+  ACVAE_TRY(acvae::constraints_check_loop(con, V, end_idx, Tc, 1));
+  if (con.on() && (caps || (flags & ACVAE_FLAG_ROLLOUT_GRAD))) return ACVAE_EINVAL;
   if (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) return ACVAE_EINVAL;          // (a NaN top_p fails both comparisons)
   const bool truncate = top_k > 0 || top_p < 1.f;
   if (truncate && (sample_method == ACVAE_SAMPLE_GREEDY || (flags & ACVAE_FLAG_ROLLOUT_GRAD))) return ACVAE_EINVAL;
@@ -797,6 +802,8 @@ static int decode_fwd_driver(const void* const* params, const float* mem_in, con
     const int M = rows_of(cnt);
     ACVAE_TRY(gemm(outputs + (long)t0 * H, ldof(cnt, H), P(TP_DEC_CLS_W), H, P(TP_DEC_CLS_B), logits + (long)t0 * V,
                    ldof(cnt, V), M, V, H, 0, st));
+    if (con.on())                                  // (cnt == 1: refused with caps) the row every consumer below reads
+      ACVAE_TRY(acvae::constrain_rows(logits + (long)t0 * V, (long)Tc * V, seqs, Tc, t0, N, V, end_idx, con, st.s));
     ACVAE_TRY(acvae_row_logsoftmax_argmax(logits + (long)t0 * V, (long)Tc * V, V, seqs + t0, sampled_logprobs + t0,
                                           lse + t0, Tc, 1, N, cnt, V, st));
     if (truncate)                                  // the same draw over the top-k / nucleus prefix of each row
@@ -894,7 +901,7 @@ extern "C" int acvae_decode_fwd_sampled(const void* const* params, const float* 
                            outputs, seqs, sampled_logprobs, attn_w, p_means, p_logs, p_z, p_means_utt, h_final, hp_final,
                            cp_final, saved_v, saved_bytes, scratch_v, scratch_bytes, N, Tc, S, E, H, A, V, Eenc, start_idx,
                            end_idx, stream, aux_stream, sample_method, temp, sample_noise, emb_keep, emb_drop_p, flags, 0,
-                           1.f, nullptr);
+                           1.f, nullptr, acvae::Constraints{});
 }
 
 extern "C" int acvae_decode_fwd_truncated(const void* const* params, const float* mem_in, const int64_t* mem_lens,
@@ -912,7 +919,30 @@ extern "C" int acvae_decode_fwd_truncated(const void* const* params, const float
                            outputs, seqs, sampled_logprobs, attn_w, p_means, p_logs, p_z, p_means_utt, h_final, hp_final,
                            cp_final, saved_v, saved_bytes, scratch_v, scratch_bytes, N, Tc, S, E, H, A, V, Eenc, start_idx,
                            end_idx, stream, aux_stream, sample_method, temp, sample_noise, emb_keep, emb_drop_p, flags,
-                           top_k, top_p, kept);
+                           top_k, top_p, kept, acvae::Constraints{});
+}
+
+extern "C" int acvae_decode_fwd_constrained(const void* const* params, const float* mem_in, const int64_t* mem_lens,
+                                            const int64_t* caps, int64_t ld_caps, const int64_t* lens1, const float* q_z,
+                                            const float* eps_p, const int* ss_flags_host, const int* dis_flags_host,
+                                            float* logits, float* outputs, int64_t* seqs, float* sampled_logprobs,
+                                            float* attn_w, float* p_means, float* p_logs, float* p_z, float* p_means_utt,
+                                            float* h_final, float* hp_final, float* cp_final, void* saved_v,
+                                            int64_t saved_bytes, void* scratch_v, int64_t scratch_bytes, int N, int Tc,
+                                            int S, int E, int H, int A, int V, int Eenc, int start_idx, int end_idx,
+                                            void* stream, void* aux_stream, int sample_method, float temp,
+                                            const float* sample_noise, const uint8_t* emb_keep, float emb_drop_p, int flags,
+                                            int top_k, float top_p, int32_t* kept, float repetition_penalty,
+                                            int no_repeat_ngram_size, int min_length, const int* suppress_host,
+                                            int n_suppress) {
+  acvae::Constraints con;
+  con.repetition_penalty = repetition_penalty; con.no_repeat_ngram_size = no_repeat_ngram_size;
+  con.min_length = min_length; con.suppress = suppress_host; con.n_suppress = n_suppress;
+  return decode_fwd_driver(params, mem_in, mem_lens, caps, ld_caps, lens1, q_z, eps_p, ss_flags_host, dis_flags_host, logits,
+                           outputs, seqs, sampled_logprobs, attn_w, p_means, p_logs, p_z, p_means_utt, h_final, hp_final,
+                           cp_final, saved_v, saved_bytes, scratch_v, scratch_bytes, N, Tc, S, E, H, A, V, Eenc, start_idx,
+                           end_idx, stream, aux_stream, sample_method, temp, sample_noise, emb_keep, emb_drop_p, flags,
+                           top_k, top_p, kept, con);
 }
 
 extern "C" int acvae_decode_bwd_defers(const int* dis_flags_host, int Tc, void* stream, void* aux_stream, int flags) {

@@ -6,6 +6,7 @@
 // The training-time composites are decoder.hip.
 #include <utility>
 #include "common.h"
+#include "constrain.h"
 #include "conv.h"
 #include "rnn.h"
 #include "text_common.h"
@@ -169,13 +170,16 @@ extern "C" int acvae_decoder_step_fwd(const void* const* params, const int64_t* 
 namespace {
 struct SearchMember { const void* const* params; const float* mem; const int64_t* mem_lens; const float* eps; int S, E, H, A; };
 struct MemberLayout { StepLayout sl; long step, encd, encp, h, hp, cp, lz, mean, logv, z, h2, hp2, cp2, attp, attw, logits, rnn; };
-struct SearchLayout { MemberLayout m[ACVAE_ENSEMBLE_MAX]; long scores, topk, best, words, total; int keep_attw; };
-// keep_attw: member 0's decoder attention weights of every step, [T][R][S], for the trace-back; else [R][S], overwritten
-int search_layout(const SearchMember* mb, int M, int N, int beam, int T, int V, int keep_attw, SearchLayout& L) {
+struct SearchLayout { MemberLayout m[ACVAE_ENSEMBLE_MAX]; long scores, topk, best, words, whist, total; int keep_attw, keep_hist; };
+// keep_attw: member 0's decoder attention weights of every step, [T][R][S], for the trace-back; else [R][S], overwritten.
+// keep_hist: the rows' word histories of a constrained beam search, int64 [2][R][T] (the one read, the one gathered into).
+int search_layout(const SearchMember* mb, int M, int N, int beam, int T, int V, int keep_attw, int keep_hist,
+                  SearchLayout& L) {
   if (M < 1 || M > ACVAE_ENSEMBLE_MAX || N <= 0 || beam <= 0 || T <= 0) return ACVAE_EINVAL;
   const long R = (long)N * beam;
   if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
   L.keep_attw = keep_attw;
+  L.keep_hist = keep_hist;
   Bump b;
   for (int m = 0; m < M; ++m) {
     MemberLayout& o = L.m[m];
@@ -196,15 +200,24 @@ int search_layout(const SearchMember* mb, int M, int N, int beam, int T, int V, 
   L.topk = b.take(R);
   L.best = b.take(R);
   L.words = b.take(2 * ((long)(3 * T + 2) * R));        // int64: word [R], argmax [R], per step idx / parent / word [T][R]
+  L.whist = keep_hist ? b.take(2 * (2 * R * T)) : 0;     // int64; behind everything else: the rest lies where it lay
   L.total = b.off;
   return ACVAE_OK;
 }
 
 struct GatherJob { const float* src; float* dst; int width; };
 using GatherTable = acvae::JobTable<GatherJob, 4>;
-__global__ __launch_bounds__(256) void beam_gather_kernel(GatherTable g, const int64_t* __restrict__ parent) {
-  const GatherJob j = g.job[blockIdx.y];
+// A constrained beam search's word histories follow their parents too: one more job (blockIdx.y == g.n, launched only
+// then), row r's history becomes its parent's t words and the word the row was given at step t.
+struct HistJob { const int64_t* src; int64_t* dst; const int64_t* word; int t, T; };
+__global__ __launch_bounds__(256) void beam_gather_kernel(GatherTable g, const int64_t* __restrict__ parent, HistJob hj) {
   const long r = blockIdx.x, p = parent[r];
+  if ((int)blockIdx.y == g.n) {
+    for (int i = threadIdx.x; i < hj.t; i += blockDim.x) hj.dst[r * hj.T + i] = hj.src[p * hj.T + i];
+    if (threadIdx.x == 0) hj.dst[r * hj.T + hj.t] = hj.word[r];
+    return;
+  }
+  const GatherJob j = g.job[blockIdx.y];
   for (int i = threadIdx.x; i < j.width; i += blockDim.x) j.dst[r * j.width + i] = j.src[p * j.width + i];
 }
 __global__ void fill_words_kernel(int64_t* w, int64_t v, int n) {
@@ -247,9 +260,15 @@ __global__ __launch_bounds__(256) void beam_trace_kernel(const int64_t* __restri
 // The driver behind both entry points; they have refused every bad argument, so nothing here fails before a launch.
 // greedy: seqs [R,T], logprobs [R,T].  Beam: seqs [N,T], logprobs [N] or null, attw_out [N,S,T] or null (not null only
 // with a layout made with keep_attw).
+// con: the controls of constrained decoding (constrain.hip), applied to every member's logits in front of the mixing; the
+// history of a row is its seqs row (greedy) or the word history kept beside the states (beam, L.keep_hist).  With
+// nothing on, no launch is added and no buffer is kept.
 int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_idx, int64_t end_idx, int greedy,
-           int64_t* seqs, float* logprobs, float* attw_out, float* sc, int N, int beam, int T, int V, hipStream_t s) {
+           int64_t* seqs, float* logprobs, float* attw_out, float* sc, int N, int beam, int T, int V,
+           const acvae::Constraints& con, hipStream_t s) {
   const int R = N * beam;
+  int64_t* wh = L.keep_hist ? (int64_t*)(sc + L.whist) : nullptr;   // the rows' histories at this step
+  int64_t* wh2 = wh ? wh + (long)R * T : nullptr;
   // per member: the buffers that change hands from step to step (greedy swaps them, the beam search gathers by parent)
   struct State { float *h, *hp, *cp, *lz, *h2, *hp2, *cp2, *z; } state[ACVAE_ENSEMBLE_MAX];
   const float* logit_ptr[ACVAE_ENSEMBLE_MAX];
@@ -294,6 +313,7 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
                            sc + o.mean, sc + o.logv, x.z, x.hp2, x.cp2, sc + o.attp, ssc, o.sl, N, beam, b.S, b.E, V, st));
       ACVAE_TRY(decoder_step(b.params, w_t, x.h, b.mem, b.mem_lens, sc + o.encd, x.z, sc + o.logits, x.h2, attw_t,
                              sc + o.rnn, ssc, o.sl, N, beam, b.S, b.E, b.H, b.A, V, st));
+      ACVAE_TRY(acvae::constrain_rows(sc + o.logits, V, greedy ? seqs : wh, T, t, R, V, (int)end_idx, con, s));
     }
     if (greedy) {
       ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, nullptr, 0, arg, best, 1, R, V, s));
@@ -313,8 +333,11 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
         const State& x = state[m];
         GatherTable g;
         g.add({x.h2, x.h, mb[m].H}); g.add({x.hp2, x.hp, mb[m].E}); g.add({x.cp2, x.cp, mb[m].E}); g.add({x.z, x.lz, mb[m].E});
-        hipLaunchKernelGGL(beam_gather_kernel, dim3(R, g.n), dim3(256), 0, s, g, par_t);
+        const bool hist = wh && m == 0;                  // the histories ride with member 0's states
+        hipLaunchKernelGGL(beam_gather_kernel, dim3(R, g.n + (hist ? 1 : 0)), dim3(256), 0, s, g, par_t,
+                           HistJob{wh, wh2, nxt_t, t, T});
       }
+      std::swap(wh, wh2);
       w_t = nxt_t;
     }
   }
@@ -326,40 +349,28 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
 }
 }  // namespace
 
-extern "C" int64_t acvae_beam_search_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A, int V) {
-  const SearchMember mb{nullptr, nullptr, nullptr, nullptr, S, E, H, A};
-  SearchLayout L;
-  return search_layout(&mb, 1, N, beam, max_length, V, 1, L) == ACVAE_OK ? L.total * 4 : -1;
-}
-
-extern "C" int acvae_beam_search(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
-                                 int64_t start_idx, int64_t* seqs, float* attw_out, void* scratch_v, int64_t scratch_bytes,
-                                 int N, int beam, int max_length, int S, int E, int H, int A, int V, void* stream) {
+namespace {
+int beam_search_entry(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
+                      int64_t start_idx, int64_t* seqs, float* attw_out, void* scratch_v, int64_t scratch_bytes, int N,
+                      int beam, int max_length, int S, int E, int H, int A, int V, int64_t end_idx,
+                      const acvae::Constraints& con, void* stream) {
   const SearchMember mb{params, mem, mem_lens, eps, S, E, H, A};
   SearchLayout L;
-  ACVAE_TRY(search_layout(&mb, 1, N, beam, max_length, V, 1, L));
+  ACVAE_TRY(acvae::constraints_check_loop(con, V, (int)end_idx, max_length, beam));
+  ACVAE_TRY(search_layout(&mb, 1, N, beam, max_length, V, 1, con.on(), L));
   if (!params || !mem || !mem_lens || !eps || !seqs || !attw_out || !scratch_v) return ACVAE_EINVAL;
   // the prior LSTM is E wide; acvae_topk_flat_batched selects k <= 16 and would answer a wider beam with the same code
   if (start_idx < 0 || start_idx >= V || beam > 16 || H != E) return ACVAE_EINVAL;
   if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
-  return search(&mb, 1, L, start_idx, 0, 0, seqs, nullptr, attw_out, (float*)scratch_v, N, beam, max_length, V,
+  return search(&mb, 1, L, start_idx, end_idx, 0, seqs, nullptr, attw_out, (float*)scratch_v, N, beam, max_length, V, con,
                 (hipStream_t)stream);
 }
 
-extern "C" int64_t acvae_ensemble_search_scratch_bytes(int M, int N, int beam, int max_length, const int* S, const int* E,
-                                                       const int* H, const int* A, int V) {
-  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A) return -1;
-  SearchMember mb[ACVAE_ENSEMBLE_MAX];
-  for (int m = 0; m < M; ++m) mb[m] = {nullptr, nullptr, nullptr, nullptr, S[m], E[m], H[m], A[m]};
-  SearchLayout L;
-  return search_layout(mb, M, N, beam, max_length, V, 0, L) == ACVAE_OK ? L.total * 4 : -1;
-}
-
-extern "C" int acvae_ensemble_search(const void* const* const* params, const float* const* mem,
-                                     const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
-                                     const int* H, const int* A, int M, int64_t start_idx, int64_t end_idx, int greedy,
-                                     int64_t* seqs, float* logprobs, void* scratch_v, int64_t scratch_bytes, int N, int beam,
-                                     int max_length, int V, void* stream) {
+int ensemble_search_entry(const void* const* const* params, const float* const* mem, const int64_t* const* mem_lens,
+                          const float* const* eps, const int* S, const int* E, const int* H, const int* A, int M,
+                          int64_t start_idx, int64_t end_idx, int greedy, int64_t* seqs, float* logprobs, void* scratch_v,
+                          int64_t scratch_bytes, int N, int beam, int max_length, int V, const acvae::Constraints& con,
+                          void* stream) {
   if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !params || !mem || !mem_lens || !eps || !S || !E || !H || !A) return ACVAE_EINVAL;
   SearchMember mb[ACVAE_ENSEMBLE_MAX];
   for (int m = 0; m < M; ++m) {
@@ -369,10 +380,90 @@ extern "C" int acvae_ensemble_search(const void* const* const* params, const flo
   if (!seqs || !logprobs || !scratch_v) return ACVAE_EINVAL;
   if (beam > 64 || (greedy && beam != 1)) return ACVAE_EINVAL;
   if (start_idx < 0 || start_idx >= V || end_idx < 0 || end_idx >= V) return ACVAE_EINVAL;
+  ACVAE_TRY(acvae::constraints_check_loop(con, V, (int)end_idx, max_length, beam));
   SearchLayout L;
-  ACVAE_TRY(search_layout(mb, M, N, beam, max_length, V, 0, L));
+  ACVAE_TRY(search_layout(mb, M, N, beam, max_length, V, 0, con.on() && !greedy, L));
   if (!greedy && beam > 16) return ACVAE_EUNSUPPORTED;   // acvae_topk_flat_batched selects k <= 16: refused here, not mid-call
   if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
-  return search(mb, M, L, start_idx, end_idx, greedy, seqs, logprobs, nullptr, (float*)scratch_v, N, beam, max_length, V,
+  return search(mb, M, L, start_idx, end_idx, greedy, seqs, logprobs, nullptr, (float*)scratch_v, N, beam, max_length, V, con,
                 (hipStream_t)stream);
+}
+
+acvae::Constraints constraints_of(float repetition_penalty, int no_repeat_ngram_size, int min_length,
+                                  const int* suppress_host, int n_suppress) {
+  acvae::Constraints c;
+  c.repetition_penalty = repetition_penalty; c.no_repeat_ngram_size = no_repeat_ngram_size; c.min_length = min_length;
+  c.suppress = suppress_host; c.n_suppress = n_suppress;
+  return c;
+}
+
+int64_t beam_scratch(int N, int beam, int max_length, int S, int E, int H, int A, int V, int keep_hist) {
+  const SearchMember mb{nullptr, nullptr, nullptr, nullptr, S, E, H, A};
+  SearchLayout L;
+  return search_layout(&mb, 1, N, beam, max_length, V, 1, keep_hist, L) == ACVAE_OK ? L.total * 4 : -1;
+}
+int64_t ensemble_scratch(int M, int N, int beam, int max_length, const int* S, const int* E, const int* H, const int* A, int V,
+                         int keep_hist) {
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A) return -1;
+  SearchMember mb[ACVAE_ENSEMBLE_MAX];
+  for (int m = 0; m < M; ++m) mb[m] = {nullptr, nullptr, nullptr, nullptr, S[m], E[m], H[m], A[m]};
+  SearchLayout L;
+  return search_layout(mb, M, N, beam, max_length, V, 0, keep_hist, L) == ACVAE_OK ? L.total * 4 : -1;
+}
+}  // namespace
+
+extern "C" int64_t acvae_beam_search_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A, int V) {
+  return beam_scratch(N, beam, max_length, S, E, H, A, V, 0);
+}
+extern "C" int64_t acvae_beam_search_constrained_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A,
+                                                               int V) {
+  return beam_scratch(N, beam, max_length, S, E, H, A, V, 1);
+}
+
+extern "C" int acvae_beam_search(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
+                                 int64_t start_idx, int64_t* seqs, float* attw_out, void* scratch_v, int64_t scratch_bytes,
+                                 int N, int beam, int max_length, int S, int E, int H, int A, int V, void* stream) {
+  return beam_search_entry(params, mem, mem_lens, eps, start_idx, seqs, attw_out, scratch_v, scratch_bytes, N, beam,
+                           max_length, S, E, H, A, V, 0, acvae::Constraints{}, stream);
+}
+extern "C" int acvae_beam_search_constrained(const void* const* params, const float* mem, const int64_t* mem_lens,
+                                             const float* eps, int64_t start_idx, int64_t* seqs, float* attw_out,
+                                             void* scratch_v, int64_t scratch_bytes, int N, int beam, int max_length, int S,
+                                             int E, int H, int A, int V, void* stream, int64_t end_idx,
+                                             float repetition_penalty, int no_repeat_ngram_size, int min_length,
+                                             const int* suppress_host, int n_suppress) {
+  return beam_search_entry(params, mem, mem_lens, eps, start_idx, seqs, attw_out, scratch_v, scratch_bytes, N, beam,
+                           max_length, S, E, H, A, V, end_idx,
+                           constraints_of(repetition_penalty, no_repeat_ngram_size, min_length, suppress_host, n_suppress),
+                           stream);
+}
+
+extern "C" int64_t acvae_ensemble_search_scratch_bytes(int M, int N, int beam, int max_length, const int* S, const int* E,
+                                                       const int* H, const int* A, int V) {
+  return ensemble_scratch(M, N, beam, max_length, S, E, H, A, V, 0);
+}
+extern "C" int64_t acvae_ensemble_search_constrained_scratch_bytes(int M, int N, int beam, int max_length, const int* S,
+                                                                   const int* E, const int* H, const int* A, int V) {
+  return ensemble_scratch(M, N, beam, max_length, S, E, H, A, V, 1);
+}
+
+extern "C" int acvae_ensemble_search(const void* const* const* params, const float* const* mem,
+                                     const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
+                                     const int* H, const int* A, int M, int64_t start_idx, int64_t end_idx, int greedy,
+                                     int64_t* seqs, float* logprobs, void* scratch_v, int64_t scratch_bytes, int N, int beam,
+                                     int max_length, int V, void* stream) {
+  return ensemble_search_entry(params, mem, mem_lens, eps, S, E, H, A, M, start_idx, end_idx, greedy, seqs, logprobs,
+                               scratch_v, scratch_bytes, N, beam, max_length, V, acvae::Constraints{}, stream);
+}
+extern "C" int acvae_ensemble_search_constrained(const void* const* const* params, const float* const* mem,
+                                                 const int64_t* const* mem_lens, const float* const* eps, const int* S,
+                                                 const int* E, const int* H, const int* A, int M, int64_t start_idx,
+                                                 int64_t end_idx, int greedy, int64_t* seqs, float* logprobs,
+                                                 void* scratch_v, int64_t scratch_bytes, int N, int beam, int max_length,
+                                                 int V, void* stream, float repetition_penalty, int no_repeat_ngram_size,
+                                                 int min_length, const int* suppress_host, int n_suppress) {
+  return ensemble_search_entry(params, mem, mem_lens, eps, S, E, H, A, M, start_idx, end_idx, greedy, seqs, logprobs,
+                               scratch_v, scratch_bytes, N, beam, max_length, V,
+                               constraints_of(repetition_penalty, no_repeat_ngram_size, min_length, suppress_host, n_suppress),
+                               stream);
 }

@@ -30,7 +30,7 @@ from .encoder import ptr_table, scratch_buffer
 from .evaluate import collect_predictions, predictions_payload
 from .frontend import refuse_augmented
 from .seq_train_model import ScstWrapper
-from .vae_model import Hybrid_VAEModel
+from .vae_model import CONSTRAINTS_OFF, Hybrid_VAEModel, _constraint_args
 
 MAX_MEMBERS = int(_lib._defs["ACVAE_ENSEMBLE_MAX"])
 
@@ -68,15 +68,25 @@ class Ensemble(nn.Module):
         self.noise = None
 
     @torch.no_grad()
-    def forward(self, feats, feat_lens, method="greedy", beam_size=5, max_length=20):
+    def forward(self, feats, feat_lens, method="greedy", beam_size=5, max_length=20, repetition_penalty=None,
+                no_repeat_ngram_size=None, min_length=None, suppress_tokens=None):
         """-> ``{"seqs": int64 [N, max_length], "logprobs": f32}`` on the device.  ``logprobs``: greedy [N, max_length], the
         mixture's log-probability of each chosen word (entries behind a row's ``end_idx`` carry no meaning); beam [N], beam
         0's final score.  A greedy row that has produced ``end_idx`` keeps ``end_idx`` to the end (base_runner.py:584,
-        622-630)."""
+        622-630).
+
+        ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length`` / ``suppress_tokens``: constrained decoding
+        (``Hybrid_VAEModel._constraints``), applied to every member's logits in front of the mixing; ``logprobs`` are then
+        those of the constrained mixture."""
         if method not in ("greedy", "beam"):
             raise ValueError(f"Ensemble: method must be 'greedy' or 'beam', not {method!r}")
         beam = 1 if method == "greedy" else int(beam_size)
         T = int(max_length)
+        con = self.models[0]._constraints(                                # (vocabulary and end_idx are shared)
+            dict(method=method, beam_size=beam, max_length=T, repetition_penalty=repetition_penalty,
+                 no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, suppress_tokens=suppress_tokens),
+            rollout=True)
+        on = con != CONSTRAINTS_OFF
         replay = self.noise.get("eps") if self.noise is not None else None
         self.noise = None
         M = len(self.models)
@@ -104,13 +114,15 @@ class Ensemble(nn.Module):
         host = [a.ctypes.data for a in (S_, E_, H_, A_)]
         seqs = torch.empty(N, T, dtype=torch.long, device=dev)
         logprobs = torch.empty((N, T) if method == "greedy" else (N,), device=dev)
-        sb = _lib.call("acvae_ensemble_search_scratch_bytes", M, N, beam, T, *host, self.vocab_size)
+        sb = _lib.call("acvae_ensemble_search_constrained_scratch_bytes" if on else "acvae_ensemble_search_scratch_bytes",
+                       M, N, beam, T, *host, self.vocab_size)
         if sb < 0:
             raise RuntimeError(f"acvae_ensemble_search: unsupported dimensions (N={N}, beam={beam}, max_length={T})")
         scratch = scratch_buffer(sb, dev)
-        _lib.call("acvae_ensemble_search", params, ptr_table(mems), ptr_table(lens), ptr_table(epss), *host, M,
-                  self.start_idx, self.end_idx, 1 if method == "greedy" else 0, seqs, logprobs, scratch, sb, N, beam, T,
-                  self.vocab_size, _lib.current_stream())
+        _lib.call("acvae_ensemble_search_constrained" if on else "acvae_ensemble_search", params, ptr_table(mems),
+                  ptr_table(lens), ptr_table(epss), *host, M, self.start_idx, self.end_idx, 1 if method == "greedy" else 0,
+                  seqs, logprobs, scratch, sb, N, beam, T, self.vocab_size, _lib.current_stream(),
+                  *(_constraint_args(con) if on else ()))
         return {"seqs": seqs, "logprobs": logprobs}
 
 
@@ -118,7 +130,8 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
                       batch_size=32, frontend=None, **kwargs):
     """The decoding half of ``BaseRunner.ensemble`` (base_runner.py:433-478): ``items`` are ``(audio_id, feature [T, F])`` as
     for ``evaluate()``, batched with ``collate_fn([1])`` (no replication); ``kwargs`` (``method``, ``beam_size``,
-    ``max_length``) go to ``Ensemble.forward``.  Writes the JSON payload of ``evaluate()`` or, with ``dcase_format``, the
+    ``max_length`` and the constrained-decoding keywords) go to ``Ensemble.forward``.  Writes the JSON payload of
+    ``evaluate()`` or, with ``dcase_format``, the
     reference's two-column CSV (``file_name``, ``caption_predicted``).  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are
     ``(audio_id, 1-D waveform)`` and the log-mel features are formed on the device, once for all members.  Returns the payload
     dict; scoring stays outside."""

@@ -111,7 +111,9 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
     ``"gumbel"``) with ``temp``, ``rng`` ("host" | "device") and the truncation keywords ``top_k`` (the k most probable
     words of each step, 0 = off) and ``top_p`` (the nucleus of that mass, 1.0 = off), e.g. ``method="sample", beam_size=5,
     top_p=0.9, rng="device"`` for five sampled captions per clip; ``top_k`` / ``top_p`` with any other method are a
-    ValueError (``Hybrid_VAEModel._truncation``).  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
+    ValueError (``Hybrid_VAEModel._truncation``).  Constrained decoding, with every method but "dbs":
+    ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``suppress_tokens`` (``Hybrid_VAEModel._constraints``),
+    e.g. ``method="beam", beam_size=3, no_repeat_ngram_size=3``.  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
     or int16 PCM (``acvae_amd.frontend.read_wav``); the log-mel features are formed on the device in front of either
     forward path.  Returns the payload dict."""
     refuse_augmented(frontend, "evaluate")

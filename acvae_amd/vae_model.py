@@ -28,6 +28,19 @@ from .encoder import ptr_table, scratch_buffer
 from .word_model import CaptionModel
 
 
+CONSTRAINT_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_length", "suppress_tokens")
+CONSTRAINTS_OFF = (1.0, 0, 0, ())           # repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens
+SUPPRESS_MAX = int(_lib._defs["ACVAE_SUPPRESS_MAX"])
+
+
+def _constraint_args(constrain):
+    """(theta, n, m, ids) -> the five trailing arguments of the ``acvae_*_constrained`` entries.  The list is a HOST array
+    that the entry reads before it returns; the ctypes pointer keeps the array alive until then."""
+    theta, n, m, ids = constrain
+    arr = np.ascontiguousarray(ids, dtype=np.int32)
+    return float(theta), int(n), int(m), (arr.ctypes.data_as(_lib.ctypes.c_void_p) if len(ids) else None), len(ids)
+
+
 class _DecodeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, mem, mem_lens_d, caps_d, lens1_d, q_z, eps_p, ss_flags, dis_flags, Tc, sampling, *weights):
@@ -62,13 +75,20 @@ class _DecodeFn(torch.autograd.Function):
         # top-k / nucleus truncation of the sampled steps: its own entry, and the size of every kept prefix beside the words
         truncate = sampling.get("truncate") if sampling else None
         kept = torch.empty(N, Tc, dtype=torch.int32, device=dev) if truncate else None
+        # constrained decoding (_constraints): its own entry again, which takes the truncation arguments on or off
+        constrain = sampling.get("constrain") if sampling else None
+        entry, extra = "acvae_decode_fwd_sampled", ()
+        if truncate or constrain:
+            entry = "acvae_decode_fwd_truncated"
+            extra = (int(truncate[0]), float(truncate[1]), kept) if truncate else (0, 1.0, None)
+        if constrain:
+            entry, extra = "acvae_decode_fwd_constrained", extra + _constraint_args(constrain)
         _lib.persist_status(dev)                 # the device's status words are registered before the first persistent launch
-        _lib.call("acvae_decode_fwd_truncated" if truncate else "acvae_decode_fwd_sampled", ptr_table(params), mem,
+        _lib.call(entry, ptr_table(params), mem,
                   mem_lens_d, caps_d, caps_d.stride(0) if train else 0, lens1_d, q_z, eps_p, ss_arr, dis_arr, logits,
                   outputs, seqs, slp, attw, pm, pl, pz, putt, hfin, hp, cp, saved, saved_b, scratch, scratch_b, *dims, model.start_idx,
                   model.end_idx, _lib.current_stream(), model._aux_stream(), int(method), float(temp), noise, keep,
-                  float(drop_p), _lib.call_flags() | (_lib.FLAG_ROLLOUT_GRAD if rollout else 0),
-                  *((int(truncate[0]), float(truncate[1]), kept) if truncate else ()))
+                  float(drop_p), _lib.call_flags() | (_lib.FLAG_ROLLOUT_GRAD if rollout else 0), *extra)
         ctx.set_materialize_grads(False)         # outputs the loss does not use (outputs, p_z, ..) arrive as None, not as zero tensors
         ctx.model, ctx.saved, ctx.dims, ctx.dis_arr = model, saved, dims, dis_arr
         ctx.emb_keep, ctx.emb_p, ctx.rollout = keep, float(drop_p), rollout
@@ -295,10 +315,17 @@ class Hybrid_VAEModel(CaptionModel):
                         torch.float32)
 
     @torch.no_grad()
-    def beam_search(self, encoded, max_length, beam_size):
+    def beam_search(self, encoded, max_length, beam_size, **constraints):
         """Validation beam search, models/vae_model.py:896-995: beams expanded over the flat beam*V log-probabilities of
         a clip, states re-gathered by prev_word_inds; returns beam 0 (the reference never fills done_beams, :986-995).
-        All clips advance together; no host synchronisation inside the loop."""
+        All clips advance together; no host synchronisation inside the loop.
+
+        ``constraints``: ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``suppress_tokens`` (see
+        ``_constraints``), applied to every beam row's logits against the row's own word history."""
+        con = self._constraints(dict(constraints, method="beam", max_length=max_length, beam_size=beam_size), rollout=True)
+        unknown = set(constraints) - set(CONSTRAINT_KEYS)
+        if unknown:
+            raise TypeError(f"beam_search: unexpected keyword(s) {sorted(unknown)}")
         mem_all = self._projected_memory(encoded)
         dev = mem_all.device
         lens_all = torch.as_tensor(encoded["audio_embeds_lens"]).to(device=dev, dtype=torch.long).contiguous()
@@ -310,10 +337,13 @@ class Hybrid_VAEModel(CaptionModel):
         eps_all = self._search_noise(N, max_length, beam_size, E, dev, replay)
         seqs = torch.empty(N, max_length, dtype=torch.long, device=dev)
         attw = torch.empty(N, S, max_length, device=dev)
-        sb = _lib.call("acvae_beam_search_scratch_bytes", N, beam_size, max_length, S, E, H, A, V)
+        on = con != CONSTRAINTS_OFF                       # (the word histories of a constrained search need more scratch)
+        sb = _lib.call("acvae_beam_search_constrained_scratch_bytes" if on else "acvae_beam_search_scratch_bytes", N,
+                       beam_size, max_length, S, E, H, A, V)
         scratch = scratch_buffer(sb, dev)
-        _lib.call("acvae_beam_search", ptr_table(self._text_table()), mem_all, lens_all, eps_all, int(self.start_idx), seqs,
-                  attw, scratch, sb, N, beam_size, max_length, S, E, H, A, V, _lib.current_stream())
+        _lib.call("acvae_beam_search_constrained" if on else "acvae_beam_search", ptr_table(self._text_table()), mem_all,
+                  lens_all, eps_all, int(self.start_idx), seqs, attw, scratch, sb, N, beam_size, max_length, S, E, H, A, V,
+                  _lib.current_stream(), *((int(self.end_idx),) + _constraint_args(con) if on else ()))
         return {"seqs": seqs, "attn_weights": attw}
 
     @torch.no_grad()
@@ -438,8 +468,10 @@ class Hybrid_VAEModel(CaptionModel):
         method = kwargs.get("method", "greedy")
         max_length = kwargs.get("max_length", self.max_length)
         self._truncation(kwargs, rollout=True)
+        self._constraints(kwargs, rollout=True)
         if method == "beam":                                              # vae_model.py:884-886
-            return self.beam_search(encoded, max_length, kwargs.get("beam_size", 3))
+            return self.beam_search(encoded, max_length, kwargs.get("beam_size", 3),
+                                    **{k: kwargs[k] for k in CONSTRAINT_KEYS if k in kwargs})
         if method == "dbs":                                               # vae_model.py:887-893
             return self.diverse_beam_search(encoded, max_length, kwargs.get("beam_size", 5), kwargs.get("group_size", 5),
                                             kwargs.get("diversity_lambda", 0.5), kwargs.get("temperature", 1.0),
@@ -459,8 +491,13 @@ class Hybrid_VAEModel(CaptionModel):
 
         ``top_k`` (default 0 = off) / ``top_p`` (default 1.0 = off) with ``method="sample"`` or ``"gumbel"``: every sampled
         word is drawn among the ``top_k`` most probable words and / or the nucleus of mass ``top_p`` only (see
-        ``_truncation``); the output dict then also holds ``"kept"``, int32 [N, Tc], the number of words each draw chose from."""
+        ``_truncation``); the output dict then also holds ``"kept"``, int32 [N, Tc], the number of words each draw chose from.
+
+        ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length`` / ``suppress_tokens`` (all off by default; 2-input
+        forward only): constrained decoding on the device, see ``_constraints``.  ``"logits"`` then holds the constrained
+        rows and ``"sampled_logprobs"`` is their log-softmax at the chosen word."""
         self._truncation(kwargs, rollout=len(input) == 2)      # (refusals come in front of the encoder's launches)
+        self._constraints(kwargs, rollout=len(input) == 2)
         self._forward_token = getattr(self, "_forward_token", 0) + 1     # per-forward caches (decoder.embedding_table)
         clip_index = kwargs.pop("clip_index", None)
         if clip_index is not None and len(input) != 4:
@@ -551,6 +588,7 @@ class Hybrid_VAEModel(CaptionModel):
         into the clip's.  In train() the replicas of a clip therefore share the encoder's dropout masks and the BatchNorm
         statistics are those of the clips, not of the repeated batch."""
         self._truncation(kwargs, rollout=True)
+        self._constraints(kwargs, rollout=True)
         self._forward_token = getattr(self, "_forward_token", 0) + 1
         encoded = self.encoder(feats, feat_lens)
         n = int(sample_n)
@@ -604,6 +642,79 @@ class Hybrid_VAEModel(CaptionModel):
                              "one the words are drawn from; use torch.no_grad() or eval()")
         return top_k, p32
 
+    def _constraints(self, kwargs, rollout=False):
+        """The constrained-decoding keywords of a forward -> (repetition_penalty, no_repeat_ngram_size, min_length,
+        suppress_tokens), ``CONSTRAINTS_OFF`` when nothing is on (``None`` = off for each).
+
+        All act on a row's logits x at step t, in front of the selection, against the row's history h[0..t) (the words it
+        has emitted; ``<start>`` is not part of it):
+          ``repetition_penalty`` theta (1.0 = off; finite, > 0; the kernel uses float32(theta)): every distinct word w of h
+            gets x[w] / theta if x[w] > 0, else x[w] * theta;
+          ``no_repeat_ngram_size`` n (0 = off): every word that would complete an n-gram the caption already holds is banned
+            (n = 1 bans every word of h);
+          ``min_length`` m (0 = off; <= ``max_length``): ``end_idx`` is banned at steps t < m;
+          ``suppress_tokens`` (() = off): at most ``SUPPRESS_MAX`` vocabulary ids banned at every step, ``end_idx`` not
+            among them.
+        A ban sets the logit to -inf; the penalty comes first and a ban wins.  Accepted with greedy / "sample" / "gumbel"
+        (``top_k`` / ``top_p`` then truncate the constrained row) and "beam".
+
+        ValueError, naming the keyword: a value out of range; ``method="dbs"`` (its histories live on the host); the
+        4-input (training) forward (``rollout`` False); a 2-input forward that records a differentiable rollout (the
+        backward does not know the penalty's factor); a vocabulary too small for a row to keep a word,
+        ``V <= len(suppress_tokens) + max_length + beam``."""
+        V, end = int(self.vocab_size), int(self.end_idx)
+        theta, n, m, ids = (kwargs.get(k) for k in CONSTRAINT_KEYS)
+        theta = 1.0 if theta is None else theta
+        n = 0 if n is None else n
+        m = 0 if m is None else m
+        ids = () if ids is None else ids
+        try:
+            th32 = float(np.float32(theta))              # the value the kernel uses
+        except (TypeError, ValueError):
+            raise ValueError(f"repetition_penalty must be a finite number > 0 (1.0 = off), got {theta!r}") from None
+        if isinstance(theta, bool) or not (np.isfinite(th32) and th32 > 0.0):
+            raise ValueError(f"repetition_penalty must be a finite number > 0 (1.0 = off), got {theta!r}")
+        for name, v in (("no_repeat_ngram_size", n), ("min_length", m)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 or v > 0x7fffffff:
+                raise ValueError(f"{name} must be an integer >= 0 (0 = off), got {v!r}")
+        n, m = int(n), int(m)
+        max_length = kwargs.get("max_length", self.max_length)
+        if m > max_length:
+            raise ValueError(f"min_length={m} exceeds max_length={max_length}")
+        if isinstance(ids, torch.Tensor):
+            ids = ids.detach().cpu().reshape(-1).tolist()
+        try:
+            ids = list(np.asarray(ids).reshape(-1).tolist()) if isinstance(ids, np.ndarray) else list(ids)
+        except TypeError:
+            raise ValueError(f"suppress_tokens must be a sequence of vocabulary ids, got {ids!r}") from None
+        for w in ids:
+            if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not (0 <= w < V):
+                raise ValueError(f"suppress_tokens: {w!r} is not a vocabulary id in [0, {V})")
+            if w == end:
+                raise ValueError(f"suppress_tokens must not hold end_idx ({end}): no caption could end")
+        if len(ids) > SUPPRESS_MAX:
+            raise ValueError(f"suppress_tokens holds {len(ids)} ids, at most {SUPPRESS_MAX}")
+        con = (th32, n, m, tuple(int(w) for w in ids))
+        if con == CONSTRAINTS_OFF:
+            return CONSTRAINTS_OFF
+        given = " / ".join(f"{k}={v!r}" for k, v, on in zip(CONSTRAINT_KEYS, (theta, n, m, list(con[3])),
+                                                            (th32 != 1.0, n > 0, m > 0, len(ids) > 0)) if on)
+        method = kwargs.get("method", "greedy")
+        if method == "dbs":
+            raise ValueError(f"{given} with method='dbs': diverse beam search keeps its histories on the host and is not "
+                             "constrained; use 'greedy', 'sample', 'gumbel' or 'beam'")
+        if not rollout:
+            raise ValueError(f"{given} in the 4-input (training) forward: a teacher-forced row has no history of its own; "
+                             "constrained decoding belongs to the 2-input forward")
+        if self._records_rollout():
+            raise ValueError(f"{given} in a forward that records a differentiable rollout (train() with gradients enabled): "
+                             "the backward does not know the penalty's factor; use torch.no_grad() or eval()")
+        beam = int(kwargs.get("beam_size", 3)) if method == "beam" else 1
+        if V <= len(ids) + int(max_length) + beam:
+            raise ValueError(f"{given}: a vocabulary of {V} words may leave a row without a word; it must exceed "
+                             f"len(suppress_tokens) + max_length + beam = {len(ids)} + {max_length} + {beam}")
+        return con
+
     def _host_prepare(self, N, dev, caps, cap_lens, kwargs):
         """The decode loop's host-side random decisions, in the reference's per-step order (scheduled-sampling coin
         :826, prior noise text_encoder.py:259 on the CPU generator (F9), disentangle coin :802-806), and the device
@@ -629,6 +740,7 @@ class Hybrid_VAEModel(CaptionModel):
         V = self.vocab_size
         code = 0 if method == "greedy" else (1 if method == "gumbel" else 2)
         top_k, top_p = self._truncation(kwargs, rollout=not train)
+        constrain = self._constraints(kwargs, rollout=not train)
         # rng="device" (or model.sample_rng = "device") - opt-in, not the reference's stream: ONE draw on the CPU generator
         # seeds a counter-based generator on the device that fills the [Tc,N,V] noise (acvae_sample_noise); same
         # distributions, so the captions are samples of the same model, but not the words the reference would draw from
@@ -686,6 +798,8 @@ class Hybrid_VAEModel(CaptionModel):
             sampling["sample"] = (code, temp, _lib.h2d(sample_noise, dev, torch.float32).contiguous())
         if top_k > 0 or top_p < 1.0:
             sampling["truncate"] = (top_k, top_p)
+        if constrain != CONSTRAINTS_OFF:
+            sampling["constrain"] = constrain
         if drop_p > 0.0:
             if dec_keep is None:
                 dec_keep = torch.as_tensor(replay["dec_keep"])[:Tc]

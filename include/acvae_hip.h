@@ -948,6 +948,75 @@ int acvae_ensemble_search(const void* const* const* params, const float* const* 
                           int64_t start_idx, int64_t end_idx, int greedy, int64_t* seqs, float* logprobs, void* scratch,
                           int64_t scratch_bytes, int N, int beam, int max_length, int V, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Constrained decoding on the device: four controls on a row's logits x at step t, applied inside every decoding loop in
+ * front of the selection.  No counterpart in the reference.  h[0..t) is the row's history: the words it has emitted so
+ * far, <start> not among them.  All are off by default, and with all four off every entry below runs exactly the launches
+ * of its unconstrained base.
+ *   repetition_penalty theta (off: 1.0f)  for every DISTINCT word w of h: x[w] <- x[w] / theta if x[w] > 0, else
+ *                                         x[w] * theta; fp32, once per distinct word; theta finite and > 0;
+ *   no_repeat_ngram_size n   (off: 0)     n >= 1 and t >= n - 1: for every i in [n - 1, t) with
+ *                                         h[i-n+1 .. i) == h[t-n+1 .. t), ban h[i]: no n-gram of the finished caption
+ *                                         occurs twice; n = 1 bans every word of h;
+ *   min_length m             (off: 0)     ban end_idx at steps t < m; 0 <= m <= max_length;
+ *   suppress_host, n_suppress (off: 0)    ban these ids at every step: a HOST array (may be NULL when n_suppress is 0) of
+ *                                         at most ACVAE_SUPPRESS_MAX ids in [0, V), copied into the kernel arguments.
+ * A ban writes -inf.  The penalty is applied first and a ban wins over it.  The edited row is the row everything
+ * downstream sees: argmax, sampling (top_k / top_p truncate the constrained row), mixing and the flat top-k; the logits a
+ * decode forward returns hold the constrained rows and sampled_logprobs is log_softmax of the constrained row at the
+ * chosen word.  Finished rows keep emitting end_idx: the drivers' overrides come after the selection.  A history word
+ * outside [0, V) is skipped.
+ *
+ * acvae_constrain_logits: the kernel alone, in place on R rows (row r at logits + r * ld, ld >= V; its history at
+ * hist + r * hist_ld, int64, hist_ld >= t; hist may be NULL when t is 0).  One wavefront per row, O(t + n_suppress) logits
+ * touched, no workspace.  With everything off it launches nothing and returns ACVAE_OK.
+ *
+ * acvae_decode_fwd_constrained: acvae_decode_fwd_truncated (which is its all-off case) with the controls; the history
+ * of a row is its `seqs` row, the kernel runs between the classifier and the log-softmax of every step.
+ * acvae_beam_search_constrained / acvae_ensemble_search_constrained: acvae_beam_search (which has no end_idx of its own, so
+ * it is added) / acvae_ensemble_search with the controls on every member's logits in front of the mixing.  The greedy
+ * history is the `seqs` row; the beam search keeps a word history per row that follows its parent every step (one more job
+ * of the state gather), which needs the scratch of the *_constrained_scratch_bytes functions (the base sizes suffice when
+ * every control is off).
+ *
+ * ACVAE_EINVAL, before anything is launched: theta not finite or <= 0; n < 0; m < 0 or (drivers) m > max_length;
+ * n_suppress outside [0, ACVAE_SUPPRESS_MAX]; an id outside [0, V); n_suppress > 0 with a NULL list; and with a control on:
+ * end_idx outside [0, V); V <= n_suppress + max_length + beam (beam = 1 for the decode forward; a row must keep a word, and
+ * a clip `beam` finite scores); in the decode forward, caps != NULL (a teacher-forced row has no history of its own) or
+ * ACVAE_FLAG_ROLLOUT_GRAD (the backward does not know the penalty's factor).
+ * Out of scope: diverse beam search (its histories live on the host), constraints in differentiable rollouts and in the
+ * training forward, per-row settings, finishing beams on end_idx and length-normalised beam scores.
+ * ------------------------------------------------------------------------------------------- */
+#define ACVAE_SUPPRESS_MAX 64
+int acvae_constrain_logits(float* logits, int64_t ld, const int64_t* hist, int64_t hist_ld, int t, int R, int V,
+                           int end_idx, float repetition_penalty, int no_repeat_ngram_size, int min_length,
+                           const int* suppress_host, int n_suppress, void* stream);
+int acvae_decode_fwd_constrained(const void* const* params, const float* mem_in, const int64_t* mem_lens,
+                                 const int64_t* caps, int64_t ld_caps, const int64_t* lens1, const float* q_z,
+                                 const float* eps_p, const int* ss_flags_host, const int* dis_flags_host, float* logits,
+                                 float* outputs, int64_t* seqs, float* sampled_logprobs, float* attn_w, float* p_means,
+                                 float* p_logs, float* p_z, float* p_means_utt, float* h_final, float* hp_final,
+                                 float* cp_final, void* saved, int64_t saved_bytes, void* scratch, int64_t scratch_bytes,
+                                 int N, int Tc, int S, int E, int H, int A, int V, int Eenc, int start_idx, int end_idx,
+                                 void* stream, void* aux_stream, int sample_method, float temp, const float* sample_noise,
+                                 const uint8_t* emb_keep, float emb_drop_p, int flags, int top_k, float top_p,
+                                 int32_t* kept, float repetition_penalty, int no_repeat_ngram_size, int min_length,
+                                 const int* suppress_host, int n_suppress);
+int64_t acvae_beam_search_constrained_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A, int V);
+int acvae_beam_search_constrained(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
+                                  int64_t start_idx, int64_t* seqs, float* attn_weights, void* scratch,
+                                  int64_t scratch_bytes, int N, int beam, int max_length, int S, int E, int H, int A, int V,
+                                  void* stream, int64_t end_idx, float repetition_penalty, int no_repeat_ngram_size,
+                                  int min_length, const int* suppress_host, int n_suppress);
+int64_t acvae_ensemble_search_constrained_scratch_bytes(int M, int N, int beam, int max_length, const int* S, const int* E,
+                                                        const int* H, const int* A, int V);
+int acvae_ensemble_search_constrained(const void* const* const* params, const float* const* mem,
+                                      const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
+                                      const int* H, const int* A, int M, int64_t start_idx, int64_t end_idx, int greedy,
+                                      int64_t* seqs, float* logprobs, void* scratch, int64_t scratch_bytes, int N, int beam,
+                                      int max_length, int V, void* stream, float repetition_penalty,
+                                      int no_repeat_ngram_size, int min_length, const int* suppress_host, int n_suppress);
+
 #ifdef __cplusplus
 }
 #endif
