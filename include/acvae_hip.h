@@ -229,7 +229,9 @@ int acvae_sample_next_word_truncated(const float* logits, int64_t ld_n, int64_t 
                                      int64_t nz_st, int method, float temp, int64_t* w_out, float* logprob_out,
                                      int64_t o_sn, int64_t o_st, int N, int T, int V, int top_k, float top_p,
                                      int32_t* kept_out, void* stream);
-/* reduction: 0 none (writes loss_rows only), 1 mean over valid rows, 2 sum.  loss_rows [N,T] (0 at invalid rows). */
+/* reduction: 0 none (writes loss_rows only), 1 mean over valid rows, 2 sum.  loss_rows [N,T] (0 at invalid rows).
+ * V >= 2: a one-word vocabulary has no s / (V - 1) and no gradient; V = 1 is ACVAE_EINVAL, forward and backward, for any
+ * smoothing.  lens1 may be NULL (every row valid), hold 0 (no valid row in the clip) or exceed T (counted as T). */
 int acvae_ls_ce_fwd(const float* logits, int64_t ld_n, int64_t ld_t, const int64_t* targets, int64_t tg_sn,
                     const int64_t* lens1, const float* lse, float smoothing, int reduction, float* loss_rows,
                     float* out_scalar, int N, int T, int V, void* stream);
