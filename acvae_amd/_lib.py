@@ -9,6 +9,8 @@ import threading
 import numpy as np
 import torch
 
+from . import streams
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "acvae_hip.h")
 LIB_PATH = os.path.join(_HERE, "libacvae_hip.so")      # the product library; tools load an A/B build with use_library()
@@ -67,9 +69,9 @@ _lib = None
 
 
 class options:
-    """Host-side defaults for the per-call `flags` of the C ABI (the library itself keeps no switches).  Tests and the
-    A/B tools change them through `with _lib.override(persist=False): ...`; the environment variables of the earlier
-    rounds still set the initial values."""
+    """Host-side defaults for the per-call `flags` of the C ABI (the library itself keeps no switch but ACVAE_CONV_WINO, the
+    benchmark's and two tests' A/B).  Tests and the A/B tools change them through `with _lib.override(persist=False): ...`;
+    the environment variables of the earlier rounds still set the initial values."""
     persist = os.environ.get("ACVAE_DECODE_PERSIST", "1") != "0"      # persistent decode / posterior launches
     defer = os.environ.get("ACVAE_DECODE_DEFER", "1") != "0"          # decode backward: parameter gradients trail on the side stream
     attn_split = True                                                 # split-over-frames attention for few query rows
@@ -148,9 +150,15 @@ def lib():
     return _lib
 
 
+def ptr_table(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
 def _conv(x):
     if isinstance(x, torch.Tensor):
         return x.data_ptr()
+    if isinstance(x, (list, tuple)):             # a list of tensors / None where the entry takes a pointer table
+        return ptr_table(x)
     return x
 
 
@@ -159,13 +167,32 @@ def current_stream():
 
 
 def call(name, *args):
-    """Call an `int acvae_*` entry point; tensors are passed as device pointers; raises on non-zero."""
+    """Call an `int acvae_*` entry point; tensors are passed as device pointers, lists of tensors as pointer tables; raises
+    on non-zero."""
     fn = getattr(lib(), name)
     rc = fn(*[_conv(a) for a in args])
     if PROTOS[name][0] is ctypes.c_int and rc != 0:
         what = ERRORS.get(rc, f"hipError_t {rc}" if rc > 0 else f"code {rc}")
         raise RuntimeError(f"{name} failed: {what}")
     return rc
+
+
+def call_keeping(keep_on, name, *args):
+    """call(name, *args) for an entry that may leave work behind on the stream ``keep_on`` when it returns (None: it does
+    not): EVERY device tensor among the arguments, the lists behind the tables included, is then kept alive for that stream."""
+    try:
+        return call(name, *args)
+    finally:
+        if keep_on is not None:
+            streams.keep(keep_on, args)
+
+
+def grad_buffer(views, p):
+    """Where a backward writes p's gradient: p's view of the train step's flat gradient (``views``: {param: view} or None)
+    as a fresh alias, which autograd adopts as .grad without a copy, or a new tensor."""
+    if views is not None and p in views:
+        return views[p].detach()
+    return torch.empty_like(p)
 
 
 # ---- persistent launches: status words (include/acvae_hip.h, acvae_persist_status_register)

@@ -456,16 +456,14 @@ int conv3x3_igemm_bf16(const bf16_t* X, const float* scale, const float* shift, 
   if (!aligned16(X) || !aligned16(Wp) || (reinterpret_cast<uintptr_t>(Y) & 3u)) return ACVAE_EALIGN;
   const int M = N * H * W;
   prof_begin(ACVAE_PROF_CONV_IGEMM, st);
-  // A/B switch: ACVAE_BF16_BDMA=0 keeps the register-staged weight panel, 2 uses the DMA for the 64-column tiles too.
-  // Measured in one job (B=32, T=1000): 128-column launches 3-4 % faster with the DMA panel (fwd 237 -> 228, 216 -> 207 us),
-  // the 64-column ones 1-3 % slower (339 -> 349 us): default 1 = DMA for the 128-column tiles only.
-  static const int bdma_mode = getenv("ACVAE_BF16_BDMA") ? atoi(getenv("ACVAE_BF16_BDMA")) : 1;
-  const bool bdma = bdma_mode == 2 || (bdma_mode == 1 && Cout > 64);
+  // The weight panel comes through the DMA for the 128-column tiles only (bdma = Cout > 64); the 64-column tile keeps the
+  // register-staged panel.  Measured in one job (B=32, T=1000): 128-column launches 3-4 % faster with the DMA panel
+  // (fwd 237 -> 228, 216 -> 207 us), the 64-column ones 1-3 % slower (339 -> 349 us).
 #define IG_LAUNCH(BN_, D_)                                                                                               \
   hipLaunchKernelGGL((conv_igemm_bf16_kernel<BN_, D_>), dim3(cdiv(M, BMT), cdiv(Cout, BN_)), dim3(256), 0, st, X, scale,  \
                      shift, Wp, Y, partials, M, H, W, Cin, Cout)
-  if (Cout <= 64) { if (bdma) IG_LAUNCH(64, true); else IG_LAUNCH(64, false); }
-  else            { if (bdma) IG_LAUNCH(128, true); else IG_LAUNCH(128, false); }
+  if (Cout <= 64) IG_LAUNCH(64, false);
+  else            IG_LAUNCH(128, true);
 #undef IG_LAUNCH
   prof_end(ACVAE_PROF_CONV_IGEMM, st);
   ACVAE_LAUNCH_CHECK();
@@ -483,7 +481,7 @@ static int wgrad_bf16_splits(int M, int Cout, int NC) {
   for (int k = 8; k <= (maxs < 8 ? 8 : maxs) && k <= 512; k += 8) {
     const long nb = tiles * k;
     const long rounds = (nb + 511) / 512;
-    static const double slab_cost = getenv("ACVAE_WGB_SLABCOST") ? atof(getenv("ACVAE_WGB_SLABCOST")) : 0.5;   // measured: 6 -> 0.5 took the seven launches from 2.26 to 1.56 ms
+    constexpr double slab_cost = 0.5;                             // measured: 6 -> 0.5 took the seven launches from 2.26 to 1.56 ms
     const double t = (double)rounds * ((double)M / k) + slab_cost * k * 32.0;    // K-steps per round x rounds + slab cost (in pixel units)
     if (t < best_t) { best_t = t; best = k; }
   }

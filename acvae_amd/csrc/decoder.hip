@@ -756,8 +756,7 @@ static int decode_fwd_driver(const void* const* params, const float* mem_in, con
   };
   float* gru_save = sv + L.gru_save;
   float* hprev_d = sv + L.hprev_d;
-  static const bool pair_env = !(getenv("ACVAE_SKINNY_PAIR") && atoi(getenv("ACVAE_SKINNY_PAIR")) == 0);
-  const bool pair_ok = pair_env && N <= 64;
+  const bool pair_ok = N <= 64;
   auto dec_step = [&](int t) -> int {
     const float* hprev = t ? outputs + (long)(t - 1) * H : zeros;
     const long ldh = t ? (long)Tc * H : H;
@@ -999,6 +998,8 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
   // the posterior's and the encoder's backward.  The caller then owns two obligations (include/acvae_hip.h): the second
   // stream must be joined before the parameter gradients are read on another stream, and saved / scratch / the incoming
   // gradients must stay untouched until it has drained.
+  // (defer implies a second stream distinct from the first, i.e. fork.on(): the heads' parameter gradients below are then
+  // always queued on it up front, and the trailing part at the end of this function never has to queue them)
   const bool defer = acvae_decode_bwd_defers(dis_flags_host, Tc, stream, aux_stream, flags) != 0;
   const bool has_ln = Eenc != E || params[TP_LN_W] != nullptr;
   TnWs tn{sc + L.tn, L.tn_floats * 4};
@@ -1065,11 +1066,9 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
   };
   // They feed nothing downstream.  With a second stream they go there, in front of the prior's BPTT: the two serial
   // chains leave most of the GPU idle, so the 75 us of these products cost the first stream nothing.
-  static const bool heads_aux = !(getenv("ACVAE_HEADS_AUX") && atoi(getenv("ACVAE_HEADS_AUX")) == 0);
   // (also in trailing-gradient mode, round 4: their 0.1 ms then run beside the persistent BPTT launch, which leaves most of the GPU
   // idle, instead of beside the encoder backward's first weight gradient)
-  const bool heads_on_aux = heads_aux && fork.on();
-  if (heads_on_aux) {
+  if (fork.on()) {
     ACVAE_TRY(heads_params(sp, tn_p, dpart_p));   // aux is behind fork.begin(): the upstream gradients are in place
   } else if (!defer) {
     ACVAE_TRY(heads_params(st, tn, dpart));
@@ -1330,7 +1329,6 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
   if (defer) {                 // d_q_z on the first stream; everything else behind the first stream's work so far, on the second
     ACVAE_TRY(dec_dz(st));
     ACVAE_TRY(Fork::edge(st.s, sp.s));
-    if (!heads_on_aux) ACVAE_TRY(heads_params(sp, tn_p, dpart_p));
     ACVAE_TRY(dec_params(sp, tn_p, dpart_p, false, !early_tn));
     ACVAE_TRY(prior_params(!early_tn));
   }

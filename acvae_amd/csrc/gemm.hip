@@ -357,10 +357,9 @@ static int skinny_plan(int M, int N, int Ktot, bool dual, bool have_ws) {
   const int tiles = cdiv(N, 32) * cdiv(M, 32);
   // split K over more workgroups when there are few tiles and K is long (the serial decode/BPTT steps)
   int S = 1;
-  static const bool splitk_on = !(getenv("ACVAE_SKINNY_SPLITK") && getenv("ACVAE_SKINNY_SPLITK")[0] == '0');  // tuning switch
   // Only the long-K, few-tile products of the BPTT steps gain: the release/acquire hand-off costs a few us
   // (measured: 48 tiles x K=512 went 6.8 -> 9.8 us with S=2, 16 tiles x K=2048 went 25 -> 13.7 us with S=8).
-  if (have_ws && splitk_on && tiles <= 16 && Ktot >= 1024) {
+  if (have_ws && tiles <= 16 && Ktot >= 1024) {
     S = 128 / tiles;
     const int maxs = Ktot / 256;       // keep >= 256 k per slice
     if (S > maxs) S = maxs;

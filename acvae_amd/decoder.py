@@ -9,7 +9,7 @@ import torch.nn as nn
 
 from . import _lib
 from .attn_model import Seq2SeqAttention
-from .encoder import ptr_table, scratch_buffer
+from .streams import scratch_buffer
 
 
 class _ProjTableFn(torch.autograd.Function):
@@ -37,7 +37,7 @@ class _ProjTableFn(torch.autograd.Function):
         E = w.shape[0]
         d_table = d_table.contiguous().float()
         st = _lib.current_stream()
-        buf = (lambda p: owner._grad_buffer(p)) if owner is not None else torch.empty_like
+        buf = (lambda p: _lib.grad_buffer(owner._grad_views, p)) if owner is not None else torch.empty_like
         seq = owner.decoder.word_embeddings if owner is not None else None
         d_emb = d_w = d_b = None
         if ctx.needs_input_grad[1]:                     # d Embedding = d_table . W  (W^T as the NT product's second operand)
@@ -174,7 +174,7 @@ class VAERNNBahdanauAttnDecoder(RNNDecoder):
             attw = torch.empty(N, S, device=dev); rnn_in = torch.empty(N, 3 * E, device=dev)
             sb = _lib.call("acvae_step_scratch_bytes", N, S, E, H, A, V)
             scratch = scratch_buffer(sb, dev)
-            _lib.call("acvae_decoder_step_fwd", ptr_table(owner._text_table()), w, h_prev, enc_mem, lens, encproj, z,
+            _lib.call("acvae_decoder_step_fwd", owner._text_table(), w, h_prev, enc_mem, lens, encproj, z,
                       logits, h_out, attw, rnn_in, scratch, sb, N, S, E, H, A, V, _lib.current_stream())
         return {"state": h_out.unsqueeze(0), "output": h_out.unsqueeze(1), "logits": logits.unsqueeze(1),
                 "weights": attw, "rnn_input": rnn_in.unsqueeze(1)}

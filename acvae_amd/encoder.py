@@ -13,24 +13,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import ptr_table           # (the call sites pass the lists; kept for callers that build a table themselves)
+from .streams import scratch_buffer
 
-_SCRATCH = {}
 _BLOCK_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_void_p)   # acvae_encoder_bwd_hooked's block_done
-
-
-def scratch_buffer(nbytes, device, tag=None):
-    """Grow-only scratch per (device, stream): contents are dead between library calls, and calls on one stream
-    are ordered, so one buffer per stream is enough (the posterior runs on a side stream beside the encoder).  A call
-    that leaves work behind on a second stream (acvae_decode_bwd) takes its own buffer (``tag``)."""
-    key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream, tag)
-    buf = _SCRATCH.get(key)
-    if buf is None or buf.numel() < nbytes:
-        _SCRATCH[key] = buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-    return buf
-
-
-def ptr_table(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
 def init_layer(layer):
@@ -91,9 +77,8 @@ class _Cnn10Fn(torch.autograd.Function):
             if len(masks) != mod._n_dropout_sites():
                 raise ValueError(f"dropout_masks must hold the {mod._n_dropout_sites()} masks of the forward in call order")
         seed = mod._next_seed() if training else 0
-        mt = ptr_table(masks) if masks is not None else None
-        _lib.call("acvae_encoder_fwd", ptr_table(tensors), feats, ae, pooled, saved, saved_b, scratch, scratch_b, arch,
-                  N, T, F, int(training), float(mod.p_block), float(mod.p_fc), seed, mt, _lib.current_stream())
+        _lib.call("acvae_encoder_fwd", tensors, feats, ae, pooled, saved, saved_b, scratch, scratch_b, arch,
+                  N, T, F, int(training), float(mod.p_block), float(mod.p_fc), seed, masks, _lib.current_stream())
         ctx.mod, ctx.feats, ctx.saved, ctx.masks, ctx.seed, ctx.training = mod, feats, saved, masks, seed, training
         ctx.arch = arch
         if mod.keep_saved:                       # test aid: relu_masks() reads the decisions out of this buffer
@@ -110,11 +95,10 @@ class _Cnn10Fn(torch.autograd.Function):
         outs = []
         for i, t in enumerate(tensors):
             if t.dtype.is_floating_point and t.requires_grad and i < len(tensors) - 2:
-                grads[i] = mod._grad_buffer(t)
+                grads[i] = _lib.grad_buffer(mod._grad_views, t)
         d_ae = d_ae.contiguous().float()
         scratch_b = _lib.call("acvae_encoder_scratch_bytes", ctx.arch, N, T, F)
         scratch = scratch_buffer(scratch_b, feats.device)
-        mt = ptr_table(ctx.masks) if ctx.masks is not None else None
         hook, failed = None, []
         if mod._grad_ready_cb is not None:
             # host callback after each ConvBlock's gradient kernels are queued: the data-parallel exchange starts the
@@ -125,8 +109,8 @@ class _Cnn10Fn(torch.autograd.Function):
                 except BaseException as exc:          # an exception cannot cross the C frame: re-raised below
                     failed.append(exc)
             hook = _BLOCK_HOOK(block_done)
-        _lib.call("acvae_encoder_bwd_hooked", ptr_table(tensors), ptr_table(grads), feats, d_ae, ctx.saved,
-                  ctx.saved.numel(), scratch, scratch_b, ctx.arch, N, T, F, int(ctx.training), float(mod.p_block), ctx.seed, mt,
+        _lib.call("acvae_encoder_bwd_hooked", tensors, grads, feats, d_ae, ctx.saved,
+                  ctx.saved.numel(), scratch, scratch_b, ctx.arch, N, T, F, int(ctx.training), float(mod.p_block), ctx.seed, ctx.masks,
                   _lib.current_stream(), ctypes.cast(hook, ctypes.c_void_p) if hook is not None else None, None)
         if failed:
             raise failed[0]
@@ -194,11 +178,6 @@ class _PannsCnn(nn.Module):
 
     def _weights(self):
         return [t for t in self._param_table()[:-2] if isinstance(t, nn.Parameter)]
-
-    def _grad_buffer(self, p):
-        if self._grad_views is not None and p in self._grad_views:
-            return self._grad_views[p].detach()     # fresh alias: autograd adopts it as .grad without a copy
-        return torch.empty_like(p)
 
     def relu_masks(self):
         """The ReLU decisions of the last forward (``keep_saved = True`` must have been set before it), one bool tensor

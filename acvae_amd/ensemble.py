@@ -26,7 +26,8 @@ import torch.nn as nn
 
 from . import _lib
 from .batch import collate_fn
-from .encoder import ptr_table, scratch_buffer
+from ._lib import ptr_table
+from .streams import scratch_buffer
 from .evaluate import collect_predictions, predictions_payload
 from .frontend import refuse_augmented
 from .seq_train_model import ScstWrapper
@@ -119,8 +120,7 @@ class Ensemble(nn.Module):
         if sb < 0:
             raise RuntimeError(f"acvae_ensemble_search: unsupported dimensions (N={N}, beam={beam}, max_length={T})")
         scratch = scratch_buffer(sb, dev)
-        _lib.call("acvae_ensemble_search_constrained" if on else "acvae_ensemble_search", params, ptr_table(mems),
-                  ptr_table(lens), ptr_table(epss), *host, M, self.start_idx, self.end_idx, 1 if method == "greedy" else 0,
+        _lib.call("acvae_ensemble_search_constrained" if on else "acvae_ensemble_search", params, mems, lens, epss, *host, M, self.start_idx, self.end_idx, 1 if method == "greedy" else 0,
                   seqs, logprobs, scratch, sb, N, beam, T, self.vocab_size, _lib.current_stream(),
                   *(_constraint_args(con) if on else ()))
         return {"seqs": seqs, "logprobs": logprobs}

@@ -1,14 +1,12 @@
 """Mirror of ``models/text_encoder.py``: ``PosteriorRNN_hybrid`` (:156-216) and ``PriorRNN`` (:218-268)
 with the reference's constructor keywords, parameter names and initialisation (``init`` :25-41)."""
-import ctypes
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib
 from .attn_model import Seq2SeqAttention
-from .encoder import ptr_table, scratch_buffer
+from .streams import scratch_buffer
 
 
 def _init_weights(m):
@@ -102,8 +100,8 @@ class _PosteriorFn(torch.autograd.Function):
         _lib.persist_status(dev)                 # the device's status words are registered before the first persistent launch
         # one layer: the one-layer entry point (the same code in the library; num_layers = 1 of the stacked call)
         name, extra = ("acvae_posterior_fwd", ()) if NL == 1 else \
-            ("acvae_posterior_stack_fwd", (ptr_table(upper), NL, keep_d, scale))
-        _lib.call(name, ptr_table(params), *extra, caps_d, caps_d.stride(0), lens1_d, eps_q, qm, ql, qz, utt, saved,
+            ("acvae_posterior_stack_fwd", (upper, NL, keep_d, scale))
+        _lib.call(name, params, *extra, caps_d, caps_d.stride(0), lens1_d, eps_q, qm, ql, qz, utt, saved,
                   saved_b, scratch, scratch_b, N, Tc, E, Hq, V, _lib.current_stream(), _lib.call_flags())
         ctx.set_materialize_grads(False)         # unused outputs arrive as None in backward (no zero-fill launches)
         ctx.mod, ctx.saved, ctx.dims, ctx.scale = mod, saved, (N, Tc, E, Hq, V), scale
@@ -119,22 +117,23 @@ class _PosteriorFn(torch.autograd.Function):
         NL = mod.num_layers
         params = mod._text_table()
         grads = [None] * len(params)
+        owner = mod._owner() if mod._owner is not None else None
+        views = getattr(owner, "_grad_views", None)
         for i, p in enumerate(params):
             if p is not None and p.requires_grad and 10 <= i <= 20:
-                grads[i] = mod._grad_buffer(p)
+                grads[i] = _lib.grad_buffer(views, p)
         upper = mod._upper_table()
         # every upper-layer gradient is written (a frozen tensor's into a throwaway buffer)
-        upper_g = [mod._grad_buffer(p) if p.requires_grad else torch.empty_like(p) for p in upper]
+        upper_g = [_lib.grad_buffer(views, p) if p.requires_grad else torch.empty_like(p) for p in upper]
         c = lambda t: None if t is None else t.contiguous().float()
         scratch_b = _lib.call("acvae_posterior_stack_scratch_bytes", N, Tc, E, Hq, V, NL)
         scratch = scratch_buffer(scratch_b, eps_q.device)
         name, extra = ("acvae_posterior_bwd", ()) if NL == 1 else \
-            ("acvae_posterior_stack_bwd", (ptr_table(upper), ptr_table(upper_g), NL, keep_d, ctx.scale))
-        _lib.call(name, ptr_table(params), ptr_table(grads), *extra, lens1_d, eps_q, ql, c(d_qm), c(d_ql), c(d_qz),
+            ("acvae_posterior_stack_bwd", (upper, upper_g, NL, keep_d, ctx.scale))
+        _lib.call(name, params, grads, *extra, lens1_d, eps_q, ql, c(d_qm), c(d_ql), c(d_qz),
                   c(d_utt), ctx.saved, ctx.saved.numel(), scratch, scratch_b, N, Tc, E, Hq, V, _lib.current_stream(),
                   _lib.call_flags())
         ctx.saved = None
-        owner = mod._owner() if mod._owner is not None else None
         if owner is not None and owner._grad_ready_cb is not None:
             owner._grad_ready_cb("text")            # decode backward always precedes this node (it consumes d_q_z)
         pairs = list(zip(params, grads)) + [(p, g if p.requires_grad else None) for p, g in zip(upper, upper_g)]
@@ -187,13 +186,6 @@ class PosteriorRNN_hybrid(PosteriorBaseEncoder):
     def keep_p(self):
         """The inter-layer dropout probability the next forward applies (0 when it draws no masks)."""
         return float(self.dropout) if self.training and self.num_layers > 1 and self.dropout > 0 else 0.0
-
-    def _grad_buffer(self, p):
-        owner = self._owner() if self._owner is not None else None
-        views = getattr(owner, "_grad_views", None) if owner is not None else None
-        if views is not None and p in views:
-            return views[p].detach()
-        return torch.empty_like(p)
 
     def forward(self, x, lengths, eps=None, keep=None):
         """x: caption ids [N,L] (float or long, as the collate fn pads with float zeros); lengths: cap_lens.
@@ -276,6 +268,6 @@ class PriorRNN(PriorBaseEncoder):
             H, A = owner.decoder.model.hidden_size, owner.decoder.attn.attn_size
             sb = _lib.call("acvae_step_scratch_bytes", N, S, E, H, A, V)
             scratch = scratch_buffer(sb, dev)
-            _lib.call("acvae_prior_step_fwd", ptr_table(owner._text_table()), w, enc_mem, lens_d, encproj, h_prev,
+            _lib.call("acvae_prior_step_fwd", owner._text_table(), w, enc_mem, lens_d, encproj, h_prev,
                       c_prev, last_z, eps, mean, logv, z, h, c, attw, scratch, sb, N, S, E, V, _lib.current_stream())
         return {"mean": mean, "log": logv, "hiddens_state": (h.unsqueeze(0), c.unsqueeze(0)), "z": z}

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, streams
 from .optim import FlatOptimizer, check_group, resolve
 from .train_util import LabelSmoothingLoss, MSELoss, Normal_kl_loss, combine_losses
 
@@ -365,9 +365,7 @@ class TrainStep:
         self.sync_buffers()
         ready = getattr(feats, "_acvae_ready", None)
         if ready is not None:                       # a batch uploaded by prefetch(): order this step behind its copy
-            cur = torch.cuda.current_stream()
-            cur.wait_event(ready)
-            feats.record_stream(cur)
+            streams.hand_over(feats, ready)
         if augment is not None:
             from .augment import apply
             if not feats.is_cuda:

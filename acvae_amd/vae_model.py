@@ -23,8 +23,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, text_encoder
-from .encoder import ptr_table, scratch_buffer
+from . import _lib, streams, text_encoder
+from .streams import scratch_buffer
 from .word_model import CaptionModel
 
 
@@ -84,7 +84,8 @@ class _DecodeFn(torch.autograd.Function):
         if constrain:
             entry, extra = "acvae_decode_fwd_constrained", extra + _constraint_args(constrain)
         _lib.persist_status(dev)                 # the device's status words are registered before the first persistent launch
-        _lib.call(entry, ptr_table(params), mem,
+        # (plain call, nothing kept: the forward entries join both streams before they return)
+        _lib.call(entry, params, mem,
                   mem_lens_d, caps_d, caps_d.stride(0) if train else 0, lens1_d, q_z, eps_p, ss_arr, dis_arr, logits,
                   outputs, seqs, slp, attw, pm, pl, pz, putt, hfin, hp, cp, saved, saved_b, scratch, scratch_b, *dims, model.start_idx,
                   model.end_idx, _lib.current_stream(), model._aux_stream(), int(method), float(temp), noise, keep,
@@ -124,7 +125,7 @@ class _DecodeFn(torch.autograd.Function):
                 d_logits = dl if d_logits is None else dl.add_(d_logits)
         for i, p in enumerate(params):
             if p is not None and p.requires_grad and i in mine:
-                grads[i] = model._grad_buffer(p)
+                grads[i] = _lib.grad_buffer(model._grad_views, p)
         c = lambda t: None if t is None else t.contiguous().float()
         d_mem = torch.empty(N, S, Eenc, device=dev)
         d_qz = None if ctx.rollout else torch.empty(N, Tc, E, device=dev)
@@ -133,32 +134,32 @@ class _DecodeFn(torch.autograd.Function):
         ups = [c(t) for t in (d_logits, d_outputs, d_pm, d_pl, d_pz, d_putt)]
         main, aux = _lib.current_stream(), model._aux_stream()
         flags = _lib.call_flags(defer=model.defer_param_grads) | (_lib.FLAG_ROLLOUT_GRAD if ctx.rollout else 0)
-        _lib.call("acvae_decode_bwd", ptr_table(params), ptr_table(grads), mem, mem_lens_d, lens1_d, eps_p, ctx.dis_arr,
-                  outputs, attw, pl, *ups, d_mem, d_qz, ctx.saved, ctx.saved.numel(), scratch, scratch_b, *ctx.dims, main,
-                  aux, ctx.emb_keep, ctx.emb_p, flags)
         defers = bool(_lib.lib().acvae_decode_bwd_defers(ctx.dis_arr, Tc, main, aux, flags))   # a yes / no answer, not a status
+        cur = torch.cuda.current_stream()
+        side = model.streams.get("decode", cur) if defers else None
+        # side: the call then leaves the parameter gradients trailing on the second stream, and autograd frees what they
+        # read (saved, the upstream gradients, the encoder memory itself without an ln projection) while it still runs.
+        # EVERY tensor argument is kept, not a chosen few: one kept without need only delays the reuse of its block until the
+        # second stream has passed, one that is missing is a silent wrong gradient, and which of them the trailing work reads
+        # is decided in csrc/decoder.hip, not here.
+        _lib.call_keeping(side, "acvae_decode_bwd", params, grads, mem, mem_lens_d, lens1_d, eps_p, ctx.dis_arr, outputs, attw,
+                          pl, *ups, d_mem, d_qz, ctx.saved, ctx.saved.numel(), scratch, scratch_b, *ctx.dims, main, aux,
+                          ctx.emb_keep, ctx.emb_p, flags)
         if model._grad_ready_cb is not None:
             ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
+            ev.record(cur)
             if not defers:                       # every gradient this call writes is ordered on the current stream
                 model._grad_ready_cb("decode", ev)
             else:                                # ... or on the decode calls' second stream: a second event behind its trailing work
                 ev_aux = torch.cuda.Event()
-                ev_aux.record(model._side_stream(torch.cuda.current_stream()))
+                ev_aux.record(side)
                 model._grad_ready_cb("decode_deferred", (ev, ev_aux))
         if defers:
             # The parameter gradients are still being computed on the decode calls' second stream (beside the posterior's and
             # the encoder's backward, which start now: d_mem and d_q_z are complete on the current stream).  Their consumers:
             # the gradient exchange (the event above) and whoever reads .grad after backward() - joined here at the end of
             # the pass.
-            side, cur = model._side_stream(torch.cuda.current_stream()), torch.cuda.current_stream()
-            # (mem too: without an ln projection the trailing products read the encoder memory itself, not a copy in `saved`)
-            for t in [ctx.saved, outputs, d_qz, mem] + [u for u in ups if u is not None]:
-                t.record_stream(side)                      # freed by autograd while the side stream still reads them
-            if any(p is not None and p.is_leaf and p.grad is not None for p in params):   # (a projected embedding table is not a leaf)
-                cur.wait_stream(side)                      # autograd will accumulate into .grad on this stream right away
-            else:
-                torch.autograd.Variable._execution_engine.queue_callback(lambda: cur.wait_stream(side))
+            streams.join_after_backward(cur, side, params)
         ctx.saved = None
         outs = [next((g for p, g in zip(params, grads) if p is w), None) for w in model._decode_weights()]
         return (None, d_mem, None, None, None, d_qz, None, None, None, None, None, *outs)
@@ -235,6 +236,7 @@ class Hybrid_VAEModel(CaptionModel):
         self.pnet._owner = weakref.ref(self)
         self.decoder._owner = weakref.ref(self)
         self._encproj_cache = {}
+        self.streams = streams.SecondStreams()
         self.use_side_stream = os.environ.get("ACVAE_SIDE_STREAM", "1") != "0"
         # the decode backward leaves its parameter gradients trailing on the second stream beside the encoder backward
         # (_DecodeFn.backward joins it; ACVAE_FLAG_DEFER_PARAM_GRADS per call); ACVAE_DECODE_DEFER=0 or
@@ -266,11 +268,6 @@ class Hybrid_VAEModel(CaptionModel):
         t = self._text_table()
         return [p for i, p in enumerate(t) if p is not None and (i < 10 or i >= 21)]
 
-    def _grad_buffer(self, p):
-        if self._grad_views is not None and p in self._grad_views:
-            return self._grad_views[p].detach()
-        return torch.empty_like(p)
-
     def _set_grad_views(self, views):
         self._grad_views = views
         self.encoder._grad_views = views
@@ -285,7 +282,7 @@ class Hybrid_VAEModel(CaptionModel):
         N, S, E = enc_mem.shape
         H, A = self.decoder.model.hidden_size, self.decoder.attn.attn_size
         out = torch.empty(N, S, A if which == 0 else E, device=enc_mem.device)
-        _lib.call("acvae_attn_precompute", ptr_table(self._text_table()), which, enc_mem, out, N, S, E, H, A,
+        _lib.call("acvae_attn_precompute", self._text_table(), which, enc_mem, out, N, S, E, H, A,
                   _lib.current_stream())
         self._encproj_cache[which] = (key, out, enc_mem)      # keep enc_mem alive so its address cannot be reused
         return out
@@ -341,7 +338,7 @@ class Hybrid_VAEModel(CaptionModel):
         sb = _lib.call("acvae_beam_search_constrained_scratch_bytes" if on else "acvae_beam_search_scratch_bytes", N,
                        beam_size, max_length, S, E, H, A, V)
         scratch = scratch_buffer(sb, dev)
-        _lib.call("acvae_beam_search_constrained" if on else "acvae_beam_search", ptr_table(self._text_table()), mem_all,
+        _lib.call("acvae_beam_search_constrained" if on else "acvae_beam_search", self._text_table(), mem_all,
                   lens_all, eps_all, int(self.start_idx), seqs, attw, scratch, sb, N, beam_size, max_length, S, E, H, A, V,
                   _lib.current_stream(), *((int(self.end_idx),) + _constraint_args(con) if on else ()))
         return {"seqs": seqs, "attn_weights": attw}
@@ -439,26 +436,9 @@ class Hybrid_VAEModel(CaptionModel):
         dev = device if device is not None else next(self.parameters()).device
         _lib.check_persist_status(dev)
 
-    def _side_stream(self, main):
-        """Second stream of the decode calls (prior chain forward, trailing parameter gradients backward)."""
-        if getattr(self, "_side", None) is None or self._side.device != main.device:
-            self._side = torch.cuda.Stream(device=main.device, priority=int(os.environ.get("ACVAE_SIDE_PRIO", "0")))
-        return self._side
-
-    def _post_stream(self, main):
-        """The posterior's own stream (forward beside the encoder, backward beside the decode calls' trailing parameter
-        gradients: on the SAME stream its backward - which the encoder's backward waits for - sat behind 0.6 ms of them)."""
-        if os.environ.get("ACVAE_POST_STREAM", "1") == "0":       # A/B: the posterior on the decode calls' second stream, as until round 4
-            return self._side_stream(main)
-        if getattr(self, "_side_q", None) is None or self._side_q.device != main.device:
-            self._side_q = torch.cuda.Stream(device=main.device, priority=int(os.environ.get("ACVAE_POST_PRIO", "0")))
-        return self._side_q
-
     def _aux_stream(self):
         """Second HIP stream handle for the decode calls (prior chain beside the decoder chain), or None."""
-        if not self.use_side_stream or os.environ.get("ACVAE_DECODE_AUX", "1") == "0":
-            return None
-        return self._side_stream(torch.cuda.current_stream()).cuda_stream
+        return self.streams.aux_handle() if self.use_side_stream else None
 
     # ---- reference API
     def train_forward(self, encoded, caps, cap_lens, **kwargs):
@@ -513,7 +493,7 @@ class Hybrid_VAEModel(CaptionModel):
             # HIP stream beside the MFMA-bound encoder; autograd replays its backward on that stream too, where it
             # overlaps with the encoder backward.
             main = torch.cuda.current_stream()
-            side = self._post_stream(main) if self.use_side_stream else main
+            side = self.streams.get("posterior", main) if self.use_side_stream else main
             eps_q = None if self.noise is None else self.noise.get("eps_q")
             q_keep = None if self.noise is None else self.noise.get("q_keep")
             lens1 = np.asarray(cap_lens) - 1
@@ -535,25 +515,16 @@ class Hybrid_VAEModel(CaptionModel):
             prep = self._host_prepare(n_rows, feats.device, caps, cap_lens, kwargs)
             if share is not None:                                  # (index on the host, index / offsets / rows on the device)
                 share = (share[0],) + tuple(_lib.h2d(a, feats.device) for a in share[:3])
-            if side is not main:
-                side.wait_stream(main)
-                prep["caps_d"].record_stream(side)
-                if q_p > 0:
-                    q_keep.record_stream(side)                     # read by the posterior's forward and backward there
-            # The encoder is queued FIRST and the posterior second (it still starts at once: the side stream only waits
-            # for what main held before this point).  Autograd runs the later-created node first, so in the backward
-            # the posterior's kernels and its gradient bucket are queued before the long encoder backward: under data
-            # parallelism the 20 MB posterior bucket then travels beside the encoder backward instead of behind it.
-            encoded = self.encoder(feats, feat_lens)
-            if share is not None:
-                encoded = self._share_rows(encoded, *share)
-            with torch.cuda.stream(side):
-                qnetout = self.qnet(prep["caps_d"], cap_lens, eps=eps_q, keep=q_keep)
-            if side is not main:
-                main.wait_stream(side)
-                for v in qnetout.values():
-                    if isinstance(v, torch.Tensor):
-                        v.record_stream(main)
+            # (caps_d and the masks are read by the posterior's forward and backward on the side stream)
+            with streams.beside(main, side, prep["caps_d"], q_keep) as on_side:
+                # The encoder is queued FIRST and the posterior second (it still starts at once: the side stream only waits
+                # for what main held before this point).  Autograd runs the later-created node first, so in the backward
+                # the posterior's kernels and its gradient bucket are queued before the long encoder backward: under data
+                # parallelism the 20 MB posterior bucket then travels beside the encoder backward instead of behind it.
+                encoded = self.encoder(feats, feat_lens)
+                if share is not None:
+                    encoded = self._share_rows(encoded, *share)
+                qnetout = on_side(self.qnet, prep["caps_d"], cap_lens, eps=eps_q, keep=q_keep)
             encoded["_prep"] = prep
             encoded.update(qnetout)
             return self.train_forward(encoded, caps, cap_lens, **kwargs)

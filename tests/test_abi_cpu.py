@@ -32,7 +32,8 @@ def test_bad_arguments_are_reported_not_thrown():
 
 def test_library_owns_no_device_memory_and_no_behaviour_switches():
     """SURVEY 8(b) Ownership: the caller owns every buffer, workspaces included - no hipMalloc / hipFree (nor the managed /
-    async / host-allocating variants) anywhere in csrc/, and no process-global acvae_set_* switches in the ABI."""
+    async / host-allocating variants) anywhere in csrc/, no process-global acvae_set_* switches in the ABI, and one
+    environment variable read in csrc/, ACVAE_CONV_WINO, which is also the only one the header names."""
     import pathlib
     import re
     root = pathlib.Path(__file__).resolve().parents[1]
@@ -44,6 +45,69 @@ def test_library_owns_no_device_memory_and_no_behaviour_switches():
     protos, _ = _lib.parse_header()
     assert not [n for n in protos if n.startswith("acvae_set_")]
     assert "ACVAE_DEV_LIB" not in (root / "acvae_amd" / "_lib.py").read_text()
+    # ... and one environment variable: every getenv( in csrc/ names ACVAE_CONV_WINO (the benchmark's and two tests' A/B)
+    reads = []
+    for path in sorted((root / "acvae_amd" / "csrc").glob("*")):
+        if path.suffix in (".hip", ".h"):
+            code = re.sub(r"//[^\n]*", "", path.read_text())
+            reads += [(path.name, m.group(1).strip()) for m in re.finditer(r"\bgetenv\s*\(([^)]*)\)", code)]
+    assert reads and all(arg == '"ACVAE_CONV_WINO"' for _, arg in reads), reads
+    # the header's conventions paragraph says the same: from where it speaks of environment variables to its next item,
+    # the only ACVAE_* name is that one
+    head = (root / "include" / "acvae_hip.h").read_text()
+    conventions = head[head.index("Conventions"):head.index("*/")]
+    assert conventions.count("environment variable") == 1
+    switches = conventions[conventions.index("environment variable"):]
+    switches = switches[:switches.index("\n *   - ")]
+    assert set(re.findall(r"ACVAE_\w+", switches)) == {"ACVAE_CONV_WINO"}
+
+
+def test_second_streams_are_handled_in_one_module():
+    """Cross-stream ordering and lifetimes (record_stream, wait_stream, the autograd engine's queue_callback) live in
+    acvae_amd/streams.py and nowhere else in the package."""
+    import pathlib
+    root = pathlib.Path(__file__).resolve().parents[1]
+    files = sorted((root / "acvae_amd").glob("*.py"))
+    assert (root / "acvae_amd" / "streams.py") in files
+    for path in files:
+        src = path.read_text()
+        found = [w for w in ("record_stream", "wait_stream(", "queue_callback") if w in src]
+        if path.name == "streams.py":
+            assert len(found) == 3, found
+        else:
+            assert not found, f"{path.name} uses {found}: that belongs in acvae_amd/streams.py"
+
+
+class _FakeTensor:
+    def __init__(self, is_cuda=True):
+        self.is_cuda, self.recorded = is_cuda, []
+
+    def record_stream(self, stream):
+        self.recorded.append(stream)
+
+
+def test_keep_walks_containers_and_records_each_device_tensor_once():
+    from acvae_amd import streams
+    a, b, c, d, e = (_FakeTensor() for _ in range(5))
+    host = _FakeTensor(is_cuda=False)
+    stream = object()
+    streams.keep(stream, a, None, [b, None, (c, [d])], {"x": e, "y": None, "z": host, "n": 3}, host, 7, "text", 1.5,
+                 (ctypes.c_int * 2)(1, 2))
+    for t in (a, b, c, d, e):
+        assert t.recorded == [stream]
+    assert host.recorded == []
+    # the same tensor several times in one call (a parameter in two tables): once
+    f = _FakeTensor()
+    streams.keep(stream, f, [f, (f,)], {"k": f})
+    assert f.recorded == [stream]
+    # ... and again by the next call
+    streams.keep(stream, [f])
+    assert f.recorded == [stream, stream]
+    streams.keep(stream)                       # nothing to keep
+    # _lib.call hands its whole argument list over: (checked here without a launch, through the same function)
+    g, h = _FakeTensor(), _FakeTensor()
+    streams.keep(stream, ([g, None], h, 4, None))
+    assert g.recorded == [stream] and h.recorded == [stream]
 
 
 def test_product_never_reaches_into_the_oracle():
