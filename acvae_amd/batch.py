@@ -110,20 +110,27 @@ def forward_batch_shared_encoder(model, batch, device=None, frontend=None, **kwa
     """Evaluation forward with N z-samples per clip that runs the encoder ONCE per clip: in evaluation mode (running
     BatchNorm statistics, no dropout) the encoder output of a replica equals that of its clip bit for bit, so the
     replicas share it and only the decode loop sees N rows per clip.  Same outputs as ``forward_batch(mode="eval")``
-    with the clip-major replication; ``batch[0]`` is replaced by the replicated keys likewise."""
+    with the clip-major replication; ``batch[0]`` is replaced by the replicated keys likewise.
+
+    ``rerank`` (an ``acvae_amd.consensus.Consensus``, default None = nothing changes): consensus reranking of every clip's
+    N captions on the device (``Hybrid_VAEModel._rerank``): ``seqs`` holds one picked row per clip and ``batch[0]`` keeps the
+    clips' keys."""
     refuse_augmented(frontend, "forward_batch_shared_encoder")
     n = kwargs["beam_size"]
+    rerank = kwargs.pop("rerank", None)
+    model._rerank_check(rerank, n, kwargs)
     assert not model.training and n > 1 and kwargs["method"] != "dbs"
     device = device if device is not None else next(model.parameters()).device
     if frontend is not None:                       # waveforms in, features out (see forward_batch)
         batch[1], batch[-1] = frontend(batch[1], batch[-1], device=device)
     encoded = model.encoder(batch[1].to(device), batch[-1])
-    batch[0] = [k for k in batch[0] for _ in range(n)]
+    if rerank is None:
+        batch[0] = [k for k in batch[0] for _ in range(n)]
     lens = torch.as_tensor(encoded["audio_embeds_lens"]).repeat_interleave(n, dim=0)
     rep = {"audio_embeds": encoded["audio_embeds"].repeat_interleave(n, dim=0),
            "audio_embeds_pooled": encoded["audio_embeds_pooled"].repeat_interleave(n, dim=0),
            "audio_embeds_lens": lens, "state": None}
-    return model.inference_forward(rep, **kwargs)
+    return model._rerank(model.inference_forward(rep, **kwargs), rerank, n)
 
 
 def forward_batch(model, batch, mode, device=None, augment=None, clip_index=None, frontend=None, **kwargs):

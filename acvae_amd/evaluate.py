@@ -113,7 +113,10 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
     top_p=0.9, rng="device"`` for five sampled captions per clip; ``top_k`` / ``top_p`` with any other method are a
     ValueError (``Hybrid_VAEModel._truncation``).  Constrained decoding, with every method but "dbs":
     ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``suppress_tokens`` (``Hybrid_VAEModel._constraints``),
-    e.g. ``method="beam", beam_size=3, no_repeat_ngram_size=3``.  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
+    e.g. ``method="beam", beam_size=3, no_repeat_ngram_size=3``.  ``rerank`` (an ``acvae_amd.consensus.Consensus``): with
+    ``beam_size=N`` rollouts per clip (2 <= N <= 16; "greedy", "sample" or "gumbel"), the caption written per clip is the
+    rollout that agrees most with the clip's other rollouts under CIDEr-D, chosen on the device
+    (``Hybrid_VAEModel._rerank``); the file then has the one-caption-per-clip form.  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
     or int16 PCM (``acvae_amd.frontend.read_wav``); the log-mel features are formed on the device in front of either
     forward path.  Returns the payload dict."""
     refuse_augmented(frontend, "evaluate")
@@ -121,6 +124,12 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
     kwargs.setdefault("beam_size", 1)
     collate = collate_fn([1, ])
     model.eval()
+    if kwargs.get("rerank") is None:
+        kwargs.pop("rerank", None)                 # absent and None alike: every call runs what it ran before
+    else:                                          # (refusals come in front of any work)
+        if not hasattr(model, "_rerank_check"):
+            raise ValueError(f"rerank: {type(model).__name__} has no N-samples-per-clip route to rerank")
+        model._rerank_check(kwargs["rerank"], kwargs["beam_size"], kwargs)
     key2pred = {}
     pending = []
 

@@ -447,6 +447,9 @@ class Hybrid_VAEModel(CaptionModel):
     def inference_forward(self, encoded, **kwargs):
         method = kwargs.get("method", "greedy")
         max_length = kwargs.get("max_length", self.max_length)
+        if kwargs.get("rerank") is not None:
+            raise ValueError("rerank belongs to the N-samples-per-clip routes, which know N: rollout_shared_encoder / "
+                             "forward_batch_shared_encoder / evaluate(beam_size=N)")
         self._truncation(kwargs, rollout=True)
         self._constraints(kwargs, rollout=True)
         if method == "beam":                                              # vae_model.py:884-886
@@ -476,7 +479,11 @@ class Hybrid_VAEModel(CaptionModel):
         ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length`` / ``suppress_tokens`` (all off by default; 2-input
         forward only): constrained decoding on the device, see ``_constraints``.  ``"logits"`` then holds the constrained
         rows and ``"sampled_logprobs"`` is their log-softmax at the chosen word."""
-        self._truncation(kwargs, rollout=len(input) == 2)      # (refusals come in front of the encoder's launches)
+        if kwargs.get("rerank") is not None:                   # (refusals come in front of the encoder's launches)
+            raise ValueError("rerank in the training forward: there is nothing to choose among" if len(input) == 4 else
+                             "rerank belongs to the N-samples-per-clip routes, which know N: rollout_shared_encoder / "
+                             "forward_batch_shared_encoder / evaluate(beam_size=N)")
+        self._truncation(kwargs, rollout=len(input) == 2)
         self._constraints(kwargs, rollout=len(input) == 2)
         self._forward_token = getattr(self, "_forward_token", 0) + 1     # per-forward caches (decoder.embedding_table)
         clip_index = kwargs.pop("clip_index", None)
@@ -557,7 +564,12 @@ class Hybrid_VAEModel(CaptionModel):
         """A 2-input forward with ``sample_n`` rollouts per clip that runs the encoder ONCE per clip: the memory rows are
         repeated on the device, clip-major (row ``n * sample_n + j``), and autograd folds the rows' memory gradients back
         into the clip's.  In train() the replicas of a clip therefore share the encoder's dropout masks and the BatchNorm
-        statistics are those of the clips, not of the repeated batch."""
+        statistics are those of the clips, not of the repeated batch.
+
+        ``rerank`` (an ``acvae_amd.consensus.Consensus``, default None = nothing changes): consensus reranking of the
+        clip's rollouts on the device, see ``_rerank``."""
+        rerank = kwargs.pop("rerank", None)
+        self._rerank_check(rerank, sample_n, kwargs)
         self._truncation(kwargs, rollout=True)
         self._constraints(kwargs, rollout=True)
         self._forward_token = getattr(self, "_forward_token", 0) + 1
@@ -567,7 +579,43 @@ class Hybrid_VAEModel(CaptionModel):
         rep = {"audio_embeds": encoded["audio_embeds"].repeat_interleave(n, dim=0),
                "audio_embeds_pooled": encoded["audio_embeds_pooled"].repeat_interleave(n, dim=0),
                "audio_embeds_lens": lens, "state": None}
-        return self.inference_forward(rep, **kwargs)
+        return self._rerank(self.inference_forward(rep, **kwargs), rerank, n)
+
+    def _rerank_check(self, rerank, sample_n, kwargs):
+        """The refusals of ``rerank=`` (ValueError, in front of every launch): a search (``method="beam"`` / ``"dbs"``
+        returns its own best hypotheses), fewer than 2 or more than 16 candidates per clip, rows longer than the kernel
+        takes, a forward that records a differentiable rollout (the picked rows are a choice among constants: nothing
+        flows back through it)."""
+        if rerank is None:
+            return
+        from . import consensus
+        if not isinstance(rerank, consensus.Consensus):
+            raise ValueError(f"rerank must be an acvae_amd.consensus.Consensus, got {type(rerank).__name__}")
+        method = kwargs.get("method", "greedy")
+        if method in ("beam", "dbs"):
+            raise ValueError(f"rerank with method={method!r}: a search returns its own best hypotheses; consensus reranking "
+                             "chooses among N rollouts of 'greedy', 'sample' or 'gumbel'")
+        consensus.check_sample_n(sample_n, "rerank")
+        max_length = kwargs.get("max_length", self.max_length)
+        if max_length > consensus.MAX_LENGTH:
+            raise ValueError(f"rerank: max_length={max_length}; the kernel takes rows of at most {consensus.MAX_LENGTH} tokens")
+        if self._records_rollout():
+            raise ValueError("rerank in a forward that records a differentiable rollout (train() with gradients enabled): "
+                             "the picked rows are a choice among constants; use torch.no_grad() or eval()")
+
+    def _rerank(self, output, rerank, sample_n):
+        """Consensus reranking of an N-samples-per-clip output (rows clip-major), on the device and without a
+        synchronisation: ``seqs`` becomes the picked rows [B, T] - per clip the rollout that agrees most with the clip's
+        other rollouts under CIDEr-D (``acvae_amd.consensus``) - and the dict gains ``candidates`` [B * N, T] (the rollouts),
+        ``consensus_scores`` f64 [B, N] and ``consensus_best`` i64 [B].  Every other entry keeps its B * N rows."""
+        if rerank is None:
+            return output
+        got = rerank.select(output["seqs"], sample_n, int(self.start_idx), int(self.end_idx))
+        output["candidates"] = output["seqs"]
+        output["seqs"] = got["seqs"]
+        output["consensus_scores"] = got["scores"]
+        output["consensus_best"] = got["best"]
+        return output
 
     def _records_rollout(self):
         """A 2-input forward records a graph (self-critical training) only in train() with gradients enabled and something

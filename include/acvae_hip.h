@@ -288,6 +288,32 @@ int acvae_ciderd_scores(const int64_t* seqs0, const int64_t* seqs1, int64_t ld, 
                         const int* row_doc, const int* row_src, const double* len_factor, int n_len, double* score,
                         void* stream);
 int acvae_ciderd_reward(const double* score, int n, int sample_n, float* reward, double* reward_mean, void* stream);
+/* Consensus (minimum-Bayes-risk) reranking of a clip's sampled captions: CIDEr-D of every candidate with the clip's OTHER
+ * candidates as its references, and the candidate that agrees most with the rest (csrc/consensus.hip, acvae_amd/consensus.py).
+ * Token rows i64 seqs [n, max_length] (row stride ld), clip-major: the candidates of clip b are rows b * sample_n + j,
+ * j = 0 .. sample_n - 1.  A row is cleaned as acvae_ciderd_scores cleans it (start_idx skipped wherever it stands, cut at the
+ * first end_idx); n-grams of orders 1..4 with the key format above; ids outside [0, 65534) count as one unknown word that
+ * no table holds.  idf_keys / idf_vals [n_idf]: ascending keys and idf of a CORPUS (not of the batch: a clip's result does
+ * not depend on what else is in the launch); a key not found has idf = log_d; n_idf == 0 is fine (the arrays are then not
+ * read), and with log_d = 1 every n-gram weighs 1.  len_factor [n_len] as above.  float64:
+ *   v_i(g) = count_i(g) idf(g);  norm_k(i) = sqrt(sum_g v_i(g)^2);  len(i) = the number of bigrams of candidate i
+ *   sim_k(i, j) = sum_{g in i} min(v_i(g), v_j(g)) v_j(g), / (norm_k(i) norm_k(j)) if both are non-zero, * len_factor[|len i - len j|]
+ *   score[b * sample_n + i] = 10 mean_k (1 / (sample_n - 1)) sum_{j != i} sim_k(i, j);  an empty candidate scores 0
+ *   best[b] = the lowest index among the maxima of the clip's scores;  picked[b, :] (optional, i64 [n / sample_n,
+ *   max_length], dense) = row b * sample_n + best[b]
+ * Every sum has a fixed order (n-grams in order of first appearance, j ascending, orders ((s0 + s1) + s2) + s3): two runs
+ * are bit-equal.  No atomics, no transcendental function.  One launch: one workgroup per clip, one wavefront per candidate,
+ * all of a clip's vectors in dynamic LDS, 3888 bytes per candidate (62208 bytes at sample_n = 16, inside the 64 KB a launch
+ * may ask for without more ado; no workspace).  Limits: 2 <= sample_n <= ACVAE_CONSENSUS_MAX_SAMPLES (the wavefronts of one
+ * workgroup), max_length <= ACVAE_CONSENSUS_MAX_LENGTH (one lane per word).  Every index is formed from the launch geometry
+ * or clamped.  A NULL seqs / len_factor / score / best, sample_n outside that range, n not a positive multiple of sample_n,
+ * max_length outside [1, 64], ld < max_length, n_len <= 0, a negative n_idf, or n_idf > 0 with a NULL table -> ACVAE_EINVAL
+ * before any launch. */
+#define ACVAE_CONSENSUS_MAX_LENGTH 64
+#define ACVAE_CONSENSUS_MAX_SAMPLES 16
+int acvae_consensus_scores(const int64_t* seqs, int64_t ld, int n, int sample_n, int max_length, int start_idx, int end_idx,
+                           const uint64_t* idf_keys, const double* idf_vals, int n_idf, double log_d,
+                           const double* len_factor, int n_len, double* score, int64_t* best, int64_t* picked, void* stream);
 /* mean((a-b)^2) over n elements and its backward (runner :317, nn.MSELoss). */
 int acvae_mse_fwd(const float* a, const float* b, float* partials, float* out_scalar, int64_t n, void* stream);
 int acvae_mse_bwd(const float* a, const float* b, const float* grad_out, float* da, float* db, int64_t n, void* stream);
