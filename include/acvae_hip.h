@@ -419,6 +419,14 @@ int acvae_encoder_bwd_hooked(const void* const* params, void* const* grads, cons
  *   acvae_bn_relu_pool_fwd  P = dropout(avg_pool2x2(relu(Y*scale + shift)))  (pool != 0) or dropout(relu(..)) (pool == 0:
  *                       ConvBlock pool_size (1,1)); bn = [4][C] as above; dropout p_drop with Philox(seed, site) or an
  *                       explicit keep mask (NCHW order), p_drop = 0 disables.
+ *                       The draw, wherever an entry takes (p_drop, seed, site, keep_mask) and keep_mask == NULL - forward
+ *                       and backward recompute it, they never store it: element e of the site's STORED output (flat index
+ *                       in NHWC order of the pooled / output tensor; n*C + c for the encoders' two head sites) takes
+ *                       word e & 3 of r = Philox4x32-10(key = (lo32(seed), hi32(seed)),
+ *                       counter = (lo32(e >> 2), hi32(e >> 2), site, 0x5eed5eed)) and is kept iff
+ *                       (float)(word >> 8) * 2^-24 >= p_drop, evaluated in fp32; kept elements are multiplied by
+ *                       1.0f / (1.0f - p_drop).  tests/philox_ref.py restates it on the host and
+ *                       tests/test_dropout_philox_gpu.py holds every kernel that draws to it bit for bit.
  *   acvae_bn_relu_bwd   backward of relu(bn(Y)) for upstream dO: upstream 0 = dO [N,H,W,C] as is, 1 = dO [N,H/2,W/2,C]
  *                       through dropout + 2x2 average pool, 2 = through dropout only.  Writes dgamma, dbeta [C] and dY.
  *                       training == 0: evaluation-mode BatchNorm (dY = scale * g).
