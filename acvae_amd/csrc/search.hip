@@ -170,16 +170,18 @@ extern "C" int acvae_decoder_step_fwd(const void* const* params, const int64_t* 
 namespace {
 struct SearchMember { const void* const* params; const float* mem; const int64_t* mem_lens; const float* eps; int S, E, H, A; };
 struct MemberLayout { StepLayout sl; long step, encd, encp, h, hp, cp, lz, mean, logv, z, h2, hp2, cp2, attp, attw, logits, rnn; };
-struct SearchLayout { MemberLayout m[ACVAE_ENSEMBLE_MAX]; long scores, topk, best, words, whist, total; int keep_attw, keep_hist; };
+struct SearchLayout { MemberLayout m[ACVAE_ENSEMBLE_MAX]; long scores, topk, best, words, whist, frec, norm, total; int keep_attw, keep_hist, keep_fin; };
 // keep_attw: member 0's decoder attention weights of every step, [T][R][S], for the trace-back; else [R][S], overwritten.
 // keep_hist: the rows' word histories of a constrained beam search, int64 [2][R][T] (the one read, the one gathered into).
-int search_layout(const SearchMember* mb, int M, int N, int beam, int T, int V, int keep_attw, int keep_hist,
+// keep_fin: the records of a finishing beam search, f [T][R], and its norm table [T].
+int search_layout(const SearchMember* mb, int M, int N, int beam, int T, int V, int keep_attw, int keep_hist, int keep_fin,
                   SearchLayout& L) {
   if (M < 1 || M > ACVAE_ENSEMBLE_MAX || N <= 0 || beam <= 0 || T <= 0) return ACVAE_EINVAL;
   const long R = (long)N * beam;
   if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
   L.keep_attw = keep_attw;
   L.keep_hist = keep_hist;
+  L.keep_fin = keep_fin;
   Bump b;
   for (int m = 0; m < M; ++m) {
     MemberLayout& o = L.m[m];
@@ -201,6 +203,8 @@ int search_layout(const SearchMember* mb, int M, int N, int beam, int T, int V, 
   L.best = b.take(R);
   L.words = b.take(2 * ((long)(3 * T + 2) * R));        // int64: word [R], argmax [R], per step idx / parent / word [T][R]
   L.whist = keep_hist ? b.take(2 * (2 * R * T)) : 0;     // int64; behind everything else: the rest lies where it lay
+  L.frec = keep_fin ? b.take((long)T * R) : 0;
+  L.norm = keep_fin ? b.take(T) : 0;
   L.total = b.off;
   return ACVAE_OK;
 }
@@ -257,17 +261,147 @@ __global__ __launch_bounds__(256) void beam_trace_kernel(const int64_t* __restri
   }
 }
 
+// ---- finishing mode (include/acvae_hip.h has the definition): hypotheses end at end_idx, n-best by score / norm[t]
+// Finishing as the entries receive it; `norm` is a HOST array [T].  Off: no launch is added and no buffer is kept.
+struct Finishing {
+  int on = 0, nbest = 1;
+  const float* norm = nullptr;
+  int64_t* nb_seqs = nullptr; float* nb_scores = nullptr; float* nb_logprobs = nullptr; int* nb_lengths = nullptr;
+};
+// Values alone (what acvae_beam_finish refuses too).
+int finishing_check(const Finishing& f, int beam, int T) {
+  if (!f.on) return ACVAE_OK;
+  if (f.nbest < 1 || f.nbest > beam || beam > 16 || T <= 0) return ACVAE_EINVAL;
+  if (!f.norm || !f.nb_seqs || !f.nb_scores || !f.nb_logprobs || !f.nb_lengths) return ACVAE_EINVAL;
+  for (int t = 0; t < T; ++t)
+    if (!isfinite(f.norm[t]) || !(f.norm[t] > 0.f)) return ACVAE_EINVAL;
+  return ACVAE_OK;
+}
+// The norm table goes to the device as the suppress list does, by value in kernel arguments, 64 entries a launch.
+struct NormChunk { float v[64]; };
+__global__ __launch_bounds__(64) void norm_fill_kernel(NormChunk c, float* __restrict__ dst, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = c.v[threadIdx.x];
+}
+int norm_upload(const float* norm_host, float* dst, int T, hipStream_t s) {
+  for (int b = 0; b < T; b += 64) {
+    NormChunk c;
+    const int n = T - b < 64 ? T - b : 64;
+    for (int i = 0; i < 64; ++i) c.v[i] = i < n ? norm_host[b + i] : 1.f;
+    hipLaunchKernelGGL(norm_fill_kernel, dim3(1), dim3(64), 0, s, c, dst + b, n);
+  }
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+// Steps 1-3 on the R rows of a step, after its top-k: record, then retire.  One thread per row.
+__global__ __launch_bounds__(256) void beam_retire_kernel(float* __restrict__ c, const int64_t* __restrict__ word,
+                                                          float* __restrict__ f, int64_t end_idx, int last, int R) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const float v = c[r];
+  const bool ends = word[r] == end_idx;
+  f[r] = (v > -INFINITY && (ends || last)) ? v : -INFINITY;
+  if (ends) c[r] = -INFINITY;
+}
+// One workgroup per clip.  nbest selection passes over the clip's T * beam records in topk_flat_kernel's idiom (value, then
+// index, through wavefront shuffles): candidate i = t * beam + j, so the lower index is the earlier step, then the lower
+// row.  Then lane q walks hypothesis q's parents back from its step and writes its words, and the workgroup copies
+// hypothesis 0's attention weights.  A parent outside [0, R) is clamped into it (the driver's come from the top-k and are
+// in range; a caller-built history is the caller's).
+constexpr int FIN_THREADS = 256;
+__global__ __launch_bounds__(FIN_THREADS) void beam_finish_kernel(
+    const int64_t* __restrict__ parent, const int64_t* __restrict__ word, long hist_stride, const float* __restrict__ f,
+    const float* __restrict__ norm, const float* __restrict__ attw, int64_t* __restrict__ seqs, float* __restrict__ logprobs,
+    float* __restrict__ attw_out, int64_t* __restrict__ nb_seqs, float* __restrict__ nb_scores,
+    float* __restrict__ nb_logprobs, int* __restrict__ nb_lengths, int R, int beam, int T, int S, int nbest,
+    int64_t end_idx) {
+  __shared__ float rv[FIN_THREADS / 64];
+  __shared__ int ri[FIN_THREADS / 64];
+  __shared__ int sel[16];                                // the selected records, -1: none left
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const long r0 = (long)n * beam;
+  const int cand = T * beam;
+  for (int q = 0; q < nbest; ++q) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = tid; i < cand; i += FIN_THREADS) {
+      const int t = i / beam;
+      const float fv = f[(long)t * R + r0 + (i - t * beam)];
+      if (!(fv > -INFINITY)) continue;                   // not a record
+      bool taken = false;
+      for (int p = 0; p < q; ++p) taken = taken || (sel[p] == i);
+      const float v = __fdiv_rn(fv, norm[t]);
+      if (!taken && (v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if ((tid & 63) == 0) { rv[tid >> 6] = bv; ri[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < FIN_THREADS / 64; ++w)
+        if (rv[w] > bv || (rv[w] == bv && ri[w] < bi)) { bv = rv[w]; bi = ri[w]; }
+      sel[q] = bi == 0x7fffffff ? -1 : bi;
+    }
+    __syncthreads();
+  }
+  if (tid < nbest) {                                     // one lane per hypothesis
+    const int i = sel[tid];
+    const int t0 = i < 0 ? -1 : i / beam;
+    long r = i < 0 ? 0 : r0 + (i - t0 * beam);
+    const long o = (long)n * nbest + tid;
+    const float fv = i < 0 ? -INFINITY : f[(long)t0 * R + r];
+    nb_logprobs[o] = fv;
+    nb_scores[o] = i < 0 ? -INFINITY : __fdiv_rn(fv, norm[t0]);
+    nb_lengths[o] = t0 + 1;
+    if (tid == 0 && logprobs) logprobs[n] = fv;
+    int64_t* row = nb_seqs + o * T;
+    int64_t* row0 = tid == 0 ? seqs : nullptr;
+    if (row0) row0 += (long)n * T;
+    for (int t = T - 1; t > t0; --t) {
+      row[t] = end_idx;
+      if (row0) row0[t] = end_idx;
+    }
+    for (int t = t0; t >= 0; --t) {
+      const int64_t w = word[t * hist_stride + r];
+      row[t] = w;
+      if (row0) row0[t] = w;
+      const long p = parent[t * hist_stride + r];
+      r = p < 0 ? 0 : (p >= R ? R - 1 : p);
+    }
+  }
+  if (!attw_out) return;                                 // uniform over the block
+  const int i0 = sel[0];
+  const int t0 = i0 < 0 ? -1 : i0 / beam;
+  long r = i0 < 0 ? 0 : r0 + (i0 - t0 * beam);
+  for (int t = T - 1; t > t0; --t)
+    for (int s = tid; s < S; s += FIN_THREADS) attw_out[((long)n * S + s) * T + t] = 0.f;
+  for (int t = t0; t >= 0; --t) {                        // the weights of step t are those of the row's parent, as beam_trace_kernel
+    long p = parent[t * hist_stride + r];
+    p = p < 0 ? 0 : (p >= R ? R - 1 : p);
+    const float* w = attw + ((long)t * R + p) * S;
+    for (int s = tid; s < S; s += FIN_THREADS) attw_out[((long)n * S + s) * T + t] = w[s];
+    r = p;
+  }
+}
+
 // The driver behind both entry points; they have refused every bad argument, so nothing here fails before a launch.
 // greedy: seqs [R,T], logprobs [R,T].  Beam: seqs [N,T], logprobs [N] or null, attw_out [N,S,T] or null (not null only
 // with a layout made with keep_attw).
 // con: the controls of constrained decoding (constrain.hip), applied to every member's logits in front of the mixing; the
 // history of a row is its seqs row (greedy) or the word history kept beside the states (beam, L.keep_hist).  With
 // nothing on, no launch is added and no buffer is kept.
+// fin: finishing mode (beam only, L.keep_fin): one beam_retire_kernel launch behind every top-k, and beam_finish_kernel in
+// the place of beam_trace_kernel.  Off: neither, as with con.
 int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_idx, int64_t end_idx, int greedy,
            int64_t* seqs, float* logprobs, float* attw_out, float* sc, int N, int beam, int T, int V,
-           const acvae::Constraints& con, hipStream_t s) {
+           const acvae::Constraints& con, const Finishing& fin, hipStream_t s) {
   const int R = N * beam;
-  int64_t* wh = L.keep_hist ? (int64_t*)(sc + L.whist) : nullptr;   // the rows' histories at this step
+  float* frec = fin.on ? sc + L.frec : nullptr;
+  if (fin.on) ACVAE_TRY(norm_upload(fin.norm, sc + L.norm, T, s));
+  int64_t* wh = L.keep_hist && con.on() ? (int64_t*)(sc + L.whist) : nullptr;   // the rows' histories at this step
   int64_t* wh2 = wh ? wh + (long)R * T : nullptr;
   // per member: the buffers that change hands from step to step (greedy swaps them, the beam search gathers by parent)
   struct State { float *h, *hp, *cp, *lz, *h2, *hp2, *cp2, *z; } state[ACVAE_ENSEMBLE_MAX];
@@ -328,6 +462,9 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
     ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, topk, sc + L.scores, V, nullptr, nullptr, 0, R, V, s));
     ACVAE_TRY(acvae_topk_flat_batched(sc + L.scores, (int64_t)beam * V, (int64_t)beam * V, beam, V, topk, idx_t, par_t,
                                       nxt_t, N, beam, s));
+    if (fin.on)
+      hipLaunchKernelGGL(beam_retire_kernel, dim3((R + 255) / 256), dim3(256), 0, s, topk, nxt_t, frec + (long)t * R,
+                         end_idx, t == T - 1, R);
     if (t + 1 < T) {                                     // vae_model.py:961-968: next step's states follow their parents
       for (int m = 0; m < M; ++m) {
         const State& x = state[m];
@@ -341,7 +478,11 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
       w_t = nxt_t;
     }
   }
-  if (!greedy)                                           // hist rows are [idx | parent | word] per step: strided views
+  if (!greedy && fin.on)
+    hipLaunchKernelGGL(beam_finish_kernel, dim3(N), dim3(FIN_THREADS), 0, s, hist + R, hist + 2 * R, 3L * R, frec,
+                       sc + L.norm, sc + L.m[0].attw, seqs, logprobs, attw_out, fin.nb_seqs, fin.nb_scores, fin.nb_logprobs,
+                       fin.nb_lengths, R, beam, T, mb[0].S, fin.nbest, end_idx);
+  else if (!greedy)                                      // hist rows are [idx | parent | word] per step: strided views
     hipLaunchKernelGGL(beam_trace_kernel, dim3(N), dim3(256), 0, s, hist + R, hist + 2 * R, topk, sc + L.m[0].attw, seqs,
                        logprobs, attw_out, 3L * R, R, beam, T, mb[0].S);
   ACVAE_LAUNCH_CHECK();
@@ -353,24 +494,26 @@ namespace {
 int beam_search_entry(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
                       int64_t start_idx, int64_t* seqs, float* attw_out, void* scratch_v, int64_t scratch_bytes, int N,
                       int beam, int max_length, int S, int E, int H, int A, int V, int64_t end_idx,
-                      const acvae::Constraints& con, void* stream) {
+                      const acvae::Constraints& con, const Finishing& fin, void* stream) {
   const SearchMember mb{params, mem, mem_lens, eps, S, E, H, A};
   SearchLayout L;
   ACVAE_TRY(acvae::constraints_check_loop(con, V, (int)end_idx, max_length, beam));
-  ACVAE_TRY(search_layout(&mb, 1, N, beam, max_length, V, 1, con.on(), L));
+  ACVAE_TRY(search_layout(&mb, 1, N, beam, max_length, V, 1, con.on() || fin.on, fin.on, L));   // (one size per mode)
+  ACVAE_TRY(finishing_check(fin, beam, max_length));
+  if (fin.on && (end_idx < 0 || end_idx >= V)) return ACVAE_EINVAL;
   if (!params || !mem || !mem_lens || !eps || !seqs || !attw_out || !scratch_v) return ACVAE_EINVAL;
   // the prior LSTM is E wide; acvae_topk_flat_batched selects k <= 16 and would answer a wider beam with the same code
   if (start_idx < 0 || start_idx >= V || beam > 16 || H != E) return ACVAE_EINVAL;
   if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
   return search(&mb, 1, L, start_idx, end_idx, 0, seqs, nullptr, attw_out, (float*)scratch_v, N, beam, max_length, V, con,
-                (hipStream_t)stream);
+                fin, (hipStream_t)stream);
 }
 
 int ensemble_search_entry(const void* const* const* params, const float* const* mem, const int64_t* const* mem_lens,
                           const float* const* eps, const int* S, const int* E, const int* H, const int* A, int M,
                           int64_t start_idx, int64_t end_idx, int greedy, int64_t* seqs, float* logprobs, void* scratch_v,
                           int64_t scratch_bytes, int N, int beam, int max_length, int V, const acvae::Constraints& con,
-                          void* stream) {
+                          const Finishing& fin, void* stream) {
   if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !params || !mem || !mem_lens || !eps || !S || !E || !H || !A) return ACVAE_EINVAL;
   SearchMember mb[ACVAE_ENSEMBLE_MAX];
   for (int m = 0; m < M; ++m) {
@@ -382,11 +525,13 @@ int ensemble_search_entry(const void* const* const* params, const float* const* 
   if (start_idx < 0 || start_idx >= V || end_idx < 0 || end_idx >= V) return ACVAE_EINVAL;
   ACVAE_TRY(acvae::constraints_check_loop(con, V, (int)end_idx, max_length, beam));
   SearchLayout L;
-  ACVAE_TRY(search_layout(mb, M, N, beam, max_length, V, 0, con.on() && !greedy, L));
+  if (fin.on && greedy) return ACVAE_EINVAL;             // a greedy row has nothing to choose among
+  ACVAE_TRY(finishing_check(fin, beam, max_length));
+  ACVAE_TRY(search_layout(mb, M, N, beam, max_length, V, 0, (con.on() || fin.on) && !greedy, fin.on, L));
   if (!greedy && beam > 16) return ACVAE_EUNSUPPORTED;   // acvae_topk_flat_batched selects k <= 16: refused here, not mid-call
   if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
   return search(mb, M, L, start_idx, end_idx, greedy, seqs, logprobs, nullptr, (float*)scratch_v, N, beam, max_length, V, con,
-                (hipStream_t)stream);
+                fin, (hipStream_t)stream);
 }
 
 acvae::Constraints constraints_of(float repetition_penalty, int no_repeat_ngram_size, int min_length,
@@ -397,18 +542,26 @@ acvae::Constraints constraints_of(float repetition_penalty, int no_repeat_ngram_
   return c;
 }
 
-int64_t beam_scratch(int N, int beam, int max_length, int S, int E, int H, int A, int V, int keep_hist) {
+Finishing finishing_of(const float* length_norm_host, int nbest, int64_t* nb_seqs, float* nb_scores, float* nb_logprobs,
+                       int* nb_lengths) {
+  Finishing f;
+  f.on = 1; f.nbest = nbest; f.norm = length_norm_host;
+  f.nb_seqs = nb_seqs; f.nb_scores = nb_scores; f.nb_logprobs = nb_logprobs; f.nb_lengths = nb_lengths;
+  return f;
+}
+
+int64_t beam_scratch(int N, int beam, int max_length, int S, int E, int H, int A, int V, int keep_hist, int keep_fin = 0) {
   const SearchMember mb{nullptr, nullptr, nullptr, nullptr, S, E, H, A};
   SearchLayout L;
-  return search_layout(&mb, 1, N, beam, max_length, V, 1, keep_hist, L) == ACVAE_OK ? L.total * 4 : -1;
+  return search_layout(&mb, 1, N, beam, max_length, V, 1, keep_hist, keep_fin, L) == ACVAE_OK ? L.total * 4 : -1;
 }
 int64_t ensemble_scratch(int M, int N, int beam, int max_length, const int* S, const int* E, const int* H, const int* A, int V,
-                         int keep_hist) {
+                         int keep_hist, int keep_fin = 0) {
   if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A) return -1;
   SearchMember mb[ACVAE_ENSEMBLE_MAX];
   for (int m = 0; m < M; ++m) mb[m] = {nullptr, nullptr, nullptr, nullptr, S[m], E[m], H[m], A[m]};
   SearchLayout L;
-  return search_layout(mb, M, N, beam, max_length, V, 0, keep_hist, L) == ACVAE_OK ? L.total * 4 : -1;
+  return search_layout(mb, M, N, beam, max_length, V, 0, keep_hist, keep_fin, L) == ACVAE_OK ? L.total * 4 : -1;
 }
 }  // namespace
 
@@ -424,7 +577,7 @@ extern "C" int acvae_beam_search(const void* const* params, const float* mem, co
                                  int64_t start_idx, int64_t* seqs, float* attw_out, void* scratch_v, int64_t scratch_bytes,
                                  int N, int beam, int max_length, int S, int E, int H, int A, int V, void* stream) {
   return beam_search_entry(params, mem, mem_lens, eps, start_idx, seqs, attw_out, scratch_v, scratch_bytes, N, beam,
-                           max_length, S, E, H, A, V, 0, acvae::Constraints{}, stream);
+                           max_length, S, E, H, A, V, 0, acvae::Constraints{}, Finishing{}, stream);
 }
 extern "C" int acvae_beam_search_constrained(const void* const* params, const float* mem, const int64_t* mem_lens,
                                              const float* eps, int64_t start_idx, int64_t* seqs, float* attw_out,
@@ -435,6 +588,24 @@ extern "C" int acvae_beam_search_constrained(const void* const* params, const fl
   return beam_search_entry(params, mem, mem_lens, eps, start_idx, seqs, attw_out, scratch_v, scratch_bytes, N, beam,
                            max_length, S, E, H, A, V, end_idx,
                            constraints_of(repetition_penalty, no_repeat_ngram_size, min_length, suppress_host, n_suppress),
+                           Finishing{}, stream);
+}
+extern "C" int64_t acvae_beam_search_finishing_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A,
+                                                             int V) {
+  return beam_scratch(N, beam, max_length, S, E, H, A, V, 1, 1);
+}
+extern "C" int acvae_beam_search_finishing(const void* const* params, const float* mem, const int64_t* mem_lens,
+                                           const float* eps, int64_t start_idx, int64_t* seqs, float* attw_out,
+                                           void* scratch_v, int64_t scratch_bytes, int N, int beam, int max_length, int S,
+                                           int E, int H, int A, int V, void* stream, int64_t end_idx,
+                                           float repetition_penalty, int no_repeat_ngram_size, int min_length,
+                                           const int* suppress_host, int n_suppress, const float* length_norm_host,
+                                           int nbest, int64_t* nbest_seqs, float* nbest_scores, float* nbest_logprobs,
+                                           int* nbest_lengths) {
+  return beam_search_entry(params, mem, mem_lens, eps, start_idx, seqs, attw_out, scratch_v, scratch_bytes, N, beam,
+                           max_length, S, E, H, A, V, end_idx,
+                           constraints_of(repetition_penalty, no_repeat_ngram_size, min_length, suppress_host, n_suppress),
+                           finishing_of(length_norm_host, nbest, nbest_seqs, nbest_scores, nbest_logprobs, nbest_lengths),
                            stream);
 }
 
@@ -453,7 +624,7 @@ extern "C" int acvae_ensemble_search(const void* const* const* params, const flo
                                      int64_t* seqs, float* logprobs, void* scratch_v, int64_t scratch_bytes, int N, int beam,
                                      int max_length, int V, void* stream) {
   return ensemble_search_entry(params, mem, mem_lens, eps, S, E, H, A, M, start_idx, end_idx, greedy, seqs, logprobs,
-                               scratch_v, scratch_bytes, N, beam, max_length, V, acvae::Constraints{}, stream);
+                               scratch_v, scratch_bytes, N, beam, max_length, V, acvae::Constraints{}, Finishing{}, stream);
 }
 extern "C" int acvae_ensemble_search_constrained(const void* const* const* params, const float* const* mem,
                                                  const int64_t* const* mem_lens, const float* const* eps, const int* S,
@@ -465,5 +636,50 @@ extern "C" int acvae_ensemble_search_constrained(const void* const* const* param
   return ensemble_search_entry(params, mem, mem_lens, eps, S, E, H, A, M, start_idx, end_idx, greedy, seqs, logprobs,
                                scratch_v, scratch_bytes, N, beam, max_length, V,
                                constraints_of(repetition_penalty, no_repeat_ngram_size, min_length, suppress_host, n_suppress),
+                               Finishing{}, stream);
+}
+extern "C" int64_t acvae_ensemble_search_finishing_scratch_bytes(int M, int N, int beam, int max_length, const int* S,
+                                                                 const int* E, const int* H, const int* A, int V) {
+  return ensemble_scratch(M, N, beam, max_length, S, E, H, A, V, 1, 1);
+}
+extern "C" int acvae_ensemble_search_finishing(const void* const* const* params, const float* const* mem,
+                                               const int64_t* const* mem_lens, const float* const* eps, const int* S,
+                                               const int* E, const int* H, const int* A, int M, int64_t start_idx,
+                                               int64_t end_idx, int greedy, int64_t* seqs, float* logprobs, void* scratch_v,
+                                               int64_t scratch_bytes, int N, int beam, int max_length, int V, void* stream,
+                                               float repetition_penalty, int no_repeat_ngram_size, int min_length,
+                                               const int* suppress_host, int n_suppress, const float* length_norm_host,
+                                               int nbest, int64_t* nbest_seqs, float* nbest_scores, float* nbest_logprobs,
+                                               int* nbest_lengths) {
+  return ensemble_search_entry(params, mem, mem_lens, eps, S, E, H, A, M, start_idx, end_idx, greedy, seqs, logprobs,
+                               scratch_v, scratch_bytes, N, beam, max_length, V,
+                               constraints_of(repetition_penalty, no_repeat_ngram_size, min_length, suppress_host, n_suppress),
+                               finishing_of(length_norm_host, nbest, nbest_seqs, nbest_scores, nbest_logprobs, nbest_lengths),
                                stream);
+}
+
+// ---- the two finishing kernels alone, on caller-built histories
+extern "C" int acvae_beam_retire(float* c, const int64_t* word, float* f, int64_t end_idx, int last, int R, void* stream) {
+  if (!c || !word || !f || R <= 0) return ACVAE_EINVAL;
+  hipLaunchKernelGGL(beam_retire_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, c, word, f, end_idx,
+                     last != 0, R);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+extern "C" int acvae_beam_finish(const int64_t* parent, const int64_t* word, int64_t hist_stride, const float* f,
+                                 const float* length_norm_host, float* norm_dev, const float* attw, int64_t* seqs,
+                                 float* logprobs, float* attw_out, int64_t* nbest_seqs, float* nbest_scores,
+                                 float* nbest_logprobs, int* nbest_lengths, int N, int beam, int T, int S, int nbest,
+                                 int64_t end_idx, void* stream) {
+  if (N <= 0 || beam <= 0 || T <= 0 || (long)N * beam > (1L << 20)) return ACVAE_EINVAL;
+  ACVAE_TRY(finishing_check(finishing_of(length_norm_host, nbest, nbest_seqs, nbest_scores, nbest_logprobs, nbest_lengths),
+                            beam, T));
+  if (!parent || !word || !f || !norm_dev || hist_stride < (long)N * beam) return ACVAE_EINVAL;
+  if ((attw == nullptr) != (attw_out == nullptr) || (attw && S <= 0)) return ACVAE_EINVAL;
+  ACVAE_TRY(norm_upload(length_norm_host, norm_dev, T, (hipStream_t)stream));
+  hipLaunchKernelGGL(beam_finish_kernel, dim3(N), dim3(FIN_THREADS), 0, (hipStream_t)stream, parent, word, (long)hist_stride,
+                     f, norm_dev, attw, seqs, logprobs, attw_out, nbest_seqs, nbest_scores, nbest_logprobs, nbest_lengths,
+                     N * beam, beam, T, S, nbest, end_idx);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
 }

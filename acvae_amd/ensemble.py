@@ -31,7 +31,7 @@ from .streams import scratch_buffer
 from .evaluate import collect_predictions, predictions_payload
 from .frontend import refuse_augmented
 from .seq_train_model import ScstWrapper
-from .vae_model import CONSTRAINTS_OFF, Hybrid_VAEModel, _constraint_args
+from .vae_model import (CONSTRAINTS_OFF, Hybrid_VAEModel, _constraint_args, _finishing_args, _finishing_output)
 
 MAX_MEMBERS = int(_lib._defs["ACVAE_ENSEMBLE_MAX"])
 
@@ -70,7 +70,8 @@ class Ensemble(nn.Module):
 
     @torch.no_grad()
     def forward(self, feats, feat_lens, method="greedy", beam_size=5, max_length=20, repetition_penalty=None,
-                no_repeat_ngram_size=None, min_length=None, suppress_tokens=None):
+                no_repeat_ngram_size=None, min_length=None, suppress_tokens=None, finish_on_end=False, length_penalty=None,
+                nbest=None):
         """-> ``{"seqs": int64 [N, max_length], "logprobs": f32}`` on the device.  ``logprobs``: greedy [N, max_length], the
         mixture's log-probability of each chosen word (entries behind a row's ``end_idx`` carry no meaning); beam [N], beam
         0's final score.  A greedy row that has produced ``end_idx`` keeps ``end_idx`` to the end (base_runner.py:584,
@@ -78,7 +79,11 @@ class Ensemble(nn.Module):
 
         ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length`` / ``suppress_tokens``: constrained decoding
         (``Hybrid_VAEModel._constraints``), applied to every member's logits in front of the mixing; ``logprobs`` are then
-        those of the constrained mixture."""
+        those of the constrained mixture.
+
+        ``finish_on_end`` / ``length_penalty`` / ``nbest`` with ``method="beam"``: hypotheses finish at ``end_idx`` and are
+        ranked by a length-normalised score (``Hybrid_VAEModel._finishing``).  ``seqs`` is then hypothesis 0, ``logprobs``
+        [N] its raw log-probability, and the dict also holds ``scores``, ``lengths`` and the ``nbest_*`` entries."""
         if method not in ("greedy", "beam"):
             raise ValueError(f"Ensemble: method must be 'greedy' or 'beam', not {method!r}")
         beam = 1 if method == "greedy" else int(beam_size)
@@ -87,6 +92,8 @@ class Ensemble(nn.Module):
             dict(method=method, beam_size=beam, max_length=T, repetition_penalty=repetition_penalty,
                  no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, suppress_tokens=suppress_tokens),
             rollout=True)
+        fin = self.models[0]._finishing(dict(method=method, beam_size=beam, max_length=T, finish_on_end=finish_on_end,
+                                             length_penalty=length_penalty, nbest=nbest))
         on = con != CONSTRAINTS_OFF
         replay = self.noise.get("eps") if self.noise is not None else None
         self.noise = None
@@ -115,11 +122,18 @@ class Ensemble(nn.Module):
         host = [a.ctypes.data for a in (S_, E_, H_, A_)]
         seqs = torch.empty(N, T, dtype=torch.long, device=dev)
         logprobs = torch.empty((N, T) if method == "greedy" else (N,), device=dev)
-        sb = _lib.call("acvae_ensemble_search_constrained_scratch_bytes" if on else "acvae_ensemble_search_scratch_bytes",
+        sb = _lib.call("acvae_ensemble_search_finishing_scratch_bytes" if fin is not None else
+                       "acvae_ensemble_search_constrained_scratch_bytes" if on else "acvae_ensemble_search_scratch_bytes",
                        M, N, beam, T, *host, self.vocab_size)
         if sb < 0:
             raise RuntimeError(f"acvae_ensemble_search: unsupported dimensions (N={N}, beam={beam}, max_length={T})")
         scratch = scratch_buffer(sb, dev)
+        if fin is not None:
+            nb, fargs, _norm = _finishing_args(fin, T, N, dev)
+            _lib.call("acvae_ensemble_search_finishing", params, mems, lens, epss, *host, M, self.start_idx, self.end_idx, 0,
+                      seqs, logprobs, scratch, sb, N, beam, T, self.vocab_size, _lib.current_stream(),
+                      *_constraint_args(con), *fargs)
+            return dict(_finishing_output(seqs, nb), logprobs=logprobs)
         _lib.call("acvae_ensemble_search_constrained" if on else "acvae_ensemble_search", params, mems, lens, epss, *host, M, self.start_idx, self.end_idx, 1 if method == "greedy" else 0,
                   seqs, logprobs, scratch, sb, N, beam, T, self.vocab_size, _lib.current_stream(),
                   *(_constraint_args(con) if on else ()))
@@ -130,7 +144,8 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
                       batch_size=32, frontend=None, **kwargs):
     """The decoding half of ``BaseRunner.ensemble`` (base_runner.py:433-478): ``items`` are ``(audio_id, feature [T, F])`` as
     for ``evaluate()``, batched with ``collate_fn([1])`` (no replication); ``kwargs`` (``method``, ``beam_size``,
-    ``max_length`` and the constrained-decoding keywords) go to ``Ensemble.forward``.  Writes the JSON payload of
+    ``max_length``, the constrained-decoding keywords and ``finish_on_end`` / ``length_penalty`` / ``nbest``, with
+    ``nbest > 1`` the clip's n-best list is written as its ``captions``) go to ``Ensemble.forward``.  Writes the JSON payload of
     ``evaluate()`` or, with ``dcase_format``, the
     reference's two-column CSV (``file_name``, ``caption_predicted``).  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are
     ``(audio_id, 1-D waveform)`` and the log-mel features are formed on the device, once for all members.  Returns the payload
@@ -150,7 +165,8 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
         if frontend is not None:
             batch[1], batch[-1] = frontend(batch[1], batch[-1], device=device)
         output = ens(batch[1].to(device), batch[-1], **kwargs)
-        collect_predictions(batch[0], output["seqs"].cpu().numpy(), vocabulary, zh, key2pred)
+        rows = output["nbest_seqs"] if "nbest_seqs" in output and output["nbest_seqs"].shape[1] > 1 else output["seqs"]
+        collect_predictions(batch[0], rows.cpu().numpy(), vocabulary, zh, key2pred)
 
     for item in items:
         if frontend is not None:                   # collate_fn pads into float32: PCM becomes the samples it stands for

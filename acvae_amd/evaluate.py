@@ -113,7 +113,10 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
     top_p=0.9, rng="device"`` for five sampled captions per clip; ``top_k`` / ``top_p`` with any other method are a
     ValueError (``Hybrid_VAEModel._truncation``).  Constrained decoding, with every method but "dbs":
     ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``suppress_tokens`` (``Hybrid_VAEModel._constraints``),
-    e.g. ``method="beam", beam_size=3, no_repeat_ngram_size=3``.  ``rerank`` (an ``acvae_amd.consensus.Consensus``): with
+    e.g. ``method="beam", beam_size=3, no_repeat_ngram_size=3``.  ``finish_on_end=True`` with ``method="beam"`` (and
+    ``length_penalty``, ``nbest``; ``Hybrid_VAEModel._finishing``): ONE beam search of width ``beam_size`` per clip, no
+    replicas, whose hypotheses finish at ``<end>``; the file holds hypothesis 0 per clip or, with ``nbest > 1``, the clip's
+    n-best list as its ``captions``.  ``rerank`` (an ``acvae_amd.consensus.Consensus``): with
     ``beam_size=N`` rollouts per clip (2 <= N <= 16; "greedy", "sample" or "gumbel"), the caption written per clip is the
     rollout that agrees most with the clip's other rollouts under CIDEr-D, chosen on the device
     (``Hybrid_VAEModel._rerank``); the file then has the one-caption-per-clip form.  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
@@ -130,6 +133,11 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
         if not hasattr(model, "_rerank_check"):
             raise ValueError(f"rerank: {type(model).__name__} has no N-samples-per-clip route to rerank")
         model._rerank_check(kwargs["rerank"], kwargs["beam_size"], kwargs)
+    finishing = bool(kwargs.get("finish_on_end"))
+    if finishing:                                  # (its refusals too come in front of any work)
+        if not hasattr(model, "_finishing"):
+            raise ValueError(f"finish_on_end: {type(model).__name__} has no finishing beam search")
+        model._finishing(kwargs)
     key2pred = {}
     pending = []
 
@@ -139,11 +147,14 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
         batch = collate(list(pending))
         pending.clear()
         with torch.no_grad():
-            if kwargs["beam_size"] > 1 and kwargs["method"] != "dbs":     # N samples per clip: one encoder pass per clip
+            if finishing:                          # one search per clip: beam_size is its width, not a number of replicas
+                output = forward_batch(model, batch, "validation", device=device, frontend=frontend, **kwargs)
+            elif kwargs["beam_size"] > 1 and kwargs["method"] != "dbs":     # N samples per clip: one encoder pass per clip
                 output = forward_batch_shared_encoder(model, batch, device=device, frontend=frontend, **kwargs)
             else:
                 output = forward_batch(model, batch, "eval", device=device, frontend=frontend, **kwargs)
-        collect_predictions(batch[0], output["seqs"].cpu().numpy(), vocabulary, zh, key2pred)
+        rows = output["nbest_seqs"] if finishing and output["nbest_seqs"].shape[1] > 1 else output["seqs"]
+        collect_predictions(batch[0], rows.cpu().numpy(), vocabulary, zh, key2pred)
 
     for item in items:
         if frontend is not None:                   # collate_fn pads into float32: PCM becomes the samples it stands for

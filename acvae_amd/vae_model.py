@@ -31,6 +31,7 @@ from .word_model import CaptionModel
 CONSTRAINT_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_length", "suppress_tokens")
 CONSTRAINTS_OFF = (1.0, 0, 0, ())           # repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens
 SUPPRESS_MAX = int(_lib._defs["ACVAE_SUPPRESS_MAX"])
+FINISH_KEYS = ("finish_on_end", "length_penalty", "nbest")
 
 
 def _constraint_args(constrain):
@@ -39,6 +40,37 @@ def _constraint_args(constrain):
     theta, n, m, ids = constrain
     arr = np.ascontiguousarray(ids, dtype=np.int32)
     return float(theta), int(n), int(m), (arr.ctypes.data_as(_lib.ctypes.c_void_p) if len(ids) else None), len(ids)
+
+
+def length_norm(max_length, length_penalty):
+    """The finishing beam search's norm table, float32 [max_length]: ``norm[t] = float32((t + 1) ** length_penalty)``, the
+    power formed in float64 on the host.  The device divides a record by its entry, one fp32 division."""
+    def power(t):
+        try:
+            return float(t + 1) ** float(length_penalty)
+        except OverflowError:
+            return float("inf")
+
+    with np.errstate(over="ignore"):                     # (an overflow is the caller's to refuse: _finishing)
+        return np.array([power(t) for t in range(int(max_length))], np.float64).astype(np.float32)
+
+
+def _finishing_args(fin, max_length, N, dev):
+    """(length_penalty, nbest) -> the n-best outputs and the six trailing arguments of the ``acvae_*_finishing`` entries.  The
+    norm table is a HOST array that the entry reads before it returns."""
+    lp, nbest = fin
+    norm = length_norm(max_length, lp)
+    out = {"nbest_seqs": torch.empty(N, nbest, max_length, dtype=torch.long, device=dev),
+           "nbest_scores": torch.empty(N, nbest, device=dev), "nbest_logprobs": torch.empty(N, nbest, device=dev),
+           "nbest_lengths": torch.empty(N, nbest, dtype=torch.int32, device=dev)}
+    args = (norm.ctypes.data_as(_lib.ctypes.c_void_p), nbest, out["nbest_seqs"], out["nbest_scores"], out["nbest_logprobs"],
+            out["nbest_lengths"])
+    return out, args, norm
+
+
+def _finishing_output(seqs, nb):
+    """The dict of a finishing search: hypothesis 0 under the keys of today, the n-best list beside it."""
+    return dict(nb, seqs=seqs, scores=nb["nbest_scores"][:, 0], lengths=nb["nbest_lengths"][:, 0])
 
 
 class _DecodeFn(torch.autograd.Function):
@@ -314,13 +346,19 @@ class Hybrid_VAEModel(CaptionModel):
     @torch.no_grad()
     def beam_search(self, encoded, max_length, beam_size, **constraints):
         """Validation beam search, models/vae_model.py:896-995: beams expanded over the flat beam*V log-probabilities of
-        a clip, states re-gathered by prev_word_inds; returns beam 0 (the reference never fills done_beams, :986-995).
+        a clip, states re-gathered by prev_word_inds.  By default it returns beam 0 at the last step, as the reference
+        does (it never fills done_beams, :986-995): a row that has emitted ``<end>`` is expanded like any other.  With
+        ``finish_on_end=True`` hypotheses finish at ``<end>``, are scored by ``logprob / length ** length_penalty`` and the
+        ``nbest`` best are returned (see ``_finishing``).
         All clips advance together; no host synchronisation inside the loop.
 
         ``constraints``: ``repetition_penalty``, ``no_repeat_ngram_size``, ``min_length``, ``suppress_tokens`` (see
-        ``_constraints``), applied to every beam row's logits against the row's own word history."""
-        con = self._constraints(dict(constraints, method="beam", max_length=max_length, beam_size=beam_size), rollout=True)
-        unknown = set(constraints) - set(CONSTRAINT_KEYS)
+        ``_constraints``), applied to every beam row's logits against the row's own word history; and ``finish_on_end``,
+        ``length_penalty``, ``nbest``."""
+        whole = dict(constraints, method="beam", max_length=max_length, beam_size=beam_size)
+        con = self._constraints(whole, rollout=True)
+        fin = self._finishing(whole)
+        unknown = set(constraints) - set(CONSTRAINT_KEYS) - set(FINISH_KEYS)
         if unknown:
             raise TypeError(f"beam_search: unexpected keyword(s) {sorted(unknown)}")
         mem_all = self._projected_memory(encoded)
@@ -334,6 +372,14 @@ class Hybrid_VAEModel(CaptionModel):
         eps_all = self._search_noise(N, max_length, beam_size, E, dev, replay)
         seqs = torch.empty(N, max_length, dtype=torch.long, device=dev)
         attw = torch.empty(N, S, max_length, device=dev)
+        if fin is not None:
+            sb = _lib.call("acvae_beam_search_finishing_scratch_bytes", N, beam_size, max_length, S, E, H, A, V)
+            scratch = scratch_buffer(sb, dev)
+            nb, fargs, _norm = _finishing_args(fin, max_length, N, dev)
+            _lib.call("acvae_beam_search_finishing", self._text_table(), mem_all, lens_all, eps_all, int(self.start_idx), seqs,
+                      attw, scratch, sb, N, beam_size, max_length, S, E, H, A, V, _lib.current_stream(), int(self.end_idx),
+                      *_constraint_args(con), *fargs)
+            return dict(_finishing_output(seqs, nb), attn_weights=attw)
         on = con != CONSTRAINTS_OFF                       # (the word histories of a constrained search need more scratch)
         sb = _lib.call("acvae_beam_search_constrained_scratch_bytes" if on else "acvae_beam_search_scratch_bytes", N,
                        beam_size, max_length, S, E, H, A, V)
@@ -452,9 +498,10 @@ class Hybrid_VAEModel(CaptionModel):
                              "forward_batch_shared_encoder / evaluate(beam_size=N)")
         self._truncation(kwargs, rollout=True)
         self._constraints(kwargs, rollout=True)
+        self._finishing(kwargs)
         if method == "beam":                                              # vae_model.py:884-886
             return self.beam_search(encoded, max_length, kwargs.get("beam_size", 3),
-                                    **{k: kwargs[k] for k in CONSTRAINT_KEYS if k in kwargs})
+                                    **{k: kwargs[k] for k in CONSTRAINT_KEYS + FINISH_KEYS if k in kwargs})
         if method == "dbs":                                               # vae_model.py:887-893
             return self.diverse_beam_search(encoded, max_length, kwargs.get("beam_size", 5), kwargs.get("group_size", 5),
                                             kwargs.get("diversity_lambda", 0.5), kwargs.get("temperature", 1.0),
@@ -478,13 +525,18 @@ class Hybrid_VAEModel(CaptionModel):
 
         ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length`` / ``suppress_tokens`` (all off by default; 2-input
         forward only): constrained decoding on the device, see ``_constraints``.  ``"logits"`` then holds the constrained
-        rows and ``"sampled_logprobs"`` is their log-softmax at the chosen word."""
+        rows and ``"sampled_logprobs"`` is their log-softmax at the chosen word.
+
+        ``finish_on_end`` (default False) / ``length_penalty`` (1.0) / ``nbest`` (1) with ``method="beam"``: hypotheses
+        finish at ``<end>`` and are ranked by a length-normalised score, see ``_finishing``.  ``seqs`` / ``attn_weights``
+        are then hypothesis 0's and the dict also holds ``scores``, ``lengths`` and the ``nbest_*`` entries."""
         if kwargs.get("rerank") is not None:                   # (refusals come in front of the encoder's launches)
             raise ValueError("rerank in the training forward: there is nothing to choose among" if len(input) == 4 else
                              "rerank belongs to the N-samples-per-clip routes, which know N: rollout_shared_encoder / "
                              "forward_batch_shared_encoder / evaluate(beam_size=N)")
         self._truncation(kwargs, rollout=len(input) == 2)
         self._constraints(kwargs, rollout=len(input) == 2)
+        self._finishing(kwargs)
         self._forward_token = getattr(self, "_forward_token", 0) + 1     # per-forward caches (decoder.embedding_table)
         clip_index = kwargs.pop("clip_index", None)
         if clip_index is not None and len(input) != 4:
@@ -733,6 +785,61 @@ class Hybrid_VAEModel(CaptionModel):
             raise ValueError(f"{given}: a vocabulary of {V} words may leave a row without a word; it must exceed "
                              f"len(suppress_tokens) + max_length + beam = {len(ids)} + {max_length} + {beam}")
         return con
+
+    def _finishing(self, kwargs):
+        """The finishing keywords of a beam search -> ``(length_penalty, nbest)``, or None when ``finish_on_end`` is off.
+
+        The one definition (include/acvae_hip.h states the same for the C entries).  Rows r = n * beam + j of clip n.  As
+        without finishing, step t forms ``scores[r, v] = c[r] + logmix_t[r, v]`` (after the constraints) and the flat top-k
+        over the clip's beam * V scores (sorted descending, ties to the lower flat index, t = 0 included) gives row r its
+        cumulative score ``c_t[r]``, parent ``p_t[r]`` and word ``w_t[r]``.  Then:
+          1. r is alive iff ``c_t[r] > -inf``;
+          2. if r is alive and (``w_t[r] == end_idx`` or ``t == max_length - 1``) the record is ``f_t[r] = c_t[r]``, else -inf;
+          3. if ``w_t[r] == end_idx``, ``c_t[r] <- -inf``: the row is retired, all its children score -inf and lose to every
+             alive candidate; where a clip has fewer than ``beam`` alive candidates the top-k takes such children: dead rows,
+             never recorded.
+        After the last step, per clip: the candidates are every (t, j) with ``f_t[n * beam + j] > -inf``; the score is
+        ``s = f_t / norm[t]``, ``norm[t] = float32((t + 1) ** length_penalty)`` (float64 power on the host, one fp32 division
+        on the device); the order is s descending, then t ascending, then j ascending, and the first ``nbest`` are returned;
+        a hypothesis's words are its parents traced back from (t, r), ``end_idx`` behind t, its length t + 1.  With fewer than
+        ``nbest`` candidates (only when bans leave a clip fewer than ``beam`` finite continuations) the missing slots are rows
+        of ``end_idx`` with score -inf and length 0.  ``length_penalty`` 1.0 (the default) is the average log-probability per
+        word, the rule of the reference's diverse beam search; 0 ranks by the raw log-probability.
+
+        The search itself is unchanged: all ``max_length`` steps run, retired and dead rows keep being stepped, nothing is
+        read back.  The output dict holds hypothesis 0 as ``seqs`` [N, T] (and ``attn_weights``, zeros behind its length),
+        ``scores`` / ``lengths`` [N], and ``nbest_seqs`` [N, nbest, T], ``nbest_scores`` / ``nbest_logprobs`` (the raw f) f32
+        [N, nbest], ``nbest_lengths`` int32 [N, nbest].
+
+        ValueError: ``finish_on_end`` with a method other than "beam"; ``length_penalty`` / ``nbest`` without
+        ``finish_on_end``; a ``length_penalty`` that is negative or not finite (or whose table overflows float32);
+        ``nbest`` outside [1, beam_size]."""
+        on, lp, nbest = (kwargs.get(k) for k in FINISH_KEYS)
+        on = False if on is None else on
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"finish_on_end must be True or False, got {on!r}")
+        if not on:
+            for k, v in (("length_penalty", lp), ("nbest", nbest)):
+                if v is not None:
+                    raise ValueError(f"{k}={v!r} without finish_on_end=True: it ranks finished hypotheses only")
+            return None
+        method = kwargs.get("method", "greedy")
+        if method != "beam":
+            raise ValueError(f"finish_on_end=True with method={method!r}: finishing belongs to method='beam'")
+        lp = 1.0 if lp is None else lp
+        try:
+            lpf = float(lp)
+        except (TypeError, ValueError):
+            raise ValueError(f"length_penalty must be a finite number >= 0, got {lp!r}") from None
+        if isinstance(lp, bool) or not (np.isfinite(lpf) and lpf >= 0.0):
+            raise ValueError(f"length_penalty must be a finite number >= 0, got {lp!r}")
+        beam = int(kwargs.get("beam_size", 3))
+        nbest = 1 if nbest is None else nbest
+        if isinstance(nbest, bool) or not isinstance(nbest, (int, np.integer)) or not (1 <= nbest <= beam):
+            raise ValueError(f"nbest must be an integer in [1, beam_size = {beam}], got {nbest!r}")
+        if not np.isfinite(length_norm(kwargs.get("max_length", self.max_length), lpf)).all():
+            raise ValueError(f"length_penalty={lp!r}: max_length ** length_penalty overflows float32")
+        return lpf, int(nbest)
 
     def _host_prepare(self, N, dev, caps, cap_lens, kwargs):
         """The decode loop's host-side random decisions, in the reference's per-step order (scheduled-sampling coin

@@ -1020,7 +1020,7 @@ int acvae_ensemble_search(const void* const* const* params, const float* const* 
  * a clip `beam` finite scores); in the decode forward, caps != NULL (a teacher-forced row has no history of its own) or
  * ACVAE_FLAG_ROLLOUT_GRAD (the backward does not know the penalty's factor).
  * Out of scope: diverse beam search (its histories live on the host), constraints in differentiable rollouts and in the
- * training forward, per-row settings, finishing beams on end_idx and length-normalised beam scores.
+ * training forward, per-row settings.  (Finishing beams on end_idx and length-normalised scores: the *_finishing entries.)
  * ------------------------------------------------------------------------------------------- */
 #define ACVAE_SUPPRESS_MAX 64
 int acvae_constrain_logits(float* logits, int64_t ld, const int64_t* hist, int64_t hist_ld, int t, int R, int V,
@@ -1051,6 +1051,76 @@ int acvae_ensemble_search_constrained(const void* const* const* params, const fl
                                       int64_t* seqs, float* logprobs, void* scratch, int64_t scratch_bytes, int N, int beam,
                                       int max_length, int V, void* stream, float repetition_penalty,
                                       int no_repeat_ngram_size, int min_length, const int* suppress_host, int n_suppress);
+
+/* ---------------------------------------------------------------------------------------------
+ * Finishing beam search: hypotheses end at end_idx, are scored by length and reported as an n-best list.  The rule is the
+ * one of the reference's diverse beam search (models/word_model.py:371-383: record a hypothesis when it emits <end> or at
+ * the last step, score logprob / length, take it out of the beam), which its beam_search never applies (done_beams is
+ * sorted and never filled).  Opt-in: the entries above are the same driver with finishing off and run what they ran.
+ *
+ * Definition.  Rows r = n * beam + j of clip n.  Step t forms scores[r,v] = c[r] + logmix_t[r,v] (acvae_ensemble_mix,
+ * after the constraints) and the flat top-k over the clip's beam * V scores (acvae_topk_flat_batched: sorted descending,
+ * ties to the lower flat index, t = 0 included) gives row r its cumulative score c_t[r], parent p_t[r] and word w_t[r].
+ * Then, per row (acvae_beam_retire):
+ *   1. r is alive iff c_t[r] > -inf;
+ *   2. f_t[r] = c_t[r] if r is alive and (w_t[r] == end_idx or t == max_length - 1), else -inf      (the record);
+ *   3. if w_t[r] == end_idx: c_t[r] <- -inf                                                        (the row is retired).
+ * All children of a retired row score -inf at the next step (acvae_ensemble_mix with prev = -inf writes -inf into every
+ * column, banned ones included; never NaN) and lose to every alive candidate; where a clip has fewer than `beam` alive
+ * candidates the top-k takes such children: dead rows, never recorded.  (The reference's logprob_table[is_end] -= 1000
+ * with -inf in the place of -1000.)  After the last step, per clip (acvae_beam_finish):
+ *   candidates  every (t, j) with f_t[n * beam + j] > -inf;
+ *   score       s = f_t / norm[t], ONE IEEE fp32 division, norm[t] = (float)pow((double)(t + 1), length_penalty) formed
+ *               on the host (length_norm_host, [max_length], every entry finite and > 0; all ones = raw scores);
+ *   order       s descending, then t ascending, then j ascending; the first `nbest` are returned;
+ *   words       the parents traced back from (t, r) to step 0; positions behind t hold end_idx; length t + 1;
+ *   missing     fewer than nbest candidates (only when bans leave a clip fewer than `beam` finite continuations): rows of
+ *               end_idx with score and log-probability -inf and length 0.
+ * The search itself is unchanged: same t = 0 rule, same noise, all max_length steps run, retired and dead rows keep being
+ * stepped, no host read-back.  Finishing adds one acvae_beam_retire launch per step and replaces the final trace by
+ * acvae_beam_finish; the norm table travels in kernel arguments (64 entries per launch) into the scratch.
+ *
+ * Outputs: nbest_seqs int64 [N,nbest,T], nbest_scores f32 [N,nbest] (s), nbest_logprobs f32 [N,nbest] (the raw f),
+ * nbest_lengths int32 [N,nbest]; seqs [N,T] = hypothesis 0; acvae_beam_search_finishing: attn_weights [N,S,T] = hypothesis
+ * 0's weights, zeros in the columns behind its length; acvae_ensemble_search_finishing: logprobs [N] = hypothesis 0's raw
+ * log-probability.  Scratch of the *_finishing_scratch_bytes functions (never below the *_constrained ones).
+ *
+ * Refused before any launch, beside what the *_constrained entries refuse: nbest outside [1, beam], a NULL output, a NULL
+ * norm table or an entry that is not finite and positive, end_idx outside [0, V), greedy != 0 in the ensemble entry
+ * (ACVAE_EINVAL); scratch below the bytes function (ACVAE_EWORKSPACE).
+ *
+ * The kernels alone, on caller-built histories (device pointers unless named _host):
+ *   acvae_beam_retire  c [R] in place, word int64 [R], f [R] out; last != 0 at the last step.
+ *   acvae_beam_finish  parent / word int64, element (t, r) at [t * hist_stride + r], hist_stride >= R = N * beam; f [T][R];
+ *                      attw [T][R][S] with attw_out [N,S,T], both or neither NULL (S is then ignored); seqs [N,T] and
+ *                      logprobs [N] may be NULL; norm_dev: T floats of device workspace the table is written to.  A parent
+ *                      outside [0, R) is clamped into it.  beam <= 16, T >= 1.
+ * Out of scope: early exit once every clip has finished (needs a read-back), compacting retired rows out of the step
+ * kernels, diverse beam search, consensus reranking of the n-best list, per-row settings, GNMT's ((5 + len) / 6)^alpha,
+ * a coverage penalty.
+ * ------------------------------------------------------------------------------------------- */
+int acvae_beam_retire(float* c, const int64_t* word, float* f, int64_t end_idx, int last, int R, void* stream);
+int acvae_beam_finish(const int64_t* parent, const int64_t* word, int64_t hist_stride, const float* f,
+                      const float* length_norm_host, float* norm_dev, const float* attw, int64_t* seqs, float* logprobs,
+                      float* attw_out, int64_t* nbest_seqs, float* nbest_scores, float* nbest_logprobs, int* nbest_lengths,
+                      int N, int beam, int T, int S, int nbest, int64_t end_idx, void* stream);
+int64_t acvae_beam_search_finishing_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A, int V);
+int acvae_beam_search_finishing(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
+                                int64_t start_idx, int64_t* seqs, float* attn_weights, void* scratch, int64_t scratch_bytes,
+                                int N, int beam, int max_length, int S, int E, int H, int A, int V, void* stream,
+                                int64_t end_idx, float repetition_penalty, int no_repeat_ngram_size, int min_length,
+                                const int* suppress_host, int n_suppress, const float* length_norm_host, int nbest,
+                                int64_t* nbest_seqs, float* nbest_scores, float* nbest_logprobs, int* nbest_lengths);
+int64_t acvae_ensemble_search_finishing_scratch_bytes(int M, int N, int beam, int max_length, const int* S, const int* E,
+                                                      const int* H, const int* A, int V);
+int acvae_ensemble_search_finishing(const void* const* const* params, const float* const* mem,
+                                    const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
+                                    const int* H, const int* A, int M, int64_t start_idx, int64_t end_idx, int greedy,
+                                    int64_t* seqs, float* logprobs, void* scratch, int64_t scratch_bytes, int N, int beam,
+                                    int max_length, int V, void* stream, float repetition_penalty, int no_repeat_ngram_size,
+                                    int min_length, const int* suppress_host, int n_suppress,
+                                    const float* length_norm_host, int nbest, int64_t* nbest_seqs, float* nbest_scores,
+                                    float* nbest_logprobs, int* nbest_lengths);
 
 #ifdef __cplusplus
 }
