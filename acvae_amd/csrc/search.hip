@@ -24,7 +24,7 @@ int step_layout(int N, int S, int E, int H, int A, int V, StepLayout& L) {
   L.encproj = b.take((long)N * S * (A > E ? A : E));
   L.rnn = b.take((long)N * 3 * E);
   L.q = b.take((long)N * (A > E ? A : E));
-  L.gates = b.take((long)N * 4 * E);
+  L.gates = b.take((long)N * (4 * E > 3 * H ? 4 * E : 3 * H));      // the prior's LSTM gates [N, 4E] and the decoder's gi [N, 3H]
   L.gh = b.take((long)N * 3 * H);
   L.ml = b.take((long)N * 2 * E);
   L.words = b.take((long)N * 2);
@@ -41,9 +41,12 @@ inline int step_attws_reset(float* sc, const StepLayout& L, hipStream_t st) {
 }
 }  // namespace
 
+// One buffer serves both step entries: acvae_decoder_step_fwd lays it out by (E, H, A), acvae_prior_step_fwd - which is not
+// told H and A - by (E, E, E), and with H < E and A <= E the latter is the larger.
 extern "C" int64_t acvae_step_scratch_bytes(int N, int S, int E, int H, int A, int V) {
-  StepLayout L;
-  return step_layout(N, S, E, H, A, V, L) == ACVAE_OK ? L.total * 4 : -1;
+  StepLayout L, Lp;
+  if (step_layout(N, S, E, H, A, V, L) != ACVAE_OK || step_layout(N, S, E, E, E, V, Lp) != ACVAE_OK) return -1;
+  return (L.total > Lp.total ? L.total : Lp.total) * 4;
 }
 
 // encproj = mem . W[:, hs_dec:]^T + b for the decoder attention (which = 0) or the prior attention (which = 1)
@@ -502,8 +505,9 @@ int beam_search_entry(const void* const* params, const float* mem, const int64_t
   ACVAE_TRY(finishing_check(fin, beam, max_length));
   if (fin.on && (end_idx < 0 || end_idx >= V)) return ACVAE_EINVAL;
   if (!params || !mem || !mem_lens || !eps || !seqs || !attw_out || !scratch_v) return ACVAE_EINVAL;
-  // the prior LSTM is E wide; acvae_topk_flat_batched selects k <= 16 and would answer a wider beam with the same code
-  if (start_idx < 0 || start_idx >= V || beam > 16 || H != E) return ACVAE_EINVAL;
+  // acvae_topk_flat_batched selects k <= 16 and would answer a wider beam with the same code.  (The decoder GRU's width H is
+  // free: the prior LSTM is E wide whatever H is, and every state row is kept, zeroed and gathered by its own width.)
+  if (start_idx < 0 || start_idx >= V || beam > 16) return ACVAE_EINVAL;
   if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
   return search(&mb, 1, L, start_idx, end_idx, 0, seqs, nullptr, attw_out, (float*)scratch_v, N, beam, max_length, V, con,
                 fin, (hipStream_t)stream);
@@ -517,7 +521,7 @@ int ensemble_search_entry(const void* const* const* params, const float* const* 
   if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !params || !mem || !mem_lens || !eps || !S || !E || !H || !A) return ACVAE_EINVAL;
   SearchMember mb[ACVAE_ENSEMBLE_MAX];
   for (int m = 0; m < M; ++m) {
-    if (!params[m] || !mem[m] || !mem_lens[m] || !eps[m] || H[m] != E[m]) return ACVAE_EINVAL;   // the prior LSTM is E wide
+    if (!params[m] || !mem[m] || !mem_lens[m] || !eps[m]) return ACVAE_EINVAL;
     mb[m] = {params[m], mem[m], mem_lens[m], eps[m], S[m], E[m], H[m], A[m]};
   }
   if (!seqs || !logprobs || !scratch_v) return ACVAE_EINVAL;

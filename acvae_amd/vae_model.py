@@ -543,6 +543,12 @@ class Hybrid_VAEModel(CaptionModel):
             raise ValueError("clip_index belongs to the training forward (feats, feat_lens, caps, cap_lens)")
         if len(input) == 4:
             feats, feat_lens, caps, cap_lens = input
+            # mean_log_out = Linear(embed_size, .) is fed the pooled GRU outputs (acvae_decode_fwd refuses the shape too:
+            # here the refusal comes in front of the encoder's launches and names the widths)
+            if self.decoder.model.hidden_size != self.decoder.embed_size:
+                raise ValueError(f"training forward: the decoder's hidden_size ({self.decoder.model.hidden_size}) must equal "
+                                 f"its embed_size ({self.decoder.embed_size}); other hidden sizes decode only (the "
+                                 "2-input forward, beam search, rollouts)")
             # one encoder pass shared by the clips' captions: B clips, N = B * k caption rows (see _share_rows)
             share = None if clip_index is None else clip_rows(clip_index, len(feat_lens), len(cap_lens))
             if share is not None and feats.shape[0] != len(feat_lens):

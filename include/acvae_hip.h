@@ -900,6 +900,8 @@ int acvae_prof_read(int tag, double* total_ms_host, int64_t* launches_host);
  * (computed into scratch) or the result of acvae_attn_precompute (hoisted out of the step loop).  word int64 [N].
  * acvae_logprob_add / acvae_topk_flat are the beam bookkeeping of vae_model.py:909-916 (log_softmax + running beam
  * score; flat top-k over beam*V with idx / V and idx % V).
+ * The widths are free of each other: E (embeddings, memory, the prior's LSTM), H (the decoder GRU), A (its attention); the
+ * searches below take them per member likewise.  acvae_step_scratch_bytes sizes ONE buffer for both step entries.
  * ------------------------------------------------------------------------------------------- */
 int64_t acvae_step_scratch_bytes(int N, int S, int E, int H, int A, int V);
 int acvae_attn_precompute(const void* const* params, int which, const float* mem, float* encproj, int N, int S, int E,
@@ -928,7 +930,7 @@ int acvae_topk_flat_batched(const float* x, int64_t n, int64_t group_stride, int
  * attn_weights [N,S,max_length].  No host synchronisation; scratch of acvae_beam_search_scratch_bytes().
  * This is the M = 1 beam case of acvae_ensemble_search (below: one driver, one acvae_ensemble_mix launch per step forms the
  * scores) plus beam 0's attention-weight history.  Refused before any launch: a dimension <= 0 (ACVAE_EINVAL);
- * N * beam > 2^20 (ACVAE_EUNSUPPORTED, -1 from the bytes function); a NULL pointer, start_idx outside [0, V), H != E, or
+ * N * beam > 2^20 (ACVAE_EUNSUPPORTED, -1 from the bytes function); a NULL pointer, start_idx outside [0, V), or
  * beam > 16 (acvae_topk_flat_batched's limit) (ACVAE_EINVAL); scratch below the bytes function (ACVAE_EWORKSPACE). */
 int64_t acvae_beam_search_scratch_bytes(int N, int beam, int max_length, int S, int E, int H, int A, int V);
 int acvae_beam_search(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
@@ -968,7 +970,7 @@ int acvae_dbs_scores(const float* logits, int64_t ld, float temperature, const f
  *   greedy == 0: beam search, flat top-k over beam * V per clip at every step, t = 0 included (as acvae_beam_search: the
  *     rows of a clip differ in z), beam 0 traced back.  logprobs f32 [N]: beam 0's final score.  With M = 1 this is
  *     acvae_beam_search (the same driver) without the attention-weight history: the same seqs bit for bit.
- * seqs int64 [N,max_length].  Refused before any launch: M outside [1, ACVAE_ENSEMBLE_MAX], a NULL entry, H[m] != E[m],
+ * seqs int64 [N,max_length].  Refused before any launch: M outside [1, ACVAE_ENSEMBLE_MAX], a NULL entry,
  * beam > 64, greedy with beam != 1, start_idx / end_idx outside [0, V) (ACVAE_EINVAL); N * beam > 2^20, or beam > 16
  * without greedy (acvae_topk_flat_batched's limit) (ACVAE_EUNSUPPORTED); scratch below
  * acvae_ensemble_search_scratch_bytes() (ACVAE_EWORKSPACE).  One stream, no host synchronisation.

@@ -586,7 +586,8 @@ def beam_search(state, feats, feat_lens, beam_size=3, max_length=MAX_LENGTH, eps
     """Instance-by-instance beam search; returns seqs i64 [N,max_length] (beam 0 of each clip; `done_beams` is
     never filled in the reference, :986-995).  eps (optional): [N, max_length, beam, E] replay of the randn draws.
     record (optional dict): record["margins"][i] lists clip i's decision margins - the k-th minus the (k+1)-th flat
-    score of every step (which beams survive) and the top-1 minus top-2 flat score of the last step (which is beam 0)."""
+    score of every step (which beams survive) and the top-1 minus top-2 flat score of the last step (which is beam 0);
+    record["topk_logprobs"] [N, max_length, beam] holds the summed log-probabilities of the beams kept at every step."""
     enc = cnn10_forward(state, feats, feat_lens, training=False)
     if "ln.weight" in state:
         enc["audio_embeds"] = F.linear(enc["audio_embeds"], state["ln.weight"], state["ln.bias"])
@@ -598,6 +599,7 @@ def beam_search(state, feats, feat_lens, beam_size=3, max_length=MAX_LENGTH, eps
     seqs_out = torch.full((N, max_length), END_IDX, dtype=torch.long)
     if record is not None:
         record["margins"] = [[] for _ in range(N)]
+        record["topk_logprobs"] = torch.zeros(N, max_length, beam_size)
     for i in range(N):
         mem = mem_all[i].unsqueeze(0).repeat(beam_size, 1, 1)
         lens = lens_all[i].repeat(beam_size)
@@ -619,6 +621,8 @@ def beam_search(state, feats, feat_lens, beam_size=3, max_length=MAX_LENGTH, eps
             if record is not None:
                 record["margins"][i].extend(_topk_margins(logprobs.view(-1), beam_size, t == max_length - 1))
             top_k_logprobs, top_k_words = logprobs.view(-1).topk(beam_size, 0, True, True)
+            if record is not None:
+                record["topk_logprobs"][i, t] = top_k_logprobs
             prev = torch.div(top_k_words, V, rounding_mode="trunc")
             next_w = top_k_words % V
             seqs = next_w.unsqueeze(1) if t == 0 else torch.cat([seqs[prev], next_w.unsqueeze(1)], dim=1)

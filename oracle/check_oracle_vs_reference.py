@@ -118,8 +118,66 @@ def main():
         same = torch.equal(ro["seqs"], oo["seqs"])
         print(f"  greedy N=5 seqs equal: {same}  distinct rows {len(set(map(tuple, ro['seqs'].tolist())))}")
         assert same
+    worst = max(worst, unequal_widths(ref))
     print("worst", worst)
     assert worst < 2e-4
+
+
+def unequal_widths(ref):
+    """Widths that are not all equal.  The training forward leaves only the attention width A free (mean_log_out is fed the
+    GRU outputs: H == E; the MSE pairs q_means_utt with p_means_utt: Hq == E); the reference's beam search and diverse beam
+    search take any GRU width H; its greedy loop keeps the outputs in an embed_size-wide buffer (models/vae_model.py:767),
+    so greedy decoding is compared at H == E."""
+    worst = 0.0
+    V, B, T, L = 37, 3, 64, 7
+    feats, caps, feat_lens, cap_lens = O.synthetic_batch(B, T, V, L, seed=3, ragged=True)
+    for E, A in ((64, 160), (64, 32), (128, 96), (64, 50)):
+        state = O.closed_form_state(O.state_shapes(V, E, E, A, E, 512))
+        model = ref_shim.build_reference_model(ref, V, E, E, attn=A)
+        load_state_into(model, state)
+        model.train()
+        torch.manual_seed(11); random.seed(11)
+        rout, rl, rg = ref_train_step(ref, model, feats, feat_lens.copy(), caps, cap_lens, V, 1.0, 0)
+        torch.manual_seed(11); random.seed(11)
+        res = O.OracleTrainer({k: v.clone() for k, v in state.items()}, V).step(feats, feat_lens.copy(), caps, cap_lens,
+                                                                                apply_update=False)
+        assert set(rg) == set(res["grads"]), set(rg) ^ set(res["grads"])
+        d = max((rout[k].detach().double() - res["out"][k].detach().double()).abs().max().item()
+                for k in ("logits", "outputs", "seqs", "attn_weights", "p_means", "p_z", "q_means", "q_means_utt", "p_means_utt"))
+        dl = abs(float(rl["loss"]) - float(res["loss"])) / max(1.0, abs(float(rl["loss"])))
+        gd = max((rg[k].double() - res["grads"][k].double()).abs().max().item() for k in rg)
+        print(f"--- train E=H=Hq={E} A={A}: outputs maxabs {d:.3e}  loss diff {dl:.2e}  grads maxabs {gd:.3e}")
+        worst = max(worst, d, dl, gd)
+        model.eval()
+        torch.manual_seed(5)
+        with torch.no_grad():
+            ro = model(feats, feat_lens.copy(), method="greedy")
+        torch.manual_seed(5)
+        with torch.no_grad():
+            oo = O.hybrid_forward({k: v.clone() for k, v in state.items()}, feats, feat_lens.copy(), training=False)
+        assert torch.equal(ro["seqs"], oo["seqs"]), (E, A)
+    for E, H, A in ((64, 96, 160), (64, 32, 96), (128, 64, 64), (64, 40, 50)):
+        state = O.closed_form_state(O.state_shapes(V, E, H, A, E, 512))
+        model = ref_shim.build_reference_model(ref, V, E, H, attn=A)
+        load_state_into(model, state)
+        model.eval()
+        torch.manual_seed(6)
+        with torch.no_grad():
+            rb = model(feats, feat_lens.copy(), method="beam", beam_size=3)["seqs"]
+        torch.manual_seed(6)
+        with torch.no_grad():
+            ob = O.beam_search({k: v.clone() for k, v in state.items()}, feats, feat_lens.copy(), 3)
+        assert torch.equal(rb, ob), (E, H, A)
+        kw = dict(beam_size=4, group_size=2, max_length=7)
+        torch.manual_seed(7)
+        with torch.no_grad():
+            rd = model(feats, feat_lens.copy(), method="dbs", **kw)["seqs"]
+        torch.manual_seed(7)
+        with torch.no_grad():
+            od = O.diverse_beam_search({k: v.clone() for k, v in state.items()}, feats, feat_lens.copy(), **kw)
+        assert torch.equal(rd, od), (E, H, A)
+        print(f"--- inference (E, H, A) = ({E}, {H}, {A}): beam-3 and diverse beam search tokens equal")
+    return worst
 
 
 if __name__ == "__main__":

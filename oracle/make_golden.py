@@ -331,6 +331,83 @@ def g9_beam(ref):
     save("g9_beam", dims=np.array([3, 96, V, E, beam]), feats=feats, feat_lens=feat_lens, eps=eps, seqs=ro["seqs"])
 
 
+G19_GRAD_KEYS = ("decoder.attn.v", "decoder.attn.h2attn.weight", "decoder.attn.h2attn.bias", "decoder.model.weight_ih_l0",
+                 "decoder.classifier.weight")
+G19_OUT_KEYS = ("seqs", "logits", "attn_weights", "p_means", "q_means_utt", "p_means_utt")
+
+
+def g19_unequal_widths(ref):
+    """G19: the text side at widths that are NOT all equal.  One training step with the attention width A = 160 beside
+    E = H = Hq = 64 (the widths the training forward leaves free: only A), one beam-3 inference at (E, H, A) = (64, 96, 160)
+    and one greedy inference at (64, 64, 160): the reference's greedy loop keeps the GRU outputs in a buffer that is embed_size
+    wide (models/vae_model.py:767), so it runs with H == E only, while its beam search takes any H.  Recorded results only: the batches and the noise are re-made from the stored seeds
+    (synthetic_batch; torch's CPU generator, which the oracle draws from in the reference's order).  The beam search's
+    summed log-probabilities of the kept beams are formed here from the logits the reference's decoder returned at every
+    step (a forward hook), by the three lines of models/vae_model.py:909-912."""
+    V, B, Tt, L, E, A, seed = 37, 3, 64, 7, 64, 160, 19
+    d = dict(train_dims=np.array([B, Tt, V, E, E, A, E, L]), train_seed=np.array(seed))
+    state = O.closed_form_state(O.state_shapes(V, E, E, A, E, 512))
+    model = ref_shim.build_reference_model(ref, V, E, E, attn=A)
+    load_state_into(model, state)
+    model.train()
+    feats, caps, feat_lens, cap_lens = O.synthetic_batch(B, Tt, V, L, seed=seed, ragged=True)
+    torch.manual_seed(seed); random.seed(seed)
+    rout, rl, rg = ref_train_step(ref, model, feats, feat_lens.copy(), caps, cap_lens, V, 1.0, 0)
+    torch.manual_seed(seed); random.seed(seed)
+    res = O.OracleTrainer({k: v.clone() for k, v in state.items()}, V).step(feats, feat_lens.copy(), caps, cap_lens, 1.0, 0,
+                                                                            apply_update=False)
+    assert abs(float(res["loss"]) - float(rl["loss"])) < 1e-4 * max(1, abs(float(rl["loss"]))), (res["loss"], rl["loss"])
+    d.update(train_cap_lens=cap_lens, train_feat_lens=feat_lens)
+    d.update({"train_" + k: rl[k] for k in ("loss", "ce", "kl", "mse", "grad_norm")})
+    d.update({"train_out_" + k: rout[k] for k in G19_OUT_KEYS})
+    d.update({"train_grad_" + k: rg[k] for k in G19_GRAD_KEYS})
+
+    E, H, A, beam = 64, 96, 160, 3
+    d.update(infer_dims=np.array([B, Tt, V, E, H, A, beam]), infer_seed=np.array(seed))
+    feats, _, feat_lens, _ = O.synthetic_batch(B, Tt, V, L, seed=seed, ragged=True)
+    state = O.closed_form_state(O.state_shapes(V, E, E, A, E, 512))         # greedy: H = E
+    model = ref_shim.build_reference_model(ref, V, E, E, attn=A)
+    load_state_into(model, state)
+    model.eval()
+    torch.manual_seed(seed + 1)
+    with torch.no_grad():
+        ro = model(feats, feat_lens.copy(), method="greedy")
+    torch.manual_seed(seed + 1)
+    with torch.no_grad():
+        oo = O.hybrid_forward({k: v.clone() for k, v in state.items()}, feats, feat_lens.copy(), training=False)
+    assert torch.equal(ro["seqs"], oo["seqs"])
+    steps = oo["_steps_run"]
+    d.update(greedy_seqs=ro["seqs"], greedy_steps_run=np.array(steps), greedy_logprobs=ro["sampled_logprobs"][:, :steps])
+    state = O.closed_form_state(O.state_shapes(V, E, H, A, E, 512))         # beam: H = 96
+    model = ref_shim.build_reference_model(ref, V, E, H, attn=A)
+    load_state_into(model, state)
+    model.eval()
+    step_logits = []
+    hook = model.decoder.register_forward_hook(lambda m, a, out: step_logits.append(out["logits"].squeeze(1).clone()))
+    torch.manual_seed(seed + 2)
+    with torch.no_grad():
+        rb = model(feats, feat_lens.copy(), method="beam", beam_size=beam)
+    hook.remove()
+    assert len(step_logits) == B * O.MAX_LENGTH
+    topk = torch.zeros(B, O.MAX_LENGTH, beam)
+    for i in range(B):
+        run = torch.zeros(beam)
+        for t in range(O.MAX_LENGTH):
+            lp = torch.log_softmax(step_logits[i * O.MAX_LENGTH + t], dim=1)
+            lp = run.unsqueeze(1).expand_as(lp) + lp
+            run, _ = lp.view(-1).topk(beam, 0, True, True)
+            topk[i, t] = run
+    torch.manual_seed(seed + 2)
+    eps = torch.stack([torch.stack([torch.randn(beam, E) for _ in range(O.MAX_LENGTH)]) for _ in range(B)])
+    rec = {}
+    with torch.no_grad():
+        ob = O.beam_search({k: v.clone() for k, v in state.items()}, feats, feat_lens.copy(), beam, O.MAX_LENGTH, eps, record=rec)
+    assert torch.equal(rb["seqs"], ob), (rb["seqs"], ob)
+    assert float((rec["topk_logprobs"] - topk).abs().max()) < 1e-4
+    d.update(beam_seqs=rb["seqs"], beam_topk_logprobs=topk)
+    save("g19_unequal_widths", **d)
+
+
 DBS_CASES = [dict(beam_size=4, group_size=2), dict(beam_size=6, group_size=3, diversity_lambda=0.8, temperature=1.5,
              group_nbest=False), dict(), dict(beam_size=6, group_size=2, diversity_lambda=2.0)]
 
@@ -475,6 +552,9 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "projemb":
         train_fixture(ref, "g16_train_step_projemb", 3, 48, 40, 64, 7, True, 0, seed=56, proj_embed=24)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "widths":
+        g19_unequal_widths(ref)
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "cnn14":
         g12_cnn14(ref)
         train_fixture(ref, "g13_train_step_cnn14", 2, 64, 40, 64, 6, True, 0, seed=36, keep_tensors=False,
@@ -493,6 +573,7 @@ def main():
     g7_decode(ref)
     g14_sampling(ref)
     g9_beam(ref)
+    g19_unequal_widths(ref)
     # G8: BASELINE config 1 shape; scalars only, noise re-drawn in the test from the stored seed.
     train_fixture(ref, "g8_config1_scalars", 8, 500, 5000, 512, 22, False, 0, seed=8, keep_tensors=False,
                   keep_noise=False)

@@ -88,13 +88,14 @@ def load_losses():
 
 
 def build_reference_model(ref, vocab, embed=512, hidden=512, q_hidden=None, encoder="Cnn10", dec_dropout=0.0,
-                          proj_embed=None):
+                          proj_embed=None, attn=None):
     """Hybrid_VAEModel(Cnn10, VAERNNBahdanauAttnDecoder, PosteriorRNN_hybrid, PriorRNN): the
-    self-consistent combination of SURVEY F6, built the way runners/pytorch_runner_vae.py:33-73 does."""
+    self-consistent combination of SURVEY F6, built the way runners/pytorch_runner_vae.py:33-73 does.
+    ``attn`` (default: ``hidden``) is the decoder attention's width, ``hidden`` the decoder GRU's, ``q_hidden`` the posterior's."""
     encoder = ref.encoder.Cnn10(64, 512) if encoder == "Cnn10" else ref.encoder.Cnn14_16k(64, 2048)
     decoder = ref.decoder.VAERNNBahdanauAttnDecoder(
         vocab_size=vocab, enc_mem_size=embed, embed_size=embed, hidden_size=hidden, dropout=dec_dropout,
-        num_layers=1, rnn_type="GRU", attn_size=hidden)
+        num_layers=1, rnn_type="GRU", attn_size=attn or hidden)
     if proj_embed is not None:          # runners/pytorch_runner_vae.py:51-56: pretrained vectors of another width
         import numpy as np
         decoder.load_word_embeddings(np.zeros((vocab, proj_embed), dtype=np.float32), tune=True, projection=True)

@@ -164,8 +164,13 @@ def test_ensemble_search_refusal_codes():
         a = Args()
         setattr(a, field, None)
         assert a.call() == EINVAL, field
-    a = Args(); a.H[1] = E + 1
-    assert a.call() == EINVAL                                       # H_m != E_m
+    a = Args(); a.H[1] = E + 1                                      # H_m != E_m is a shape the search takes: with room for
+    need = a.nbytes()                                               # equal widths only it asks for its workspace (nothing is
+    assert need > Args().nbytes()                                   # launched), it does not answer EINVAL
+    a.scratch_bytes = need - 1
+    assert a.call() == EWORKSPACE
+    a.scratch_bytes = Args().nbytes()
+    assert a.call() == EWORKSPACE
     a = Args(beam=65)
     assert a.call() == EINVAL
     a = Args(beam=17)                                               # beyond acvae_topk_flat_batched's k <= 16
@@ -225,8 +230,13 @@ def test_beam_search_refusal_codes():
     for start in (-1, V):
         a = BeamArgs(); a.start = start
         assert a.call() == EINVAL, start
-    a = BeamArgs(); a.H = E + 1
-    assert a.call() == EINVAL                                       # H != E
+    a = BeamArgs(); a.H = E + 1                                     # H != E is a shape the search takes: with room for
+    need = a.nbytes()                                               # equal widths only it asks for its workspace (nothing is
+    assert need > BeamArgs().nbytes()                               # launched), it does not answer EINVAL
+    a.scratch_bytes = need - 1
+    assert a.call() == EWORKSPACE
+    a.scratch_bytes = BeamArgs().nbytes()
+    assert a.call() == EWORKSPACE
     for beam in (65, 17):
         assert BeamArgs(beam=beam).call() == EINVAL, beam
     a = BeamArgs(N=(1 << 20) // 4 + 1, beam=4)                      # N * beam > 2^20

@@ -40,11 +40,15 @@ def _threads():                   # the helper's CPU steps: no more threads than
 
 
 def member(encoder, E, seed, end_bump=0.0, vocab=V):
-    """(model on the GPU in eval mode, its state dict on the CPU), built once per (encoder, E, seed, end_bump)."""
+    """(model on the GPU in eval mode, its state dict on the CPU), built once per (encoder, E, seed, end_bump).  E: one number
+    for every width of the text side, or (E, H, A): embed, decoder-GRU and attention widths apart (tests/widths_util.py)."""
     key = (encoder, E, seed, end_bump, vocab)
     if key not in _members:
         torch.manual_seed(seed)
-        if vocab == V:
+        if isinstance(E, tuple):
+            import widths_util as W
+            model = W.build_model(V, E[0], E[1], E[2], E[0], encoder=encoder).eval()
+        elif vocab == V:
             model = build_model(V, E, encoder=encoder).eval()
         else:
             from test_fullsize_gpu import build
@@ -60,6 +64,8 @@ CASES = {     # members (encoder, E, seed[, end_bump]), clips, T, seed of the fe
     "m2_cnn10": dict(members=[("Cnn10", 64, 11), ("Cnn10", 64, 12)], N=4, T=96, fseed=21, eseed=31),
     "m3_mixed": dict(members=[("Cnn10", 64, 13), ("Cnn14_16k", 64, 14), ("Cnn10", 128, 15)], N=3, T=128, fseed=22, eseed=32),
     "m2_end_bump": dict(members=[("Cnn10", 64, 11, 0.6), ("Cnn10", 64, 12)], N=5, T=96, fseed=23, eseed=33),
+    # members whose GRU and attention widths differ from their embed width and from each other's (seeds: see the test)
+    "m2_widths": dict(members=[("Cnn10", (64, 96, 160), 16), ("Cnn10", (64, 32, 96), 17)], N=4, T=96, fseed=25, eseed=35),
     "full_size": dict(members=[("Cnn10", 512, 5), ("Cnn10", 512, 6)], N=11, T=160, fseed=24, eseed=39, vocab=5000, maxlen=20),
 }
 
@@ -73,7 +79,7 @@ def case_data(name):
         feats, _, fl, _ = O.synthetic_batch(c["N"], c["T"], vocab, 7, seed=c["fseed"], ragged=True)
         states = [s for _, s in ms]
         _cases[name] = dict(models=[m for m, _ in ms], states=states, feats=feats, fl=fl, maxlen=c.get("maxlen", MAXLEN),
-                            dims=[m[1] for m in c["members"]], encoded=[EU.encode(s, feats, fl) for s in states], ref={})
+                            dims=[m[1][0] if isinstance(m[1], tuple) else m[1] for m in c["members"]], encoded=[EU.encode(s, feats, fl) for s in states], ref={})
     return _cases[name]
 
 
@@ -189,6 +195,19 @@ def test_distinct_members_vs_helper(name, method, beam):
     """m2_cnn10: two seeds of Cnn10 at E = 64.  m3_mixed: Cnn10 at E = 64, Cnn14_16k at E = 64 and Cnn10 at E = 128, so that
     S (T / 16 and T / 32 frames) and E differ per member."""
     check_against_helper(name, method, beam)
+
+
+@pytest.mark.parametrize("method,beam", [("greedy", 1), ("beam", 3)])
+def test_members_of_unequal_widths_vs_helper(method, beam):
+    """Two members with (E, H, A) = (64, 96, 160) and (64, 32, 96): acvae_ensemble_search gathers [H] and [E] state rows per
+    member and sizes every member's scratch by its own widths.  With the helper alone on the CPU the smallest margin of any
+    clip is 2.2e-3 (greedy) and 2.4e-3 (beam 3): no decision is left out at MARGIN = 2e-4."""
+    import widths_util as W
+    assert [m[1] for m in CASES["m2_widths"]["members"]] == W.ENSEMBLE_MEMBERS
+    d = case_data("m2_widths")
+    for st, (E, H, A) in zip(d["states"], W.ENSEMBLE_MEMBERS):
+        assert st["decoder.attn.h2attn.weight"].shape == (A, E + H) and st["decoder.model.weight_hh_l0"].shape == (3 * H, H)
+    check_against_helper("m2_widths", method, beam)
 
 
 def test_greedy_rows_that_end_early_keep_end():

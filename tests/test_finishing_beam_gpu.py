@@ -241,7 +241,7 @@ def finishing_loop(models, feats, fl, eps, beam, kw):
     for mod in models:
         state.append(mod.decoder.init_hidden(R).cuda())
         hid.append(mod.pnet.init_hidden(R, "cuda"))
-        lz.append(torch.zeros(R, 64, device="cuda"))
+        lz.append(torch.zeros(R, mod.decoder.embed_size, device="cuda"))          # (the members' own embed widths)
     w = torch.full((R,), start, dtype=torch.long, device="cuda")
     hist = np.zeros((R, 0), np.int64)
     top_k = torch.zeros(R, device="cuda")
@@ -251,7 +251,7 @@ def finishing_loop(models, feats, fl, eps, beam, kw):
     for t in range(T):
         edited, new = [], []
         for k, mod in enumerate(models):
-            pn = mod.pnet(w.unsqueeze(1), mem[k], hid[k], lz[k], lens[k], eps=eps[k][:, t].reshape(R, 64))
+            pn = mod.pnet(w.unsqueeze(1), mem[k], hid[k], lz[k], lens[k], eps=eps[k][:, t].reshape(R, -1))
             dn = mod.decoder(word=w.unsqueeze(1), state=state[k], enc_mem=mem[k], enc_mem_lens=lens[k], z=pn["z"])
             x = dn["logits"].squeeze(1).contiguous()
             if kw:

@@ -252,3 +252,49 @@ def test_g11_diverse_beam_search_token_exact():
             with torch.no_grad():
                 seqs = O.diverse_beam_search(state, T(g["feats"]), g["feat_lens"].copy(), max_length=ML, **kw)
             assert np.array_equal(seqs.numpy(), g[f"seqs_{tag}{ci}"]), (tag, kw)
+
+
+def test_g19_unequal_widths():
+    """The text side with widths that are not all equal (oracle/make_golden.py:g19_unequal_widths): a training step at
+    E = H = Hq = 64 with the attention A = 160 wide, a greedy decode at (E, H, A) = (64, 64, 160) - the reference's greedy loop
+    runs with H == E only - and a beam-3 search at (64, 96, 160).  Batches and noise come from the stored seeds."""
+    g = load_golden("g19_unequal_widths")
+    B, Tt, V, E, H, A, Hq, L = (int(x) for x in g["train_dims"])
+    assert (E, H, A, Hq) == (64, 64, 160, 64)
+    seed = int(g["train_seed"])
+    state = O.closed_form_state(O.state_shapes(V, E, H, A, Hq, 512))
+    assert state["decoder.attn.h2attn.weight"].shape == (A, E + H)
+    feats, caps, feat_lens, cap_lens = O.synthetic_batch(B, Tt, V, L, seed=seed, ragged=True)
+    assert np.array_equal(cap_lens, g["train_cap_lens"]) and np.array_equal(feat_lens, g["train_feat_lens"])
+    torch.manual_seed(seed); random.seed(seed)
+    res = O.OracleTrainer(state, V).step(feats, feat_lens.copy(), caps, cap_lens, 1.0, 0, apply_update=False)
+    for k in ("loss", "ce", "kl", "mse"):
+        assert abs(float(res[k]) - float(g["train_" + k])) <= 1e-4 * max(1.0, abs(float(g["train_" + k]))), k
+    assert abs(float(res["grad_norm"]) - float(g["train_grad_norm"])) <= 1e-4 * float(g["train_grad_norm"])
+    assert np.array_equal(res["out"]["seqs"].numpy(), g["train_out_seqs"])
+    for k in ("logits", "attn_weights", "p_means", "q_means_utt", "p_means_utt"):
+        close(res["out"][k].detach(), g["train_out_" + k])
+    grads = [k for k in g if k.startswith("train_grad_") and k != "train_grad_norm"]
+    assert len(grads) == 5
+    for k in grads:
+        close(res["grads"][k[len("train_grad_"):]], g[k], 1e-3, 1e-5)
+
+    B, Tt, V, E, H, A, beam = (int(x) for x in g["infer_dims"])
+    assert (E, H, A) == (64, 96, 160)
+    seed = int(g["infer_seed"])
+    feats, _, feat_lens, _ = O.synthetic_batch(B, Tt, V, L, seed=seed, ragged=True)
+    state = O.closed_form_state(O.state_shapes(V, E, E, A, E, 512))
+    torch.manual_seed(seed + 1)
+    with torch.no_grad():
+        o = O.hybrid_forward(state, feats, feat_lens.copy(), training=False)
+    steps = int(g["greedy_steps_run"])
+    assert o["_steps_run"] == steps and np.array_equal(o["seqs"].numpy(), g["greedy_seqs"])
+    close(o["sampled_logprobs"][:, :steps], g["greedy_logprobs"], 1e-5, 1e-6)
+    state = O.closed_form_state(O.state_shapes(V, E, H, A, E, 512))
+    torch.manual_seed(seed + 2)
+    eps = torch.stack([torch.stack([torch.randn(beam, E) for _ in range(O.MAX_LENGTH)]) for _ in range(B)])
+    rec = {}
+    with torch.no_grad():
+        seqs = O.beam_search(state, feats, feat_lens.copy(), beam, O.MAX_LENGTH, eps, record=rec)
+    assert np.array_equal(seqs.numpy(), g["beam_seqs"])
+    close(rec["topk_logprobs"], g["beam_topk_logprobs"], 1e-5, 1e-5)

@@ -232,3 +232,28 @@ def test_workspace_sizes_are_what_they_were():
         for NL, want in zip((1, 3), post):
             got = [getattr(so, n)(N, Tc, E, Hq, V, NL) for n in names[3:]]
             assert got == want, ((N, Tc, E, Hq, NL), got, want)
+
+
+def test_width_sets_meant_for_a_persistent_launch_are_taken_by_the_plans():
+    """The training width sets of tests/widths_util.py (A != E) that tests/test_text_widths_gpu.py means for the persistent
+    decode launches: the forward and BPTT plans take them, with the role counts, K-splits and d qd shares the sets are
+    there for; the two whose A is no multiple of 32 are refused (per-step paths).  Likewise the posterior widths."""
+    import widths_util as W
+    want = {  # name: (n_d1 = A/32 + 3H/32, ks_rb, ks_pa, rc_splits)
+        "E64_A32": (1 + 6, 1, 1, 1), "E64_A160": (5 + 6, 1, 1, 1), "E128_A96": (3 + 12, 1, 1, 1),
+        "E64_A160_T1056": (5 + 6, 1, 1, 2), "E512_A256": (8 + 48, 3, 2, 1)}
+    assert set(want) == set(W.TRAIN_PERSISTENT)
+    for name in W.TRAIN_SETS:
+        B, T, V, E, A, S, Tc = W.train_dims(name)
+        p = W.plans(B, Tc, S, E, E, A, E)
+        if name in W.TRAIN_PERSISTENT:
+            assert p["fwd_ok"] and p["bwd_ok"] and p["post_ok"], (name, p)
+            assert (p["fwd_n_d1"], p["ks_rb"], p["ks_pa"], p["rc_splits"]) == want[name], (name, p)
+            assert p["dqd_part_floats"] == (p["rc_splits"] * B * Tc * A if p["rc_splits"] > 1 else 0), (name, p)
+        else:
+            assert A % 32 != 0 and not p["fwd_ok"] and not p["bwd_ok"] and p["post_ok"], (name, p)
+    for E, H, A in W.INFER_SETS:                       # H != E: no persistent BPTT (a rollout's backward goes per step)
+        assert not W.plans(3, 6, 4, E, H, A, E)["bwd_ok"], (E, H, A)
+    for (E, Hq), ok in zip(W.POSTERIOR_SETS, (1, 1, 1, 1, 0)):
+        for N in (5, 32, 33):
+            assert W.plans(N, 6, 4, 64, 64, 64, Hq)["post_ok"] == (ok and N <= 32), (E, Hq, N)

@@ -2,7 +2,12 @@
 nn.GRU(num_layers, bidirectional, dropout) on the CPU in fp64 - the reference's own module, as
 tests/test_kernels_gpu.py::test_bigru_seq_and_posterior_golden_g5 - forward and backward, in eval mode and with the
 inter-layer dropout of training mode; the persistent against the per-step recurrence; the one-layer case of the new entry
-points against acvae_posterior_fwd / _bwd; and a stacked model trained end to end through TrainStep."""
+points against acvae_posterior_fwd / _bwd; and a stacked model trained end to end through TrainStep.
+
+The widths are parameters: the posterior called on its own takes any GRU width Hq beside the embed width E
+(widths_util.POSTERIOR_SETS: Hq below, above and no multiple of E, and one that is no multiple of 32 and so runs per step).
+The direct acvae_posterior_* calls get their buffers 4 KiB longer than declared, with a sentinel in the tail that must be
+untouched afterwards."""
 import copy
 import io
 import random
@@ -15,6 +20,7 @@ from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 from acvae_amd import _lib
 from acvae_amd import text_encoder as TE
 from acvae_amd.encoder import ptr_table
+from widths_util import POSTERIOR_SETS
 
 pytestmark = pytest.mark.gpu
 E, HQ, VQ = 64, 64, 30
@@ -32,7 +38,7 @@ def _caption_batch(N, seed):
     return caps, cap_lens
 
 
-def _posterior(L, p):
+def _posterior(L, p, E=E, HQ=HQ):
     torch.manual_seed(11)
     q = TE.PosteriorRNN_hybrid(E, E, VQ, hidden_size=HQ, num_layers=L, dropout=p)
     with torch.no_grad():
@@ -41,7 +47,7 @@ def _posterior(L, p):
     return q
 
 
-def _torch_posterior(q, caps, cap_lens, eps, train, seed):
+def _torch_posterior(q, caps, cap_lens, eps, train, seed, E=E):
     """PosteriorRNN_hybrid.forward (models/text_encoder.py:182-216) in fp64 on the CPU with torch's nn.GRU; the dropout
     masks come from the CPU generator under `seed`, inside self.network(...), as in the reference."""
     ref = copy.deepcopy(q).cpu().double()
@@ -60,10 +66,22 @@ def _torch_posterior(q, caps, cap_lens, eps, train, seed):
     return ref, (mean, log, z, utt)
 
 
+WORST = {}                 # worst error / tolerance per tensor group ("outputs", "gradients"), printed when the module is through
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_worst():
+    yield
+    for k in sorted(WORST):
+        print(f"\nPOSTERIOR worst error / tolerance, {k}: {WORST[k]:.3f}", end="")
+
+
 def _close(a, b, rtol, atol, what):
     a, b = a.detach().cpu().double(), b.detach().cpu().double()
     assert a.shape == b.shape, (what, a.shape, b.shape)
     err = (a - b).abs()
+    group = "gradients" if what.startswith("d ") else "outputs"
+    WORST[group] = max(WORST.get(group, 0.0), float((err / (atol + rtol * b.abs())).max()))
     ok = err <= atol + rtol * b.abs()
     assert bool(ok.all()), f"{what}: max abs err {float(err.max()):.3e} (ref max {float(b.abs().max()):.3e})"
 
@@ -80,7 +98,7 @@ def _run(q, caps, cap_lens, eps, seed, ups):
     return [o.detach().clone() for o in outs], {n: prm.grad.detach().clone() for n, prm in q.named_parameters()}
 
 
-def _upstream(N, Tc, seed):
+def _upstream(N, Tc, seed, E=E, HQ=HQ):
     g = torch.Generator().manual_seed(seed)
     return [torch.randn(N, Tc, E, generator=g) for _ in range(3)] + [torch.randn(N, 2 * HQ, generator=g)]
 
@@ -127,17 +145,29 @@ def test_persistent_and_per_step_recurrences_agree_bit_for_bit():
     assert not bad, bad
 
 
-@pytest.mark.parametrize("N", [5, 33])
-def test_one_layer_stack_entry_is_the_one_layer_call(N):
-    """acvae_posterior_stack_fwd / _bwd with num_layers = 1 (no upper table, no mask) reproduce acvae_posterior_fwd / _bwd
-    bit for bit, outputs and every gradient."""
-    q = _posterior(1, 0.0).cuda()
+TAIL = 4096
+
+
+def _with_tail(nbytes, fill):
+    """A buffer of `nbytes` declared bytes with TAIL more behind them that hold a sentinel: (declared view, whole buffer)."""
+    whole = torch.full((nbytes + TAIL,), fill, dtype=torch.uint8, device="cuda")
+    whole[nbytes:] = 0xA5
+    return whole[:nbytes], whole
+
+
+def _tail_untouched(whole, what):
+    tail = whole[-TAIL:]
+    assert bool((tail == 0xA5).all()), f"{what}: {int((tail != 0xA5).sum())} bytes behind the declared size were written"
+
+
+def _one_layer_entries(N, E=E, HQ=HQ):
+    q = _posterior(1, 0.0, E, HQ).cuda()
     caps, cap_lens = _caption_batch(N, seed=9)
     lens1 = torch.as_tensor(cap_lens - 1).cuda()
     Tc = int(cap_lens.max()) - 1
     caps_d = caps.long().cuda().contiguous()
     eps = torch.randn(N, Tc, E, generator=torch.Generator().manual_seed(5)).cuda()
-    ups = [u.cuda() for u in _upstream(N, Tc, 8)]
+    ups = [u.cuda() for u in _upstream(N, Tc, 8, E, HQ)]
     params = q._text_table()
     dims = (N, Tc, E, HQ, VQ)
     s = _lib.current_stream()
@@ -145,10 +175,11 @@ def test_one_layer_stack_entry_is_the_one_layer_call(N):
     for stacked in (False, True):
         sb = _lib.call("acvae_posterior_saved_bytes", *dims)
         cb = _lib.call("acvae_posterior_scratch_bytes", *dims)
+        assert sb > 0 and cb > 0
         assert sb == _lib.call("acvae_posterior_stack_saved_bytes", *dims, 1)
         assert cb == _lib.call("acvae_posterior_stack_scratch_bytes", *dims, 1)
-        saved = torch.empty(sb, dtype=torch.uint8, device="cuda")
-        scratch = torch.full((cb,), 0x7F, dtype=torch.uint8, device="cuda")
+        saved, saved_whole = _with_tail(sb, 0x00)
+        scratch, scratch_whole = _with_tail(cb, 0x7F)
         qm, ql, qz = (torch.empty(N, Tc, E, device="cuda") for _ in range(3))
         utt = torch.empty(N, 2 * HQ, device="cuda")
         grads = [torch.empty_like(p) if p is not None and 10 <= i <= 20 else None for i, p in enumerate(params)]
@@ -164,10 +195,81 @@ def test_one_layer_stack_entry_is_the_one_layer_call(N):
             _lib.call("acvae_posterior_bwd", ptr_table(params), ptr_table(grads), lens1, eps, ql, *ups, saved, sb, scratch,
                       cb, *dims, s, _lib.call_flags())
         torch.cuda.synchronize()
+        _lib.check_persist_status(torch.device("cuda"))
+        _tail_untouched(saved_whole, f"saved (stacked={stacked}, E={E}, Hq={HQ}, N={N})")
+        _tail_untouched(scratch_whole, f"scratch (stacked={stacked}, E={E}, Hq={HQ}, N={N})")
         results.append([qm, ql, qz, utt] + [g for g in grads if g is not None])
     assert len(results[0]) == 4 + 11
+    assert all(bool(torch.isfinite(t).all()) for t in results[0])
     for k, (a, b) in enumerate(zip(*results)):
         assert torch.equal(a, b), k
+
+
+@pytest.mark.parametrize("N", [5, 33])
+def test_one_layer_stack_entry_is_the_one_layer_call(N):
+    """acvae_posterior_stack_fwd / _bwd with num_layers = 1 (no upper table, no mask) reproduce acvae_posterior_fwd / _bwd
+    bit for bit, outputs and every gradient; neither writes behind the sizes it declares."""
+    _one_layer_entries(N)
+
+
+# ------------------------------------------------------------------------------------------------- unequal widths
+def _matches_torch_gru(Ew, Hw, L, N, mode):
+    train = mode == "train"
+    q = _posterior(L, 0.3 if L > 1 else 0.0, Ew, Hw).cuda().train(train)
+    assert q.network.weight_ih_l0.shape == (3 * Hw, Ew) and q.token_mean_log.weight.shape == (2 * Ew, 2 * Hw)
+    caps, cap_lens = _caption_batch(N, seed=N + L)
+    Tc = int(cap_lens.max()) - 1
+    eps = torch.randn(N, Tc, Ew, generator=torch.Generator().manual_seed(5))
+    ups = _upstream(N, Tc, 6, Ew, Hw)
+    outs, grads = _run(q, caps, cap_lens, eps, 21, ups)
+    _lib.check_persist_status(torch.device("cuda"))
+    ref, routs = _torch_posterior(q, caps, cap_lens, eps, train, 21, Ew)
+    tag = f"E={Ew} Hq={Hw} L={L} N={N} {mode}"
+    for got, want, key in zip(outs, routs, ("q_means", "q_logs", "q_z", "q_means_utt")):
+        _close(got, want, 1e-4, 1e-5, f"{key} {tag}")
+    torch.autograd.backward(list(routs), [u.double() for u in ups])
+    assert len(list(ref.named_parameters())) == 3 + 8 * L
+    for n, prm in ref.named_parameters():
+        want = prm.grad
+        assert float(want.abs().max()) > 0, n
+        _close(grads[n], want, 1e-4, 2e-5 * float(want.abs().max()), f"d {n} {tag}")
+
+
+@pytest.mark.parametrize("mode", ["eval", "train"])
+@pytest.mark.parametrize("N", [5, 32, 33])
+@pytest.mark.parametrize("L", [1, 2, 3])
+@pytest.mark.parametrize("Ew,Hw", POSTERIOR_SETS, ids=[f"E{e}_Hq{h}" for e, h in POSTERIOR_SETS])
+def test_posterior_widths_match_torch_gru(Ew, Hw, L, N, mode):
+    """test_stacked_posterior_matches_torch_gru, same bounds, with the embed width E and the GRU width Hq apart, and with one
+    layer as well: the input projection is [3 Hq, E], the upper layers' [3 Hq, 2 Hq], token_mean_log [2 E, 2 Hq].  N <= 32 and
+    Hq % 32 == 0 run the persistent recurrence (grid 2 Hq / 32), everything else goes per step."""
+    _matches_torch_gru(Ew, Hw, L, N, mode)
+
+
+@pytest.mark.parametrize("L", [1, 2])
+@pytest.mark.parametrize("Ew,Hw", POSTERIOR_SETS, ids=[f"E{e}_Hq{h}" for e, h in POSTERIOR_SETS])
+def test_posterior_widths_persistent_and_per_step_agree_bit_for_bit(Ew, Hw, L):
+    """N = 32, training mode: the persistent launches and the per-step loop give the same outputs and gradients at every
+    width (at Hq % 32 != 0 both runs go per step: the plan refuses the width)."""
+    q = _posterior(L, 0.3 if L > 1 else 0.0, Ew, Hw).cuda().train()
+    caps, cap_lens = _caption_batch(32, seed=3)
+    Tc = int(cap_lens.max()) - 1
+    eps = torch.randn(32, Tc, Ew, generator=torch.Generator().manual_seed(5))
+    ups = _upstream(32, Tc, 7, Ew, Hw)
+    o1, g1 = _run(q, caps, cap_lens, eps, 4, ups)
+    _lib.check_persist_status(torch.device("cuda"))
+    with _lib.override(persist=False):
+        o2, g2 = _run(q, caps, cap_lens, eps, 4, ups)
+    for a, b in zip(o1, o2):
+        assert torch.equal(a, b)
+    bad = [n for n in g1 if not torch.equal(g1[n], g2[n])]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("N", [5, 32, 33])
+@pytest.mark.parametrize("Ew,Hw", POSTERIOR_SETS[1:], ids=[f"E{e}_Hq{h}" for e, h in POSTERIOR_SETS[1:]])
+def test_posterior_widths_one_layer_stack_entry_is_the_one_layer_call(Ew, Hw, N):
+    _one_layer_entries(N, Ew, Hw)
 
 
 # ------------------------------------------------------------------------------------------------- end to end

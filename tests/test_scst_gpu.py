@@ -18,6 +18,7 @@ that finish before the last step, per case:
   decdrop (32)               0 % of 26, 5.4e-3, rows 1 / 2 at 0 / 4    end_at_step0 (31)     0 % of 30, 1.4e-1, row 3 at 0, rows 0 / 1 at 8 / 9
   e512 (31)                  0 % of 20, 9.9e-3, none                   cnn14_ln (32)         0 % of 30, 6.5e-3, none
   sample_n5 (31)             0 % of 136, 1.0e-2, rows 10 / 14 at 0 / 4 rows165 (31)          0 % of 1576, 2.4e-4, 21 of 165 rows
+  widths_e64_h96_a160 (31)   0 % of 39, 2.0e-2, row 0 at step 8
 The <end> bias bump of end_at_step0 was chosen the same way (oracle alone: + 0.5 ends no clip at step 0, + 1.0 exactly one,
 + 1.5 one and two more by step 3, + 2.0 two)."""
 import random
@@ -48,6 +49,9 @@ CASES = {
     "cnn14_ln": dict(V=40, E=64, B=3, T=96, method="sample", temp=1.0, seed=32, encoder="Cnn14_16k"),
     "sample_n5": dict(V=40, E=64, B=3, T=96, method="sample", temp=1.0, seed=31, sample_n=5),
     "rows165": dict(V=40, E=64, B=33, T=64, method="sample", temp=1.0, seed=31, sample_n=5),   # past the 32-row boundary
+    # the decoder GRU (H) and the attention (A) wider than the embeddings: a rollout has no utterance head, so its forward and
+    # acvae_decode_bwd - the only backward that runs with H != E - take any H (tests/widths_util.py)
+    "widths_e64_h96_a160": dict(V=40, E=64, H=96, A=160, B=4, T=96, method="sample", temp=1.0, seed=31),
 }
 MAXLEN = 10
 
@@ -56,7 +60,7 @@ def setup(p):
     V, E = p["V"], p["E"]
     enc = p.get("encoder", "Cnn10")
     enc_embed = 512 if enc == "Cnn10" else 2048
-    state = O.closed_form_state(O.state_shapes(V, E, E, None, E, enc_embed, encoder=enc))
+    state = O.closed_form_state(O.state_shapes(V, E, p.get("H", E), p.get("A"), E, enc_embed, encoder=enc))
     if p.get("end_bump"):
         state["decoder.classifier.bias"][END] += p["end_bump"]
     feats, _, fl, _ = O.synthetic_batch(p["B"], p["T"], V, 8, seed=p["seed"], ragged=True)
@@ -78,7 +82,12 @@ def test_scst_step_vs_oracle(case):
     nat = natural(p, state, feats, fl)
     if p.get("end_at_0"):
         assert int((nat["sampled"]["seqs"][:, 0] == END).sum()) == 1
-    model = build_model(p["V"], p["E"], state, encoder=p.get("encoder", "Cnn10"), dec_dropout=p.get("dec_dropout", 0.0))
+    if "H" in p:
+        import widths_util as W
+        model = W.build_model(p["V"], p["E"], p["H"], p["A"], p["E"], state)
+        assert state["decoder.model.weight_ih_l0"].shape == (3 * p["H"], 3 * p["E"])
+    else:
+        model = build_model(p["V"], p["E"], state, encoder=p.get("encoder", "Cnn10"), dec_dropout=p.get("dec_dropout", 0.0))
     sc = StubScorer()
     out, rollout = hip_scst(model, nat, feats, fl, keys, key2refs, vocab, sc, **kwargs_of(p))
     assert out["sampled_logprobs"].requires_grad and rollout["logits"].requires_grad
