@@ -574,10 +574,13 @@ extern "C" int64_t acvae_decode_saved_lse_offset(int N, int Tc, int S, int E, in
   DecLayout L;
   return dec_layout(N, Tc, S, E, H, A, V, Eenc, L) == ACVAE_OK ? L.lse * 4 : -1;
 }
+// ONE scratch size for the forward and the backward (the caller asks once): both refuse anything below it, not only what falls
+// below their own share, so that a caller's short buffer shows at the first call and not only in the backward
+static inline long dec_scratch_floats(const DecLayout& L) { return L.scratch_fwd > L.scratch_bwd ? L.scratch_fwd : L.scratch_bwd; }
 extern "C" int64_t acvae_decode_scratch_bytes(int N, int Tc, int S, int E, int H, int A, int V, int Eenc) {
   DecLayout L;
   if (dec_layout(N, Tc, S, E, H, A, V, Eenc, L) != ACVAE_OK) return -1;
-  return (L.scratch_fwd > L.scratch_bwd ? L.scratch_fwd : L.scratch_bwd) * 4;
+  return dec_scratch_floats(L) * 4;
 }
 
 extern "C" int acvae_decode_fwd(const void* const* params, const float* mem_in, const int64_t* mem_lens,
@@ -631,7 +634,7 @@ static int decode_fwd_driver(const void* const* params, const float* mem_in, con
   const bool rollout_grad = !train && (flags & ACVAE_FLAG_ROLLOUT_GRAD);
   if (train && (!lens1 || !q_z || !ss_flags_host || !dis_flags_host || !p_means_utt)) return ACVAE_EINVAL;
   if (train && H != E) return ACVAE_EUNSUPPORTED;  // mean_log_out = Linear(embed_size, .) is fed the GRU output
-  if (saved_bytes < L.saved_total * 4 || scratch_bytes < L.scratch_fwd * 4) return ACVAE_EWORKSPACE;
+  if (saved_bytes < L.saved_total * 4 || scratch_bytes < dec_scratch_floats(L) * 4) return ACVAE_EWORKSPACE;
   float* sv = (float*)saved_v;
   float* sc = (float*)scratch_v;
   auto P = [&](int i) { return (const float*)params[i]; };
@@ -974,7 +977,7 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
       !scratch_v)
     return ACVAE_EINVAL;
   if (rollout ? d_p_means_utt != nullptr : (!lens1 || !dis_flags_host || !d_q_z)) return ACVAE_EINVAL;
-  if (saved_bytes < L.saved_total * 4 || scratch_bytes < L.scratch_bwd * 4) return ACVAE_EWORKSPACE;
+  if (saved_bytes < L.saved_total * 4 || scratch_bytes < dec_scratch_floats(L) * 4) return ACVAE_EWORKSPACE;
   float* sv = (float*)saved_v;
   float* sc = (float*)scratch_v;
   std::vector<int> rollout_flags;

@@ -22,6 +22,16 @@
  *     _attn_split are per-call `flags` (ACVAE_FLAG_*).  The library reads ONE environment variable, once per process into
  *     a static constant (never written afterwards): ACVAE_CONV_WINO (encoder.hip: 0 = implicit-GEMM convolutions), the
  *     A/B switch the benchmark and the tests still use.
+ *   - Workspaces (`saved`, `scratch`, `ws`), sized by the `*_bytes` function named beside each entry:
+ *       (1) the declared size is exact: a call touches no byte outside [ptr, ptr + declared bytes);
+ *       (2) the contents on entry are arbitrary (whatever the allocator last held there): every ticket, arrival counter and
+ *           accumulator inside a workspace is zeroed by the call itself.  The caller zeroes ONLY: the first 1024 bytes of
+ *           acvae_attn_fwd's workspace, once; the tickets of the reducers' test entries called with reset_tickets = 0 (an
+ *           earlier call with reset_tickets = 1 does it); the status words of acvae_persist_status_register;
+ *       (3) a workspace below the declared size is ACVAE_EWORKSPACE before any HIP call, and nothing is touched.  Where one
+ *           function sizes one buffer for two entries it returns the larger need: acvae_decode_scratch_bytes - the forward
+ *           and the backward both refuse anything below it; acvae_step_scratch_bytes - acvae_prior_step_fwd is not told H
+ *           and A and refuses what is below its own (E, E, E) layout, acvae_decoder_step_fwd what is below its (E, H, A) one.
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it and nothing synchronises.
  *   - return 0 on success, a negative ACVAE_E* code for bad arguments, or a positive hipError_t.
  *   - fp32 everywhere ("dtype f32"), token ids / lengths int64 (as torch.long).

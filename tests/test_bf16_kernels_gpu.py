@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 from acvae_amd import _lib
 from test_kernels_gpu import S, assert_every_element, chain_tol, nhwc, ws_buf
+from ws_guard import ws_guards  # noqa: F401  (autouse fixture: every guard of ws_buf intact after each test)
 
 pytestmark = pytest.mark.gpu
 

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from acvae_amd import _lib
+from ws_guard import guarded, ws_guards  # noqa: F401  (autouse fixture: every guard intact after each test)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,8 +39,9 @@ def stream():
 
 
 def garbage_ws(nbytes):
-    """Slabs (and, until a reset, tickets) of large finite values: a slab element read before it is written shows."""
-    return torch.full((max(int(nbytes), 4),), 0x7F, dtype=torch.uint8, device="cuda")
+    """Exactly `nbytes` between guards (tests/ws_guard.py); slabs (and, until a reset, tickets) of 0xFF bytes - NaN and full
+    counters: a slab element read before it is written shows.  The handle answers data_ptr() and numel() as a tensor."""
+    return guarded(nbytes, 0xFF)
 
 
 def ints(v):
@@ -130,11 +132,11 @@ def test_each_job_equals_its_own_fused_call_and_the_tickets_reset_themselves():
     for i, (g, w) in enumerate(zip(first, want)):
         assert_bits(g, w, f"job {i + 1} {JOBS[i][:3]}")       # job 4: the whole wide matrix, so the left columns as well
     assert bool((first[3][:, :LEFT] == SENTINEL).all()), "job 4 wrote outside its column block"
-    assert not bool(ws[:4 * TN_TICKETS].view(torch.int32).any().cpu()), "a ticket was left behind"
+    assert not bool(ws.view[:4 * TN_TICKETS].view(torch.int32).any().cpu()), "a ticket was left behind"
     second = group_call(jobs, ws, reset=False)                # no zeroing in between: the slabs hold the first launch's partials
     for i, (g, w) in enumerate(zip(second, first)):
         assert_bits(g, w, f"second launch, job {i + 1}")
-    assert not bool(ws[:4 * TN_TICKETS].view(torch.int32).any().cpu())
+    assert not bool(ws.view[:4 * TN_TICKETS].view(torch.int32).any().cpu())
 
 
 def test_reversed_table_gives_the_same_results():
@@ -170,4 +172,4 @@ def test_one_slice_job_writes_c_itself():
     assert_bits(got[0], want[0], "one slice, beside a sliced job")
     assert_bits(got[1], want[1], "sliced job beside it")
     assert group_ws_bytes([one]) == 0
-    assert_bits(group_call([one], garbage_ws(4), reset=False)[0], want[0], "one slice, alone")
+    assert_bits(group_call([one], garbage_ws(0), reset=False)[0], want[0], "one slice, alone")

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from acvae_amd import _lib
+from ws_guard import guarded, ws_guards  # noqa: F401  (autouse fixture: every guard intact after each test)
 
 pytestmark = pytest.mark.gpu
 
@@ -71,12 +72,13 @@ class Mat:
 
 
 def garbage_ws(nbytes):
-    """A workspace whose slabs hold large finite values (0x7f7f7f7f ~ 3.4e38), tickets as well until a reset zeroes them."""
-    return torch.full((int(nbytes),), 0x7F, dtype=torch.uint8, device="cuda")
+    """A workspace of exactly `nbytes` between guards (tests/ws_guard.py) whose slabs hold NaN (0xFF bytes), tickets full
+    counters until a reset zeroes them.  The handle answers data_ptr() and numel() as the tensor it stands for."""
+    return guarded(nbytes, 0xFF)
 
 
 def tickets(ws, words):
-    return ws[:4 * words].view(torch.int32).cpu()
+    return ws.view[:4 * words].view(torch.int32).cpu()
 
 
 # ------------------------------------------------------------------------------------------------ skinny split-K
@@ -309,7 +311,7 @@ class TnCase:
     def two_launch(self):
         C = self.C0.cuda()
         nb = lib().acvae_gemm_tn_workspace_bytes(self.M, self.N, self.K)
-        slab = torch.empty(max(int(nb), 4), dtype=torch.uint8, device="cuda")
+        slab = garbage_ws(nb)
         rc = lib().acvae_gemm_tn(self.A.ptr, self.M, self.B.ptr, self.N, C.data_ptr(), self.N, self.M, self.N, self.K,
                                  self.acc, slab.data_ptr(), nb, stream())
         assert rc == 0, rc
@@ -345,7 +347,7 @@ def test_fused_tn_equals_the_two_launch_form_bit_for_bit(M, N, K, acc, slices):
 def test_fused_tn_single_slice_and_short_workspace_against_fp64():
     one = TnCase(5, 5000, 512, 672, True)
     assert one.plan() == 1 and one.ws_bytes() == 0
-    ws = garbage_ws(64)
+    ws = garbage_ws(0)
     got_one = one.fused(ws, reset=True)
     short = TnCase(6, 512, 512, 672, False)
     assert short.plan() == 11 and short.plan(short.ws_bytes() - 4) == 1
@@ -367,8 +369,8 @@ def test_fused_tn_ticket_reuse_sequence():
         c = TnCase(900 + i, M, N, K, i % 2 == 1)
         assert c.plan() == s, (M, N, K, c.plan(), s)
         cases.append(c)
-    ws = garbage_ws(max(c.ws_bytes() for c in cases))
-    got = [c.fused(ws, reset=(i == 0)) for i, c in enumerate(cases)]
+    ws = garbage_ws(max(c.ws_bytes() for c in cases))       # one workspace for the sequence; each call is told its own size
+    got = [c.fused(ws, reset=(i == 0), ws_bytes=c.ws_bytes()) for i, c in enumerate(cases)]
     want = [c.two_launch() for c in cases]
     torch.cuda.synchronize()
     for i, (g_, w_) in enumerate(zip(got, want)):
@@ -499,7 +501,7 @@ def test_colsum_batch_fallbacks():
              (short, small, "workspace too small")]
     for b, nb, what in cases:
         assert b.plan(nb) == 0, what
-        ws = garbage_ws(max(nb, b.ws_bytes()))
+        ws = garbage_ws(nb)
         out, out_b = b.run(ws, nb, reset=True)
         torch.cuda.synchronize()
         b.check(out, out_b, what)

@@ -23,6 +23,7 @@ import torch.nn.functional as F
 import acvae_oracle as O
 from acvae_amd import _lib
 from conftest import load_golden
+from ws_guard import guarded, ws_guards  # noqa: F401  (autouse fixture: every guard intact after each test)
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
@@ -37,7 +38,8 @@ def nhwc(x):
 
 
 def ws_buf(nbytes):
-    return torch.empty(int(nbytes), dtype=torch.uint8, device="cuda")
+    """Exactly `nbytes` between guards (tests/ws_guard.py), every byte 0xFF: NaN as a float, a full counter as a ticket."""
+    return guarded(nbytes, 0xFF).view
 
 
 def chain_tol(K):

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 from acvae_amd import _lib
 from acvae_amd.encoder import ResNet38
+from ws_guard import guarded, ws_guards  # noqa: F401  (autouse fixture: every guard intact after each test)
 
 pytestmark = pytest.mark.gpu
 NULL = None
@@ -64,7 +65,7 @@ def test_res_join_kernels_vs_fp64(N, H, W, C, ds, training):
     G, dy2, dyd = (torch.empty(N, H, W, C, device="cuda") for _ in range(3))
     dg2, db2, dgd, dbd = (torch.empty(C, device="cuda") for _ in range(4))
     wsb = _lib.call("acvae_res_join_bwd_workspace_bytes", N, H, W, C)
-    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    ws = guarded(wsb, 0xFF).view
     _lib.call("acvae_res_join_bwd", dev(dO), out, dev(y2), dev(bn2), dev(yd), dev(bnd) if ds else NULL, G, dy2, dyd if ds else NULL,
               dg2, db2, dgd if ds else NULL, dbd if ds else NULL, training, ws, wsb, N, H, W, C, _lib.current_stream())
     # fp64: the decisions the kernel took (out > 0 of its own output)
@@ -106,7 +107,7 @@ def test_conv1x1_kernels_vs_fp64(N, H, W, Cin, Cout):
     refx = base.double().reshape(M, Cin) + dY.double().reshape(M, Cout) @ Wt.double().reshape(Cout, Cin)
     close(dX.reshape(M, Cin), refx, 1e-5, 1e-5, "conv1x1 dgrad (+=)")
     wsb = _lib.call("acvae_conv1x1_wgrad_workspace_bytes", N, H, W, Cin, Cout)
-    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    ws = guarded(wsb, 0xFF).view
     dW = torch.empty(Cout, Cin, 1, 1, device="cuda")
     _lib.call("acvae_conv1x1_wgrad", dY.cuda(), X.cuda(), dW, ws, wsb, N, H, W, Cin, Cout, _lib.current_stream())
     close(dW.reshape(Cout, Cin), dY.double().reshape(M, Cout).T @ X.double().reshape(M, Cin), 1e-5, 1e-4, "conv1x1 wgrad")

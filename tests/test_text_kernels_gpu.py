@@ -11,6 +11,7 @@ import torch
 import text_ref as R
 from acvae_amd import _lib
 from text_ref import D
+from ws_guard import guarded, ws_guards  # noqa: F401  (autouse fixture: every guard intact after each test)
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
@@ -27,7 +28,9 @@ def nans(*shape):
 
 
 def nan_ws(nbytes):
-    return torch.full((max(int(nbytes), 4),), 0xFF, dtype=torch.uint8, device="cuda")      # every float a NaN
+    """Exactly `nbytes` between guards (tests/ws_guard.py), every float a NaN."""
+    assert nbytes > 0, nbytes
+    return guarded(nbytes, 0xFF).view
 
 
 def check(got, ref, tol, what):
@@ -52,7 +55,7 @@ def attn_fwd_call(c, N, Tq, S_, A, E, ws, flags):
     d = c["dev"]
     ctx, w = nans(N, Tq, E), nans(N, Tq, S_)
     _lib.call("acvae_attn_fwd", d["q"], Tq * A, A, d["p"], d["enc"], d["lens"], d["v"], ctx, Tq * E, E, w, Tq * S_, S_, N, Tq,
-              S_, A, E, ws, 0 if ws is None else ws.numel(), S(), flags)
+              S_, A, E, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), S(), flags)
     return ctx, w
 
 
@@ -63,8 +66,12 @@ def test_attn_fwd_one_workgroup_form(N, Tq, S_, A, E, lens, what):
     ctx against fp64; masked weights exactly 0 (their bound is 0), a len == 0 row uniform."""
     c = fwd_case(N, Tq, S_, A, E, lens_key(lens))
     ctx, w = attn_fwd_call(c, N, Tq, S_, A, E, None, 0)
-    wsb = max(_lib.call("acvae_attn_fwd_workspace_bytes", N, Tq, S_, A, E), 4096)
-    ctx2, w2 = attn_fwd_call(c, N, Tq, S_, A, E, torch.zeros(wsb, dtype=torch.uint8, device="cuda"), _lib.FLAG_NO_ATTN_SPLIT)
+    # the declared size (0 where the shape never splits: a non-null pointer to no bytes), counters poisoned too: with
+    # ACVAE_FLAG_NO_ATTN_SPLIT the call does not touch the workspace
+    wsb = _lib.call("acvae_attn_fwd_workspace_bytes", N, Tq, S_, A, E)
+    ws = guarded(wsb, 0xFF)
+    ctx2, w2 = attn_fwd_call(c, N, Tq, S_, A, E, ws, _lib.FLAG_NO_ATTN_SPLIT)
+    assert bool((ws.view == 0xFF).all())
     check(w, c["w"], c["tw"], f"attn_fwd.weights {what}")
     check(ctx, c["ctx"], c["tc"], f"attn_fwd.ctx {what}")
     assert torch.equal(w, w2) and torch.equal(ctx, ctx2)
@@ -98,8 +105,8 @@ def test_attn_fwd_split_form_against_fp64(N, Tq, S_, A, E, strided, what):
     d = c["dev"]
     wsb = _lib.call("acvae_attn_fwd_workspace_bytes", N, Tq, S_, A, E)
     assert wsb > 1024
-    ws = torch.zeros(wsb, dtype=torch.uint8, device="cuda")
-    ws[1024:] = 0xFF                                     # counters zero, partials NaN
+    ws = guarded(wsb, 0xFF).view                         # include/acvae_hip.h: the caller zeroes the first 1024 bytes (the
+    ws[:1024] = 0                                        # arrival counters), ONCE; the partials behind them hold NaN
     ld = 3 * E if strided else E
     cb = torch.full((N, Tq, ld), SENT, device="cuda"); cb[..., (E if strided else 0):(2 * E if strided else E)] = NAN
     w = nans(N, Tq, S_)
