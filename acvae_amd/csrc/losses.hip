@@ -5,6 +5,7 @@
 // All HBM-bound: vectorised streaming + wave64 shuffle reductions; every reduction is a fixed-shape
 // two-level tree (per-block partials, then one block) so results are run-to-run deterministic.
 #include "common.h"
+#include "dbs_rules.h"
 #include "../../include/acvae_hip.h"
 
 namespace {
@@ -600,6 +601,60 @@ __global__ __launch_bounds__(256) void dbs_scores_kernel(const float* __restrict
     o[c] = pv + v;
   }
 }
+// The same scores with the penalty taken from the earlier groups' tables instead of a dense count vector (the one-call
+// diverse beam search, search.hip): tables int32 [G][T][R], element (e, s, r) = step s of group e, row r = n * bdash + b.
+// Group e < g has run local step le = min(lt + g - e, T - 1); the word its beam b holds at column lt is found by walking
+// the parents from le down to lt + 1 (at most 15 steps).  The clip's (at most 240) words are listed in LDS; the row is
+// written without a penalty, then the first occurrence of every listed word rewrites its column with the word's
+// multiplicity as the count: the arithmetic of dbs_scores_kernel on a dense count vector, column by column.  A parent
+// outside [0, R) is clamped into it, a word outside [0, V) is skipped.  One workgroup per row.
+constexpr int DBS_LIST_MAX = 240;
+__global__ __launch_bounds__(256) void dbs_scores_sparse_kernel(const float* __restrict__ logits, long ld, float temperature,
+                                                                float lambda, const float* __restrict__ prev,
+                                                                float* __restrict__ out, const int* __restrict__ par_tab,
+                                                                const int* __restrict__ word_tab, int V, int bdash, int R,
+                                                                int T, int g, int lt) {
+  __shared__ float red[16];
+  __shared__ int lw[DBS_LIST_MAX];
+  const int n = blockIdx.x;
+  const int L = g * bdash;
+  if ((int)threadIdx.x < L) {
+    const int e = threadIdx.x / bdash, b = threadIdx.x - e * bdash;
+    lw[threadIdx.x] = acvae::dbs::column_word(par_tab, word_tab, e, g, lt, (long)(n / bdash) * bdash + b, T, R);
+  }
+  const float* x = logits + (long)n * ld;
+  float m = -INFINITY;
+  for (int c = threadIdx.x; c < V; c += blockDim.x) m = fmaxf(m, x[c]);
+  m = block_max(m, red);
+  float s = 0.f;
+  for (int c = threadIdx.x; c < V; c += blockDim.x) s += expf(x[c] - m);
+  s = block_sum(s, red);
+  const float lse1 = m + logf(s);
+  float m2 = -INFINITY;
+  for (int c = threadIdx.x; c < V; c += blockDim.x) m2 = fmaxf(m2, (x[c] - lse1) / temperature);
+  m2 = block_max(m2, red);
+  float s2 = 0.f;
+  for (int c = threadIdx.x; c < V; c += blockDim.x) s2 += expf((x[c] - lse1) / temperature - m2);
+  s2 = block_sum(s2, red);
+  const float lse2 = m2 + logf(s2);
+  const float pv = prev ? prev[n] : 0.f;
+  float* o = out + (long)n * V;
+  for (int c = threadIdx.x; c < V; c += blockDim.x) {
+    float v = (x[c] - lse1) / temperature - lse2;
+    o[c] = pv + v;
+  }
+  __syncthreads();                                       // the row is written (and lw, long since) before a column is rewritten
+  if ((int)threadIdx.x < L) {
+    const int c = lw[threadIdx.x];
+    if (c < 0 || c >= V) return;
+    bool first;
+    const float count = (float)acvae::dbs::multiplicity(lw, L, (int)threadIdx.x, &first);
+    if (!first) return;
+    float v = (x[c] - lse1) / temperature - lse2;
+    v -= count * lambda;
+    o[c] = pv + v;
+  }
+}
 // flat top-k (k <= 16) of x[0..n), sorted descending, ties -> lower index first (torch.topk(sorted=True) order for
 // distinct values); one workgroup, k selection passes.  Also emits idx / V and idx % V.
 __global__ __launch_bounds__(1024) void topk_flat_kernel(const float* __restrict__ x, long n, int k, int V,
@@ -890,6 +945,22 @@ extern "C" int acvae_dbs_scores(const float* logits, int64_t ld, float temperatu
   if (!logits || !out || N <= 0 || V <= 0 || !(temperature > 0.f) || rows_per_count < 0) return ACVAE_EINVAL;
   hipLaunchKernelGGL(dbs_scores_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, logits, ld, temperature, counts,
                      diversity_lambda, prev, out, V, rows_per_count);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_dbs_scores_sparse(const float* logits, int64_t ld, float temperature, float diversity_lambda,
+                                       const float* prev, float* out, const int* parent_tab, const int* word_tab, int N,
+                                       int bdash, int T, int V, int G, int g, int lt, void* stream) {
+  if (!logits || !out || N <= 0 || V <= 0 || ld < V || !(temperature > 0.f) || !(fabsf(diversity_lambda) < INFINITY))
+    return ACVAE_EINVAL;
+  if (bdash < 1 || T < 1 || G < 1 || g < 0 || g >= G || lt < 0 || lt >= T) return ACVAE_EINVAL;
+  if (bdash > 16 || G > 16) return ACVAE_EUNSUPPORTED;
+  if (g > 0 && (!parent_tab || !word_tab)) return ACVAE_EINVAL;
+  const long R = (long)N * bdash;
+  if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
+  hipLaunchKernelGGL(dbs_scores_sparse_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, logits, (long)ld,
+                     temperature, diversity_lambda, prev, out, parent_tab, word_tab, V, bdash, (int)R, T, g, lt);
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }

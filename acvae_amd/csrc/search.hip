@@ -2,12 +2,14 @@
 //   - single decode steps, the per-step API of the reference's pnet / decoder modules (acvae_prior_step_fwd,
 //     acvae_decoder_step_fwd, acvae_attn_precompute);
 //   - the search over M members' averaged word probabilities, greedy or beam (acvae_ensemble_search), and the validation
-//     beam search of one model (acvae_beam_search), which is its M = 1 case plus beam 0's attention-weight history.
+//     beam search of one model (acvae_beam_search), which is its M = 1 case plus beam 0's attention-weight history;
+//   - diverse beam search over M >= 1 members (acvae_ensemble_dbs_search; acvae_dbs_search is its M = 1 case), at the end.
 // The training-time composites are decoder.hip.
 #include <utility>
 #include "common.h"
 #include "constrain.h"
 #include "conv.h"
+#include "dbs_rules.h"
 #include "rnn.h"
 #include "text_common.h"
 
@@ -684,6 +686,263 @@ extern "C" int acvae_beam_finish(const int64_t* parent, const int64_t* word, int
   hipLaunchKernelGGL(beam_finish_kernel, dim3(N), dim3(FIN_THREADS), 0, (hipStream_t)stream, parent, word, (long)hist_stride,
                      f, norm_dev, attw, seqs, logprobs, attw_out, nbest_seqs, nbest_scores, nbest_logprobs, nbest_lengths,
                      N * beam, beam, T, S, nbest, end_idx);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+// ==========================================================================================
+// Diverse beam search as ONE call, over M >= 1 members (include/acvae_hip.h has the definition): CaptionModel.
+// diverse_beam_search, models/word_model.py:297-394, with Hybrid_VAEModel's step.  G groups of bdash beams per clip, all
+// N clips together: a group's step runs R = N * bdash rows through prior_step / decoder_step exactly as search() does, so
+// the logits are the step API's bits.  Every (time step, group) pair is: the members' steps, the mix (M > 1 only), the
+// scores with the sparse penalty (losses.hip), the flat top-k, dbs_advance_kernel, and the state gather by parent.  The
+// groups' parent / word / record tables [G][T][R] stay in the scratch; dbs_finish_kernel ranks and traces at the end.
+// No atomics, no hand-off between workgroups, no host synchronisation.
+// ==========================================================================================
+namespace {
+// Behind the top-k of step (g, lt): the step's parent and word go into the group's tables, the row's record is its
+// score c if it emitted end_idx or this is the last step (else "none", a NaN), and a recorded row is retired:
+// c <- c - 1000.0f.  One thread per row.
+__global__ __launch_bounds__(256) void dbs_advance_kernel(float* __restrict__ c, const int64_t* __restrict__ parent,
+                                                          const int64_t* __restrict__ word, int* __restrict__ par_out,
+                                                          int* __restrict__ word_out, float* __restrict__ rec_out,
+                                                          int64_t end_idx, int last, int R) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const float v = c[r];
+  const int64_t w = word[r];
+  const bool ends = acvae::dbs::recorded(w, end_idx, last);
+  par_out[r] = (int)parent[r];
+  word_out[r] = (int)w;
+  rec_out[r] = ends ? v : acvae::dbs::no_record();
+  if (ends) c[r] = acvae::dbs::retired(v);
+}
+// One wavefront per (clip, group).  `keep` selection passes over the group's T * bdash records in beam_finish_kernel's
+// idiom: key (double)c / (double)(lt + 1), descending, ties to the lower candidate index i = lt * bdash + b, which is the
+// order of recording.  Then lane q walks record q's parents back from its step.  A parent outside [0, R) is clamped.
+__global__ __launch_bounds__(64) void dbs_finish_kernel(const int* __restrict__ par_tab, const int* __restrict__ word_tab,
+                                                        const float* __restrict__ rec, int64_t* __restrict__ seqs,
+                                                        double* __restrict__ scores, int* __restrict__ lengths, int R,
+                                                        int bdash, int T, int keep, int64_t end_idx) {
+  __shared__ int sel[16];
+  namespace D = acvae::dbs;
+  const int n = blockIdx.x, g = blockIdx.y, G = gridDim.y, lane = threadIdx.x;
+  const int cand = T * bdash;
+  for (int q = 0; q < keep; ++q) {
+    double bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < cand; i += 64) {
+      const int lt = D::cand_step(i, bdash);
+      const float fv = rec[D::at(g, lt, D::cand_row(i, bdash, n), T, R)];
+      if (!D::is_record(fv)) continue;
+      bool taken = false;
+      for (int p = 0; p < q; ++p) taken = taken || (sel[p] == i);
+      const double v = D::key(fv, lt);
+      if (!taken && D::better(v, i, bv, bi)) { bv = v; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (D::better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) sel[q] = bi == 0x7fffffff ? -1 : bi;
+    __syncthreads();
+  }
+  if (lane >= keep) return;
+  const int i = sel[lane];
+  const int t0 = i < 0 ? -1 : D::cand_step(i, bdash);
+  const long r = i < 0 ? 0 : D::cand_row(i, bdash, n);
+  const long o = D::out_row(n, g, lane, G, keep);
+  scores[o] = i < 0 ? -INFINITY : D::key(rec[D::at(g, t0, r, T, R)], t0);
+  lengths[o] = t0 + 1;
+  D::trace(par_tab, word_tab, g, t0, r, T, R, end_idx, seqs + o * T);
+}
+
+struct DbsMemberLayout { StepLayout sl; long step, encd, encp, cur, h2, hp2, cp2, z, mean, logv, attp, attw, logits, rnn; };
+struct DbsLayout { DbsMemberLayout m[ACVAE_ENSEMBLE_MAX]; long mix, scores, gscore, gword, gpar, idx, par_tab, word_tab, rec, total; };
+// cur: the G groups' states a step reads, [G][R][H + 3E] as h | hp | cp | last_z blocks per group; everything else is
+// rewritten by every step and shared by the groups.
+int dbs_layout(const SearchMember* mb, int M, int N, int G, int bdash, int T, int V, DbsLayout& L) {
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || N <= 0 || G <= 0 || bdash <= 0 || T <= 0) return ACVAE_EINVAL;
+  if (G > 16 || bdash > 16) return ACVAE_EUNSUPPORTED;
+  const long R = (long)N * bdash;
+  if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
+  Bump b;
+  for (int m = 0; m < M; ++m) {
+    DbsMemberLayout& o = L.m[m];
+    const long S = mb[m].S, e = mb[m].E, h = mb[m].H;
+    ACVAE_TRY(step_layout((int)R, mb[m].S, mb[m].E, mb[m].H, mb[m].A, V, o.sl));
+    o.step = b.take(o.sl.total);
+    o.encd = b.take((long)N * S * mb[m].A);
+    o.encp = b.take((long)N * S * e);
+    o.cur = b.take((long)G * R * (h + 3 * e));
+    o.h2 = b.take(R * h); o.hp2 = b.take(R * e); o.cp2 = b.take(R * e); o.z = b.take(R * e);
+    o.mean = b.take(R * e); o.logv = b.take(R * e);
+    o.attp = b.take(R * S); o.attw = b.take(R * S);
+    o.logits = b.take(R * V);
+    o.rnn = b.take(R * 3 * e);
+  }
+  L.mix = M > 1 ? b.take(R * V) : 0;
+  L.scores = b.take(R * V);
+  L.gscore = b.take((long)G * R);
+  L.gword = b.take(2 * (long)G * R);                     // int64 [G][R]: the word each group's next step is fed
+  L.gpar = b.take(2 * (long)G * R);                      // int64 [G][R]: its parent rows
+  L.idx = b.take(2 * R);                                 // int64 [R]: the top-k's flat indices (unused)
+  L.par_tab = b.take((long)G * T * R);                   // int32 [G][T][R]
+  L.word_tab = b.take((long)G * T * R);
+  L.rec = b.take((long)G * T * R);
+  L.total = b.off;
+  return ACVAE_OK;
+}
+
+int dbs_search(const SearchMember* mb, int M, const DbsLayout& L, int64_t start_idx, int64_t end_idx, int N, int G,
+               int bdash, int T, int V, float temperature, float lambda, int group_nbest, int64_t* seqs, double* scores,
+               int* lengths, float* sc, hipStream_t s) {
+  const int R = N * bdash;
+  const float* logit_ptr[ACVAE_ENSEMBLE_MAX];
+  int64_t logit_ld[ACVAE_ENSEMBLE_MAX];
+  for (int m = 0; m < M; ++m) {
+    const DbsMemberLayout& o = L.m[m];
+    const SearchMember& b = mb[m];
+    float* ssc = sc + o.step;
+    ACVAE_TRY(acvae_skinny_ws_reset(ssc + o.sl.skws, s));
+    ACVAE_TRY(step_attws_reset(ssc, o.sl, s));
+    ACVAE_TRY(acvae_attn_precompute(b.params, 0, b.mem, sc + o.encd, N, b.S, b.E, b.H, b.A, s));
+    ACVAE_TRY(acvae_attn_precompute(b.params, 1, b.mem, sc + o.encp, N, b.S, b.E, b.E, b.E, s));
+    ACVAE_TRY(zero(sc + o.cur, (long)G * R * (b.H + 3 * b.E), s));         // lt = 0: every state is zero
+    logit_ptr[m] = sc + o.logits;
+    logit_ld[m] = V;
+  }
+  float* gscore = sc + L.gscore;
+  int64_t* gword = (int64_t*)(sc + L.gword);
+  int64_t* gpar = (int64_t*)(sc + L.gpar);
+  int64_t* idx = (int64_t*)(sc + L.idx);
+  int* par_tab = (int*)(sc + L.par_tab);
+  int* word_tab = (int*)(sc + L.word_tab);
+  float* rec = sc + L.rec;
+  ACVAE_TRY(zero(gscore, (long)G * R, s));
+  hipLaunchKernelGGL(fill_words_kernel, dim3((G * R + 255) / 256), dim3(256), 0, s, gword, start_idx, G * R);
+  long k = 0;
+  for (int t = 0; t < T + G - 1; ++t) {
+    for (int g = 0; g < G; ++g) {
+      const int lt = t - g;
+      if (lt < 0 || lt > T - 1) continue;
+      int64_t* w_g = gword + (long)g * R;
+      int64_t* par_g = gpar + (long)g * R;
+      float* c_g = gscore + (long)g * R;
+      for (int m = 0; m < M; ++m) {
+        const DbsMemberLayout& o = L.m[m];
+        const SearchMember& b = mb[m];
+        float* cur = sc + o.cur + (long)g * R * (b.H + 3 * b.E);
+        float *h = cur, *hp = h + (long)R * b.H, *cp = hp + (long)R * b.E, *lz = cp + (long)R * b.E;
+        float* ssc = sc + o.step;
+        Ctx st{s, ssc + o.sl.skws};
+        ACVAE_TRY(prior_step(b.params, w_g, b.mem, b.mem_lens, sc + o.encp, hp, cp, lz, b.eps + k * R * b.E, sc + o.mean,
+                             sc + o.logv, sc + o.z, sc + o.hp2, sc + o.cp2, sc + o.attp, ssc, o.sl, N, bdash, b.S, b.E, V,
+                             st));
+        ACVAE_TRY(decoder_step(b.params, w_g, h, b.mem, b.mem_lens, sc + o.encd, sc + o.z, sc + o.logits, sc + o.h2,
+                               sc + o.attw, sc + o.rnn, ssc, o.sl, N, bdash, b.S, b.E, b.H, b.A, V, st));
+      }
+      const float* x = sc + L.m[0].logits;
+      if (M > 1) {                                       // log(mean_m softmax(logits_m)) takes the logits' place
+        ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, sc + L.mix, V, nullptr, nullptr, 0, R, V, s));
+        x = sc + L.mix;
+      }
+      ACVAE_TRY(acvae_dbs_scores_sparse(x, V, temperature, lambda, c_g, sc + L.scores, par_tab, word_tab, N, bdash, T, V, G,
+                                        g, lt, s));
+      ACVAE_TRY(acvae_topk_flat_batched(sc + L.scores, lt == 0 ? (int64_t)V : (int64_t)bdash * V, (int64_t)bdash * V, bdash,
+                                        V, c_g, idx, par_g, w_g, N, bdash, s));
+      const long at = ((long)g * T + lt) * R;
+      hipLaunchKernelGGL(dbs_advance_kernel, dim3((R + 255) / 256), dim3(256), 0, s, c_g, par_g, w_g, par_tab + at,
+                         word_tab + at, rec + at, end_idx, lt == T - 1, R);
+      if (lt + 1 < T) {                                  // the group's next step reads its states through the parents
+        for (int m = 0; m < M; ++m) {
+          const DbsMemberLayout& o = L.m[m];
+          const SearchMember& b = mb[m];
+          float* cur = sc + o.cur + (long)g * R * (b.H + 3 * b.E);
+          float *h = cur, *hp = h + (long)R * b.H, *cp = hp + (long)R * b.E, *lz = cp + (long)R * b.E;
+          GatherTable gt;
+          gt.add({sc + o.h2, h, b.H}); gt.add({sc + o.hp2, hp, b.E}); gt.add({sc + o.cp2, cp, b.E}); gt.add({sc + o.z, lz, b.E});
+          hipLaunchKernelGGL(beam_gather_kernel, dim3(R, gt.n), dim3(256), 0, s, gt, par_g, HistJob{});
+        }
+      }
+      ++k;
+    }
+  }
+  hipLaunchKernelGGL(dbs_finish_kernel, dim3(N, G), dim3(64), 0, s, par_tab, word_tab, rec, seqs, scores, lengths, R, bdash,
+                     T, group_nbest ? bdash : 1, end_idx);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+int dbs_entry(const SearchMember* mb, int M, int64_t start_idx, int64_t end_idx, int N, int G, int bdash, int T, int V,
+              float temperature, float lambda, int group_nbest, int64_t* seqs, double* scores, int* lengths, void* scratch_v,
+              int64_t scratch_bytes, void* stream) {
+  DbsLayout L;
+  ACVAE_TRY(dbs_layout(mb, M, N, G, bdash, T, V, L));
+  for (int m = 0; m < M; ++m)
+    if (!mb[m].params || !mb[m].mem || !mb[m].mem_lens || !mb[m].eps) return ACVAE_EINVAL;
+  if (!seqs || !scores || !lengths || !scratch_v) return ACVAE_EINVAL;
+  if (start_idx < 0 || start_idx >= V || end_idx < 0 || end_idx >= V) return ACVAE_EINVAL;
+  if (!(temperature > 0.f) || !isfinite(temperature) || !isfinite(lambda)) return ACVAE_EINVAL;
+  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
+  return dbs_search(mb, M, L, start_idx, end_idx, N, G, bdash, T, V, temperature, lambda, group_nbest, seqs, scores, lengths,
+                    (float*)scratch_v, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int64_t acvae_dbs_search_scratch_bytes(int N, int G, int bdash, int T, int S, int E, int H, int A, int V) {
+  const SearchMember mb{nullptr, nullptr, nullptr, nullptr, S, E, H, A};
+  DbsLayout L;
+  return dbs_layout(&mb, 1, N, G, bdash, T, V, L) == ACVAE_OK ? L.total * 4 : -1;
+}
+extern "C" int acvae_dbs_search(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
+                                int64_t start_idx, int64_t end_idx, int N, int G, int bdash, int T, int S, int E, int H, int A,
+                                int V, float temperature, float diversity_lambda, int group_nbest, int64_t* seqs,
+                                double* scores, int* lengths, void* scratch, int64_t scratch_bytes, void* stream) {
+  const SearchMember mb{params, mem, mem_lens, eps, S, E, H, A};
+  return dbs_entry(&mb, 1, start_idx, end_idx, N, G, bdash, T, V, temperature, diversity_lambda, group_nbest, seqs, scores,
+                   lengths, scratch, scratch_bytes, stream);
+}
+extern "C" int64_t acvae_ensemble_dbs_search_scratch_bytes(int M, int N, int G, int bdash, int T, const int* S, const int* E,
+                                                           const int* H, const int* A, int V) {
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A) return -1;
+  SearchMember mb[ACVAE_ENSEMBLE_MAX];
+  for (int m = 0; m < M; ++m) mb[m] = {nullptr, nullptr, nullptr, nullptr, S[m], E[m], H[m], A[m]};
+  DbsLayout L;
+  return dbs_layout(mb, M, N, G, bdash, T, V, L) == ACVAE_OK ? L.total * 4 : -1;
+}
+extern "C" int acvae_ensemble_dbs_search(const void* const* const* params, const float* const* mem,
+                                         const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
+                                         const int* H, const int* A, int M, int64_t start_idx, int64_t end_idx, int N, int G,
+                                         int bdash, int T, int V, float temperature, float diversity_lambda, int group_nbest,
+                                         int64_t* seqs, double* scores, int* lengths, void* scratch, int64_t scratch_bytes,
+                                         void* stream) {
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !params || !mem || !mem_lens || !eps || !S || !E || !H || !A) return ACVAE_EINVAL;
+  SearchMember mb[ACVAE_ENSEMBLE_MAX];
+  for (int m = 0; m < M; ++m) mb[m] = {params[m], mem[m], mem_lens[m], eps[m], S[m], E[m], H[m], A[m]};
+  return dbs_entry(mb, M, start_idx, end_idx, N, G, bdash, T, V, temperature, diversity_lambda, group_nbest, seqs, scores,
+                   lengths, scratch, scratch_bytes, stream);
+}
+
+// ---- the advance and finish kernels alone, on caller-built tables
+extern "C" int acvae_dbs_advance(float* c, const int64_t* parent, const int64_t* word, int* parent_out, int* word_out,
+                                 float* rec_out, int64_t end_idx, int last, int R, void* stream) {
+  if (!c || !parent || !word || !parent_out || !word_out || !rec_out || R <= 0) return ACVAE_EINVAL;
+  hipLaunchKernelGGL(dbs_advance_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, c, parent, word,
+                     parent_out, word_out, rec_out, end_idx, last != 0, R);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+extern "C" int acvae_dbs_finish(const int* parent_tab, const int* word_tab, const float* rec, int64_t* seqs, double* scores,
+                                int* lengths, int N, int G, int bdash, int T, int group_nbest, int64_t end_idx,
+                                void* stream) {
+  if (!parent_tab || !word_tab || !rec || !seqs || !scores || !lengths || N <= 0 || G <= 0 || bdash <= 0 || T <= 0)
+    return ACVAE_EINVAL;
+  if (G > 16 || bdash > 16 || (long)N * bdash > (1L << 20)) return ACVAE_EUNSUPPORTED;
+  hipLaunchKernelGGL(dbs_finish_kernel, dim3(N, G), dim3(64), 0, (hipStream_t)stream, parent_tab, word_tab, rec, seqs,
+                     scores, lengths, N * bdash, bdash, T, group_nbest ? bdash : 1, end_idx);
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }

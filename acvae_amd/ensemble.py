@@ -1,11 +1,12 @@
-"""Ensemble decoding: greedy and beam search over several trained models at once.
+"""Ensemble decoding: greedy, beam and diverse beam search over several trained models at once.
 
 Mirrors ``BaseRunner.ensemble`` / ``_ensemble_batch`` / ``_ensemble_batch_beam_search`` (``runners/base_runner.py:397-694``,
 inherited by the VAE runner): at every step the members' word probabilities are averaged (mean of softmax, then log,
 :616-618, 675-680) and the word is picked from the average.  The whole search is ONE library call
 (``acvae_ensemble_search``): per step every member runs its prior step and its decoder step on its own states, one
 ``acvae_ensemble_mix`` launch forms the mixture's log-probabilities, and the pick is the mix kernel's own argmax (greedy) or
-the flat top-k of ``acvae_beam_search`` (beam).
+the flat top-k of ``acvae_beam_search`` (beam).  ``method="dbs"`` is ``acvae_ensemble_dbs_search``, likewise one call: the mixture's
+log-probabilities take the logits' place in ``Hybrid_VAEModel.diverse_beam_search``.
 
 The reference's ensemble code cannot run a ``Hybrid_VAEModel`` (it calls ``model.decoder`` without ``z`` and never runs
 the prior network), so its mixing rule is carried onto this model's step as ``Hybrid_VAEModel.beam_search`` runs it.  Two
@@ -71,7 +72,7 @@ class Ensemble(nn.Module):
     @torch.no_grad()
     def forward(self, feats, feat_lens, method="greedy", beam_size=5, max_length=20, repetition_penalty=None,
                 no_repeat_ngram_size=None, min_length=None, suppress_tokens=None, finish_on_end=False, length_penalty=None,
-                nbest=None):
+                nbest=None, group_size=5, diversity_lambda=0.5, temperature=1.0, group_nbest=True):
         """-> ``{"seqs": int64 [N, max_length], "logprobs": f32}`` on the device.  ``logprobs``: greedy [N, max_length], the
         mixture's log-probability of each chosen word (entries behind a row's ``end_idx`` carry no meaning); beam [N], beam
         0's final score.  A greedy row that has produced ``end_idx`` keeps ``end_idx`` to the end (base_runner.py:584,
@@ -83,11 +84,27 @@ class Ensemble(nn.Module):
 
         ``finish_on_end`` / ``length_penalty`` / ``nbest`` with ``method="beam"``: hypotheses finish at ``end_idx`` and are
         ranked by a length-normalised score (``Hybrid_VAEModel._finishing``).  ``seqs`` is then hypothesis 0, ``logprobs``
-        [N] its raw log-probability, and the dict also holds ``scores``, ``lengths`` and the ``nbest_*`` entries."""
-        if method not in ("greedy", "beam"):
-            raise ValueError(f"Ensemble: method must be 'greedy' or 'beam', not {method!r}")
+        [N] its raw log-probability, and the dict also holds ``scores``, ``lengths`` and the ``nbest_*`` entries.
+
+        ``method="dbs"`` with ``beam_size`` / ``group_size`` / ``diversity_lambda`` / ``temperature`` / ``group_nbest``:
+        diverse beam search over the mixture (``Hybrid_VAEModel.diverse_beam_search``; ``acvae_ensemble_dbs_search``, one
+        call).  -> ``{"seqs": int64 [N, rows, max_length], "scores": f64 [N, rows], "lengths": int32 [N, rows]}``, rows =
+        ``beam_size`` with ``group_nbest`` (as for a single model) else ``group_size``.  Member m's noise is drawn with
+        the calls its own search would make, members in order.  The decoding constraints and the finishing keywords are
+        refused with it, as for a single model; ``group_size`` is at most 16."""
+        if method not in ("greedy", "beam", "dbs"):
+            raise ValueError(f"Ensemble: method must be 'greedy', 'beam' or 'dbs', not {method!r}")
         beam = 1 if method == "greedy" else int(beam_size)
         T = int(max_length)
+        if method == "dbs":
+            G = int(group_size)
+            bdash = beam // G if G >= 1 else 0
+            if bdash < 1 or bdash > 16:
+                raise ValueError("Ensemble: beam_size // group_size must be in 1..16")
+            if G > 16:
+                raise ValueError(f"Ensemble: group_size {G}, at most 16 (a single model falls back to its host loop)")
+            if not float(temperature) > 0:
+                raise ValueError(f"Ensemble: temperature must be > 0, not {temperature!r}")
         con = self.models[0]._constraints(                                # (vocabulary and end_idx are shared)
             dict(method=method, beam_size=beam, max_length=T, repetition_penalty=repetition_penalty,
                  no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, suppress_tokens=suppress_tokens),
@@ -110,7 +127,12 @@ class Ensemble(nn.Module):
             mem = model._projected_memory(encoded)
             N, S, E = mem.shape
             H, A = model.decoder.model.hidden_size, model.decoder.attn.attn_size
-            eps = model._search_noise(N, T, beam, E, dev, None if replay is None else replay[k])
+            if method == "dbs":
+                if replay is not None:
+                    raise ValueError("Ensemble: noise['eps'] replays a beam search's noise, not a diverse beam search's")
+                eps = model._dbs_noise(N, T * G, bdash, E, dev)
+            else:
+                eps = model._search_noise(N, T, beam, E, dev, None if replay is None else replay[k])
             mems.append(mem)
             lens.append(torch.as_tensor(encoded["audio_embeds_lens"]).to(device=dev, dtype=torch.long).contiguous())
             epss.append(eps)
@@ -120,6 +142,21 @@ class Ensemble(nn.Module):
         params = (ctypes.c_void_p * M)(*[ctypes.cast(t, ctypes.c_void_p).value for t in tables])
         S_, E_, H_, A_ = (np.ascontiguousarray([d[j] for d in dims], dtype=np.int32) for j in range(4))
         host = [a.ctypes.data for a in (S_, E_, H_, A_)]
+        if method == "dbs":
+            rows = G * bdash if group_nbest else G
+            seqs = torch.empty(N, rows, T, dtype=torch.long, device=dev)
+            scores = torch.empty(N, rows, dtype=torch.float64, device=dev)
+            lengths = torch.empty(N, rows, dtype=torch.int32, device=dev)
+            sb = _lib.call("acvae_ensemble_dbs_search_scratch_bytes", M, N, G, bdash, T, *host, self.vocab_size)
+            if sb < 0:
+                raise RuntimeError(f"acvae_ensemble_dbs_search: unsupported dimensions (N={N}, group_size={G}, "
+                                   f"bdash={bdash}, max_length={T})")
+            scratch = scratch_buffer(sb, dev)
+            _lib.call("acvae_ensemble_dbs_search", params, mems, lens, epss, *host, M, self.start_idx, self.end_idx, N, G,
+                      bdash, T, self.vocab_size, float(temperature), float(diversity_lambda), 1 if group_nbest else 0, seqs,
+                      scores, lengths, scratch, sb, _lib.current_stream())
+            return Hybrid_VAEModel._dbs_rows({"seqs": seqs, "scores": scores, "lengths": lengths}, beam, group_nbest,
+                                             self.end_idx)
         seqs = torch.empty(N, T, dtype=torch.long, device=dev)
         logprobs = torch.empty((N, T) if method == "greedy" else (N,), device=dev)
         sb = _lib.call("acvae_ensemble_search_finishing_scratch_bytes" if fin is not None else
@@ -145,7 +182,9 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
     """The decoding half of ``BaseRunner.ensemble`` (base_runner.py:433-478): ``items`` are ``(audio_id, feature [T, F])`` as
     for ``evaluate()``, batched with ``collate_fn([1])`` (no replication); ``kwargs`` (``method``, ``beam_size``,
     ``max_length``, the constrained-decoding keywords and ``finish_on_end`` / ``length_penalty`` / ``nbest``, with
-    ``nbest > 1`` the clip's n-best list is written as its ``captions``) go to ``Ensemble.forward``.  Writes the JSON payload of
+    ``nbest > 1`` the clip's n-best list is written as its ``captions``; with ``method="dbs"`` its ``group_size`` /
+    ``diversity_lambda`` / ``temperature`` / ``group_nbest``, and every returned beam is written as one of the clip's
+    ``captions``, as ``evaluate`` does for a single model) go to ``Ensemble.forward``.  Writes the JSON payload of
     ``evaluate()`` or, with ``dcase_format``, the
     reference's two-column CSV (``file_name``, ``caption_predicted``).  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are
     ``(audio_id, 1-D waveform)`` and the log-mel features are formed on the device, once for all members.  Returns the payload

@@ -116,7 +116,9 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
     e.g. ``method="beam", beam_size=3, no_repeat_ngram_size=3``.  ``finish_on_end=True`` with ``method="beam"`` (and
     ``length_penalty``, ``nbest``; ``Hybrid_VAEModel._finishing``): ONE beam search of width ``beam_size`` per clip, no
     replicas, whose hypotheses finish at ``<end>``; the file holds hypothesis 0 per clip or, with ``nbest > 1``, the clip's
-    n-best list as its ``captions``.  ``rerank`` (an ``acvae_amd.consensus.Consensus``): with
+    n-best list as its ``captions``.  ``method="dbs"`` (``group_size``, ``diversity_lambda``, ``temperature``,
+    ``group_nbest``): one diverse beam search per clip, one library call per batch, every returned beam one of the clip's
+    ``captions``; ``dbs_impl="host"`` runs the host loop over the step API instead (same captions).  ``rerank`` (an ``acvae_amd.consensus.Consensus``): with
     ``beam_size=N`` rollouts per clip (2 <= N <= 16; "greedy", "sample" or "gumbel"), the caption written per clip is the
     rollout that agrees most with the clip's other rollouts under CIDEr-D, chosen on the device
     (``Hybrid_VAEModel._rerank``); the file then has the one-caption-per-clip form.  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32

@@ -389,15 +389,78 @@ class Hybrid_VAEModel(CaptionModel):
                   _lib.current_stream(), *((int(self.end_idx),) + _constraint_args(con) if on else ()))
         return {"seqs": seqs, "attn_weights": attw}
 
+    @staticmethod
+    def _dbs_rows(out, beam_size, group_nbest, end_idx):
+        """With ``group_nbest`` the reference returns ``beam_size`` rows per clip and fills ``bdash * group_size`` of them:
+        where ``group_size`` does not divide ``beam_size`` the rest hold ``end_idx`` (score -inf, length 0), as they did."""
+        seqs, scores, lengths = out["seqs"], out["scores"], out["lengths"]
+        extra = beam_size - seqs.shape[1] if group_nbest else 0
+        if extra <= 0:
+            return out
+        N, _, T = seqs.shape
+        return {"seqs": torch.cat([seqs, seqs.new_full((N, extra, T), end_idx)], dim=1),
+                "scores": torch.cat([scores, scores.new_full((N, extra), float("-inf"))], dim=1),
+                "lengths": torch.cat([lengths, lengths.new_zeros((N, extra))], dim=1)}
+
+    @staticmethod
+    def _dbs_noise(N, n_steps, bdash, E, dev):
+        """The prior's noise of one diverse beam search on the device, step-major [n_steps, N, bdash, E] as the library reads
+        it, drawn on the CPU generator in the reference's order: clip, then step k of the (t, group) schedule
+        (text_encoder.py:259 inside those loops), ``torch.randn(bdash, E)`` each."""
+        return _lib.h2d_fill((n_steps, N, bdash, E), torch.float32, dev,
+                             lambda buf: [torch.randn(bdash, E, out=buf[k, i]) for i in range(N) for k in range(n_steps)])
+
     @torch.no_grad()
-    def diverse_beam_search(self, encoded, max_length, beam_size, group_size, diversity_lambda, temperature, group_nbest):
+    def diverse_beam_search(self, encoded, max_length, beam_size, group_size, diversity_lambda, temperature, group_nbest,
+                            dbs_impl="device"):
         """CaptionModel.diverse_beam_search (models/word_model.py:297-394) with this model's hooks (vae_model.py:
         997-1040): per clip, ``group_size`` groups of ``bdash = beam_size // group_size`` beams; group g runs one
         step behind group g-1 and its log-probabilities at a local step are lowered by ``diversity_lambda`` x the
-        number of times the earlier groups chose each word at that step; finished beams score logprob / length.
-        Returns {"seqs": i64 [N, beam_size or group_size, max_length]}.  Host bookkeeping (sequence tables, finished
-        beams) as in the reference, which also reads the chosen words back every step; prior / decoder step, the score
-        transform and the flat top-k are library calls."""
+        number of the earlier groups' beams that hold each word at that step; finished beams score logprob / length.
+        The whole search is ONE library call (``acvae_dbs_search``, include/acvae_hip.h has the definition) with no host
+        synchronisation.  Returns, on the device, {"seqs": i64 [N, rows, max_length], "scores": f64 [N, rows] (logprob /
+        length of each returned beam), "lengths": i32 [N, rows]}, rows = ``beam_size`` with ``group_nbest`` (the first
+        ``bdash * group_size`` are beams, see ``_dbs_rows``) else ``group_size``.
+
+        ``dbs_impl="host"`` runs the loop over the step API that the call replaces (``diverse_beam_search_host``: the same
+        tokens and scores bit for bit, three read-backs per step); it is also taken when ``group_size > 16``, the library's
+        limit."""
+        if dbs_impl not in ("device", "host"):
+            raise ValueError(f"dbs_impl must be 'device' or 'host', not {dbs_impl!r}")
+        bdash = beam_size // group_size
+        if bdash < 1 or bdash > 16:
+            raise ValueError("diverse_beam_search: beam_size // group_size must be in 1..16")
+        if dbs_impl == "host" or group_size > 16:
+            return self.diverse_beam_search_host(encoded, max_length, beam_size, group_size, diversity_lambda, temperature,
+                                                 group_nbest)
+        mem = self._projected_memory(encoded)
+        dev = mem.device
+        lens = torch.as_tensor(encoded["audio_embeds_lens"]).to(device=dev, dtype=torch.long).contiguous()
+        N, S, E = mem.shape
+        V = self.vocab_size
+        H, A = self.decoder.model.hidden_size, self.decoder.attn.attn_size
+        G, T = int(group_size), int(max_length)
+        eps = self._dbs_noise(N, T * G, bdash, E, dev)
+        rows = G * bdash if group_nbest else G
+        seqs = torch.empty(N, rows, T, dtype=torch.long, device=dev)
+        scores = torch.empty(N, rows, dtype=torch.float64, device=dev)
+        lengths = torch.empty(N, rows, dtype=torch.int32, device=dev)
+        sb = _lib.call("acvae_dbs_search_scratch_bytes", N, G, bdash, T, S, E, H, A, V)
+        if sb < 0:
+            raise RuntimeError(f"acvae_dbs_search: unsupported dimensions (N={N}, group_size={G}, bdash={bdash}, "
+                               f"max_length={T})")
+        scratch = scratch_buffer(sb, dev)
+        _lib.call("acvae_dbs_search", self._text_table(), mem, lens, eps, int(self.start_idx), int(self.end_idx), N, G, bdash,
+                  T, S, E, H, A, V, float(temperature), float(diversity_lambda), 1 if group_nbest else 0, seqs, scores,
+                  lengths, scratch, sb, _lib.current_stream())
+        return self._dbs_rows({"seqs": seqs, "scores": scores, "lengths": lengths}, beam_size, group_nbest, int(self.end_idx))
+
+    @torch.no_grad()
+    def diverse_beam_search_host(self, encoded, max_length, beam_size, group_size, diversity_lambda, temperature,
+                                 group_nbest):
+        """``diverse_beam_search`` as a host loop (``dbs_impl="host"``): host bookkeeping (sequence tables, finished beams)
+        as in the reference, which also reads the chosen words back every step; prior / decoder step, the score transform
+        and the flat top-k are library calls.  The yardstick of the one-call search, and its stand-in beyond 16 groups."""
         mem_all = self._projected_memory(encoded)
         dev = mem_all.device
         lens_all = torch.as_tensor(encoded["audio_embeds_lens"]).to(torch.long)
@@ -468,13 +531,19 @@ class Hybrid_VAEModel(CaptionModel):
                 top[i][ended] -= np.float32(1000)
             score[g] = top
             carry[g] = (dn["state"], pn["hiddens_state"], pn["z"], nxt_d.clone(), prev_d.clone())
-        out = torch.full((N, beam_size if group_nbest else group_size, max_length), self.end_idx, dtype=torch.long)
+        rows = bdash * group_size if group_nbest else group_size
+        out = torch.full((N, rows, max_length), self.end_idx, dtype=torch.long)
+        out_scores = torch.zeros(N, rows, dtype=torch.float64)
+        out_lengths = torch.zeros(N, rows, dtype=torch.int32)
         for i in range(N):
             ranked = [sorted(d, key=lambda x: -x["score"])[:bdash] for d in done[i]]
             chosen = sum(ranked, []) if group_nbest else [d[0] for d in ranked]
             for r, beam in enumerate(chosen):
                 out[i, r, :len(beam["seq"])] = torch.from_numpy(beam["seq"])
-        return {"seqs": out.to(dev)}
+                out_scores[i, r] = beam["score"]
+                out_lengths[i, r] = len(beam["seq"])
+        return self._dbs_rows({"seqs": out.to(dev), "scores": out_scores.to(dev), "lengths": out_lengths.to(dev)}, beam_size,
+                              group_nbest, int(self.end_idx))
 
     def check_persistent_launches(self, device=None):
         """Raise if a persistent decode / posterior launch on the model's device gave up (its outputs are NaN then).  Call
@@ -505,7 +574,7 @@ class Hybrid_VAEModel(CaptionModel):
         if method == "dbs":                                               # vae_model.py:887-893
             return self.diverse_beam_search(encoded, max_length, kwargs.get("beam_size", 5), kwargs.get("group_size", 5),
                                             kwargs.get("diversity_lambda", 0.5), kwargs.get("temperature", 1.0),
-                                            kwargs.get("group_nbest", True))
+                                            kwargs.get("group_nbest", True), dbs_impl=kwargs.get("dbs_impl", "device"))
         return self.stepwise_forward(encoded, None, None, **kwargs)     # greedy / "gumbel" / anything else = multinomial
 
     def forward(self, *input, **kwargs):
@@ -529,7 +598,11 @@ class Hybrid_VAEModel(CaptionModel):
 
         ``finish_on_end`` (default False) / ``length_penalty`` (1.0) / ``nbest`` (1) with ``method="beam"``: hypotheses
         finish at ``<end>`` and are ranked by a length-normalised score, see ``_finishing``.  ``seqs`` / ``attn_weights``
-        are then hypothesis 0's and the dict also holds ``scores``, ``lengths`` and the ``nbest_*`` entries."""
+        are then hypothesis 0's and the dict also holds ``scores``, ``lengths`` and the ``nbest_*`` entries.
+
+        ``method="dbs"`` (``beam_size``, ``group_size``, ``diversity_lambda``, ``temperature``, ``group_nbest``): diverse beam
+        search as one library call, see ``diverse_beam_search``; ``dbs_impl="host"`` (default ``"device"``) runs the host loop
+        over the step API instead, with the same tokens and scores."""
         if kwargs.get("rerank") is not None:                   # (refusals come in front of the encoder's launches)
             raise ValueError("rerank in the training forward: there is nothing to choose among" if len(input) == 4 else
                              "rerank belongs to the N-samples-per-clip routes, which know N: rollout_shared_encoder / "

@@ -1031,7 +1031,7 @@ int acvae_ensemble_search(const void* const* const* params, const float* const* 
  * end_idx outside [0, V); V <= n_suppress + max_length + beam (beam = 1 for the decode forward; a row must keep a word, and
  * a clip `beam` finite scores); in the decode forward, caps != NULL (a teacher-forced row has no history of its own) or
  * ACVAE_FLAG_ROLLOUT_GRAD (the backward does not know the penalty's factor).
- * Out of scope: diverse beam search (its histories live on the host), constraints in differentiable rollouts and in the
+ * Out of scope: diverse beam search (acvae_dbs_search takes no controls), constraints in differentiable rollouts and in the
  * training forward, per-row settings.  (Finishing beams on end_idx and length-normalised scores: the *_finishing entries.)
  * ------------------------------------------------------------------------------------------- */
 #define ACVAE_SUPPRESS_MAX 64
@@ -1133,6 +1133,74 @@ int acvae_ensemble_search_finishing(const void* const* const* params, const floa
                                     int min_length, const int* suppress_host, int n_suppress,
                                     const float* length_norm_host, int nbest, int64_t* nbest_seqs, float* nbest_scores,
                                     float* nbest_logprobs, int* nbest_lengths);
+
+/* ---------------------------------------------------------------------------------------------
+ * Diverse beam search as one call: CaptionModel.diverse_beam_search (models/word_model.py:297-394) on Hybrid_VAEModel's
+ * step, for all N clips at once, one model (acvae_dbs_search) or M members (acvae_ensemble_dbs_search; one driver, the
+ * former is its M = 1 case).  No host synchronisation, no read-back; bit-identical in tokens and scores to the loop over
+ * the step API, acvae_dbs_scores and acvae_topk_flat_batched that it replaces.
+ *
+ * Definition.  G groups of bdash beams per clip, R = N * bdash rows per group, row r = n * bdash + b of clip n,
+ * T = max_length.  The schedule is the list of pairs (t, g), t = 0 .. T + G - 2, g = 0 .. G - 1, with 0 <= lt = t - g <= T - 1,
+ * in that order; pair k of the n_steps = T * G reads the noise eps[k] [R][E].  Step (t, g):
+ *   inputs   lt = 0: the word is start_idx, every state zero; else the word chosen at the group's previous local step and
+ *            the states (decoder hidden [H]; the prior's h, c and last_z [E]) of the row's parent at that step;
+ *   step     prior step, then decoder step, on the group's R rows (the launches of acvae_beam_search's driver);
+ *   scores   score[r,c] = log_softmax(log_softmax(logits[r]) / temperature)[c] - diversity_lambda * count_n[c] + prev_g[r],
+ *            count_n[c] = the number of beams of the groups e < g of clip n whose CURRENT history holds word c at column lt:
+ *            group e's beams after its latest local step min(lt + g - e, T - 1), traced through the parents since.
+ *            prev_g = the group's running scores, zero at lt = 0.  Bit for bit acvae_dbs_scores on the dense counts;
+ *   top-k    per clip the flat top-bdash over bdash * V scores (lt = 0: over the first row's V), acvae_topk_flat_batched:
+ *            value c, parent and word per row;
+ *   record   a row is recorded iff its word is end_idx or lt = T - 1, with c as it is; then its running score becomes
+ *            c - 1000.0f.  A retired row keeps being expanded and is recorded again whenever it emits end_idx again.
+ * After the last step, per clip and group: the records ranked by (double)c / (double)(lt + 1) (IEEE fp64), descending,
+ * ties in the order of recording (lt, then beam, ascending); the first bdash are kept.  Output rows per clip: with
+ * group_nbest != 0 the groups' kept records in group order (rows = G * bdash), else each group's best (rows = G).
+ * seqs int64 [N,rows,T]: the record's lt + 1 words through its parents, then end_idx; scores f64 [N,rows];
+ * lengths int32 [N,rows].
+ *
+ * Ensembles: every member steps on the shared word with its own states and noise (eps[m] [n_steps][R][E[m]]); one
+ * acvae_ensemble_mix launch (prev = NULL) forms log(mean_m softmax(logits_m)) per row, which takes the logits' place in
+ * `scores`.  With M = 1 the mix is skipped: acvae_ensemble_dbs_search is acvae_dbs_search bit for bit.
+ *
+ * Refused before any launch: a dimension <= 0, a NULL pointer, start_idx / end_idx outside [0, V), temperature not finite
+ * and > 0, diversity_lambda not finite, M outside [1, ACVAE_ENSEMBLE_MAX] (ACVAE_EINVAL); bdash > 16 (the top-k's limit),
+ * G > 16 (the penalty list holds (G - 1) * bdash <= 240 words) or N * bdash > 2^20 (ACVAE_EUNSUPPORTED, -1 from the bytes
+ * functions); scratch below the bytes function (ACVAE_EWORKSPACE).  The declared size is exact and the scratch may hold
+ * anything on entry.
+ *
+ * The kernels alone, on caller-built tables (int32 [G][T][R], element (e, s, r) at [(e * T + s) * R + r]):
+ *   acvae_dbs_scores_sparse  acvae_dbs_scores for group g at local step lt with the penalty read from the tables of the
+ *                            groups e < g (parent_tab / word_tab may be NULL when g is 0); N clips, rows R = N * bdash;
+ *                            logits row stride ld, prev [R] may be NULL, out [R][V].  A parent outside [0, R) is clamped
+ *                            into it, a word outside [0, V) is skipped.
+ *   acvae_dbs_advance        behind a top-k: c [R] in place (retired where recorded), parent / word int64 [R] in,
+ *                            parent_out / word_out int32 [R] and rec_out f32 [R] (c, or NaN for "none") out; last != 0 at
+ *                            lt = T - 1.
+ *   acvae_dbs_finish         rec f32 [G][T][R]; outputs as above.
+ * Out of scope: one batch of G * R rows per time step (other launch shapes, other bits), the decoding constraints,
+ * truncation and reranking, an early exit, attention-weight histories.
+ * ------------------------------------------------------------------------------------------- */
+int acvae_dbs_scores_sparse(const float* logits, int64_t ld, float temperature, float diversity_lambda, const float* prev,
+                            float* out, const int* parent_tab, const int* word_tab, int N, int bdash, int T, int V, int G,
+                            int g, int lt, void* stream);
+int acvae_dbs_advance(float* c, const int64_t* parent, const int64_t* word, int* parent_out, int* word_out, float* rec_out,
+                      int64_t end_idx, int last, int R, void* stream);
+int acvae_dbs_finish(const int* parent_tab, const int* word_tab, const float* rec, int64_t* seqs, double* scores,
+                     int* lengths, int N, int G, int bdash, int T, int group_nbest, int64_t end_idx, void* stream);
+int64_t acvae_dbs_search_scratch_bytes(int N, int G, int bdash, int T, int S, int E, int H, int A, int V);
+int acvae_dbs_search(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
+                     int64_t start_idx, int64_t end_idx, int N, int G, int bdash, int T, int S, int E, int H, int A, int V,
+                     float temperature, float diversity_lambda, int group_nbest, int64_t* seqs, double* scores,
+                     int* lengths, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t acvae_ensemble_dbs_search_scratch_bytes(int M, int N, int G, int bdash, int T, const int* S, const int* E,
+                                                const int* H, const int* A, int V);
+int acvae_ensemble_dbs_search(const void* const* const* params, const float* const* mem, const int64_t* const* mem_lens,
+                              const float* const* eps, const int* S, const int* E, const int* H, const int* A, int M,
+                              int64_t start_idx, int64_t end_idx, int N, int G, int bdash, int T, int V, float temperature,
+                              float diversity_lambda, int group_nbest, int64_t* seqs, double* scores, int* lengths,
+                              void* scratch, int64_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 }
