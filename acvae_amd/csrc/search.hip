@@ -4,6 +4,8 @@
 //   - the search over M members' averaged word probabilities, greedy or beam (acvae_ensemble_search), and the validation
 //     beam search of one model (acvae_beam_search), which is its M = 1 case plus beam 0's attention-weight history;
 //   - diverse beam search over M >= 1 members (acvae_ensemble_dbs_search; acvae_dbs_search is its M = 1 case), at the end.
+// The two drivers keep their own loops, search() over t and dbs_search() over (t, group), and share what belongs to a
+// member: its layout (MemberLayout), its prologue, its step and its gather by parent.
 // The training-time composites are decoder.hip.
 #include <utility>
 #include "common.h"
@@ -174,7 +176,27 @@ extern "C" int acvae_decoder_step_fwd(const void* const* params, const int64_t* 
 // ==========================================================================================
 namespace {
 struct SearchMember { const void* const* params; const float* mem; const int64_t* mem_lens; const float* eps; int S, E, H, A; };
-struct MemberLayout { StepLayout sl; long step, encd, encp, h, hp, cp, lz, mean, logv, z, h2, hp2, cp2, attp, attw, logits, rnn; };
+// One member's buffers, for either driver; a step runs R rows (the beams of the N clips, or those of one DBS group).
+//   cur: the states a step reads, [G][R][H + 3E]: one block h | hp | cp | last_z per group (beam and greedy: G = 1);
+//   nxt: the states a step writes, one such block shared by the groups: a beam search gathers it into cur by parent,
+//        greedy swaps the two.  (The parts of a block lie on 16 bytes when H and E are multiples of 4: DESIGN.md 4e.)
+struct MemberLayout { StepLayout sl; long step, encd, encp, cur, nxt, mean, logv, attp, attw, logits, rnn; };
+int member_layout(Bump& b, const SearchMember& mb, int N, long R, int G, int attw_steps, int V, MemberLayout& o) {
+  const long S = mb.S, e = mb.E, h = mb.H;
+  ACVAE_TRY(step_layout((int)R, mb.S, mb.E, mb.H, mb.A, V, o.sl));
+  o.step = b.take(o.sl.total);
+  o.encd = b.take((long)N * S * mb.A); o.encp = b.take((long)N * S * e);
+  o.cur = b.take((long)G * R * (h + 3 * e)); o.nxt = b.take(R * (h + 3 * e));
+  o.mean = b.take(R * e); o.logv = b.take(R * e);
+  o.attp = b.take(R * S); o.attw = b.take((long)attw_steps * R * S);
+  o.logits = b.take(R * V); o.rnn = b.take(R * 3 * e);
+  return ACVAE_OK;
+}
+struct States { float *h, *hp, *cp, *lz; };
+inline States states_at(float* block, long R, const SearchMember& b) {
+  return {block, block + R * b.H, block + R * (b.H + b.E), block + R * (b.H + 2 * b.E)};
+}
+
 struct SearchLayout { MemberLayout m[ACVAE_ENSEMBLE_MAX]; long scores, topk, best, words, whist, frec, norm, total; int keep_attw, keep_hist, keep_fin; };
 // keep_attw: member 0's decoder attention weights of every step, [T][R][S], for the trace-back; else [R][S], overwritten.
 // keep_hist: the rows' word histories of a constrained beam search, int64 [2][R][T] (the one read, the one gathered into).
@@ -184,25 +206,9 @@ int search_layout(const SearchMember* mb, int M, int N, int beam, int T, int V, 
   if (M < 1 || M > ACVAE_ENSEMBLE_MAX || N <= 0 || beam <= 0 || T <= 0) return ACVAE_EINVAL;
   const long R = (long)N * beam;
   if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
-  L.keep_attw = keep_attw;
-  L.keep_hist = keep_hist;
-  L.keep_fin = keep_fin;
+  L.keep_attw = keep_attw; L.keep_hist = keep_hist; L.keep_fin = keep_fin;
   Bump b;
-  for (int m = 0; m < M; ++m) {
-    MemberLayout& o = L.m[m];
-    const long S = mb[m].S, e = mb[m].E, h = mb[m].H;
-    ACVAE_TRY(step_layout((int)R, mb[m].S, mb[m].E, mb[m].H, mb[m].A, V, o.sl));
-    o.step = b.take(o.sl.total);
-    o.encd = b.take((long)N * S * mb[m].A);
-    o.encp = b.take((long)N * S * e);
-    o.h = b.take(R * h); o.hp = b.take(R * e); o.cp = b.take(R * e); o.lz = b.take(R * e);
-    o.mean = b.take(R * e); o.logv = b.take(R * e); o.z = b.take(R * e);
-    o.h2 = b.take(R * h); o.hp2 = b.take(R * e); o.cp2 = b.take(R * e);
-    o.attp = b.take(R * S);
-    o.attw = b.take((keep_attw && m == 0 ? T : 1) * R * S);
-    o.logits = b.take(R * V);
-    o.rnn = b.take(R * 3 * e);
-  }
+  for (int m = 0; m < M; ++m) ACVAE_TRY(member_layout(b, mb[m], N, R, 1, keep_attw && m == 0 ? T : 1, V, L.m[m]));
   L.scores = b.take(R * V);
   L.topk = b.take(R);
   L.best = b.take(R);
@@ -229,6 +235,41 @@ __global__ __launch_bounds__(256) void beam_gather_kernel(GatherTable g, const i
   const GatherJob j = g.job[blockIdx.y];
   for (int i = threadIdx.x; i < j.width; i += blockDim.x) j.dst[r * j.width + i] = j.src[p * j.width + i];
 }
+
+// ---- what both drivers do with a member (sc: the call's scratch, o: the member's part of it).  In front of the first step:
+// tickets and counters zeroed, both attention projections, every group's states zero, the logits entered.
+int member_prologue(const SearchMember& b, const MemberLayout& o, float* sc, int N, long R, int G, int V,
+                    const float*& logit_ptr, int64_t& logit_ld, hipStream_t s) {
+  float* ssc = sc + o.step;
+  ACVAE_TRY(acvae_skinny_ws_reset(ssc + o.sl.skws, s));
+  ACVAE_TRY(step_attws_reset(ssc, o.sl, s));
+  ACVAE_TRY(acvae_attn_precompute(b.params, 0, b.mem, sc + o.encd, N, b.S, b.E, b.H, b.A, s));
+  ACVAE_TRY(acvae_attn_precompute(b.params, 1, b.mem, sc + o.encp, N, b.S, b.E, b.E, b.E, s));
+  ACVAE_TRY(zero(sc + o.cur, (long)G * R * (b.H + 3 * b.E), s));
+  logit_ptr = sc + o.logits; logit_ld = V;
+  return ACVAE_OK;
+}
+// One step of N * Tq rows fed `word`, from the state block `cur` into `nxt`: the prior step, then the decoder step on its z.
+int member_step(const SearchMember& b, const MemberLayout& o, float* sc, const int64_t* word, float* cur, float* nxt,
+                const float* eps, float* attw, int N, int Tq, int V, hipStream_t s) {
+  const States c = states_at(cur, (long)N * Tq, b), n = states_at(nxt, (long)N * Tq, b);
+  float* ssc = sc + o.step;
+  Ctx st{s, ssc + o.sl.skws};
+  ACVAE_TRY(prior_step(b.params, word, b.mem, b.mem_lens, sc + o.encp, c.hp, c.cp, c.lz, eps, sc + o.mean, sc + o.logv, n.lz,
+                       n.hp, n.cp, sc + o.attp, ssc, o.sl, N, Tq, b.S, b.E, V, st));
+  return decoder_step(b.params, word, c.h, b.mem, b.mem_lens, sc + o.encd, n.lz, sc + o.logits, n.h, attw, sc + o.rnn, ssc,
+                      o.sl, N, Tq, b.S, b.E, b.H, b.A, V, st);
+}
+// The next step's states follow their parents (vae_model.py:961-968): row r of `cur` becomes row parent[r] of `nxt`; hj, if
+// not null, is the word-history job of a constrained beam search riding along.
+void member_gather(const SearchMember& b, float* cur, float* nxt, int R, const int64_t* parent, const HistJob* hj,
+                   hipStream_t s) {
+  const States c = states_at(cur, R, b), n = states_at(nxt, R, b);
+  GatherTable g;
+  g.add({n.h, c.h, b.H}); g.add({n.hp, c.hp, b.E}); g.add({n.cp, c.cp, b.E}); g.add({n.lz, c.lz, b.E});
+  hipLaunchKernelGGL(beam_gather_kernel, dim3(R, g.n + (hj ? 1 : 0)), dim3(256), 0, s, g, parent, hj ? *hj : HistJob{});
+}
+
 __global__ void fill_words_kernel(int64_t* w, int64_t v, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) w[i] = v;
@@ -408,26 +449,13 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
   if (fin.on) ACVAE_TRY(norm_upload(fin.norm, sc + L.norm, T, s));
   int64_t* wh = L.keep_hist && con.on() ? (int64_t*)(sc + L.whist) : nullptr;   // the rows' histories at this step
   int64_t* wh2 = wh ? wh + (long)R * T : nullptr;
-  // per member: the buffers that change hands from step to step (greedy swaps them, the beam search gathers by parent)
-  struct State { float *h, *hp, *cp, *lz, *h2, *hp2, *cp2, *z; } state[ACVAE_ENSEMBLE_MAX];
+  // per member: the state blocks that change hands from step to step (greedy swaps them, the beam search gathers by parent)
+  float *cur[ACVAE_ENSEMBLE_MAX], *nxt[ACVAE_ENSEMBLE_MAX];
   const float* logit_ptr[ACVAE_ENSEMBLE_MAX];
   int64_t logit_ld[ACVAE_ENSEMBLE_MAX];
   for (int m = 0; m < M; ++m) {
-    const MemberLayout& o = L.m[m];
-    const SearchMember& b = mb[m];
-    float* ssc = sc + o.step;
-    ACVAE_TRY(acvae_skinny_ws_reset(ssc + o.sl.skws, s));
-    ACVAE_TRY(step_attws_reset(ssc, o.sl, s));
-    ACVAE_TRY(acvae_attn_precompute(b.params, 0, b.mem, sc + o.encd, N, b.S, b.E, b.H, b.A, s));
-    ACVAE_TRY(acvae_attn_precompute(b.params, 1, b.mem, sc + o.encp, N, b.S, b.E, b.E, b.E, s));
-    State& x = state[m];
-    x = {sc + o.h, sc + o.hp, sc + o.cp, sc + o.lz, sc + o.h2, sc + o.hp2, sc + o.cp2, sc + o.z};
-    ACVAE_TRY(zero(x.h, (long)R * b.H, s));
-    ACVAE_TRY(zero(x.hp, (long)R * b.E, s));
-    ACVAE_TRY(zero(x.cp, (long)R * b.E, s));
-    ACVAE_TRY(zero(x.lz, (long)R * b.E, s));
-    logit_ptr[m] = sc + o.logits;
-    logit_ld[m] = V;
+    ACVAE_TRY(member_prologue(mb[m], L.m[m], sc, N, R, 1, V, logit_ptr[m], logit_ld[m], s));
+    cur[m] = sc + L.m[m].cur; nxt[m] = sc + L.m[m].nxt;
   }
   float* topk = sc + L.topk;
   float* best = sc + L.best;
@@ -444,24 +472,15 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
     for (int m = 0; m < M; ++m) {
       const MemberLayout& o = L.m[m];
       const SearchMember& b = mb[m];
-      const State& x = state[m];
-      float* ssc = sc + o.step;
       float* attw_t = sc + o.attw + (L.keep_attw && m == 0 ? (long)t * R * b.S : 0);
-      Ctx st{s, ssc + o.sl.skws};
-      ACVAE_TRY(prior_step(b.params, w_t, b.mem, b.mem_lens, sc + o.encp, x.hp, x.cp, x.lz, b.eps + (long)t * R * b.E,
-                           sc + o.mean, sc + o.logv, x.z, x.hp2, x.cp2, sc + o.attp, ssc, o.sl, N, beam, b.S, b.E, V, st));
-      ACVAE_TRY(decoder_step(b.params, w_t, x.h, b.mem, b.mem_lens, sc + o.encd, x.z, sc + o.logits, x.h2, attw_t,
-                             sc + o.rnn, ssc, o.sl, N, beam, b.S, b.E, b.H, b.A, V, st));
+      ACVAE_TRY(member_step(b, o, sc, w_t, cur[m], nxt[m], b.eps + (long)t * R * b.E, attw_t, N, beam, V, s));
       ACVAE_TRY(acvae::constrain_rows(sc + o.logits, V, greedy ? seqs : wh, T, t, R, V, (int)end_idx, con, s));
     }
     if (greedy) {
       ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, nullptr, 0, arg, best, 1, R, V, s));
       hipLaunchKernelGGL(greedy_pick_kernel, dim3((R + 255) / 256), dim3(256), 0, s, arg, best, seqs, logprobs, word,
                          end_idx, t, T, R);
-      for (int m = 0; m < M; ++m) {                      // the new states become the next step's previous ones
-        State& x = state[m];
-        std::swap(x.h, x.h2); std::swap(x.hp, x.hp2); std::swap(x.cp, x.cp2); std::swap(x.lz, x.z);
-      }
+      for (int m = 0; m < M; ++m) std::swap(cur[m], nxt[m]);   // the new states become the next step's previous ones
       continue;
     }
     ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, topk, sc + L.scores, V, nullptr, nullptr, 0, R, V, s));
@@ -470,15 +489,9 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
     if (fin.on)
       hipLaunchKernelGGL(beam_retire_kernel, dim3((R + 255) / 256), dim3(256), 0, s, topk, nxt_t, frec + (long)t * R,
                          end_idx, t == T - 1, R);
-    if (t + 1 < T) {                                     // vae_model.py:961-968: next step's states follow their parents
-      for (int m = 0; m < M; ++m) {
-        const State& x = state[m];
-        GatherTable g;
-        g.add({x.h2, x.h, mb[m].H}); g.add({x.hp2, x.hp, mb[m].E}); g.add({x.cp2, x.cp, mb[m].E}); g.add({x.z, x.lz, mb[m].E});
-        const bool hist = wh && m == 0;                  // the histories ride with member 0's states
-        hipLaunchKernelGGL(beam_gather_kernel, dim3(R, g.n + (hist ? 1 : 0)), dim3(256), 0, s, g, par_t,
-                           HistJob{wh, wh2, nxt_t, t, T});
-      }
+    if (t + 1 < T) {
+      const HistJob hj{wh, wh2, nxt_t, t, T};            // the histories ride with member 0's states
+      for (int m = 0; m < M; ++m) member_gather(mb[m], cur[m], nxt[m], R, par_t, wh && m == 0 ? &hj : nullptr, s);
       std::swap(wh, wh2);
       w_t = nxt_t;
     }
@@ -496,6 +509,24 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
 }  // namespace
 
 namespace {
+// SearchMember[M] from the per-member arrays (the widths alone for a size function; a null array leaves null pointers).
+int members_of(SearchMember* mb, int M, const int* S, const int* E, const int* H, const int* A,
+               const void* const* const* params = nullptr, const float* const* mem = nullptr,
+               const int64_t* const* mem_lens = nullptr, const float* const* eps = nullptr) {
+  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A) return ACVAE_EINVAL;
+  for (int m = 0; m < M; ++m)
+    mb[m] = {params ? params[m] : nullptr, mem ? mem[m] : nullptr, mem_lens ? mem_lens[m] : nullptr,
+             eps ? eps[m] : nullptr, S[m], E[m], H[m], A[m]};
+  return ACVAE_OK;
+}
+bool members_complete(const SearchMember* mb, int M) {
+  for (int m = 0; m < M; ++m)
+    if (!mb[m].params || !mb[m].mem || !mb[m].mem_lens || !mb[m].eps) return false;
+  return true;
+}
+template <class Layout>                                  // what a size function answers: -1 where the layout was refused
+int64_t layout_bytes(int rc, const Layout& L) { return rc == ACVAE_OK ? L.total * 4 : -1; }
+
 int beam_search_entry(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
                       int64_t start_idx, int64_t* seqs, float* attw_out, void* scratch_v, int64_t scratch_bytes, int N,
                       int beam, int max_length, int S, int E, int H, int A, int V, int64_t end_idx,
@@ -506,7 +537,7 @@ int beam_search_entry(const void* const* params, const float* mem, const int64_t
   ACVAE_TRY(search_layout(&mb, 1, N, beam, max_length, V, 1, con.on() || fin.on, fin.on, L));   // (one size per mode)
   ACVAE_TRY(finishing_check(fin, beam, max_length));
   if (fin.on && (end_idx < 0 || end_idx >= V)) return ACVAE_EINVAL;
-  if (!params || !mem || !mem_lens || !eps || !seqs || !attw_out || !scratch_v) return ACVAE_EINVAL;
+  if (!members_complete(&mb, 1) || !seqs || !attw_out || !scratch_v) return ACVAE_EINVAL;
   // acvae_topk_flat_batched selects k <= 16 and would answer a wider beam with the same code.  (The decoder GRU's width H is
   // free: the prior LSTM is E wide whatever H is, and every state row is kept, zeroed and gathered by its own width.)
   if (start_idx < 0 || start_idx >= V || beam > 16) return ACVAE_EINVAL;
@@ -520,13 +551,9 @@ int ensemble_search_entry(const void* const* const* params, const float* const* 
                           int64_t start_idx, int64_t end_idx, int greedy, int64_t* seqs, float* logprobs, void* scratch_v,
                           int64_t scratch_bytes, int N, int beam, int max_length, int V, const acvae::Constraints& con,
                           const Finishing& fin, void* stream) {
-  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !params || !mem || !mem_lens || !eps || !S || !E || !H || !A) return ACVAE_EINVAL;
   SearchMember mb[ACVAE_ENSEMBLE_MAX];
-  for (int m = 0; m < M; ++m) {
-    if (!params[m] || !mem[m] || !mem_lens[m] || !eps[m]) return ACVAE_EINVAL;
-    mb[m] = {params[m], mem[m], mem_lens[m], eps[m], S[m], E[m], H[m], A[m]};
-  }
-  if (!seqs || !logprobs || !scratch_v) return ACVAE_EINVAL;
+  ACVAE_TRY(members_of(mb, M, S, E, H, A, params, mem, mem_lens, eps));
+  if (!members_complete(mb, M) || !seqs || !logprobs || !scratch_v) return ACVAE_EINVAL;
   if (beam > 64 || (greedy && beam != 1)) return ACVAE_EINVAL;
   if (start_idx < 0 || start_idx >= V || end_idx < 0 || end_idx >= V) return ACVAE_EINVAL;
   ACVAE_TRY(acvae::constraints_check_loop(con, V, (int)end_idx, max_length, beam));
@@ -556,18 +583,15 @@ Finishing finishing_of(const float* length_norm_host, int nbest, int64_t* nb_seq
   return f;
 }
 
-int64_t beam_scratch(int N, int beam, int max_length, int S, int E, int H, int A, int V, int keep_hist, int keep_fin = 0) {
-  const SearchMember mb{nullptr, nullptr, nullptr, nullptr, S, E, H, A};
-  SearchLayout L;
-  return search_layout(&mb, 1, N, beam, max_length, V, 1, keep_hist, keep_fin, L) == ACVAE_OK ? L.total * 4 : -1;
-}
 int64_t ensemble_scratch(int M, int N, int beam, int max_length, const int* S, const int* E, const int* H, const int* A, int V,
-                         int keep_hist, int keep_fin = 0) {
-  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A) return -1;
+                         int keep_hist, int keep_fin = 0, int keep_attw = 0) {
   SearchMember mb[ACVAE_ENSEMBLE_MAX];
-  for (int m = 0; m < M; ++m) mb[m] = {nullptr, nullptr, nullptr, nullptr, S[m], E[m], H[m], A[m]};
+  if (members_of(mb, M, S, E, H, A) != ACVAE_OK) return -1;
   SearchLayout L;
-  return search_layout(mb, M, N, beam, max_length, V, 0, keep_hist, keep_fin, L) == ACVAE_OK ? L.total * 4 : -1;
+  return layout_bytes(search_layout(mb, M, N, beam, max_length, V, keep_attw, keep_hist, keep_fin, L), L);
+}
+int64_t beam_scratch(int N, int beam, int max_length, int S, int E, int H, int A, int V, int keep_hist, int keep_fin = 0) {
+  return ensemble_scratch(1, N, beam, max_length, &S, &E, &H, &A, V, keep_hist, keep_fin, 1);
 }
 }  // namespace
 
@@ -759,30 +783,14 @@ __global__ __launch_bounds__(64) void dbs_finish_kernel(const int* __restrict__ 
   D::trace(par_tab, word_tab, g, t0, r, T, R, end_idx, seqs + o * T);
 }
 
-struct DbsMemberLayout { StepLayout sl; long step, encd, encp, cur, h2, hp2, cp2, z, mean, logv, attp, attw, logits, rnn; };
-struct DbsLayout { DbsMemberLayout m[ACVAE_ENSEMBLE_MAX]; long mix, scores, gscore, gword, gpar, idx, par_tab, word_tab, rec, total; };
-// cur: the G groups' states a step reads, [G][R][H + 3E] as h | hp | cp | last_z blocks per group; everything else is
-// rewritten by every step and shared by the groups.
+struct DbsLayout { MemberLayout m[ACVAE_ENSEMBLE_MAX]; long mix, scores, gscore, gword, gpar, idx, par_tab, word_tab, rec, total; };
 int dbs_layout(const SearchMember* mb, int M, int N, int G, int bdash, int T, int V, DbsLayout& L) {
   if (M < 1 || M > ACVAE_ENSEMBLE_MAX || N <= 0 || G <= 0 || bdash <= 0 || T <= 0) return ACVAE_EINVAL;
   if (G > 16 || bdash > 16) return ACVAE_EUNSUPPORTED;
   const long R = (long)N * bdash;
   if (R > (1L << 20)) return ACVAE_EUNSUPPORTED;
   Bump b;
-  for (int m = 0; m < M; ++m) {
-    DbsMemberLayout& o = L.m[m];
-    const long S = mb[m].S, e = mb[m].E, h = mb[m].H;
-    ACVAE_TRY(step_layout((int)R, mb[m].S, mb[m].E, mb[m].H, mb[m].A, V, o.sl));
-    o.step = b.take(o.sl.total);
-    o.encd = b.take((long)N * S * mb[m].A);
-    o.encp = b.take((long)N * S * e);
-    o.cur = b.take((long)G * R * (h + 3 * e));
-    o.h2 = b.take(R * h); o.hp2 = b.take(R * e); o.cp2 = b.take(R * e); o.z = b.take(R * e);
-    o.mean = b.take(R * e); o.logv = b.take(R * e);
-    o.attp = b.take(R * S); o.attw = b.take(R * S);
-    o.logits = b.take(R * V);
-    o.rnn = b.take(R * 3 * e);
-  }
+  for (int m = 0; m < M; ++m) ACVAE_TRY(member_layout(b, mb[m], N, R, G, 1, V, L.m[m]));
   L.mix = M > 1 ? b.take(R * V) : 0;
   L.scores = b.take(R * V);
   L.gscore = b.take((long)G * R);
@@ -802,18 +810,8 @@ int dbs_search(const SearchMember* mb, int M, const DbsLayout& L, int64_t start_
   const int R = N * bdash;
   const float* logit_ptr[ACVAE_ENSEMBLE_MAX];
   int64_t logit_ld[ACVAE_ENSEMBLE_MAX];
-  for (int m = 0; m < M; ++m) {
-    const DbsMemberLayout& o = L.m[m];
-    const SearchMember& b = mb[m];
-    float* ssc = sc + o.step;
-    ACVAE_TRY(acvae_skinny_ws_reset(ssc + o.sl.skws, s));
-    ACVAE_TRY(step_attws_reset(ssc, o.sl, s));
-    ACVAE_TRY(acvae_attn_precompute(b.params, 0, b.mem, sc + o.encd, N, b.S, b.E, b.H, b.A, s));
-    ACVAE_TRY(acvae_attn_precompute(b.params, 1, b.mem, sc + o.encp, N, b.S, b.E, b.E, b.E, s));
-    ACVAE_TRY(zero(sc + o.cur, (long)G * R * (b.H + 3 * b.E), s));         // lt = 0: every state is zero
-    logit_ptr[m] = sc + o.logits;
-    logit_ld[m] = V;
-  }
+  for (int m = 0; m < M; ++m)                            // lt = 0: every group's states are zero
+    ACVAE_TRY(member_prologue(mb[m], L.m[m], sc, N, R, G, V, logit_ptr[m], logit_ld[m], s));
   float* gscore = sc + L.gscore;
   int64_t* gword = (int64_t*)(sc + L.gword);
   int64_t* gpar = (int64_t*)(sc + L.gpar);
@@ -821,6 +819,7 @@ int dbs_search(const SearchMember* mb, int M, const DbsLayout& L, int64_t start_
   int* par_tab = (int*)(sc + L.par_tab);
   int* word_tab = (int*)(sc + L.word_tab);
   float* rec = sc + L.rec;
+  auto group_states = [&](int m, int g) { return sc + L.m[m].cur + (long)g * R * (mb[m].H + 3 * mb[m].E); };
   ACVAE_TRY(zero(gscore, (long)G * R, s));
   hipLaunchKernelGGL(fill_words_kernel, dim3((G * R + 255) / 256), dim3(256), 0, s, gword, start_idx, G * R);
   long k = 0;
@@ -831,19 +830,9 @@ int dbs_search(const SearchMember* mb, int M, const DbsLayout& L, int64_t start_
       int64_t* w_g = gword + (long)g * R;
       int64_t* par_g = gpar + (long)g * R;
       float* c_g = gscore + (long)g * R;
-      for (int m = 0; m < M; ++m) {
-        const DbsMemberLayout& o = L.m[m];
-        const SearchMember& b = mb[m];
-        float* cur = sc + o.cur + (long)g * R * (b.H + 3 * b.E);
-        float *h = cur, *hp = h + (long)R * b.H, *cp = hp + (long)R * b.E, *lz = cp + (long)R * b.E;
-        float* ssc = sc + o.step;
-        Ctx st{s, ssc + o.sl.skws};
-        ACVAE_TRY(prior_step(b.params, w_g, b.mem, b.mem_lens, sc + o.encp, hp, cp, lz, b.eps + k * R * b.E, sc + o.mean,
-                             sc + o.logv, sc + o.z, sc + o.hp2, sc + o.cp2, sc + o.attp, ssc, o.sl, N, bdash, b.S, b.E, V,
-                             st));
-        ACVAE_TRY(decoder_step(b.params, w_g, h, b.mem, b.mem_lens, sc + o.encd, sc + o.z, sc + o.logits, sc + o.h2,
-                               sc + o.attw, sc + o.rnn, ssc, o.sl, N, bdash, b.S, b.E, b.H, b.A, V, st));
-      }
+      for (int m = 0; m < M; ++m)
+        ACVAE_TRY(member_step(mb[m], L.m[m], sc, w_g, group_states(m, g), sc + L.m[m].nxt, mb[m].eps + k * R * mb[m].E,
+                              sc + L.m[m].attw, N, bdash, V, s));
       const float* x = sc + L.m[0].logits;
       if (M > 1) {                                       // log(mean_m softmax(logits_m)) takes the logits' place
         ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, sc + L.mix, V, nullptr, nullptr, 0, R, V, s));
@@ -856,17 +845,8 @@ int dbs_search(const SearchMember* mb, int M, const DbsLayout& L, int64_t start_
       const long at = ((long)g * T + lt) * R;
       hipLaunchKernelGGL(dbs_advance_kernel, dim3((R + 255) / 256), dim3(256), 0, s, c_g, par_g, w_g, par_tab + at,
                          word_tab + at, rec + at, end_idx, lt == T - 1, R);
-      if (lt + 1 < T) {                                  // the group's next step reads its states through the parents
-        for (int m = 0; m < M; ++m) {
-          const DbsMemberLayout& o = L.m[m];
-          const SearchMember& b = mb[m];
-          float* cur = sc + o.cur + (long)g * R * (b.H + 3 * b.E);
-          float *h = cur, *hp = h + (long)R * b.H, *cp = hp + (long)R * b.E, *lz = cp + (long)R * b.E;
-          GatherTable gt;
-          gt.add({sc + o.h2, h, b.H}); gt.add({sc + o.hp2, hp, b.E}); gt.add({sc + o.cp2, cp, b.E}); gt.add({sc + o.z, lz, b.E});
-          hipLaunchKernelGGL(beam_gather_kernel, dim3(R, gt.n), dim3(256), 0, s, gt, par_g, HistJob{});
-        }
-      }
+      if (lt + 1 < T)                                    // the group's next step reads its states through the parents
+        for (int m = 0; m < M; ++m) member_gather(mb[m], group_states(m, g), sc + L.m[m].nxt, R, par_g, nullptr, s);
       ++k;
     }
   }
@@ -881,9 +861,7 @@ int dbs_entry(const SearchMember* mb, int M, int64_t start_idx, int64_t end_idx,
               int64_t scratch_bytes, void* stream) {
   DbsLayout L;
   ACVAE_TRY(dbs_layout(mb, M, N, G, bdash, T, V, L));
-  for (int m = 0; m < M; ++m)
-    if (!mb[m].params || !mb[m].mem || !mb[m].mem_lens || !mb[m].eps) return ACVAE_EINVAL;
-  if (!seqs || !scores || !lengths || !scratch_v) return ACVAE_EINVAL;
+  if (!members_complete(mb, M) || !seqs || !scores || !lengths || !scratch_v) return ACVAE_EINVAL;
   if (start_idx < 0 || start_idx >= V || end_idx < 0 || end_idx >= V) return ACVAE_EINVAL;
   if (!(temperature > 0.f) || !isfinite(temperature) || !isfinite(lambda)) return ACVAE_EINVAL;
   if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
@@ -893,9 +871,7 @@ int dbs_entry(const SearchMember* mb, int M, int64_t start_idx, int64_t end_idx,
 }  // namespace
 
 extern "C" int64_t acvae_dbs_search_scratch_bytes(int N, int G, int bdash, int T, int S, int E, int H, int A, int V) {
-  const SearchMember mb{nullptr, nullptr, nullptr, nullptr, S, E, H, A};
-  DbsLayout L;
-  return dbs_layout(&mb, 1, N, G, bdash, T, V, L) == ACVAE_OK ? L.total * 4 : -1;
+  return acvae_ensemble_dbs_search_scratch_bytes(1, N, G, bdash, T, &S, &E, &H, &A, V);
 }
 extern "C" int acvae_dbs_search(const void* const* params, const float* mem, const int64_t* mem_lens, const float* eps,
                                 int64_t start_idx, int64_t end_idx, int N, int G, int bdash, int T, int S, int E, int H, int A,
@@ -907,11 +883,10 @@ extern "C" int acvae_dbs_search(const void* const* params, const float* mem, con
 }
 extern "C" int64_t acvae_ensemble_dbs_search_scratch_bytes(int M, int N, int G, int bdash, int T, const int* S, const int* E,
                                                            const int* H, const int* A, int V) {
-  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !S || !E || !H || !A) return -1;
   SearchMember mb[ACVAE_ENSEMBLE_MAX];
-  for (int m = 0; m < M; ++m) mb[m] = {nullptr, nullptr, nullptr, nullptr, S[m], E[m], H[m], A[m]};
+  if (members_of(mb, M, S, E, H, A) != ACVAE_OK) return -1;
   DbsLayout L;
-  return dbs_layout(mb, M, N, G, bdash, T, V, L) == ACVAE_OK ? L.total * 4 : -1;
+  return layout_bytes(dbs_layout(mb, M, N, G, bdash, T, V, L), L);
 }
 extern "C" int acvae_ensemble_dbs_search(const void* const* const* params, const float* const* mem,
                                          const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
@@ -919,9 +894,9 @@ extern "C" int acvae_ensemble_dbs_search(const void* const* const* params, const
                                          int bdash, int T, int V, float temperature, float diversity_lambda, int group_nbest,
                                          int64_t* seqs, double* scores, int* lengths, void* scratch, int64_t scratch_bytes,
                                          void* stream) {
-  if (M < 1 || M > ACVAE_ENSEMBLE_MAX || !params || !mem || !mem_lens || !eps || !S || !E || !H || !A) return ACVAE_EINVAL;
   SearchMember mb[ACVAE_ENSEMBLE_MAX];
-  for (int m = 0; m < M; ++m) mb[m] = {params[m], mem[m], mem_lens[m], eps[m], S[m], E[m], H[m], A[m]};
+  if (!params || !mem || !mem_lens || !eps) return ACVAE_EINVAL;   // (in front of the layout's refusals, as M and the widths)
+  ACVAE_TRY(members_of(mb, M, S, E, H, A, params, mem, mem_lens, eps));
   return dbs_entry(mb, M, start_idx, end_idx, N, G, bdash, T, V, temperature, diversity_lambda, group_nbest, seqs, scores,
                    lengths, scratch, scratch_bytes, stream);
 }

@@ -17,7 +17,6 @@ departures, both documented in INTEGRATION.md:
     clip differ in ``z`` from the first step on (the reference takes row 0 only at t = 0, :681-682).
 """
 import copy
-import ctypes
 import json
 from pathlib import Path
 
@@ -25,14 +24,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, search
 from .batch import collate_fn
-from ._lib import ptr_table
-from .streams import scratch_buffer
 from .evaluate import collect_predictions, predictions_payload
 from .frontend import refuse_augmented
 from .seq_train_model import ScstWrapper
-from .vae_model import (CONSTRAINTS_OFF, Hybrid_VAEModel, _constraint_args, _finishing_args, _finishing_output)
+from .vae_model import Hybrid_VAEModel
 
 MAX_MEMBERS = int(_lib._defs["ACVAE_ENSEMBLE_MAX"])
 
@@ -79,11 +76,11 @@ class Ensemble(nn.Module):
         622-630).
 
         ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length`` / ``suppress_tokens``: constrained decoding
-        (``Hybrid_VAEModel._constraints``), applied to every member's logits in front of the mixing; ``logprobs`` are then
+        (``acvae_amd.search.constraints``), applied to every member's logits in front of the mixing; ``logprobs`` are then
         those of the constrained mixture.
 
         ``finish_on_end`` / ``length_penalty`` / ``nbest`` with ``method="beam"``: hypotheses finish at ``end_idx`` and are
-        ranked by a length-normalised score (``Hybrid_VAEModel._finishing``).  ``seqs`` is then hypothesis 0, ``logprobs``
+        ranked by a length-normalised score (``acvae_amd.search.finishing``).  ``seqs`` is then hypothesis 0, ``logprobs``
         [N] its raw log-probability, and the dict also holds ``scores``, ``lengths`` and the ``nbest_*`` entries.
 
         ``method="dbs"`` with ``beam_size`` / ``group_size`` / ``diversity_lambda`` / ``temperature`` / ``group_nbest``:
@@ -94,8 +91,7 @@ class Ensemble(nn.Module):
         refused with it, as for a single model; ``group_size`` is at most 16."""
         if method not in ("greedy", "beam", "dbs"):
             raise ValueError(f"Ensemble: method must be 'greedy', 'beam' or 'dbs', not {method!r}")
-        beam = 1 if method == "greedy" else int(beam_size)
-        T = int(max_length)
+        beam, T = 1 if method == "greedy" else int(beam_size), int(max_length)
         if method == "dbs":
             G = int(group_size)
             bdash = beam // G if G >= 1 else 0
@@ -105,76 +101,33 @@ class Ensemble(nn.Module):
                 raise ValueError(f"Ensemble: group_size {G}, at most 16 (a single model falls back to its host loop)")
             if not float(temperature) > 0:
                 raise ValueError(f"Ensemble: temperature must be > 0, not {temperature!r}")
-        con = self.models[0]._constraints(                                # (vocabulary and end_idx are shared)
-            dict(method=method, beam_size=beam, max_length=T, repetition_penalty=repetition_penalty,
-                 no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, suppress_tokens=suppress_tokens),
-            rollout=True)
-        fin = self.models[0]._finishing(dict(method=method, beam_size=beam, max_length=T, finish_on_end=finish_on_end,
-                                             length_penalty=length_penalty, nbest=nbest))
-        on = con != CONSTRAINTS_OFF
+        keywords = dict(method=method, beam_size=beam, max_length=T, repetition_penalty=repetition_penalty,
+                        no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, suppress_tokens=suppress_tokens,
+                        finish_on_end=finish_on_end, length_penalty=length_penalty, nbest=nbest)
+        con = search.constraints(keywords, self.vocab_size, self.end_idx, T, True, False)   # (no_grad: nothing is recorded)
+        fin = search.finishing(keywords, T)
         replay = self.noise.get("eps") if self.noise is not None else None
         self.noise = None
-        M = len(self.models)
-        if replay is not None and len(replay) != M:
-            raise ValueError(f"Ensemble: noise['eps'] holds {len(replay)} tensors for {M} members")
+        if replay is not None and len(replay) != len(self.models):
+            raise ValueError(f"Ensemble: noise['eps'] holds {len(replay)} tensors for {len(self.models)} members")
         _lib.require_cuda(feats)
-        dev = feats.device
-        mems, lens, epss, tables, dims = [], [], [], [], []
+        members = []
         for k, model in enumerate(self.models):
             model.eval()                                                   # base_runner.py:573-574
             model._forward_token = getattr(model, "_forward_token", 0) + 1     # per-forward caches, as Hybrid_VAEModel.forward
             encoded = model.encoder(feats, copy.copy(np.asarray(feat_lens)))    # its own copy: the encoder divides it in place
-            mem = model._projected_memory(encoded)
-            N, S, E = mem.shape
-            H, A = model.decoder.model.hidden_size, model.decoder.attn.attn_size
             if method == "dbs":
                 if replay is not None:
                     raise ValueError("Ensemble: noise['eps'] replays a beam search's noise, not a diverse beam search's")
-                eps = model._dbs_noise(N, T * G, bdash, E, dev)
+                noise = lambda N, E, dev: search._dbs_noise(N, T * G, bdash, E, dev)
             else:
-                eps = model._search_noise(N, T, beam, E, dev, None if replay is None else replay[k])
-            mems.append(mem)
-            lens.append(torch.as_tensor(encoded["audio_embeds_lens"]).to(device=dev, dtype=torch.long).contiguous())
-            epss.append(eps)
-            tables.append(ptr_table(model._text_table()))
-            dims.append((S, E, H, A))
-        N = mems[0].shape[0]
-        params = (ctypes.c_void_p * M)(*[ctypes.cast(t, ctypes.c_void_p).value for t in tables])
-        S_, E_, H_, A_ = (np.ascontiguousarray([d[j] for d in dims], dtype=np.int32) for j in range(4))
-        host = [a.ctypes.data for a in (S_, E_, H_, A_)]
+                noise = lambda N, E, dev: search._search_noise(N, T, beam, E, dev, None if replay is None else replay[k])
+            members.append(model._search_member(encoded, noise))
         if method == "dbs":
-            rows = G * bdash if group_nbest else G
-            seqs = torch.empty(N, rows, T, dtype=torch.long, device=dev)
-            scores = torch.empty(N, rows, dtype=torch.float64, device=dev)
-            lengths = torch.empty(N, rows, dtype=torch.int32, device=dev)
-            sb = _lib.call("acvae_ensemble_dbs_search_scratch_bytes", M, N, G, bdash, T, *host, self.vocab_size)
-            if sb < 0:
-                raise RuntimeError(f"acvae_ensemble_dbs_search: unsupported dimensions (N={N}, group_size={G}, "
-                                   f"bdash={bdash}, max_length={T})")
-            scratch = scratch_buffer(sb, dev)
-            _lib.call("acvae_ensemble_dbs_search", params, mems, lens, epss, *host, M, self.start_idx, self.end_idx, N, G,
-                      bdash, T, self.vocab_size, float(temperature), float(diversity_lambda), 1 if group_nbest else 0, seqs,
-                      scores, lengths, scratch, sb, _lib.current_stream())
-            return Hybrid_VAEModel._dbs_rows({"seqs": seqs, "scores": scores, "lengths": lengths}, beam, group_nbest,
-                                             self.end_idx)
-        seqs = torch.empty(N, T, dtype=torch.long, device=dev)
-        logprobs = torch.empty((N, T) if method == "greedy" else (N,), device=dev)
-        sb = _lib.call("acvae_ensemble_search_finishing_scratch_bytes" if fin is not None else
-                       "acvae_ensemble_search_constrained_scratch_bytes" if on else "acvae_ensemble_search_scratch_bytes",
-                       M, N, beam, T, *host, self.vocab_size)
-        if sb < 0:
-            raise RuntimeError(f"acvae_ensemble_search: unsupported dimensions (N={N}, beam={beam}, max_length={T})")
-        scratch = scratch_buffer(sb, dev)
-        if fin is not None:
-            nb, fargs, _norm = _finishing_args(fin, T, N, dev)
-            _lib.call("acvae_ensemble_search_finishing", params, mems, lens, epss, *host, M, self.start_idx, self.end_idx, 0,
-                      seqs, logprobs, scratch, sb, N, beam, T, self.vocab_size, _lib.current_stream(),
-                      *_constraint_args(con), *fargs)
-            return dict(_finishing_output(seqs, nb), logprobs=logprobs)
-        _lib.call("acvae_ensemble_search_constrained" if on else "acvae_ensemble_search", params, mems, lens, epss, *host, M, self.start_idx, self.end_idx, 1 if method == "greedy" else 0,
-                  seqs, logprobs, scratch, sb, N, beam, T, self.vocab_size, _lib.current_stream(),
-                  *(_constraint_args(con) if on else ()))
-        return {"seqs": seqs, "logprobs": logprobs}
+            return search.diverse_beam_search(members, True, G, bdash, T, self.vocab_size, self.start_idx, self.end_idx,
+                                              temperature, diversity_lambda, group_nbest, beam)
+        return search.beam_search(members, True, method == "greedy", beam, T, self.vocab_size, self.start_idx, self.end_idx,
+                                  con, fin)
 
 
 def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None, dcase_format=False, zh=False,

@@ -23,54 +23,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, streams, text_encoder
+from . import _lib, search, streams, text_encoder
 from .streams import scratch_buffer
 from .word_model import CaptionModel
-
-
-CONSTRAINT_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "min_length", "suppress_tokens")
-CONSTRAINTS_OFF = (1.0, 0, 0, ())           # repetition_penalty, no_repeat_ngram_size, min_length, suppress_tokens
-SUPPRESS_MAX = int(_lib._defs["ACVAE_SUPPRESS_MAX"])
-FINISH_KEYS = ("finish_on_end", "length_penalty", "nbest")
-
-
-def _constraint_args(constrain):
-    """(theta, n, m, ids) -> the five trailing arguments of the ``acvae_*_constrained`` entries.  The list is a HOST array
-    that the entry reads before it returns; the ctypes pointer keeps the array alive until then."""
-    theta, n, m, ids = constrain
-    arr = np.ascontiguousarray(ids, dtype=np.int32)
-    return float(theta), int(n), int(m), (arr.ctypes.data_as(_lib.ctypes.c_void_p) if len(ids) else None), len(ids)
-
-
-def length_norm(max_length, length_penalty):
-    """The finishing beam search's norm table, float32 [max_length]: ``norm[t] = float32((t + 1) ** length_penalty)``, the
-    power formed in float64 on the host.  The device divides a record by its entry, one fp32 division."""
-    def power(t):
-        try:
-            return float(t + 1) ** float(length_penalty)
-        except OverflowError:
-            return float("inf")
-
-    with np.errstate(over="ignore"):                     # (an overflow is the caller's to refuse: _finishing)
-        return np.array([power(t) for t in range(int(max_length))], np.float64).astype(np.float32)
-
-
-def _finishing_args(fin, max_length, N, dev):
-    """(length_penalty, nbest) -> the n-best outputs and the six trailing arguments of the ``acvae_*_finishing`` entries.  The
-    norm table is a HOST array that the entry reads before it returns."""
-    lp, nbest = fin
-    norm = length_norm(max_length, lp)
-    out = {"nbest_seqs": torch.empty(N, nbest, max_length, dtype=torch.long, device=dev),
-           "nbest_scores": torch.empty(N, nbest, device=dev), "nbest_logprobs": torch.empty(N, nbest, device=dev),
-           "nbest_lengths": torch.empty(N, nbest, dtype=torch.int32, device=dev)}
-    args = (norm.ctypes.data_as(_lib.ctypes.c_void_p), nbest, out["nbest_seqs"], out["nbest_scores"], out["nbest_logprobs"],
-            out["nbest_lengths"])
-    return out, args, norm
-
-
-def _finishing_output(seqs, nb):
-    """The dict of a finishing search: hypothesis 0 under the keys of today, the n-best list beside it."""
-    return dict(nb, seqs=seqs, scores=nb["nbest_scores"][:, 0], lengths=nb["nbest_lengths"][:, 0])
+from .search import CONSTRAINTS_OFF, _constraint_args, length_norm  # noqa: F401  (their earlier home: older callers)
 
 
 class _DecodeFn(torch.autograd.Function):
@@ -114,7 +70,7 @@ class _DecodeFn(torch.autograd.Function):
             entry = "acvae_decode_fwd_truncated"
             extra = (int(truncate[0]), float(truncate[1]), kept) if truncate else (0, 1.0, None)
         if constrain:
-            entry, extra = "acvae_decode_fwd_constrained", extra + _constraint_args(constrain)
+            entry, extra = "acvae_decode_fwd_constrained", extra + search._constraint_args(constrain)
         _lib.persist_status(dev)                 # the device's status words are registered before the first persistent launch
         # (plain call, nothing kept: the forward entries join both streams before they return)
         _lib.call(entry, params, mem,
@@ -331,18 +287,6 @@ class Hybrid_VAEModel(CaptionModel):
             mem = proj
         return mem
 
-    @staticmethod
-    def _search_noise(N, max_length, beam, E, dev, replay):
-        """The prior's noise of one search on the device, step-major [max_length, N, beam, E] as the library reads it.  The
-        reference walks the clips one after the other; their searches are independent, so all N x beam rows advance together
-        inside one library call.  Its noise order (clip-major: text_encoder.py:259 inside the clip loop) is kept by drawing
-        eps[clip][t] in that order on the host; ``replay`` [N, max_length, beam, E] is uploaded instead of a draw."""
-        if replay is None:
-            return _lib.h2d_fill((max_length, N, beam, E), torch.float32, dev,
-                                 lambda buf: [torch.randn(beam, E, out=buf[t, i]) for i in range(N) for t in range(max_length)])
-        return _lib.h2d(torch.as_tensor(replay).reshape(N, max_length, beam, E).transpose(0, 1).contiguous(), dev,
-                        torch.float32)
-
     @torch.no_grad()
     def beam_search(self, encoded, max_length, beam_size, **constraints):
         """Validation beam search, models/vae_model.py:896-995: beams expanded over the flat beam*V log-probabilities of
@@ -358,57 +302,24 @@ class Hybrid_VAEModel(CaptionModel):
         whole = dict(constraints, method="beam", max_length=max_length, beam_size=beam_size)
         con = self._constraints(whole, rollout=True)
         fin = self._finishing(whole)
-        unknown = set(constraints) - set(CONSTRAINT_KEYS) - set(FINISH_KEYS)
+        unknown = set(constraints) - set(search.CONSTRAINT_KEYS) - set(search.FINISH_KEYS)
         if unknown:
             raise TypeError(f"beam_search: unexpected keyword(s) {sorted(unknown)}")
-        mem_all = self._projected_memory(encoded)
-        dev = mem_all.device
-        lens_all = torch.as_tensor(encoded["audio_embeds_lens"]).to(device=dev, dtype=torch.long).contiguous()
-        N, S, E = mem_all.shape
-        V = self.vocab_size
-        H, A = self.decoder.model.hidden_size, self.decoder.attn.attn_size
         replay = self.noise.get("eps_beam") if self.noise is not None else None
         self.noise = None
-        eps_all = self._search_noise(N, max_length, beam_size, E, dev, replay)
-        seqs = torch.empty(N, max_length, dtype=torch.long, device=dev)
-        attw = torch.empty(N, S, max_length, device=dev)
-        if fin is not None:
-            sb = _lib.call("acvae_beam_search_finishing_scratch_bytes", N, beam_size, max_length, S, E, H, A, V)
-            scratch = scratch_buffer(sb, dev)
-            nb, fargs, _norm = _finishing_args(fin, max_length, N, dev)
-            _lib.call("acvae_beam_search_finishing", self._text_table(), mem_all, lens_all, eps_all, int(self.start_idx), seqs,
-                      attw, scratch, sb, N, beam_size, max_length, S, E, H, A, V, _lib.current_stream(), int(self.end_idx),
-                      *_constraint_args(con), *fargs)
-            return dict(_finishing_output(seqs, nb), attn_weights=attw)
-        on = con != CONSTRAINTS_OFF                       # (the word histories of a constrained search need more scratch)
-        sb = _lib.call("acvae_beam_search_constrained_scratch_bytes" if on else "acvae_beam_search_scratch_bytes", N,
-                       beam_size, max_length, S, E, H, A, V)
-        scratch = scratch_buffer(sb, dev)
-        _lib.call("acvae_beam_search_constrained" if on else "acvae_beam_search", self._text_table(), mem_all,
-                  lens_all, eps_all, int(self.start_idx), seqs, attw, scratch, sb, N, beam_size, max_length, S, E, H, A, V,
-                  _lib.current_stream(), *((int(self.end_idx),) + _constraint_args(con) if on else ()))
-        return {"seqs": seqs, "attn_weights": attw}
+        member = self._search_member(
+            encoded, lambda N, E, dev: search._search_noise(N, max_length, beam_size, E, dev, replay))
+        return search.beam_search([member], False, False, beam_size, max_length, self.vocab_size, int(self.start_idx),
+                                  int(self.end_idx), con, fin)
 
-    @staticmethod
-    def _dbs_rows(out, beam_size, group_nbest, end_idx):
-        """With ``group_nbest`` the reference returns ``beam_size`` rows per clip and fills ``bdash * group_size`` of them:
-        where ``group_size`` does not divide ``beam_size`` the rest hold ``end_idx`` (score -inf, length 0), as they did."""
-        seqs, scores, lengths = out["seqs"], out["scores"], out["lengths"]
-        extra = beam_size - seqs.shape[1] if group_nbest else 0
-        if extra <= 0:
-            return out
-        N, _, T = seqs.shape
-        return {"seqs": torch.cat([seqs, seqs.new_full((N, extra, T), end_idx)], dim=1),
-                "scores": torch.cat([scores, scores.new_full((N, extra), float("-inf"))], dim=1),
-                "lengths": torch.cat([lengths, lengths.new_zeros((N, extra))], dim=1)}
-
-    @staticmethod
-    def _dbs_noise(N, n_steps, bdash, E, dev):
-        """The prior's noise of one diverse beam search on the device, step-major [n_steps, N, bdash, E] as the library reads
-        it, drawn on the CPU generator in the reference's order: clip, then step k of the (t, group) schedule
-        (text_encoder.py:259 inside those loops), ``torch.randn(bdash, E)`` each."""
-        return _lib.h2d_fill((n_steps, N, bdash, E), torch.float32, dev,
-                             lambda buf: [torch.randn(bdash, E, out=buf[k, i]) for i in range(N) for k in range(n_steps)])
+    def _search_member(self, encoded, noise):
+        """A member as ``acvae_amd.search`` takes it -> (memory [N, S, E], lengths i64 [N], noise, table, (S, E, H, A)).
+        ``noise(N, E, device)`` draws on the host while the encoder runs: the lengths' pageable upload waits for the stream."""
+        mem = self._projected_memory(encoded)
+        eps = noise(mem.shape[0], mem.shape[2], mem.device)
+        lens = torch.as_tensor(encoded["audio_embeds_lens"]).to(device=mem.device, dtype=torch.long).contiguous()
+        dims = (mem.shape[1], mem.shape[2], self.decoder.model.hidden_size, self.decoder.attn.attn_size)
+        return mem, lens, eps, self._text_table(), dims
 
     @torch.no_grad()
     def diverse_beam_search(self, encoded, max_length, beam_size, group_size, diversity_lambda, temperature, group_nbest,
@@ -420,7 +331,7 @@ class Hybrid_VAEModel(CaptionModel):
         The whole search is ONE library call (``acvae_dbs_search``, include/acvae_hip.h has the definition) with no host
         synchronisation.  Returns, on the device, {"seqs": i64 [N, rows, max_length], "scores": f64 [N, rows] (logprob /
         length of each returned beam), "lengths": i32 [N, rows]}, rows = ``beam_size`` with ``group_nbest`` (the first
-        ``bdash * group_size`` are beams, see ``_dbs_rows``) else ``group_size``.
+        ``bdash * group_size`` are beams, see ``search._dbs_rows``) else ``group_size``.
 
         ``dbs_impl="host"`` runs the loop over the step API that the call replaces (``diverse_beam_search_host``: the same
         tokens and scores bit for bit, three read-backs per step); it is also taken when ``group_size > 16``, the library's
@@ -433,117 +344,13 @@ class Hybrid_VAEModel(CaptionModel):
         if dbs_impl == "host" or group_size > 16:
             return self.diverse_beam_search_host(encoded, max_length, beam_size, group_size, diversity_lambda, temperature,
                                                  group_nbest)
-        mem = self._projected_memory(encoded)
-        dev = mem.device
-        lens = torch.as_tensor(encoded["audio_embeds_lens"]).to(device=dev, dtype=torch.long).contiguous()
-        N, S, E = mem.shape
-        V = self.vocab_size
-        H, A = self.decoder.model.hidden_size, self.decoder.attn.attn_size
         G, T = int(group_size), int(max_length)
-        eps = self._dbs_noise(N, T * G, bdash, E, dev)
-        rows = G * bdash if group_nbest else G
-        seqs = torch.empty(N, rows, T, dtype=torch.long, device=dev)
-        scores = torch.empty(N, rows, dtype=torch.float64, device=dev)
-        lengths = torch.empty(N, rows, dtype=torch.int32, device=dev)
-        sb = _lib.call("acvae_dbs_search_scratch_bytes", N, G, bdash, T, S, E, H, A, V)
-        if sb < 0:
-            raise RuntimeError(f"acvae_dbs_search: unsupported dimensions (N={N}, group_size={G}, bdash={bdash}, "
-                               f"max_length={T})")
-        scratch = scratch_buffer(sb, dev)
-        _lib.call("acvae_dbs_search", self._text_table(), mem, lens, eps, int(self.start_idx), int(self.end_idx), N, G, bdash,
-                  T, S, E, H, A, V, float(temperature), float(diversity_lambda), 1 if group_nbest else 0, seqs, scores,
-                  lengths, scratch, sb, _lib.current_stream())
-        return self._dbs_rows({"seqs": seqs, "scores": scores, "lengths": lengths}, beam_size, group_nbest, int(self.end_idx))
+        member = self._search_member(encoded, lambda N, E, dev: search._dbs_noise(N, T * G, bdash, E, dev))
+        return search.diverse_beam_search([member], False, G, bdash, T, self.vocab_size, int(self.start_idx), int(self.end_idx),
+                                          temperature, diversity_lambda, group_nbest, beam_size)
 
-    @torch.no_grad()
-    def diverse_beam_search_host(self, encoded, max_length, beam_size, group_size, diversity_lambda, temperature,
-                                 group_nbest):
-        """``diverse_beam_search`` as a host loop (``dbs_impl="host"``): host bookkeeping (sequence tables, finished beams)
-        as in the reference, which also reads the chosen words back every step; prior / decoder step, the score transform
-        and the flat top-k are library calls.  The yardstick of the one-call search, and its stand-in beyond 16 groups."""
-        mem_all = self._projected_memory(encoded)
-        dev = mem_all.device
-        lens_all = torch.as_tensor(encoded["audio_embeds_lens"]).to(torch.long)
-        N, S, E = mem_all.shape
-        V = self.vocab_size
-        bdash = beam_size // group_size
-        if bdash < 1 or bdash > 16:
-            raise ValueError("diverse_beam_search: beam_size // group_size must be in 1..16")
-        R = N * bdash
-        st = _lib.current_stream
-        # The clips are independent, so they advance together: rows = clips x bdash per (t, group) step; one host read-back
-        # per step for the whole batch (the reference reads back per clip and step).  The reference's noise order — clip,
-        # then t, then group (text_encoder.py:259 inside those loops) — is kept by drawing every eps up front in it.
-        steps = [(t, g) for t in range(max_length + group_size - 1) for g in range(group_size)
-                 if 0 <= t - g <= max_length - 1]
-        eps_all = _lib.h2d_fill((N, len(steps), bdash, E), torch.float32, dev,
-                                lambda buf: [torch.randn(bdash, E, out=buf[i, k]) for i in range(N)
-                                             for k in range(len(steps))])
-        mem = mem_all.repeat_interleave(bdash, dim=0).contiguous()
-        lens = lens_all.repeat_interleave(bdash)
-        scores = torch.empty(R, V, device=dev)
-        vals = torch.empty(R, device=dev)
-        idx, prev_d, nxt_d = (torch.empty(R, dtype=torch.long, device=dev) for _ in range(3))
-        seq = [[np.zeros((bdash, 0), np.int64) for _ in range(group_size)] for _ in range(N)]
-        score = [np.zeros((N, bdash), np.float32) for _ in range(group_size)]
-        done = [[[] for _ in range(group_size)] for _ in range(N)]
-        carry = [None] * group_size
-        base = (np.arange(N) * bdash)[:, None]
-        for k, (t, g) in enumerate(steps):
-            lt = t - g
-            if lt == 0:
-                w = torch.full((R,), self.start_idx, dtype=torch.long, device=dev)
-                state = self.decoder.init_hidden(R).to(dev)
-                hid = self.pnet.init_hidden(R, dev)
-                last_z = torch.zeros(R, E, device=dev)
-            else:
-                state0, hid0, z0, w, parent = carry[g]
-                state = state0[:, parent].contiguous()
-                hid = (hid0[0][:, parent].contiguous(), hid0[1][:, parent].contiguous())
-                last_z = z0[parent].contiguous()
-            pn = self.pnet(w.unsqueeze(1), mem, hid, last_z, lens, eps=eps_all[:, k].reshape(R, E))
-            dn = self.decoder(word=w.unsqueeze(1), state=state, enc_mem=mem, enc_mem_lens=lens, z=pn["z"])
-            logits = dn["logits"].squeeze(1)
-            counts = None
-            if g > 0:                                        # add_diversity (:298-312), one count vector per clip
-                c = np.zeros((N, V), np.float32)
-                for i in range(N):
-                    for earlier in range(g):
-                        np.add.at(c[i], seq[i][earlier][:, lt], 1.0)
-                counts = _lib.h2d(c, dev)
-            _lib.call("acvae_dbs_scores", logits, V, float(temperature), counts, float(diversity_lambda),
-                      _lib.h2d(score[g].reshape(-1), dev), scores, R, V, bdash if g > 0 else 0, st())
-            _lib.call("acvae_topk_flat_batched", scores, V if lt == 0 else bdash * V, bdash * V, bdash, V, vals, idx, prev_d,
-                      nxt_d, N, bdash, st())
-            top = vals.cpu().numpy().reshape(N, bdash).copy()              # one read-back per step for all clips
-            parent_h = prev_d.cpu().numpy().reshape(N, bdash) - base        # beam index within the clip
-            nxt_h = nxt_d.cpu().numpy().reshape(N, bdash)
-            last = t == max_length + g - 1
-            for i in range(N):
-                sq = np.concatenate([seq[i][g][parent_h[i]] if lt > 0 else seq[i][g], nxt_h[i][:, None]], axis=1)
-                seq[i][g] = sq
-                ended = sq[:, lt] == self.end_idx
-                if last:
-                    ended[:] = True
-                for b_ in range(bdash):
-                    if ended[b_]:
-                        done[i][g].append({"seq": sq[b_].copy(), "score": float(top[i, b_]) / (lt + 1)})
-                top[i][ended] -= np.float32(1000)
-            score[g] = top
-            carry[g] = (dn["state"], pn["hiddens_state"], pn["z"], nxt_d.clone(), prev_d.clone())
-        rows = bdash * group_size if group_nbest else group_size
-        out = torch.full((N, rows, max_length), self.end_idx, dtype=torch.long)
-        out_scores = torch.zeros(N, rows, dtype=torch.float64)
-        out_lengths = torch.zeros(N, rows, dtype=torch.int32)
-        for i in range(N):
-            ranked = [sorted(d, key=lambda x: -x["score"])[:bdash] for d in done[i]]
-            chosen = sum(ranked, []) if group_nbest else [d[0] for d in ranked]
-            for r, beam in enumerate(chosen):
-                out[i, r, :len(beam["seq"])] = torch.from_numpy(beam["seq"])
-                out_scores[i, r] = beam["score"]
-                out_lengths[i, r] = len(beam["seq"])
-        return self._dbs_rows({"seqs": out.to(dev), "scores": out_scores.to(dev), "lengths": out_lengths.to(dev)}, beam_size,
-                              group_nbest, int(self.end_idx))
+    diverse_beam_search_host = search.diverse_beam_search_host     # (``dbs_impl="host"``: the loop over the step API)
+    _search_noise = staticmethod(search._search_noise)             # (its earlier home, as the three names above)
 
     def check_persistent_launches(self, device=None):
         """Raise if a persistent decode / posterior launch on the model's device gave up (its outputs are NaN then).  Call
@@ -570,7 +377,7 @@ class Hybrid_VAEModel(CaptionModel):
         self._finishing(kwargs)
         if method == "beam":                                              # vae_model.py:884-886
             return self.beam_search(encoded, max_length, kwargs.get("beam_size", 3),
-                                    **{k: kwargs[k] for k in CONSTRAINT_KEYS + FINISH_KEYS if k in kwargs})
+                                    **{k: kwargs[k] for k in search.CONSTRAINT_KEYS + search.FINISH_KEYS if k in kwargs})
         if method == "dbs":                                               # vae_model.py:887-893
             return self.diverse_beam_search(encoded, max_length, kwargs.get("beam_size", 5), kwargs.get("group_size", 5),
                                             kwargs.get("diversity_lambda", 0.5), kwargs.get("temperature", 1.0),
@@ -713,26 +520,7 @@ class Hybrid_VAEModel(CaptionModel):
         return self._rerank(self.inference_forward(rep, **kwargs), rerank, n)
 
     def _rerank_check(self, rerank, sample_n, kwargs):
-        """The refusals of ``rerank=`` (ValueError, in front of every launch): a search (``method="beam"`` / ``"dbs"``
-        returns its own best hypotheses), fewer than 2 or more than 16 candidates per clip, rows longer than the kernel
-        takes, a forward that records a differentiable rollout (the picked rows are a choice among constants: nothing
-        flows back through it)."""
-        if rerank is None:
-            return
-        from . import consensus
-        if not isinstance(rerank, consensus.Consensus):
-            raise ValueError(f"rerank must be an acvae_amd.consensus.Consensus, got {type(rerank).__name__}")
-        method = kwargs.get("method", "greedy")
-        if method in ("beam", "dbs"):
-            raise ValueError(f"rerank with method={method!r}: a search returns its own best hypotheses; consensus reranking "
-                             "chooses among N rollouts of 'greedy', 'sample' or 'gumbel'")
-        consensus.check_sample_n(sample_n, "rerank")
-        max_length = kwargs.get("max_length", self.max_length)
-        if max_length > consensus.MAX_LENGTH:
-            raise ValueError(f"rerank: max_length={max_length}; the kernel takes rows of at most {consensus.MAX_LENGTH} tokens")
-        if self._records_rollout():
-            raise ValueError("rerank in a forward that records a differentiable rollout (train() with gradients enabled): "
-                             "the picked rows are a choice among constants; use torch.no_grad() or eval()")
+        search.rerank_check(rerank, sample_n, kwargs, self.max_length, self._records_rollout())
 
     def _rerank(self, output, rerank, sample_n):
         """Consensus reranking of an N-samples-per-clip output (rows clip-major), on the device and without a
@@ -753,172 +541,15 @@ class Hybrid_VAEModel(CaptionModel):
         to train; every other 2-input forward is the inference path."""
         return torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
 
+    # ---- the keyword validators of a forward: acvae_amd.search's (which documents them), on this model's values
     def _truncation(self, kwargs, rollout=False):
-        """The ``top_k`` / ``top_p`` keywords of a forward -> (top_k, top_p), (0, 1.0) when both are off.
-
-        ``top_k`` (int >= 0, 0 = off) keeps the k most probable words of a step; ``top_p`` (in (0, 1], exactly 1.0 = off) keeps
-        the nucleus: the shortest prefix of the words, most probable first, whose mass reaches ``top_p``.  With both, the
-        shorter prefix.  Equal logits rank by lower index.  The mass is that of the distribution the method samples from:
-        softmax(logits / temp) for ``method="sample"``; softmax(logits) for ``"gumbel"``, where ``temp`` changes no word
-        (it divides every score alike - in the reference too).  The draw is the untruncated one restricted to the kept
-        words, on the same noise: the host's draws on the CPU generator and the device generator's counters do not depend
-        on the keywords.  ``sampled_logprobs`` stays the log-probability under the FULL distribution.
-
-        ValueError: a value out of range; truncation together with ``method="greedy"``, ``"beam"`` or ``"dbs"`` (nothing
-        is sampled there); truncation in a forward that records a differentiable rollout (``rollout``: a 2-input forward),
-        where ``sampled_logprobs`` would not be the log-probability of the distribution sampled from."""
-        top_k, top_p = kwargs.get("top_k", 0), kwargs.get("top_p", 1.0)
-        top_k = 0 if top_k is None else top_k
-        top_p = 1.0 if top_p is None else top_p
-        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0 or top_k > 0x7fffffff:
-            raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {top_k!r}")
-        try:
-            p32 = float(np.float32(top_p))               # the value the kernel compares with
-        except (TypeError, ValueError):
-            raise ValueError(f"top_p must be a number in (0, 1] (1.0 = off), got {top_p!r}") from None
-        if isinstance(top_p, bool) or not (0.0 < p32 <= 1.0):
-            raise ValueError(f"top_p must lie in (0, 1] (1.0 = off), got {top_p!r}")
-        top_k = int(top_k)
-        if top_k == 0 and p32 == 1.0:
-            return 0, 1.0
-        given = " / ".join(f"{n}={v!r}" for n, v, on in (("top_k", top_k, top_k > 0), ("top_p", top_p, p32 < 1.0)) if on)
-        method = kwargs.get("method", "greedy")
-        if method in ("greedy", "beam", "dbs"):
-            raise ValueError(f"{given} truncates sampled decoding (method='sample' or 'gumbel'): method={method!r} samples "
-                             "nothing")
-        if rollout and self._records_rollout():
-            raise ValueError(f"{given} in a forward that records a differentiable rollout (train() with gradients enabled): "
-                             "sampled_logprobs is the log-probability under the full distribution, not under the truncated "
-                             "one the words are drawn from; use torch.no_grad() or eval()")
-        return top_k, p32
+        return search.truncation(kwargs, rollout, self._records_rollout())
 
     def _constraints(self, kwargs, rollout=False):
-        """The constrained-decoding keywords of a forward -> (repetition_penalty, no_repeat_ngram_size, min_length,
-        suppress_tokens), ``CONSTRAINTS_OFF`` when nothing is on (``None`` = off for each).
-
-        All act on a row's logits x at step t, in front of the selection, against the row's history h[0..t) (the words it
-        has emitted; ``<start>`` is not part of it):
-          ``repetition_penalty`` theta (1.0 = off; finite, > 0; the kernel uses float32(theta)): every distinct word w of h
-            gets x[w] / theta if x[w] > 0, else x[w] * theta;
-          ``no_repeat_ngram_size`` n (0 = off): every word that would complete an n-gram the caption already holds is banned
-            (n = 1 bans every word of h);
-          ``min_length`` m (0 = off; <= ``max_length``): ``end_idx`` is banned at steps t < m;
-          ``suppress_tokens`` (() = off): at most ``SUPPRESS_MAX`` vocabulary ids banned at every step, ``end_idx`` not
-            among them.
-        A ban sets the logit to -inf; the penalty comes first and a ban wins.  Accepted with greedy / "sample" / "gumbel"
-        (``top_k`` / ``top_p`` then truncate the constrained row) and "beam".
-
-        ValueError, naming the keyword: a value out of range; ``method="dbs"`` (its histories live on the host); the
-        4-input (training) forward (``rollout`` False); a 2-input forward that records a differentiable rollout (the
-        backward does not know the penalty's factor); a vocabulary too small for a row to keep a word,
-        ``V <= len(suppress_tokens) + max_length + beam``."""
-        V, end = int(self.vocab_size), int(self.end_idx)
-        theta, n, m, ids = (kwargs.get(k) for k in CONSTRAINT_KEYS)
-        theta = 1.0 if theta is None else theta
-        n = 0 if n is None else n
-        m = 0 if m is None else m
-        ids = () if ids is None else ids
-        try:
-            th32 = float(np.float32(theta))              # the value the kernel uses
-        except (TypeError, ValueError):
-            raise ValueError(f"repetition_penalty must be a finite number > 0 (1.0 = off), got {theta!r}") from None
-        if isinstance(theta, bool) or not (np.isfinite(th32) and th32 > 0.0):
-            raise ValueError(f"repetition_penalty must be a finite number > 0 (1.0 = off), got {theta!r}")
-        for name, v in (("no_repeat_ngram_size", n), ("min_length", m)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 or v > 0x7fffffff:
-                raise ValueError(f"{name} must be an integer >= 0 (0 = off), got {v!r}")
-        n, m = int(n), int(m)
-        max_length = kwargs.get("max_length", self.max_length)
-        if m > max_length:
-            raise ValueError(f"min_length={m} exceeds max_length={max_length}")
-        if isinstance(ids, torch.Tensor):
-            ids = ids.detach().cpu().reshape(-1).tolist()
-        try:
-            ids = list(np.asarray(ids).reshape(-1).tolist()) if isinstance(ids, np.ndarray) else list(ids)
-        except TypeError:
-            raise ValueError(f"suppress_tokens must be a sequence of vocabulary ids, got {ids!r}") from None
-        for w in ids:
-            if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not (0 <= w < V):
-                raise ValueError(f"suppress_tokens: {w!r} is not a vocabulary id in [0, {V})")
-            if w == end:
-                raise ValueError(f"suppress_tokens must not hold end_idx ({end}): no caption could end")
-        if len(ids) > SUPPRESS_MAX:
-            raise ValueError(f"suppress_tokens holds {len(ids)} ids, at most {SUPPRESS_MAX}")
-        con = (th32, n, m, tuple(int(w) for w in ids))
-        if con == CONSTRAINTS_OFF:
-            return CONSTRAINTS_OFF
-        given = " / ".join(f"{k}={v!r}" for k, v, on in zip(CONSTRAINT_KEYS, (theta, n, m, list(con[3])),
-                                                            (th32 != 1.0, n > 0, m > 0, len(ids) > 0)) if on)
-        method = kwargs.get("method", "greedy")
-        if method == "dbs":
-            raise ValueError(f"{given} with method='dbs': diverse beam search keeps its histories on the host and is not "
-                             "constrained; use 'greedy', 'sample', 'gumbel' or 'beam'")
-        if not rollout:
-            raise ValueError(f"{given} in the 4-input (training) forward: a teacher-forced row has no history of its own; "
-                             "constrained decoding belongs to the 2-input forward")
-        if self._records_rollout():
-            raise ValueError(f"{given} in a forward that records a differentiable rollout (train() with gradients enabled): "
-                             "the backward does not know the penalty's factor; use torch.no_grad() or eval()")
-        beam = int(kwargs.get("beam_size", 3)) if method == "beam" else 1
-        if V <= len(ids) + int(max_length) + beam:
-            raise ValueError(f"{given}: a vocabulary of {V} words may leave a row without a word; it must exceed "
-                             f"len(suppress_tokens) + max_length + beam = {len(ids)} + {max_length} + {beam}")
-        return con
+        return search.constraints(kwargs, self.vocab_size, self.end_idx, self.max_length, rollout, self._records_rollout())
 
     def _finishing(self, kwargs):
-        """The finishing keywords of a beam search -> ``(length_penalty, nbest)``, or None when ``finish_on_end`` is off.
-
-        The one definition (include/acvae_hip.h states the same for the C entries).  Rows r = n * beam + j of clip n.  As
-        without finishing, step t forms ``scores[r, v] = c[r] + logmix_t[r, v]`` (after the constraints) and the flat top-k
-        over the clip's beam * V scores (sorted descending, ties to the lower flat index, t = 0 included) gives row r its
-        cumulative score ``c_t[r]``, parent ``p_t[r]`` and word ``w_t[r]``.  Then:
-          1. r is alive iff ``c_t[r] > -inf``;
-          2. if r is alive and (``w_t[r] == end_idx`` or ``t == max_length - 1``) the record is ``f_t[r] = c_t[r]``, else -inf;
-          3. if ``w_t[r] == end_idx``, ``c_t[r] <- -inf``: the row is retired, all its children score -inf and lose to every
-             alive candidate; where a clip has fewer than ``beam`` alive candidates the top-k takes such children: dead rows,
-             never recorded.
-        After the last step, per clip: the candidates are every (t, j) with ``f_t[n * beam + j] > -inf``; the score is
-        ``s = f_t / norm[t]``, ``norm[t] = float32((t + 1) ** length_penalty)`` (float64 power on the host, one fp32 division
-        on the device); the order is s descending, then t ascending, then j ascending, and the first ``nbest`` are returned;
-        a hypothesis's words are its parents traced back from (t, r), ``end_idx`` behind t, its length t + 1.  With fewer than
-        ``nbest`` candidates (only when bans leave a clip fewer than ``beam`` finite continuations) the missing slots are rows
-        of ``end_idx`` with score -inf and length 0.  ``length_penalty`` 1.0 (the default) is the average log-probability per
-        word, the rule of the reference's diverse beam search; 0 ranks by the raw log-probability.
-
-        The search itself is unchanged: all ``max_length`` steps run, retired and dead rows keep being stepped, nothing is
-        read back.  The output dict holds hypothesis 0 as ``seqs`` [N, T] (and ``attn_weights``, zeros behind its length),
-        ``scores`` / ``lengths`` [N], and ``nbest_seqs`` [N, nbest, T], ``nbest_scores`` / ``nbest_logprobs`` (the raw f) f32
-        [N, nbest], ``nbest_lengths`` int32 [N, nbest].
-
-        ValueError: ``finish_on_end`` with a method other than "beam"; ``length_penalty`` / ``nbest`` without
-        ``finish_on_end``; a ``length_penalty`` that is negative or not finite (or whose table overflows float32);
-        ``nbest`` outside [1, beam_size]."""
-        on, lp, nbest = (kwargs.get(k) for k in FINISH_KEYS)
-        on = False if on is None else on
-        if not isinstance(on, (bool, np.bool_)):
-            raise ValueError(f"finish_on_end must be True or False, got {on!r}")
-        if not on:
-            for k, v in (("length_penalty", lp), ("nbest", nbest)):
-                if v is not None:
-                    raise ValueError(f"{k}={v!r} without finish_on_end=True: it ranks finished hypotheses only")
-            return None
-        method = kwargs.get("method", "greedy")
-        if method != "beam":
-            raise ValueError(f"finish_on_end=True with method={method!r}: finishing belongs to method='beam'")
-        lp = 1.0 if lp is None else lp
-        try:
-            lpf = float(lp)
-        except (TypeError, ValueError):
-            raise ValueError(f"length_penalty must be a finite number >= 0, got {lp!r}") from None
-        if isinstance(lp, bool) or not (np.isfinite(lpf) and lpf >= 0.0):
-            raise ValueError(f"length_penalty must be a finite number >= 0, got {lp!r}")
-        beam = int(kwargs.get("beam_size", 3))
-        nbest = 1 if nbest is None else nbest
-        if isinstance(nbest, bool) or not isinstance(nbest, (int, np.integer)) or not (1 <= nbest <= beam):
-            raise ValueError(f"nbest must be an integer in [1, beam_size = {beam}], got {nbest!r}")
-        if not np.isfinite(length_norm(kwargs.get("max_length", self.max_length), lpf)).all():
-            raise ValueError(f"length_penalty={lp!r}: max_length ** length_penalty overflows float32")
-        return lpf, int(nbest)
+        return search.finishing(kwargs, self.max_length)
 
     def _host_prepare(self, N, dev, caps, cap_lens, kwargs):
         """The decode loop's host-side random decisions, in the reference's per-step order (scheduled-sampling coin
@@ -1003,7 +634,7 @@ class Hybrid_VAEModel(CaptionModel):
             sampling["sample"] = (code, temp, _lib.h2d(sample_noise, dev, torch.float32).contiguous())
         if top_k > 0 or top_p < 1.0:
             sampling["truncate"] = (top_k, top_p)
-        if constrain != CONSTRAINTS_OFF:
+        if constrain != search.CONSTRAINTS_OFF:
             sampling["constrain"] = constrain
         if drop_p > 0.0:
             if dec_keep is None:

@@ -12,7 +12,8 @@ import constrain_util as CU
 from acvae_amd import _lib
 from acvae_amd.decoder import VAERNNBahdanauAttnDecoder
 from acvae_amd.encoder import Cnn10
-from acvae_amd.vae_model import CONSTRAINTS_OFF, Hybrid_VAEModel
+from acvae_amd.search import CONSTRAINTS_OFF
+from acvae_amd.vae_model import Hybrid_VAEModel
 
 EINVAL = -1
 NEG_INF = np.float32(-np.inf)
@@ -318,6 +319,73 @@ def test_ensemble_and_beam_search_validate_the_same_way(model):
         model.beam_search({}, 10, 3, no_repeat_ngram_size=-1)
     with pytest.raises(TypeError, match="top_k"):
         model.beam_search({}, 10, 3, top_k=3)
+
+
+def test_ensemble_validates_its_keywords_without_consulting_a_member(model):
+    """Ensemble.forward hands acvae_amd.search the ensemble's own vocabulary size and end_idx: the refusals carry the texts a
+    single model gives, and no member's validator is called (here the first member's would fail the test)."""
+    import copy
+    import re
+    from acvae_amd.ensemble import Ensemble
+
+    def never(*a, **kw):
+        raise AssertionError("Ensemble.forward consulted a member's validator")
+    first = copy.copy(model)                                # shares the weights; the shadowing attributes are its own
+    for name in ("_constraints", "_finishing", "_truncation", "_records_rollout"):
+        object.__setattr__(first, name, never)
+    ens = Ensemble([first, model])
+    feats, lens = torch.zeros(2, 64, 64), np.array([64, 64])
+    end, V = int(model.end_idx), int(model.vocab_size)
+    for kw, text in (
+            (dict(repetition_penalty=-2.0), "repetition_penalty must be a finite number > 0 (1.0 = off), got -2.0"),
+            (dict(no_repeat_ngram_size=1.5), "no_repeat_ngram_size must be an integer >= 0 (0 = off), got 1.5"),
+            (dict(min_length=11), "min_length=11 exceeds max_length=10"),
+            (dict(suppress_tokens=[end]), f"suppress_tokens must not hold end_idx ({end}): no caption could end"),
+            (dict(suppress_tokens=[V]), f"suppress_tokens: {V} is not a vocabulary id in [0, {V})"),
+            (dict(method="dbs", beam_size=4, group_size=2, min_length=3),
+             "min_length=3 with method='dbs': diverse beam search keeps its histories on the host and is not constrained; use "
+             "'greedy', 'sample', 'gumbel' or 'beam'"),
+            (dict(method="greedy", finish_on_end=True),
+             "finish_on_end=True with method='greedy': finishing belongs to method='beam'"),
+            (dict(method="beam", beam_size=3, nbest=2),
+             "nbest=2 without finish_on_end=True: it ranks finished hypotheses only"),
+            (dict(method="beam", beam_size=3, finish_on_end=True, nbest=4),
+             "nbest must be an integer in [1, beam_size = 3], got 4"),
+            (dict(method="beam", beam_size=3, finish_on_end=True, length_penalty=-1.0),
+             "length_penalty must be a finite number >= 0, got -1.0")):
+        with pytest.raises(ValueError, match=re.escape(text)):
+            ens(feats, lens.copy(), **dict(dict(method="beam", max_length=10), **kw))
+        single = dict(dict(method="beam", max_length=10), **kw)
+        with pytest.raises(ValueError, match=re.escape(text)):            # the single model's text is the same one
+            model._constraints(single, rollout=True)
+            model._finishing(single)
+
+
+def test_search_functions_and_the_models_delegates_agree(model):
+    """acvae_amd.search's validators on the model's values return what the model's one-line delegates return, for the keyword
+    sets of this file."""
+    from acvae_amd import search
+    model.eval()
+    V, end, ml = model.vocab_size, model.end_idx, model.max_length
+    sets = [dict(method=method, max_length=10, **kw) for kw in ON for method in ("greedy", "sample", "gumbel", "beam")]
+    sets += [dict(method=m, **kw) for m in ("greedy", "dbs") for kw in (
+        dict(), dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=()),
+        dict(repetition_penalty=None, no_repeat_ngram_size=None, min_length=None, suppress_tokens=None),
+        dict(repetition_penalty=1, suppress_tokens=[]), dict(repetition_penalty=1.0 + 1e-12))]
+    sets.append(dict(method="beam", max_length=10, repetition_penalty=1.3, no_repeat_ngram_size=np.int64(3), min_length=2,
+                     suppress_tokens=np.array([3, 0])))
+    sets.append(dict(suppress_tokens=torch.tensor([4, 5]), max_length=10))
+    for kw in sets:
+        got = search.constraints(kw, V, end, ml, True, False)
+        assert got == model._constraints(kw, rollout=True) and type(got) is tuple, kw
+        assert search.truncation(kw, True, False) == model._truncation(kw, rollout=True) == (0, 1.0)
+        assert search.finishing(kw, ml) is None and model._finishing(kw) is None
+    for kw in (dict(method="beam", beam_size=4, finish_on_end=True),
+               dict(method="beam", finish_on_end=True, nbest=3, length_penalty=0.5),
+               dict(method="beam", beam_size=2, finish_on_end=np.bool_(True), nbest=np.int64(2), length_penalty=0)):
+        assert search.finishing(kw, ml) == model._finishing(kw) and search.finishing(kw, ml) is not None
+    for kw in (dict(method="sample", top_k=7, top_p=0.25), dict(method="gumbel", top_p=0.9)):
+        assert search.truncation(kw, True, False) == model._truncation(kw, rollout=True) != (0, 1.0)
 
 
 def test_scst_wrappers_drop_the_new_keywords():

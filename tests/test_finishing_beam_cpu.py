@@ -124,7 +124,7 @@ def test_retire_step_by_hand():
 
 
 def test_length_norm_matches_the_package():
-    from acvae_amd.vae_model import length_norm
+    from acvae_amd.search import length_norm
     for lp in (0.0, 0.5, 0.7, 1.0, 2.3):
         a, b = length_norm(70, lp), BF.length_norm(70, lp)
         assert a.dtype == np.float32 and np.array_equal(a.view(np.int32), b.view(np.int32))

@@ -23,7 +23,7 @@ from acvae_amd import _lib
 from acvae_amd import evaluate as EV
 from acvae_amd.encoder import ptr_table
 from acvae_amd.ensemble import Ensemble, ensemble_evaluate
-from acvae_amd.vae_model import _constraint_args
+from acvae_amd.search import _constraint_args, _search_noise
 from test_constrained_decoding_gpu import SEARCH, SML, SV, caption, controls_of, host_loop, search_noise, st
 from test_fullsize_decode_gpu import LP_TOL
 from test_model_gpu import build_model
@@ -389,7 +389,7 @@ def test_with_end_suppressed_hypothesis_0_is_todays_beam_0():
     mem = m._projected_memory(enc)
     lens = torch.as_tensor(enc["audio_embeds_lens"]).to(device="cuda", dtype=torch.long).contiguous()
     S, E = mem.shape[1], mem.shape[2]
-    eps_d = m._search_noise(N, T, beam, E, mem.device, eps)
+    eps_d = _search_noise(N, T, beam, E, mem.device, eps)
     con = (1.0, 0, 0, (END,))
     norm = BF.length_norm(T, 0.0)
     dims = (N, beam, T, S, E, E, E, V)

@@ -79,7 +79,8 @@ import widths_util as W
 from acvae_amd import _lib
 from acvae_amd import text_encoder as TE
 from acvae_amd.ensemble import Ensemble
-from acvae_amd.vae_model import _constraint_args, _DecodeFn, length_norm
+from acvae_amd.search import _constraint_args, length_norm
+from acvae_amd.vae_model import _DecodeFn
 from test_dropout_philox_gpu import make_encoder
 from ws_guard import FILLS, guarded, ws_guards  # noqa: F401  (autouse fixture: every guard intact after each test)
 
