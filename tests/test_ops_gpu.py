@@ -46,6 +46,30 @@ def test_gemm_nt(M, N, K):
     close(c, ref + (A.double() @ B.double().T).float(), 1e-4, 2e-4)
 
 
+@pytest.mark.parametrize("accumulate", [0, 1], ids=["write", "accumulate"])
+@pytest.mark.parametrize("M,N,K", [(4100, 64, 36), (4100, 33, 30), (4100, 130, 64), (4100, 129, 31)],
+                         ids=["BN64_vec", "BN64_scalar", "BN128_vec", "BN128_scalar"])
+def test_gemm_nt_tile_kernel(M, N, K, accumulate):
+    """The four instantiations of the 128-row tile kernel gemm_nt_kernel<BN, VEC4> (test_gemm_nt reaches <128, true> only:
+    every other shape there takes the skinny kernel): M > 4096 rows, N on either side of 64, K % 4 == 0 or not.  C starts
+    as NaN (or random values to accumulate onto) with ldc > N and a sentinel in the gaps; every element within
+    chain_tol(K) of float64 (tests/test_handoff_gpu.py)."""
+    from test_handoff_gpu import assert_every_element
+    assert _lib.lib().acvae_gemm_nt_split_plan(M, N, K, 0, 1) == 0 and _lib.lib().acvae_gemm_nt_split_plan(M, N, K, 0, 0) == 0
+    g = torch.Generator().manual_seed(M + 7 * N + K)
+    A = torch.randn(M, K, generator=g); B = torch.randn(N, K, generator=g); bias = torch.randn(N, generator=g)
+    C0 = torch.randn(M, N, generator=g)
+    ref = A.double() @ B.double().T + bias.double() + (C0.double() if accumulate else 0.0)
+    ldc, SENTINEL = N + 3, -12345.5
+    c = torch.full((M, ldc), SENTINEL, device="cuda")
+    c[:, :N] = dev(C0) if accumulate else float("nan")
+    _lib.call("acvae_gemm_nt", dev(A), K, dev(B), K, dev(bias), c, ldc, M, N, K, accumulate, S())
+    torch.cuda.synchronize()
+    assert bool((c[:, N:] == SENTINEL).all()), "wrote into the gap between rows"
+    assert bool(torch.isfinite(c[:, :N]).all()), "an element was never written"
+    assert_every_element(c[:, :N], ref, K, f"gemm_nt tile kernel M={M} N={N} K={K} accumulate={accumulate}")
+
+
 def test_gemm_nt_strided_rows():
     # decode-step addressing: rows are column t of batch-major [N,Tc,*] buffers
     g = torch.Generator().manual_seed(3)
