@@ -796,7 +796,9 @@ static int decode_fwd_driver(const void* const* params, const float* mem_in, con
     tb.add({P(TP_P_WHH), Hp, sv + L.wt_phh, 4 * Hp, 4 * Hp, Hp});           // [Hp][4Hp]
     tb.add({P(TP_P_ML_W), Hp, sv + L.wt_pml, 2 * E, 2 * E, Hp});            // [Hp][2E]
     tb.add({P(TP_P_ATT_W), 2 * E, sv + L.wt_patt, E, E, 2 * E});            // [2E][E]
-    tb.add({P(TP_MLO_W), H, sv + L.wt_mlo, 2 * E, 2 * E, H});               // [H][2E]
+    // the utterance head's weight is [2E][E]: only the training forward (H == E) has the head, and only its backward reads
+    // wt_mlo.  A recorded rollout may have H != E, where a [2E][H] read would run past the end of the parameter
+    if (train) tb.add({P(TP_MLO_W), H, sv + L.wt_mlo, 2 * E, 2 * E, H});    // [H][2E]
     return acvae_transpose_batch(tb, ts);
   };
   float* lse = sv + L.lse;

@@ -100,6 +100,29 @@ def predictions_payload(key2pred, zh=False):
     return {"predictions": out}
 
 
+def _diversity_check(diversity, model, kwargs, finishing):
+    """The refusals of ``diversity=`` (ValueError, in front of any work) -> the number of captions a clip gets from this
+    call, which is the N of ``diversity.update`` (None without the keyword)."""
+    if diversity is None:
+        return None
+    from .diversity import MAX_LENGTH, Diversity
+    if not isinstance(diversity, Diversity):
+        raise ValueError(f"diversity must be an acvae_amd.diversity.Diversity, got {type(diversity).__name__}")
+    beam, method = kwargs["beam_size"], kwargs["method"]
+    if finishing:                                  # the n-best list of one search per clip
+        per_clip = kwargs.get("nbest", 1)
+    elif method == "dbs":                          # the filled rows: bdash * group_size beams, or one per group
+        groups = kwargs.get("group_size", 5)
+        per_clip = (beam // groups) * groups if kwargs.get("group_nbest", True) else groups
+    else:                                          # beam_size rollouts (or searches) per clip over one encoder pass
+        per_clip = beam
+    per_clip = diversity.check(per_clip, "evaluate(diversity=)")
+    max_length = kwargs.get("max_length", getattr(model, "max_length", None))
+    if max_length is not None and max_length > MAX_LENGTH:
+        raise ValueError(f"evaluate(diversity=): max_length={max_length}; the kernel takes rows of at most {MAX_LENGTH} tokens")
+    return per_clip
+
+
 def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size=1, device=None, frontend=None,
              **kwargs):
     """Decode an evaluation set and (optionally) write the prediction file.
@@ -123,7 +146,12 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
     rollout that agrees most with the clip's other rollouts under CIDEr-D, chosen on the device
     (``Hybrid_VAEModel._rerank``); the file then has the one-caption-per-clip form.  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are ``(audio_id, 1-D waveform)``, fp32
     or int16 PCM (``acvae_amd.frontend.read_wav``); the log-mel features are formed on the device in front of either
-    forward path.  Returns the payload dict."""
+    forward path.  ``diversity`` (an ``acvae_amd.diversity.Diversity``, default None = nothing changes): wherever a clip gets
+    2 .. 16 captions (``beam_size=N`` rollouts, with ``rerank`` its candidates; the filled rows of ``method="dbs"``; the
+    n-best list of a finishing search), their n-gram statistics are counted on the device before the rows are downloaded,
+    one launch per batch and no copy; read ``diversity.result()`` afterwards (Div1, Div2, gDiv1, mBLeu_1..4).  One caption
+    per clip or more than 16, or ``max_length > 64``: ValueError in front of any work.  The payload and the file are the
+    same with and without it.  Returns the payload dict."""
     refuse_augmented(frontend, "evaluate")
     kwargs.setdefault("method", "greedy")
     kwargs.setdefault("beam_size", 1)
@@ -140,8 +168,20 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
         if not hasattr(model, "_finishing"):
             raise ValueError(f"finish_on_end: {type(model).__name__} has no finishing beam search")
         model._finishing(kwargs)
+    diversity = kwargs.pop("diversity", None)      # (None: nothing else changes, every call runs what it ran before)
+    per_clip = _diversity_check(diversity, model, kwargs, finishing)
     key2pred = {}
     pending = []
+
+    def measure(output):
+        """The clip's captions as they stand on the device, clip-major, to ``diversity.update``: nothing comes back."""
+        if finishing:
+            rows = output["nbest_seqs"]
+        elif kwargs["method"] == "dbs":            # (the filled rows only, not the end_idx filler of search._dbs_rows)
+            rows = output["seqs"][:, :per_clip]
+        else:
+            rows = output["candidates"] if "candidates" in output else output["seqs"]
+        diversity.update(rows.reshape(-1, rows.shape[-1]), per_clip)
 
     def flush():
         if not pending:
@@ -155,6 +195,8 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
                 output = forward_batch_shared_encoder(model, batch, device=device, frontend=frontend, **kwargs)
             else:
                 output = forward_batch(model, batch, "eval", device=device, frontend=frontend, **kwargs)
+            if diversity is not None:
+                measure(output)
         rows = output["nbest_seqs"] if finishing and output["nbest_seqs"].shape[1] > 1 else output["seqs"]
         collect_predictions(batch[0], rows.cpu().numpy(), vocabulary, zh, key2pred)
 

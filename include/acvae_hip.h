@@ -324,6 +324,28 @@ int acvae_ciderd_reward(const double* score, int n, int sample_n, float* reward,
 int acvae_consensus_scores(const int64_t* seqs, int64_t ld, int n, int sample_n, int max_length, int start_idx, int end_idx,
                            const uint64_t* idf_keys, const double* idf_vals, int n_idf, double log_d,
                            const double* len_factor, int n_len, double* score, int64_t* best, int64_t* picked, void* stream);
+/* Diversity of a clip's N captions: the integer statistics behind Div-n, mBLEU and the vocabulary size (csrc/diversity.hip,
+ * acvae_amd/diversity.py evaluates the formulas on the host).  Token rows i64 seqs [n, max_length] (row stride ld), clip-major
+ * as above, cleaned as acvae_consensus_scores cleans them (start_idx skipped wherever it stands, cut at the first end_idx;
+ * what stands behind the first end_idx is never interpreted).  A kept id outside [0, V) is one shared out-of-range word.
+ * With h_i the cleaned candidate i, L_i its length and c_i(g) the count of n-gram g in it (orders k = 1..4), the record of
+ * clip b is ACVAE_DIVERSITY_HEAD + ACVAE_DIVERSITY_PER_CANDIDATE * sample_n int32 at record[b * that]:
+ *   [0]            words = sum_i L_i
+ *   [1 + k']       distinct_k = the number of different order-k n-grams over all candidates, k' = k - 1 = 0..3
+ *   [5 + 6 i]      testlen = L_i
+ *   [5 + 6 i + 1]  reflen = the L_j, j != i, that minimises (|L_j - L_i|, L_j) lexicographically (BLEU's "closest")
+ *   [5 + 6 i + 2 + k']  correct_k = sum over the different order-k n-grams g of h_i of min(c_i(g), max_{j != i} c_j(g))
+ * (guess_k = max(0, L_i - k + 1) follows from testlen.)  seen [V + 1] int32: the plain value 1 is stored at every kept word,
+ * slot V for the out-of-range word; the kernel never clears it, so it accumulates over launches (the caller zeroes it once).
+ * Integers only: no atomics, no workspace, no scratch; identical racing stores into `seen` are the only sharing between
+ * workgroups, so the result does not depend on launch order.  One launch: one workgroup per clip, one wavefront per
+ * candidate, static LDS.  Every index is formed from the launch geometry or clamped.  A NULL seqs / record / seen, sample_n
+ * outside [2, ACVAE_CONSENSUS_MAX_SAMPLES], n not a positive multiple of sample_n, max_length outside [1, 64], ld < max_length
+ * or V outside [1, 65534] -> ACVAE_EINVAL before any launch. */
+#define ACVAE_DIVERSITY_HEAD 5
+#define ACVAE_DIVERSITY_PER_CANDIDATE 6
+int acvae_diversity_stats(const int64_t* seqs, int64_t ld, int n, int sample_n, int max_length, int start_idx, int end_idx,
+                          int V, int* record, int* seen, void* stream);
 /* mean((a-b)^2) over n elements and its backward (runner :317, nn.MSELoss). */
 int acvae_mse_fwd(const float* a, const float* b, float* partials, float* out_scalar, int64_t n, void* stream);
 int acvae_mse_bwd(const float* a, const float* b, const float* grad_out, float* da, float* db, int64_t n, void* stream);
