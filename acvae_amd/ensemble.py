@@ -26,7 +26,7 @@ import torch.nn as nn
 
 from . import _lib, search
 from .batch import collate_fn
-from .evaluate import collect_predictions, predictions_payload
+from .evaluate import accuracy_check, accuracy_rows, captions_per_clip, collect_predictions, predictions_payload
 from .frontend import refuse_augmented
 from .seq_train_model import ScstWrapper
 from .vae_model import Hybrid_VAEModel
@@ -141,8 +141,21 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
     ``evaluate()`` or, with ``dcase_format``, the
     reference's two-column CSV (``file_name``, ``caption_predicted``).  ``frontend`` (``acvae_amd.frontend.LogMel``): the items are
     ``(audio_id, 1-D waveform)`` and the log-mel features are formed on the device, once for all members.  Returns the payload
-    dict; scoring stays outside."""
+    dict.  ``accuracy`` (an ``acvae_amd.accuracy.Accuracy``, default None = nothing changes): the rows the file shows (one
+    caption per clip; the filled rows of ``method="dbs"``; the n-best list of a finishing search) are handed to it with the
+    batch's keys before they are downloaded, as ``evaluate(accuracy=)`` does, with the same refusals in front of any work;
+    read ``accuracy.result()`` afterwards.  METEOR and SPICE stay outside."""
     refuse_augmented(frontend, "ensemble_evaluate")
+    accuracy = kwargs.pop("accuracy", None)
+    shown = None
+    if accuracy is not None:                       # one search per clip: the captions it returns, by forward's defaults
+        counts = dict(method=kwargs.get("method", "greedy"), beam_size=kwargs.get("beam_size", 5),
+                      group_size=kwargs.get("group_size", 5), group_nbest=kwargs.get("group_nbest", True))
+        if kwargs.get("finish_on_end"):
+            shown = kwargs.get("nbest") or 1
+        else:
+            shown = captions_per_clip(counts, False) if counts["method"] == "dbs" else 1
+        shown = accuracy_check(accuracy, shown, kwargs.get("max_length", 20), zh, "ensemble_evaluate")
     ens = models_or_ensemble if isinstance(models_or_ensemble, Ensemble) else Ensemble(models_or_ensemble)
     device = next(ens.parameters()).device
     collate = collate_fn([1, ])
@@ -158,6 +171,8 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
             batch[1], batch[-1] = frontend(batch[1], batch[-1], device=device)
         output = ens(batch[1].to(device), batch[-1], **kwargs)
         rows = output["nbest_seqs"] if "nbest_seqs" in output and output["nbest_seqs"].shape[1] > 1 else output["seqs"]
+        if accuracy is not None:                   # the rows the file shows, as they stand on the device
+            accuracy.update(batch[0], accuracy_rows(rows, shown), shown)
         collect_predictions(batch[0], rows.cpu().numpy(), vocabulary, zh, key2pred)
 
     for item in items:

@@ -7,7 +7,8 @@ sentences with the training vocabulary and write the prediction file the referen
     {"predictions": [{"filename": id, "caption": str, "tokens": str}, ...]}                       one caption per clip
     {"predictions": [{"filename": id, "captions": [{"caption", "cap_id", "tokens"}, ...]}, ...]}  N captions per clip
 
-Scoring itself (pycocoevalcap BLEU/ROUGE/CIDEr/METEOR/SPICE, base_runner.py:295-320) is outside the path.
+Of the scoring (pycocoevalcap BLEU/ROUGE/CIDEr/METEOR/SPICE, base_runner.py:295-320) BLEU, ROUGE-L and CIDEr are scored on
+the device with ``accuracy=`` (acvae_amd/accuracy.py); METEOR and SPICE need Java and stay outside.
 """
 import io
 import json
@@ -100,6 +101,17 @@ def predictions_payload(key2pred, zh=False):
     return {"predictions": out}
 
 
+def captions_per_clip(kwargs, finishing):
+    """The number of caption rows a clip gets from a decode with these keywords (``rerank`` apart)."""
+    beam, method = kwargs["beam_size"], kwargs["method"]
+    if finishing:                                  # the n-best list of one search per clip
+        return kwargs.get("nbest", 1)
+    if method == "dbs":                            # the filled rows: bdash * group_size beams, or one per group
+        groups = kwargs.get("group_size", 5)
+        return (beam // groups) * groups if kwargs.get("group_nbest", True) else groups
+    return beam                                    # beam_size rollouts (or searches) per clip over one encoder pass
+
+
 def _diversity_check(diversity, model, kwargs, finishing):
     """The refusals of ``diversity=`` (ValueError, in front of any work) -> the number of captions a clip gets from this
     call, which is the N of ``diversity.update`` (None without the keyword)."""
@@ -108,19 +120,39 @@ def _diversity_check(diversity, model, kwargs, finishing):
     from .diversity import MAX_LENGTH, Diversity
     if not isinstance(diversity, Diversity):
         raise ValueError(f"diversity must be an acvae_amd.diversity.Diversity, got {type(diversity).__name__}")
-    beam, method = kwargs["beam_size"], kwargs["method"]
-    if finishing:                                  # the n-best list of one search per clip
-        per_clip = kwargs.get("nbest", 1)
-    elif method == "dbs":                          # the filled rows: bdash * group_size beams, or one per group
-        groups = kwargs.get("group_size", 5)
-        per_clip = (beam // groups) * groups if kwargs.get("group_nbest", True) else groups
-    else:                                          # beam_size rollouts (or searches) per clip over one encoder pass
-        per_clip = beam
-    per_clip = diversity.check(per_clip, "evaluate(diversity=)")
+    per_clip = diversity.check(captions_per_clip(kwargs, finishing), "evaluate(diversity=)")
     max_length = kwargs.get("max_length", getattr(model, "max_length", None))
     if max_length is not None and max_length > MAX_LENGTH:
         raise ValueError(f"evaluate(diversity=): max_length={max_length}; the kernel takes rows of at most {MAX_LENGTH} tokens")
     return per_clip
+
+
+def accuracy_check(accuracy, per_clip, max_length, zh, who="evaluate"):
+    """The refusals of ``accuracy=`` (ValueError, in front of any work): ``per_clip`` captions a clip gets in the file, rows
+    of ``max_length`` tokens -> the N of ``accuracy.update`` (None without the keyword)."""
+    if accuracy is None:
+        return None
+    from .accuracy import MAX_LENGTH, Accuracy
+    if not isinstance(accuracy, Accuracy):
+        raise ValueError(f"accuracy must be an acvae_amd.accuracy.Accuracy, got {type(accuracy).__name__}")
+    if zh:
+        raise ValueError(f"{who}(accuracy=): zh=True is not scored: the references are split at whitespace")
+    per_clip = accuracy.check(per_clip, f"{who}(accuracy=)")
+    if max_length is not None and max_length > MAX_LENGTH:
+        raise ValueError(f"{who}(accuracy=): max_length={max_length}; the kernel takes rows of at most {MAX_LENGTH} tokens")
+    if max_length is not None and accuracy.width is not None and max_length != accuracy.width:
+        raise ValueError(f"{who}(accuracy=): max_length={max_length} after updates with rows of {accuracy.width} tokens: all "
+                         "updates of one object share one row width (reset() starts over)")
+    return per_clip
+
+
+def accuracy_rows(rows, per_clip):
+    """The rows of a batch that the file shows, on the device, as ``accuracy.update`` takes them: [B * per_clip, T].  A
+    diverse beam search's rows beyond ``per_clip`` are the end_idx filler of ``search._dbs_rows`` and stay out (the one case
+    in which the rows are copied: everywhere else this is a view)."""
+    if rows.dim() == 3:
+        rows = rows[:, :per_clip]
+    return rows.reshape(-1, rows.shape[-1])
 
 
 def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size=1, device=None, frontend=None,
@@ -151,7 +183,13 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
     n-best list of a finishing search), their n-gram statistics are counted on the device before the rows are downloaded,
     one launch per batch and no copy; read ``diversity.result()`` afterwards (Div1, Div2, gDiv1, mBLeu_1..4).  One caption
     per clip or more than 16, or ``max_length > 64``: ValueError in front of any work.  The payload and the file are the
-    same with and without it.  Returns the payload dict."""
+    same with and without it.  ``accuracy`` (an ``acvae_amd.accuracy.Accuracy``, default None = nothing changes): the rows the
+    file shows (one caption per clip, with ``rerank`` the picked one; the ``beam_size=N`` rollouts; the filled rows of
+    ``method="dbs"``; the n-best list of a finishing search) are handed to it with the batch's keys before they are
+    downloaded, no launch and no copy; read ``accuracy.result()`` afterwards (Bleu_1..4, ROUGE_L, CIDEr against the clips'
+    references).  A wrong type, more than 16 captions per clip, ``max_length > 64``, another N or row width than the
+    object's earlier updates, or ``zh=True``: ValueError in front of any work.  ``accuracy`` and ``diversity`` work
+    together.  Returns the payload dict."""
     refuse_augmented(frontend, "evaluate")
     kwargs.setdefault("method", "greedy")
     kwargs.setdefault("beam_size", 1)
@@ -170,6 +208,12 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
         model._finishing(kwargs)
     diversity = kwargs.pop("diversity", None)      # (None: nothing else changes, every call runs what it ran before)
     per_clip = _diversity_check(diversity, model, kwargs, finishing)
+    accuracy = kwargs.pop("accuracy", None)        # (likewise)
+    shown = None
+    if accuracy is not None:                       # the captions the file shows per clip: with rerank the picked one
+        shown = 1 if "rerank" in kwargs else captions_per_clip(kwargs, finishing)
+        shown = accuracy_check(accuracy, 1 if shown is None else shown,
+                               kwargs.get("max_length", getattr(model, "max_length", None)), zh)
     key2pred = {}
     pending = []
 
@@ -188,6 +232,7 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
             return
         batch = collate(list(pending))
         pending.clear()
+        clip_keys = list(batch[0])                 # (the N-samples route replaces batch[0] by the replicated keys)
         with torch.no_grad():
             if finishing:                          # one search per clip: beam_size is its width, not a number of replicas
                 output = forward_batch(model, batch, "validation", device=device, frontend=frontend, **kwargs)
@@ -198,6 +243,8 @@ def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size
             if diversity is not None:
                 measure(output)
         rows = output["nbest_seqs"] if finishing and output["nbest_seqs"].shape[1] > 1 else output["seqs"]
+        if accuracy is not None:                   # the rows the file shows, as they stand on the device
+            accuracy.update(clip_keys, accuracy_rows(rows, shown), shown)
         collect_predictions(batch[0], rows.cpu().numpy(), vocabulary, zh, key2pred)
 
     for item in items:

@@ -346,6 +346,35 @@ int acvae_consensus_scores(const int64_t* seqs, int64_t ld, int n, int sample_n,
 #define ACVAE_DIVERSITY_PER_CANDIDATE 6
 int acvae_diversity_stats(const int64_t* seqs, int64_t ld, int n, int sample_n, int max_length, int start_idx, int end_idx,
                           int V, int* record, int* seen, void* stream);
+/* Captions against their references: the integer statistics behind BLEU-1..4 and ROUGE-L (csrc/accuracy.hip;
+ * acvae_amd/accuracy.py evaluates the formulas on the host).  Token rows i64 seqs [n, max_length] (row stride ld), clip-major:
+ * row r belongs to clip r / sample_n, 1 <= sample_n <= ACVAE_CONSENSUS_MAX_SAMPLES.  A row is cleaned as
+ * acvae_diversity_stats cleans it (start_idx skipped wherever it stands, cut at the first end_idx; what stands behind the
+ * first end_idx is never interpreted).  The references: ref_words [n_words] int32, the words of all references one after the
+ * other, a vocabulary id or, for a word outside the vocabulary, any value outside [0, V) (the sentinel; -1 by convention);
+ * ref_off [n_refs + 1]: the words of reference j are ref_words[ref_off[j] .. ref_off[j + 1]); clip_ref [n_clips + 1]: the
+ * references of clip b are clip_ref[b] .. clip_ref[b + 1] - 1.  A reference has at least one word and may have any number.
+ * Matching: a candidate word outside [0, V) matches no reference word, a reference word outside [0, V) matches no candidate
+ * word, and two n-grams match only if every word matches.  With h the cleaned row, L its length, R its clip's references
+ * and c_s(g) the count of n-gram g in sentence s, the record of row r is ACVAE_ACCURACY_RECORD int32 at record[9 r]:
+ *   [0]        testlen = L
+ *   [1]        reflen = the len(r), r in R, that minimises (|len(r) - L|, len(r))  ("closest"; ties go to the shorter)
+ *   [2 + k']   correct_k = sum over the distinct order-k n-grams g of h of min(c_h(g), max_{r in R} c_r(g)), k' = k - 1 = 0..3
+ *   [6]        lcs_p = max_{r in R} LCS(h, r), the length of the longest common subsequence
+ *   [7], [8]   lcs_r, len_r = the pair (LCS(h, r), len(r)) with the largest quotient, compared by integer
+ *              cross-multiplication; ties go to the earlier reference
+ * A clip without references gets reflen = lcs_p = lcs_r = len_r = 0 and correct_k = 0.
+ * Integers only: no atomics, no workspace, no scratch, two runs are bit-equal.  One launch, one wavefront per row; the
+ * references are streamed 64 words per step, so their number and their lengths are not bounded by the kernel.  Every index
+ * is formed from the launch geometry or clamped to its array: offsets that are not monotone or not in range give empty
+ * references, never a read outside ref_words [n_words], ref_off [n_refs + 1] or clip_ref [n_clips + 1].  A NULL pointer,
+ * sample_n outside [1, ACVAE_CONSENSUS_MAX_SAMPLES], n not a positive multiple of sample_n, max_length outside [1, 64],
+ * ld < max_length, V outside [1, 65534], n_clips != n / sample_n, a negative n_words or n_refs, or n_words above 2^30 (the
+ * kernel's word indices are int32) -> ACVAE_EINVAL before any launch. */
+#define ACVAE_ACCURACY_RECORD 9
+int acvae_accuracy_stats(const int64_t* seqs, int64_t ld, int n, int sample_n, int max_length, int start_idx, int end_idx,
+                         int V, const int* ref_words, int n_words, const int* ref_off, int n_refs, const int* clip_ref,
+                         int n_clips, int* record, void* stream);
 /* mean((a-b)^2) over n elements and its backward (runner :317, nn.MSELoss). */
 int acvae_mse_fwd(const float* a, const float* b, float* partials, float* out_scalar, int64_t n, void* stream);
 int acvae_mse_bwd(const float* a, const float* b, const float* grad_out, float* da, float* db, int64_t n, void* stream);
