@@ -254,36 +254,68 @@ class _PinnedRing:
     first copy out of it wait for the GPU to drain, and torch's caching host allocator needs a fresh block whenever
     the host runs ahead of the previous copies, so the per-step host->device copies stage through memory that is
     pinned once.  A slot is reused only after the copy that last read it has passed (event), which blocks only when
-    the host is a whole ring ahead of the GPU."""
+    the host is a whole ring ahead of the GPU.
+
+    Several host threads may stage through one ring (there is one per device, not per thread).  ``head`` and ``live`` are
+    read and written under ``lock`` only.  A slot enters ``live`` the moment it is reserved, without an event yet, so that
+    it is never invisible between ``_reserve`` and ``_commit``; whoever is handed an overlapping slot first waits for that
+    commit and then for the copy.  All waiting is done with the lock released: a waiter never keeps another thread from
+    reserving or committing, and a wait is only ever for an entry reserved earlier, so waits cannot form a cycle."""
 
     def __init__(self, nbytes=32 << 20):
         self.buf = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
         self.head = 0
-        self.live = []           # (start, end, event) in allocation order
+        self.live = []           # [start, end, event or None (reserved, not sent yet), threading.Event: sent] in allocation order
+        self.lock = threading.Lock()
 
     def _reserve(self, n):
         span = (n + 255) & ~255
-        if self.head + span > self.buf.numel():
-            self.head = 0
-        s, e = self.head, self.head + span
-        self.head = e
-        # every live entry that overlaps the slot must have been copied out (not only the oldest one: after a wrap an
-        # old tail entry the new lap never reaches can sit in front of newer ones that do overlap); entries whose copy
-        # has already passed are dropped on the way so the list stays short
-        keep = []
-        for (ls, le, ev) in self.live:
-            if ls < e and le > s:
-                ev.synchronize()
-            elif not ev.query():
-                keep.append((ls, le, ev))
-        self.live = keep
+        wait = []
+        with self.lock:
+            if self.head + span > self.buf.numel():
+                self.head = 0
+            s, e = self.head, self.head + span
+            self.head = e
+            # every live entry that overlaps the slot must have been copied out (not only the oldest one: after a wrap an
+            # old tail entry the new lap never reaches can sit in front of newer ones that do overlap); entries whose copy
+            # has already passed are dropped on the way so the list stays short.  An overlapped entry stays listed until
+            # it has been waited for: it may reach beyond this slot, into one that another thread is handed meanwhile.
+            keep = []
+            for ent in self.live:
+                if ent[0] < e and ent[1] > s:
+                    wait.append(ent)
+                    keep.append(ent)
+                elif ent[2] is None or not ent[2].query():
+                    keep.append(ent)
+            keep.append([s, e, None, threading.Event()])
+            self.live[:] = keep
+        for ent in wait:
+            ent[3].wait()                        # reserved by another thread and not sent yet: until it is (or is given up)
+            if ent[2] is not None:
+                ent[2].synchronize()
+        if wait:
+            with self.lock:
+                self.live[:] = [x for x in self.live if not any(x is w for w in wait)]
         return s, e
+
+    def _commit(self, s, e, ev):
+        """The slot [s, e) handed out by ``_reserve`` has been sent and ``ev`` is recorded behind its copy; ``ev=None``: it
+        was given up (the producer raised), nothing reads it."""
+        with self.lock:
+            for i, ent in enumerate(self.live):
+                if ent[0] == s and ent[1] == e and ent[2] is None and not ent[3].is_set():
+                    if ev is None:
+                        del self.live[i]
+                    ent[2] = ev
+                    ent[3].set()
+                    return
+        raise RuntimeError(f"pinned ring: no reserved slot [{s}, {e}) to commit")
 
     def _send(self, slot, s, e, dev):
         out = slot.to(dev, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        self.live.append((s, e, ev))
+        self._commit(s, e, ev)
         return out
 
     def stage(self, t, dev):
@@ -291,9 +323,13 @@ class _PinnedRing:
         if n == 0 or n > self.buf.numel() // 4:
             return t.pin_memory().to(dev, non_blocking=True)
         s, e = self._reserve(n)
-        slot = self.buf[s:s + n].view(t.dtype).view(t.shape)
-        np.copyto(slot.numpy(), t.numpy())       # plain memcpy: torch's copy_ fans a 1 MB copy out over the intra-op pool
-        return self._send(slot, s, e, dev)
+        try:
+            slot = self.buf[s:s + n].view(t.dtype).view(t.shape)
+            np.copyto(slot.numpy(), t.numpy())   # plain memcpy: torch's copy_ fans a 1 MB copy out over the intra-op pool
+            return self._send(slot, s, e, dev)
+        except BaseException:
+            self._give_up(s, e)
+            raise
 
     def fill(self, shape, dtype, dev, fill):
         """Reserve a slot, let ``fill(slot_tensor)`` produce the data in place (e.g. torch.randn(..., out=)), send it."""
@@ -303,12 +339,36 @@ class _PinnedRing:
             fill(t)
             return t.pin_memory().to(dev, non_blocking=True)
         s, e = self._reserve(n)
-        slot = self.buf[s:s + n].view(dtype).view(shape)
-        fill(slot)
-        return self._send(slot, s, e, dev)
+        try:
+            slot = self.buf[s:s + n].view(dtype).view(shape)
+            fill(slot)
+            return self._send(slot, s, e, dev)
+        except BaseException:
+            self._give_up(s, e)
+            raise
+
+    def _give_up(self, s, e):
+        """A reserved slot whose producer raised: unless it was sent all the same, nobody must wait for it for ever."""
+        try:
+            self._commit(s, e, None)
+        except RuntimeError:
+            pass                                 # (committed before the exception: the entry has its event)
 
 
 _RINGS = {}
+_RINGS_LOCK = threading.Lock()
+
+
+def _ring(dev):
+    """The device's ring, made on first use (once, whichever thread comes first)."""
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    ring = _RINGS.get(key)
+    if ring is None:
+        with _RINGS_LOCK:
+            ring = _RINGS.get(key)
+            if ring is None:
+                ring = _RINGS[key] = _PinnedRing()
+    return ring
 
 
 def h2d(t, dev, dtype=None):
@@ -322,11 +382,7 @@ def h2d(t, dev, dtype=None):
     dev = torch.device(dev)
     if dev.type != "cuda":
         raise RuntimeError("acvae_amd: the HIP path needs a GPU device (no CPU fallback)")
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    ring = _RINGS.get(key)
-    if ring is None:
-        ring = _RINGS[key] = _PinnedRing()
-    return ring.stage(t.contiguous(), dev)
+    return _ring(dev).stage(t.contiguous(), dev)
 
 
 def h2d_fill(shape, dtype, dev, fill):
@@ -334,8 +390,4 @@ def h2d_fill(shape, dtype, dev, fill):
     dev = torch.device(dev)
     if dev.type != "cuda":
         raise RuntimeError("acvae_amd: the HIP path needs a GPU device (no CPU fallback)")
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    ring = _RINGS.get(key)
-    if ring is None:
-        ring = _RINGS[key] = _PinnedRing()
-    return ring.fill(tuple(shape), dtype, dev, fill)
+    return _ring(dev).fill(tuple(shape), dtype, dev, fill)

@@ -109,9 +109,10 @@ class RNNDecoder(BaseDecoder):
             return we.weight
         owner = self._owner() if getattr(self, "_owner", None) is not None else None
         token = getattr(owner, "_forward_token", None)       # refreshed at every model forward (and reused by its backward)
-        # valid for ONE model forward and only while the three parameters are what they were when it was built (an
-        # optimiser step, load_state_dict or an in-place edit bumps _version); callers outside a model forward (the
-        # step-wise decoder / prior API) have no token and always rebuild
+        # valid for ONE model forward and only while the three parameters are what they were when it was built
+        # (load_state_dict or an in-place edit bumps _version; the fused optimiser step does NOT - it writes the flat buffer
+        # through raw pointers - so TrainStep drops the cache after every update, Hybrid_VAEModel.drop_step_caches); callers
+        # outside a model forward (the step-wise decoder / prior API) have no token and always rebuild
         # (the grad mode is NOT part of the key: the backward of that forward runs with grad mode off and must find the
         # forward's table, whose grad_fn routes the table's gradient to the three parameters)
         key = (token, we[0].weight._version, we[1].weight._version, we[1].bias._version, we[0].weight.data_ptr(),

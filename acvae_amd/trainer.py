@@ -424,6 +424,9 @@ class TrainStep:
             self.optimizer.step()                  # the instance attribute: an LR scheduler's step tracking sees the call
         finally:
             self._pending = None
+            # the fused update writes the flat parameter buffer through raw pointers: no _version moves, so what the model
+            # caches per weight (attention projections of the step API, projected embedding table) is dropped by hand
+            self.model.drop_step_caches()
         parts["loss"] = loss.detach()
         parts["grad_norm"] = self.total_norm
         # DDP's broadcast_buffers: rank 0's BatchNorm running statistics reach the other ranks before the next forward

@@ -233,6 +233,8 @@ class Hybrid_VAEModel(CaptionModel):
         self.staged = None         # device copies of caps / cap_lens-1 made by the last training forward
         self.noise = None          # optional replay: dict(eps_q=[N,Tc,E], eps_p=[Tc,N,E], q_keep=[Lq-1,N,Tc,2Hq] (a stacked
         #                            posterior's dropout masks, text_encoder.posterior_keep_masks)) consumed by the next forward
+        #                            that draws: a call refused for its arguments before anything is drawn (ValueError /
+        #                            TypeError in front of the encoder, e.g. a bad clip_index) leaves it pending for the next
         self._grad_views = None    # {param: flat-gradient view}, set by the train-step harness
         self._grad_ready_cb = None # called with "text" once every text-side gradient has been written
 
@@ -262,8 +264,18 @@ class Hybrid_VAEModel(CaptionModel):
 
     def _encproj(self, which, enc_mem):
         """Hoisted encoder half of an attention (0: decoder.attn, 1: pnet.word_attn) for single-step calls; cached per
-        memory tensor so a beam-search loop projects the clip once instead of once per step."""
-        key = (which, enc_mem.data_ptr(), tuple(enc_mem.shape), enc_mem._version)
+        memory tensor so a beam-search loop projects the clip once instead of once per step.
+
+        The entry is that of ``enc_mem`` AND of the ``h2attn`` weights it was computed from: the key holds the memory's and
+        the weights' address and ``_version`` (``load_state_dict``, an in-place edit and a re-seated ``.data`` all show
+        there), and whoever changes parameters behind torch's back - the fused optimiser writes the flat buffer through raw
+        pointers - calls ``drop_step_caches()``; ``TrainStep`` does after every update.  What nothing here can see is a
+        change of ``enc_mem``'s CONTENTS that leaves its ``_version`` alone, i.e. a library call that writes into a tensor
+        which then comes back as ``enc_mem``: such a caller calls ``drop_step_caches()`` itself."""
+        attn = self.decoder.attn if which == 0 else self.pnet.word_attn
+        w, b = attn.h2attn.weight, attn.h2attn.bias
+        key = (which, enc_mem.data_ptr(), tuple(enc_mem.shape), enc_mem._version,
+               w.data_ptr(), w._version, b.data_ptr(), b._version)
         hit = self._encproj_cache.get(which)
         if hit is not None and hit[0] == key:
             return hit[1]
@@ -274,6 +286,13 @@ class Hybrid_VAEModel(CaptionModel):
                   _lib.current_stream())
         self._encproj_cache[which] = (key, out, enc_mem)      # keep enc_mem alive so its address cannot be reused
         return out
+
+    def drop_step_caches(self):
+        """Forget what the step API and the decoder keep between calls (the hoisted attention projections of ``_encproj``,
+        the projected embedding table): for whoever changed parameters or an encoder memory's contents in a way torch's
+        version counters do not show."""
+        self._encproj_cache.clear()
+        self.decoder._table_cache = None
 
     def _projected_memory(self, encoded):
         """The contiguous encoder memory [N, S, E] after the optional ``ln`` projection (vae_model.py:754-755)."""
