@@ -50,8 +50,9 @@ struct PbParams {
   // written by the launch (dctx: [N, Tc, E], one slot per step)
   float *dgi, *dgh, *dqd, *dctx, *dencproj, *dmem, *dvpart, *dgates, *dml_all, *dhp;
   // clips of more than 64 frames: the attention role runs as rc_splits workgroups per clip (set by the launcher); their shares
-  // of d qd [rc_splits][N][Tc][A] (PbPlan::dqd_part_floats; RA adds them and writes the sum to dqd) and the forward's rnn_d
-  // ([N][Tc][3E]: ctx = columns E..2E)
+  // of d qd [rc_splits][N][Tc][A] (PbPlan::dqd_part_floats; RA adds them and writes the sum to dqd for the steps it reads,
+  // 1 .. Tc - 1.  Step 0's rows of dqd are the CALLER's: they meet h_{-1} = 0 only, so acvae_decode_bwd zeroes dqd at its
+  // entry instead of the launch summing shares nobody needs) and the forward's rnn_d ([N][Tc][3E]: ctx = columns E..2E)
   float* dqd_part;
   const float* ctx;
   int rc_splits;

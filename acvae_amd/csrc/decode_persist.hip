@@ -813,6 +813,8 @@ __device__ void role_ra(const PbParams& p, int slice, PbSmem& sm) {
       if (!pd_wait(p.cnt + PB_C_RC * p.Tc + (t + 1), (unsigned)(p.N * p.rc_splits), p.abort_word, p.spin_limit, &sm.flag)) return;
       const long qidx = (long)arow * p.Tc * A + (long)(t + 1) * A + 4 * lh;
       if (p.rc_splits == 1) pb_gemm1(acc, p.dqd, qidx, b_att, A, wave);   // A <= 512 (decode_persist_bwd_ok)
+      // (slice 0 keeps the share sums as dqd's rows of step t + 1; step 0's rows are never read here and never written:
+      // the caller owns them, PbParams::dqd_part)
       else pb_gemm1_shares(acc, p.dqd_part, qidx, (long)p.N * p.Tc * A, p.rc_splits, b_att, A, wave,
                            (slice == 0 && li < p.N) ? p.dqd + qidx : nullptr);
       pb_stash(sm.red, acc, wave, li, lh);

@@ -1020,6 +1020,9 @@ extern "C" int acvae_decode_bwd(const void* const* params, void* const* grads, c
     if (persist_bwd) {
       zb.add(sc + L.pd_cnt_b, pb_plan.counter_words);
       zb.add(sc + L.dmem_p, (long)N * S * E);
+      // split attention role: the launch writes d qd's share sums for the steps it reads (1 .. Tc - 1) only.  Step 0's rows
+      // belong to this entry: dec_tn multiplies them by h_{-1} = 0, which is 0 only while they are finite.
+      if (pb_plan.rc_splits > 1) zb.add(sc + L.dqd, (long)R * A);
       flags |= ACVAE_FLAG_INT_CNT_ZEROED;
     }
     // the two embedding-table gradients start from zero (embed_scatter adds rows): here instead of two 10 MB memsets in the

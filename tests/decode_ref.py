@@ -32,7 +32,9 @@ FWD = ("logits", "outputs", "attn_w", "p_means", "p_logs", "p_z", "p_means_utt",
 FLOOR, FACTOR, POOL_MARGIN = 1e-5, 8.0, 1e-4
 START, END = 1, 2
 MUTANTS = ("no_max_pool", "mean_over_Tc", "embed_once", "mem_one_past", "no_last_dh", "no_last_z", "dis_z_to_q",
-           "no_keep_scale", "no_ln_bias")
+           "no_keep_scale", "no_ln_bias", "dqd_share0_only", "softmax_sum_per_share")
+SPLIT_MUTANTS = MUTANTS[-2:]        # the two mistakes of an attention backward split into shares of SHARE frames
+SHARE = 64                          # frames per attention workgroup of the persistent BPTT (csrc/persist_plan.h PB_RC_FRAMES)
 
 
 # ---------------------------------------------------------------------------------------------------------- the loop
@@ -56,6 +58,43 @@ class _EmbedOnce(torch.autograd.Function):
         g = d.new_zeros(ctx.shape)
         g[w] = d
         return g, None
+
+
+class _SoftmaxPerShare(torch.autograd.Function):
+    """MUTANT softmax_sum_per_share: the softmax backward ds = w (dw - sum_s w dw) with the sum taken over the 64 frames of
+    the element's own share instead of over the clip (the shares of a split attention backward do not talk to each other:
+    the whole sum has to come from elsewhere)."""
+
+    @staticmethod
+    def forward(ctx, score):
+        w = torch.softmax(score, dim=-1)
+        ctx.save_for_backward(w)
+        return w
+
+    @staticmethod
+    def backward(ctx, dw):
+        (w,) = ctx.saved_tensors
+        ds = torch.empty_like(w)
+        for s0 in range(0, w.shape[-1], SHARE):
+            ws, dws = w[..., s0:s0 + SHARE], dw[..., s0:s0 + SHARE]
+            ds[..., s0:s0 + SHARE] = ws * (dws - (ws * dws).sum(-1, keepdim=True))
+        return ds
+
+
+def _split_attention(st, prefix, h, mem, mem_lens, mutant):
+    """oracle.seq2seq_attention with its two halves taken apart (qd = h W_q^T, the memory half with the bias), so that a
+    SPLIT_MUTANT can reach between them.  Equal to the oracle's up to the rounding of one more addition."""
+    W, b, v = st[prefix + ".h2attn.weight"], st[prefix + ".h2attn.bias"], st[prefix + ".v"]
+    Hq, S = h.shape[1], mem.shape[1]
+    qd = F.linear(h, W[:, :Hq]).unsqueeze(1).expand(-1, S, -1)
+    if mutant == "dqd_share0_only":        # MUTANT: the frames of the shares behind the first never reach d qd
+        first = (torch.arange(S) < SHARE).view(1, S, 1)
+        qd = torch.where(first, qd, qd.detach())
+    score = torch.tanh(qd + F.linear(mem, W[:, Hq:], b)) @ v
+    mask = torch.arange(S).unsqueeze(0) < torch.as_tensor(mem_lens).view(-1, 1)
+    score = score.masked_fill(~mask, -1e10)
+    weights = _SoftmaxPerShare.apply(score) if mutant == "softmax_sum_per_share" else torch.softmax(score, dim=-1)
+    return (weights.unsqueeze(1) @ mem).squeeze(1), weights
 
 
 def _dec_table(st):
@@ -107,7 +146,10 @@ def decode(state, mem, mem_lens, words, lens1, q_z, eps_p, dis_flags, emb_keep=N
         if emb_keep is not None and p > 0.0:
             kept = emb * emb_keep[t].to(dtype)
             emb = _swap_grad(kept * (1.0 / (1.0 - p)), kept) if mutant == "no_keep_scale" else kept * (1.0 / (1.0 - p))
-        ctx, aw = O.seq2seq_attention(st, "decoder.attn", h, att_mem, mem_lens)
+        if mutant in SPLIT_MUTANTS:
+            ctx, aw = _split_attention(st, "decoder.attn", h, att_mem, mem_lens, mutant)
+        else:
+            ctx, aw = O.seq2seq_attention(st, "decoder.attn", h, att_mem, mem_lens)
         h = O.gru_cell(torch.cat((emb, ctx, z), dim=-1), h, st["decoder.model.weight_ih_l0"], st["decoder.model.weight_hh_l0"],
                        st["decoder.model.bias_ih_l0"], st["decoder.model.bias_hh_l0"])
         out["logits"].append(F.linear(h, st["decoder.classifier.weight"], st["decoder.classifier.bias"]))
@@ -213,13 +255,22 @@ class Case:
     seed: int = 1
     path: str = "persist"             # persist | per_step | no_split | defer | defer_per_step
     persist_ok: bool = True           # what widths_util.plans must say about both persistent launches at this shape
+    mem_lens: tuple = ()              # the clips' frames, explicit (N of them, the first S); (): S, S - 2, S - 4, .., 1
+    att: str = ""                     # S > 64, persistent: the forward attention the plan must choose (resident | streamed)
 
     @property
     def Eenc(self):
         return 512 if self.ln else self.E
 
     def ref_key(self):
-        return dataclasses.replace(self, name="", path="", persist_ok=True)
+        return dataclasses.replace(self, name="", path="", persist_ok=True, att="")
+
+    def frames(self):
+        """The clips' memory lengths."""
+        if self.mem_lens:
+            assert len(self.mem_lens) == self.N and max(self.mem_lens) == self.mem_lens[0] == self.S and min(self.mem_lens) >= 1
+            return list(self.mem_lens)
+        return ([self.S] + [max(1, self.S - 2 * n) for n in range(1, self.N - 1)] + ([1] if self.N > 1 else []))[:self.N]
 
 
 def make_state(c):
@@ -250,9 +301,8 @@ def inputs(c):
     if c.words == "random":
         caps[:, 0] = START
         caps[0, Tc - 1] = V - 1
-    mem_lens = [S] + [max(1, S - 2 * n) for n in range(1, N - 1)] + ([1] if N > 1 else [])
     d = dict(caps=caps, lens1=torch.tensor(lens1), mem=torch.randn(N, S, c.Eenc, generator=g),
-             mem_lens=torch.tensor(mem_lens[:N]), q_z=torch.randn(N, Tc, E, generator=g),
+             mem_lens=torch.tensor(c.frames()), q_z=torch.randn(N, Tc, E, generator=g),
              eps_p=torch.randn(Tc, N, E, generator=g))
     d["emb_keep"] = (torch.rand(Tc, N, E, generator=g) >= c.p).to(torch.uint8) if c.p > 0 else None
     shapes = dict(logits=(N, Tc, V), outputs=(N, Tc, H), p_means=(N, Tc, E), p_logs=(N, Tc, E), p_z=(N, Tc, E),
@@ -328,6 +378,29 @@ def pool_margin(c):
 
 # The cases of tests/test_decode_composite_gpu.py: the smallest shapes at which each branch can still go wrong.
 ALL, ONE = UPS, lambda k: (k,)
+_L = dict(A=160, V=51, att="resident")          # E = 64, A = 160: the forward attention keeps S <= 187 frames on the CU
+_P = dict(E=512, H=512, N=2, Tc=3, ln=False, V=300, seed=2, att="streamed")      # production E: more than 64 frames are streamed
+S_LONG = [
+    Case("S66", S=66, **_L),                                               # two shares, the last of 2 frames
+    Case("S66-defer", S=66, path="defer", **_L),
+    Case("S65", S=65, N=4, mem_lens=(65, 64, 63, 1), seed=2, **_L),              # last share of ONE frame; a clip ends at the share
+    Case("S128", S=128, mem_lens=(128, 65, 1), **_L),                      #   boundary, one just inside share 0; two full shares
+    Case("S129", S=129, **_L),                                             # three shares, the last of 1 frame
+    Case("S130", S=130, **_L),                                             # ... of 2 frames
+    Case("S130-per_step", S=130, path="per_step", **_L),
+    Case("S187", S=187, N=4, mem_lens=(187, 130, 64, 1), **_L),            # ... of 59; every clip but the first leaves a share
+    Case("S187-per_step", S=187, N=4, mem_lens=(187, 130, 64, 1), path="per_step", **_L),           # (or two) fully masked
+    Case("S66-Tc1", S=66, Tc=1, **_L),                                     # the launch writes NO row of dqd
+    Case("S66-Tc2", S=66, Tc=2, **_L),
+    Case("S66-N1", S=66, N=1, seed=2, **_L),
+    Case("S66-N32", S=66, N=32, Tc=2, **_L),                               # 64 attention workgroups
+    Case("S66-ss_mixed", S=66, ss="mixed", **_L),                          # the context a PER-STEP forward saved in rnn_d
+    Case("S66-only_outputs", S=66, ups=ONE("outputs"), **_L),              # NULL d_logits upstream
+    Case("S66-emb_dropout", S=66, p=0.3, **_L),                            # the ctx slot between the embedding and z columns
+    Case("E512_A512_S66", S=66, A=512, **_P),                              # the batched pb_gemm1_shares (A = 512), ks_rb 3, ks_pa 2
+    Case("E512_A256_S130", S=130, A=256, **dict(_P, seed=3)),                            # its one-group-at-a-time form with three shares
+    Case("S130_A320", S=130, A=320, V=51, seed=2, att="streamed"),                 # E = 64 streamed: [S][A] does not fit the LDS
+]
 CASES = [
     # widths (widths_util.TRAIN_SETS) and paths
     Case("E64_A32"),
@@ -355,7 +428,10 @@ CASES = [
     Case("S64", S=64, A=160),
     Case("S64-per_step", S=64, A=160, path="per_step"),
     Case("S64-no_split", S=64, A=160, path="no_split"),
-    Case("S66-per_step", S=66, A=160, V=51, path="per_step"),     # (the persistent launches at S > 64: see DESIGN.md section 2)
+    # S > 64: the persistent BPTT's attention role runs as 2 or 3 workgroups per clip (shares of 64 frames) that hand d qd over
+    # as parts and take the softmax backward's sum from <dctx, ctx>; each has a per-step partner on the same reference
+    Case("S66-per_step", S=66, A=160, V=51, path="per_step"),
+    *S_LONG,
     # words: one owner of all N Tc rows; N Tc across embed_scatter_kernel's bitmap words
     Case("same_word", words="same"),
     Case("rows31", N=31, Tc=1, words="last"),

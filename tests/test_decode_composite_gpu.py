@@ -10,8 +10,8 @@ left out, under
 
     |got - ref| <= max(1e-5, 8 r32) max(|ref|, rms(ref))        r32: the float32 run of the same reference against float64
 
-per tensor and per case (tests/decode_ref.py tolerance; tests/test_decode_ref_cpu.py shows the bound flags nine kinds of
-wrong backward).  A tensor no given upstream reaches is exactly zero in the reference and must be written as exactly zero.
+per tensor and per case (tests/decode_ref.py tolerance; tests/test_decode_ref_cpu.py shows the bound flags eleven kinds of
+wrong backward, the two mistakes of a split attention backward at every S > 64 case itself).  A tensor no given upstream reaches is exactly zero in the reference and must be written as exactly zero.
 d_mem_in at frames >= mem_lens[n] is exactly zero in the reference; what the HIP path leaves there is printed and held to
 the bound like every other element.  The max-pool margin of the float64 outputs is asserted (>= 1e-4), so no arg-max
 decision is close enough to flip.
@@ -21,18 +21,26 @@ its shape, the flags it passes, acvae_decode_bwd_defers, the split attention's e
 status words afterwards.  Cases that feed model words (mixed scheduled sampling, the differentiable rollouts) replay the
 HIP forward's own `seqs` into the reference as constants, so no decision is compared.
 
+Clips of more than 64 frames (decode_ref.S_LONG): the persistent BPTT's attention role then runs as 2 or 3 workgroups per
+clip.  Each such case also asserts and prints rc_splits, dqd_part_floats > 0, dv_rows = N rc_splits, which forward attention
+form the plan chooses (memory-resident or streamed; both occur) and that both grids fit the device at one workgroup per CU.
+They cover a last share of 1, 2, 59 and 64 frames, clips that leave one or two of their shares fully masked, Tc = 1 and 2,
+N = 1 and 32, a per-step forward feeding the split backward, a NULL d_logits, embedding dropout, A = 512 (the batched sum of
+the d qd shares) and E = 512 with three shares; S = 66, 130 and 187 also run per step on the same reference.
+
 Worst measured error / tolerance on the MI355X, per tensor group (test_zz_worst_ratio_per_group prints the table):
-    forward outputs               0.11  (p_means, rows33)
-    input gradients               0.18  (d_mem_in, only_p_logs)
-    decoder gradients             0.33  (attn.h2attn.bias, E64_A32-per_step)
+    forward outputs               0.20  (cp, E512_A512_S66)
+    input gradients               0.39  (d_mem_in, S66-Tc1)
+    decoder gradients             0.57  (attn.h2attn.bias, S66)
     prior gradients               0.36  (word_attn.h2attn.bias, only_p_logs)
     mean_log_out / ln gradients   0.15  (ln.weight, only_outputs)
 No tensor needed more than the factor 8; d_mem_in at frames >= mem_lens was exactly 0 in every case; the smallest max-pool
 margin was 2.6e-4.
 
-Not among the cases: the persistent launches at S > 64 (S = 66 runs per step).  There the persistent BPTT leaves step 0's
-rows of its d qd sum unwritten, and the query half of decoder.attn.h2attn.weight's gradient multiplies whatever the scratch
-holds there by h_{-1} = 0: NaN under the 0xFF fill of this file.  See DESIGN.md section 2."""
+What these cases found: with rc_splits > 1 the persistent BPTT writes the sum of the d qd shares for steps 1 .. Tc - 1
+only, and the query half of decoder.attn.h2attn.weight's gradient multiplied whatever the scratch held in step 0's rows by
+h_{-1} = 0: NaN under the 0xFF fill of this file, in every persistent case above and in no other tensor.
+acvae_decode_bwd now zeroes dqd at its entry.  See DESIGN.md section 2."""
 import ctypes
 
 import pytest
@@ -119,6 +127,16 @@ def run_hip(c):
         if c.S >= 64:
             assert plan["rc_splits"] == -(-c.S // 64), plan            # 64 frames per attention workgroup of the BPTT
             path["attention shares per clip (BPTT)"] = plan["rc_splits"]
+        if c.S > 64:      # the split attention role: d qd handed over as shares, one dvpart row per clip and share
+            assert plan["dqd_part_floats"] == plan["rc_splits"] * N * Tc * A > 0, plan
+            assert plan["dv_rows"] == N * plan["rc_splits"], plan
+            assert not c.att or plan["fwd_att_resident"] == int(c.att == "resident"), (c.name, plan)
+            path.update({"dqd_part_floats": plan["dqd_part_floats"], "dv_rows": plan["dv_rows"],
+                         "att_resident (forward)": plan["fwd_att_resident"], "grids": (plan["fwd_grid"], plan["bwd_grid"])})
+            if persist:   # one workgroup per CU always fits (LDS <= 150 KB): then the library takes the launches it is asked for
+                cus = torch.cuda.get_device_properties(0).multi_processor_count
+                assert max(plan["fwd_grid"], plan["bwd_grid"]) <= cus, (c.name, plan, cus)
+                path["grid resident"] = True
         if c.path in ("per_step", "no_split") and c.S == 64:
             assert _lib.call("acvae_attn_fwd_workspace_bytes", N, 1, S, A, E) > 0      # the split form is eligible here ...
             path["attention"] = "one workgroup (NO_ATTN_SPLIT)" if c.path == "no_split" else "split over frames"

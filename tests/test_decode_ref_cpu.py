@@ -6,7 +6,10 @@
   max(1e-5, 8 r32) <= 8e-4 stays below the 2e-3 |ref| the whole-model check grads_match_oracle allows an element: the new
   bound is the tighter one on every tensor), and widths_util.plans says about the persistent launches what the case means;
 - the bound is not vacuous: every MUTANT of the backward (one defect each, at the smallest case that can show it) is
-  flagged on at least one tensor, while the float32 restatement of the same case stays within an eighth of the bound."""
+  flagged on at least one tensor, while the float32 restatement of the same case stays within an eighth of the bound;
+- the S > 64 cases cover the share layouts of the persistent BPTT's split attention role and both forward attention forms,
+  and the two mistakes of a split attention backward (frames >= 64 left out of d qd; the softmax backward's sum taken per
+  share) are flagged at every one of those cases."""
 import dataclasses
 import math
 import random
@@ -68,11 +71,39 @@ def test_case_is_reachable_and_takes_its_path(case):
         plan = W.plans(case.N, case.Tc, case.S, case.E, case.H, case.A, case.E)
         assert (plan["fwd_ok"] == 1 and plan["bwd_ok"] == 1) == case.persist_ok, (case.name, plan)
         assert case.persist_ok or case.path in ("per_step", "no_split", "defer_per_step"), case.name
-        if case.S >= 64:               # S = 66 is past the streamed-attention threshold: two attention shares per clip
-            assert plan["rc_splits"] == -(-case.S // 64) and (plan["dqd_part_floats"] > 0) == (case.S > 64), plan
+        if case.S >= 64:               # 64 frames per attention workgroup of the BPTT: S > 64 hands d qd over as shares
+            assert plan["rc_splits"] == -(-case.S // R.SHARE) and (plan["dqd_part_floats"] > 0) == (case.S > 64), plan
+            assert plan["dv_rows"] == case.N * plan["rc_splits"], plan
+        if case.S > 64:
+            assert case.att in ("resident", "streamed") or case.path == "per_step", case.name
+            assert not case.att or plan["fwd_att_resident"] == int(case.att == "resident"), (case.name, plan)
+            assert max(plan["fwd_grid"], plan["bwd_grid"]) <= 256, plan       # one workgroup per CU of an MI355X is enough
     lens = d["lens1"].tolist()
     assert case.N == 1 or case.full or (min(lens) == 1 and max(lens) == case.Tc)
+    assert d["mem_lens"].tolist() == case.frames()
     assert case.N == 1 or (int(d["mem_lens"].min()) == 1 and int(d["mem_lens"].max()) == case.S)
+
+
+def persistent_long():
+    """The S > 64 cases whose backward is the persistent launch."""
+    return [c for c in R.CASES if c.S > 64 and c.path in ("persist", "defer") and c.persist_ok and not c.rollout]
+
+
+def test_long_clips_cover_the_share_layouts_and_both_attention_forms():
+    cases = persistent_long()
+    assert len(cases) >= 17
+    fwd = {c.att for c in cases if c.ss == "all"}                    # (a mixed-sampling forward runs per step)
+    assert fwd == {"resident", "streamed"}, fwd
+    tails = {(-(-n // R.SHARE), n - (n - 1) // R.SHARE * R.SHARE) for c in cases for n in c.frames() if n > R.SHARE}
+    assert {(2, 1), (2, 2), (2, 64), (3, 1), (3, 2), (3, 59)} <= tails, tails       # (shares, frames of the last share)
+    # clips that leave one share or two of their workgroups fully masked, beside a clip that fills them
+    assert any(c.S > 128 and any(n <= 64 for n in c.frames()) and any(64 < n <= 128 for n in c.frames()) for c in cases)
+    # each per-step partner shares its reference with a persistent case
+    keys = {c.ref_key() for c in cases}
+    partners = [c for c in R.CASES if c.S > 64 and c.path == "per_step"]
+    assert {c.S for c in partners} == {66, 130, 187} and all(c.ref_key() in keys for c in partners)
+    assert any(c.A == 512 for c in cases) and any(c.E == 512 and c.A < 512 and c.S > 128 for c in cases)
+    assert {c.Tc for c in cases} >= {1, 2, 3, 7} and {c.N for c in cases} >= {1, 32}
 
 
 SMALL = dict(N=2, Tc=2, S=2)
@@ -86,6 +117,8 @@ MUTANT_CASES = {
     "dis_z_to_q": R.Case("m", N=2, Tc=1, S=2, dis="all", ups=("logits",)),
     "no_keep_scale": R.Case("m", N=2, Tc=1, S=2, p=0.3, ups=("logits",)),
     "no_ln_bias": R.Case("m", N=2, Tc=1, S=2, ups=("logits",)),
+    "dqd_share0_only": R.Case("m", N=2, Tc=2, S=66, ups=("logits",)),           # mem_lens = [66, 1]: two frames in share 1
+    "softmax_sum_per_share": R.Case("m", N=2, Tc=1, S=66, ups=("logits",)),
 }
 
 
@@ -107,6 +140,34 @@ def test_the_bound_flags_the_mutant(mutant):
     print(mutant, "flagged on", flagged)
     assert flagged, f"{mutant}: within the bound on every tensor (worst {max(over.values()):.3g})"
     assert all(not k.startswith("fwd.") for k in flagged), flagged               # a mutant changes the backward only
+
+
+LONG_REFS = {}
+for _c in persistent_long():
+    LONG_REFS.setdefault(_c.ref_key(), _c)
+
+
+@pytest.mark.parametrize("case", list(LONG_REFS.values()), ids=[c.name for c in LONG_REFS.values()])
+@pytest.mark.parametrize("mutant", R.SPLIT_MUTANTS)
+def test_the_bound_flags_a_wrong_split_attention_in_every_long_case(mutant, case):
+    """The two mistakes a split attention backward can make, at every S > 64 case itself (one run per distinct reference;
+    every such case has a clip of more than 64 frames).  One pair is the same function: with Tc = 1, d qd of the only step
+    meets h_{-1} = 0 in the weight gradient and no earlier step in dh, so leaving frames out of it changes NOTHING - there
+    the mutant must give the float64 reference back, and the case is in the list for the rows of dqd nobody writes."""
+    c = case
+    assert max(c.frames()) > R.SHARE
+    y = R.yardstick(c)
+    d = R.inputs(c)
+    words = R.fed_words(c, d["caps"], None if c.ss == "all" else R.surrogate_words(c))
+    bad = R._run(c, d, words, torch.float64, mutant)
+    over = {k: R.excess(bad[k], ref, r32) for k, (ref, r32) in y.items()}
+    flagged = sorted(k for k, v in over.items() if v > 1.0)
+    print(c.name, mutant, "flagged on", flagged)
+    assert all(not k.startswith("fwd.") for k in flagged), flagged
+    if mutant == "dqd_share0_only" and c.Tc == 1:
+        assert max(over.values()) <= 1e-6, over                     # (float64 rounding of the restated attention, no more)
+        return
+    assert flagged, f"{c.name} {mutant}: within the bound on every tensor (worst {max(over.values()):.3g})"
 
 
 def test_measure_edges():

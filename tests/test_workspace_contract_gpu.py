@@ -38,9 +38,11 @@ acvae_posterior_stack_bwd           skinny, column-sum and TN tickets; pq_cnt; t
 acvae_decode_fwd / _sampled /       skinny tickets of both chains; the split         csrc/decoder.hip:660-666 ZeroBatch
 _truncated / _constrained           attention's counters attfws_d / attfws_p;        (:661 skinny, :662 attention, :663 pd_cnt,
                                     persistent decode counters pd_cnt; h_{-1}         :665 h0)
-acvae_decode_bwd                    skinny / column-sum / TN tickets of both         csrc/decoder.hip:1016-1026 ZeroBatch
-                                    chains; persistent BPTT counters pd_cnt_b and    (:1017 tickets, :1019 pd_cnt_b, :1020
-                                    the accumulator dmem_p; both embedding-table     dmem_p, :1025 tables)
+acvae_decode_bwd                    skinny / column-sum / TN tickets of both         csrc/decoder.hip:1018-1031 ZeroBatch
+                                    chains; persistent BPTT counters pd_cnt_b and    (:1019 tickets, :1021 pd_cnt_b, :1022
+                                    the accumulator dmem_p; with clips of more       dmem_p, :1025 dqd, :1030 tables)
+                                    than 64 frames dqd, whose step-0 rows that
+                                    launch never writes; both embedding-table
                                     gradients
    a persistent launcher zeroes its own counters when its caller has not (no ACVAE_FLAG_INT_CNT_ZEROED):
                                                                                      csrc/decode_persist.hip:1405
@@ -566,6 +568,22 @@ def test_decode_training_contract(name, persist):
     got = contract(fam, other, f"decode training {name} persist={persist}")
     for k, want in fam.python_path().items():
         close(got[k], want, f"decode training {name} {k}")
+
+
+@pytest.mark.parametrize("persist", [True, False], ids=["persistent", "per_step"])
+def test_decode_training_contract_long_clips(persist):
+    """Clips of more than 64 frames: the scratch layout holds a non-empty region for the d qd shares of the persistent BPTT's
+    split attention role (two shares at S = 66; three at S = 130, the shape whose leftovers the stale run starts from), and
+    acvae_decode_bwd zeroes the rows of dqd that launch never writes."""
+    name = "E64_A160"
+    fam, other = DecodeTrainFam(name, 3, 7, 66, persist), DecodeTrainFam(name, 4, 9, 130, persist)
+    plan, oplan = W.plans(3, 7, 66, fam.E, fam.H, fam.A, fam.E), W.plans(4, 9, 130, fam.E, fam.H, fam.A, fam.E)
+    for p, n, tc, shares in ((plan, 3, 7, 2), (oplan, 4, 9, 3)):
+        assert p["fwd_ok"] == 1 and p["bwd_ok"] == 1 and p["rc_splits"] == shares, p
+        assert p["dqd_part_floats"] == shares * n * tc * fam.A and p["dv_rows"] == shares * n, p
+    got = contract(fam, other, f"decode training {name} S=66 persist={persist}")
+    for k, want in fam.python_path().items():
+        close(got[k], want, f"decode training {name} S=66 {k}")
 
 
 class DecodeInferFam(Family):

@@ -80,8 +80,8 @@ int main(int argc, char** argv) {
   const acvae::PdPlan f = acvae::decode_fwd_plan(d[0], d[1], d[2], d[3], d[4], d[5], true);
   const acvae::PbPlan b = acvae::decode_bwd_plan(d[0], d[1], d[2], d[3], d[4], d[5]);
   const acvae::PqPlan q = acvae::posterior_plan(d[0], d[1], d[6]);
-  std::printf("%d %d %d %d %d %d %d %d %d %ld %d %d\n", (int)f.shape_ok, f.att_resident, f.n_d1, f.grid, (int)b.shape_ok, b.ks_rb,
-              b.ks_pa, b.rc_splits, b.grid, b.dqd_part_floats, (int)q.shape_ok, q.grid);
+  std::printf("%d %d %d %d %d %d %d %d %d %ld %d %d %d\n", (int)f.shape_ok, f.att_resident, f.n_d1, f.grid, (int)b.shape_ok, b.ks_rb,
+              b.ks_pa, b.rc_splits, b.grid, b.dqd_part_floats, (int)q.shape_ok, q.grid, b.dv_rows);
   return 0;
 }
 """
@@ -115,7 +115,7 @@ def plans(N, Tc, S, E, H, A, Hq):
     assert r.returncode == 0, r.stdout + r.stderr
     v = [int(x) for x in r.stdout.split()]
     keys = ("fwd_ok", "fwd_att_resident", "fwd_n_d1", "fwd_grid", "bwd_ok", "ks_rb", "ks_pa", "rc_splits", "bwd_grid",
-            "dqd_part_floats", "post_ok", "post_grid")
+            "dqd_part_floats", "post_ok", "post_grid", "dv_rows")
     return dict(zip(keys, v))
 
 
