@@ -15,6 +15,7 @@ import json
 import pickle
 from pathlib import Path
 
+import numpy as np
 import torch
 
 from .batch import collate_fn, forward_batch, forward_batch_shared_encoder
@@ -153,6 +154,95 @@ def accuracy_rows(rows, per_clip):
     if rows.dim() == 3:
         rows = rows[:, :per_clip]
     return rows.reshape(-1, rows.shape[-1])
+
+
+def evaluate_likelihood(model, items, key2caps, vocabulary, output=None, batch_size=1, z=("posterior", "prior"), samples=1,
+                        frontend=None, device=None):
+    """Score the GIVEN captions of an evaluation set under the model (``acvae_amd.likelihood`` says what is measured): held-out
+    likelihood and perplexity, per-caption KL, teacher-forced top-1 / top-5 word accuracy.
+
+    ``items``: ``(audio_id, feature [T, F])`` as ``evaluate`` takes them (``frontend=``: ``(audio_id, 1-D waveform)``; an
+    ``Augmented`` front end is refused), batched ``batch_size`` clips at a time.  ``key2caps[audio_id]``: the clip's captions,
+    tokenized as the vocabulary's words are (strings split at whitespace, or word lists, as for ``Accuracy``); a word outside
+    the vocabulary maps to ``<unk>``; ``<start>`` / ``<end>`` are added here.  ``z``: a mode or a tuple of modes; ONE encoder
+    pass per batch is shared by the modes, each of which is one ``score_captions`` forward with ``samples`` draws per caption.
+    -> ``{mode: Likelihood.result()}``, the pairs keyed ``[audio_id, caption number]``; written to ``output`` as JSON.
+
+    The items stream batch by batch, as in ``evaluate``; ``key2caps`` is checked as a whole first.
+
+    ValueError in front of any launch and any random draw: what ``score_captions`` refuses (``samples`` outside 1 .. 16, an
+    unknown mode, a decoder with ``hidden_size != embed_size``, unequal numbers of captions per clip in ``key2caps`` while
+    ``batch_size > 1``: pad the smaller sets, or score one clip per batch), an entry of ``key2caps`` without captions, a
+    caption without words.  An item whose id ``key2caps`` lacks is known only when it arrives: ValueError in front of its own
+    batch's launches."""
+    from . import likelihood as lk
+    who = "evaluate_likelihood"
+    modes = (z,) if isinstance(z, str) else tuple(z)
+    if not modes:
+        raise ValueError(f"{who}: no mode in z")
+    refuse_augmented(frontend, who)
+    for mode in modes:
+        lk.check_mode(mode, who)
+    samples = lk.check_samples(samples, who)
+    lk.check_model(model, who)
+    start, end = vocabulary("<start>"), vocabulary("<end>")
+    # the captions are checked as a whole, in front of any work and without touching the items, which stream batch by
+    # batch as in ``evaluate`` (a lazily loading set is never held in memory at once)
+    tokens, counts = {}, set()
+    for audio_id, given in key2caps.items():
+        given = list(given) if given is not None else []
+        if not given:
+            raise ValueError(f"{who}: clip {audio_id!r} has no captions")
+        rows_ = []
+        for cap in given:
+            words = cap.split() if isinstance(cap, str) else list(cap)
+            if not words:
+                raise ValueError(f"{who}: clip {audio_id!r} has a caption without words")
+            rows_.append([start] + [vocabulary(w) for w in words] + [end])
+        tokens[audio_id] = rows_
+        counts.add(len(rows_))
+    if batch_size > 1 and len(counts) > 1:
+        raise ValueError(f"{who}: every clip needs the same number of captions (got between {min(counts)} and {max(counts)}) "
+                         f"when clips share a batch (batch_size={batch_size}): the shared-encoder forward (clip_index=) has that "
+                         "rule; pad the smaller sets, e.g. by repeating one of the clip's captions, or use batch_size=1")
+    device = device if device is not None else next(model.parameters()).device
+    meters = {mode: lk.Likelihood(mode, samples) for mode in modes}
+    collate = collate_fn([1, ])
+    pending = []
+
+    def flush():
+        if not pending:
+            return
+        chunk = list(pending)
+        pending.clear()
+        keys = [[audio_id, i] for audio_id, _ in chunk for i in range(len(tokens[audio_id]))]
+        caps = [cap for audio_id, _ in chunk for cap in tokens[audio_id]]
+        clip = np.array([b for b, (audio_id, _) in enumerate(chunk) for _ in tokens[audio_id]], dtype=np.int64)
+        lens = np.array([len(c) for c in caps], dtype=np.int64)
+        rows = lk.Rows(lens, clip, len(chunk), samples, who)
+        padded = np.zeros((len(caps), int(lens.max())), dtype=np.int64)
+        for row, cap in zip(padded, caps):
+            row[:len(cap)] = cap
+        batch = collate(chunk)
+        feats, feat_lens, encoded = lk.encode_clips(model, batch[1], batch[-1], frontend, device)
+        for mode in modes:
+            meters[mode].update(keys, lk.score_rows(model, feats, feat_lens, encoded, torch.from_numpy(padded), rows, mode))
+
+    with lk.eval_mode(model):
+        for audio_id, data in items:
+            if audio_id not in tokens:
+                raise ValueError(f"{who}: clip {audio_id!r} has no captions in key2caps")
+            if frontend is not None:               # collate_fn pads into float32: PCM becomes the samples it stands for
+                data = frontend.to_float(data)
+            pending.append((audio_id, data))
+            if len(pending) == batch_size:
+                flush()
+        flush()
+    payload = {mode: meters[mode].result() for mode in modes}
+    if output is not None:
+        with open(Path(output), "w") as fh:
+            json.dump(payload, fh, indent=4)
+    return payload
 
 
 def evaluate(model, items, vocabulary, caption_output=None, zh=False, batch_size=1, device=None, frontend=None,

@@ -412,7 +412,10 @@ class Hybrid_VAEModel(CaptionModel):
         row r, in any order (``acvae_amd.batch.collate_groups`` sorts the rows by caption length).  Every output has N rows.
         The loss and every parameter gradient are those of the forward on ``feats[clip_index]``; see ``_share_rows`` for why
         and for the two departures (shared dropout masks, ``running_var``'s Bessel factor).  ``clip_rows`` says what is
-        refused (ValueError).
+        refused (ValueError).  ``encoder_output`` (with ``clip_index`` only, default None = nothing changes): the dict an
+        earlier ``self.encoder(feats, feat_lens)`` call returned for these B clips; the encoder is then not run and
+        ``feat_lens`` is used for its length alone, the number of clips: it is neither read nor divided (``acvae_amd.likelihood``
+        scores several ways over one encoder pass with it).
 
         ``top_k`` (default 0 = off) / ``top_p`` (default 1.0 = off) with ``method="sample"`` or ``"gumbel"``: every sampled
         word is drawn among the ``top_k`` most probable words and / or the nucleus of mass ``top_p`` only (see
@@ -440,6 +443,9 @@ class Hybrid_VAEModel(CaptionModel):
         clip_index = kwargs.pop("clip_index", None)
         if clip_index is not None and len(input) != 4:
             raise ValueError("clip_index belongs to the training forward (feats, feat_lens, caps, cap_lens)")
+        encoder_output = kwargs.pop("encoder_output", None)
+        if encoder_output is not None and (len(input) != 4 or clip_index is None):
+            raise ValueError("encoder_output belongs to the training forward with clip_index=")
         if len(input) == 4:
             feats, feat_lens, caps, cap_lens = input
             # mean_log_out = Linear(embed_size, .) is fed the pooled GRU outputs (acvae_decode_fwd refuses the shape too:
@@ -485,7 +491,7 @@ class Hybrid_VAEModel(CaptionModel):
                 # for what main held before this point).  Autograd runs the later-created node first, so in the backward
                 # the posterior's kernels and its gradient bucket are queued before the long encoder backward: under data
                 # parallelism the 20 MB posterior bucket then travels beside the encoder backward instead of behind it.
-                encoded = self.encoder(feats, feat_lens)
+                encoded = self.encoder(feats, feat_lens) if encoder_output is None else encoder_output
                 if share is not None:
                     encoded = self._share_rows(encoded, *share)
                 qnetout = on_side(self.qnet, prep["caps_d"], cap_lens, eps=eps_q, keep=q_keep)

@@ -1253,6 +1253,51 @@ int acvae_ensemble_dbs_search(const void* const* const* params, const float* con
                               float diversity_lambda, int group_nbest, int64_t* seqs, double* scores, int* lengths,
                               void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scoring GIVEN captions: per-step log-probability, rank and KL of a teacher-forced forward's outputs, and their per-row
+ * sums (csrc/likelihood.hip; acvae_amd/likelihood.py is the front).  No counterpart in the reference, whose only
+ * loss-shaped number is the label-smoothed batch scalar with its KL averaged over padded positions too (F8).
+ *
+ * acvae_caption_terms: one pass over R rows of T steps.  logits f32, row (r, t) at logits + r*ld_n + t*ld_t (V floats, as
+ * acvae_ls_ce_fwd takes them); targets int64, (r, t) at targets + r*tg_sn + t; lens1 int64 [R], NULL = every cell valid,
+ * 0 allowed, a value > T counts as T.  q_means / q_logs / p_means / p_logs f32 [R, T, E] contiguous (mu1, logvar1 of the
+ * posterior; mu2, logvar2 of the prior); if any of the four is NULL no KL is requested, E is not used and `kl` may be NULL
+ * (it is written as zeros if it is not).  A cell (r, t) is valid iff t < lens1[r].  Outputs [R, T] contiguous:
+ *   logprob f32  x[tgt] - logsumexp(x) over the row's V logits x.  The row is read once: a running maximum and a sum
+ *                of exp(x - maximum) per lane, merged against the row's maximum, so the log-sum-exp is max-subtracted
+ *                throughout and is not taken from a precomputed lse.  A logit of -inf is a word of mass 0.  A row
+ *                without a defined value - nothing but -inf, a +inf logit, a NaN logit anywhere in it (told by its
+ *                bits) - gives NaN.
+ *   rank    i32  #{v : x[v] > x[tgt]} + #{v < tgt : x[v] == x[tgt]}: the target's position under the first-maximum rule of
+ *                acvae_row_logsoftmax_argmax / torch.max, so rank == 0 iff the greedy decode emits the target.  Comparisons
+ *                of the fp32 inputs only: exact.  NaN logits compare with nothing and so count for nothing; a target
+ *                whose own logit is NaN gets INT32_MAX (no top-1 / top-5 hit).  In a row of nothing but -inf every
+ *                word ties: the rank is the target's index.
+ *   kl      f32  sum over e < E of Normal_kl_loss's term (utils/train_util.py:259-266)
+ *                lv2/2 - lv1/2 + (exp(lv1) + (mu1 - mu2)^2) / (2 exp(lv2)) - 1/2  in a fixed order.  The terms and their
+ *                sum are evaluated in float64 (a term is what is left of summands that cancel) and the cell is rounded
+ *                to fp32 once, at the store.
+ * An invalid cell is written as exact zeros in all three outputs and none of its inputs is read.  A valid cell whose
+ * target lies outside [0, V) is written as logprob = NaN, rank = INT32_MAX (its kl is the cell's own); the row is read,
+ * nothing outside it is.  Every output element is stored exactly once; no atomics, no hand-off between workgroups, no
+ * workspace; every sum has a fixed order (bit-reproducible).  One workgroup per cell: its work is V + 4E elements.  16-byte
+ * loads of the logits when the base is 16-byte aligned and ld_n and ld_t are multiples of 4 (a V that is not has a scalar
+ * tail), of the Gaussians when E is a multiple of 4 and the four bases are aligned; scalar loads otherwise.
+ * ACVAE_EINVAL before any launch: logits / targets / logprob / rank NULL, R or T < 1, V < 2, E < 0, a negative stride,
+ * R * T >= 2^31, or a KL requested with E < 1 or kl NULL.
+ *
+ * acvae_caption_sums: per row r over its valid cells t < min(max(lens1[r], 0), T) (lens1 NULL: T), t ascending, in float64:
+ *   nll[r] = sum_t -(double)logprob[r,t]      kl_sum[r] = sum_t (double)kl[r,t]   (kl NULL: 0)
+ *   tokens[r] = the number of valid cells      hit1[r] / hit5[r] = #{t : rank[r,t] < 1} / #{t : rank[r,t] < 5}   (int32)
+ * One lane per row, serial over t: bit-equal to a host loop over the same cells; no transcendental function.
+ * ------------------------------------------------------------------------------------------- */
+int acvae_caption_terms(const float* logits, int64_t ld_n, int64_t ld_t, const int64_t* targets, int64_t tg_sn,
+                        const int64_t* lens1, const float* q_means, const float* q_logs, const float* p_means,
+                        const float* p_logs, float* logprob, int32_t* rank, float* kl, int R, int T, int V, int E,
+                        void* stream);
+int acvae_caption_sums(const float* logprob, const int32_t* rank, const float* kl, const int64_t* lens1, double* nll,
+                       double* kl_sum, int32_t* tokens, int32_t* hit1, int32_t* hit5, int R, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
