@@ -171,7 +171,8 @@ def make_state(seed, enc=None):
 
 
 def ref_forward(st, feats, lens, training, masks, relu_force=None, probe=None):
-    """fp64 restatement of ResNet38.forward; st: {name: tensor} (running buffers updated in place in training)."""
+    """fp64 restatement of ResNet38.forward; st: {name: tensor} (running buffers updated in place in training).  It runs at
+    the state's dtype: tests/encoder_ref.py also evaluates it in fp32."""
     site = [0]
 
     def relu(z):
@@ -194,7 +195,7 @@ def ref_forward(st, feats, lens, training, masks, relu_force=None, probe=None):
     def conv(x, p, pad=1):
         return F.conv2d(x, st[p], padding=pad)
 
-    x = feats.double()[:, None]
+    x = feats.to(st["bn0.weight"].dtype)[:, None]
     x = bn(x.transpose(1, 3), "bn0").transpose(1, 3)
     x = relu(bn(conv(x, "conv_block1.conv1.weight"), "conv_block1.bn1"))
     x = relu(bn(conv(x, "conv_block1.conv2.weight"), "conv_block1.bn2"))

@@ -6,7 +6,11 @@ Runs the HIP training step (default launch path) and the fp32 oracle as the test
 (weights, features and noise cast to double) under the HIP path's own ReLU decisions (and, for a scheduled-sampling case,
 fed the HIP path's own words), and prints for every encoder tensor the
 relative L2 distance of the fp32 oracle and of the HIP gradient from float64.  A per-tensor bound in the test's TOL_ENC_OF
-rests on these numbers (the fp32 oracle's own distance from float64); re-check it after a change to the encoder kernels."""
+rests on these numbers (the fp32 oracle's own distance from float64); re-check it after a change to the encoder kernels.
+
+This tool is for full size.  At small shapes the same comparison is a test of the suite:
+tests/test_encoder_composite_gpu.py holds every encoder tensor of Cnn10, Cnn14_16k and ResNet38 (training, evaluation mode,
+no dropout, both convolution routes) to a margin over the fp32 reference's distance from float64 (tests/encoder_ref.py)."""
 import os
 import random
 import sys
