@@ -143,6 +143,107 @@ class Normal_kl_loss(nn.Module):
         return _KLFn.apply(mu1, lv1, mu2, lv2)
 
 
+class _KLObjectiveFn(torch.autograd.Function):
+    """acvae_kl_objective_fwd / bwd (csrc/kl_objective.hip).  Returns the scalar and, not differentiable, the diagnostics."""
+
+    @staticmethod
+    def forward(ctx, mu_q, lv_q, mu_p, lv_p, lens_d, D, lam, over_cell):
+        _lib.require_cuda(mu_q, lv_q, mu_p, lv_p, lens_d)
+        ts = [t.contiguous().float() for t in (mu_q, lv_q, mu_p, lv_p)]
+        R, T, E = ts[0].shape
+        dev = ts[0].device
+        free = lam is not None
+        nbytes = _lib.call("acvae_kl_objective_scratch_bytes", R, T, E)
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        kl, raw = _dev_scalar(dev), _dev_scalar(dev)
+        dims, steps = torch.empty(E, device=dev), torch.empty(T, device=dev)
+        n_open = torch.empty(1, dtype=torch.int32, device=dev)
+        gates = torch.empty(R * T if over_cell else E, dtype=torch.uint8, device=dev) if free else None
+        _lib.call("acvae_kl_objective_fwd", *ts, lens_d, D, int(free), int(over_cell), lam if free else 0.0, kl, raw, dims,
+                  steps, n_open, gates, scratch, nbytes, R, T, E, _lib.current_stream())
+        ctx.ts, ctx.lens_d, ctx.gates, ctx.args = ts, lens_d, gates, (D, int(over_cell), R, T, E)
+        diag = (raw[0], dims, steps, n_open[0])
+        ctx.mark_non_differentiable(*diag)
+        return (kl[0], *diag)
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        D, over_cell, R, T, E = ctx.args
+        outs = [torch.empty_like(t) if ctx.needs_input_grad[i] else None for i, t in enumerate(ctx.ts)]
+        _lib.call("acvae_kl_objective_bwd", *ctx.ts, ctx.lens_d, D, over_cell, ctx.gates, g.contiguous().float().reshape(1),
+                  *outs, R, T, E, _lib.current_stream())
+        return (*outs, None, None, None, None)
+
+
+class KLObjective(nn.Module):
+    """The variational term of the objective with its controls (include/acvae_hip.h: acvae_kl_objective_fwd has the
+    definitions).  With k[r,t,e] the term of ``Normal_kl_loss``:
+
+    ``reduction``  "all": every cell (r, t), divisor D = R * T - what ``Normal_kl_loss`` averages over, padded positions
+                   included;  "valid": the cells t < lens1[r] only, D = sum(lens1) - the positions the
+                   cross-entropy runs over, and the per-caption KL that ``acvae_amd.likelihood.score_captions`` reports.
+    ``free_bits``  None: KL = (1/D) sum over the cells and e of k.  lam >= 0 (0.0 is a clamp, not None):
+                   ``free_bits_over="dim"``: KL = sum_e max(m_e, lam), m_e the mean of k[., e] over the cells (Kingma et al.
+                   2016); "cell": KL = (1/D) sum over the cells of max(s_c, lam), s_c = sum_e k[c, e].  A dimension or cell
+                   at or under lam gets no gradient (the gate is strict).
+
+    ``forward(mu_q, lv_q, mu_p, lv_p, lens1=None, divisor=None)``: four [R, T, E] tensors -> a device scalar with autograd.
+    ``lens1`` (``cap_lens - 1``) is a host array or a device tensor, required for "valid".  From a host array D is summed on the
+    host and nothing is read back; for a device tensor pass ``divisor=`` (the sum of min(lens1, T)) or one read-back finds
+    it.  Under data parallelism D is the rank's own, the rule the cross-entropy already follows.
+    ``.last`` holds the diagnostics of the latest call, device tensors written by the forward: ``kl_raw`` (the unclamped KL
+    under the same reduction), ``kl_dims`` [E] (m_e), ``kl_steps`` [T] (mean s_c over the rows that hold step t),
+    ``gates_open`` (int32: open gates; without free bits E, or the number of cells for "cell")."""
+
+    def __init__(self, reduction="all", free_bits=None, free_bits_over="dim"):
+        super().__init__()
+        if reduction not in ("all", "valid"):
+            raise ValueError(f"KLObjective: reduction must be 'all' or 'valid', got {reduction!r}")
+        if free_bits_over not in ("dim", "cell"):
+            raise ValueError(f"KLObjective: free_bits_over must be 'dim' or 'cell', got {free_bits_over!r}")
+        if free_bits is not None:
+            if isinstance(free_bits, (bool, np.bool_)) or not isinstance(free_bits, (int, float, np.integer, np.floating)):
+                raise ValueError(f"KLObjective: free_bits must be None or a number >= 0, got {free_bits!r}")
+            free_bits = float(free_bits)
+            if not (0.0 <= free_bits < float("inf")):
+                raise ValueError(f"KLObjective: free_bits must be finite and >= 0, got {free_bits!r}")
+        self.reduction, self.free_bits, self.free_bits_over = reduction, free_bits, free_bits_over
+        self.last = {}
+
+    def forward(self, mu_q, lv_q, mu_p, lv_p, lens1=None, divisor=None):
+        shape = tuple(mu_q.shape)
+        if len(shape) != 3 or any(tuple(t.shape) != shape for t in (lv_q, mu_p, lv_p)) or min(shape) < 1:
+            raise ValueError("KLObjective: the four Gaussians must share one shape [R, T, E], got "
+                             f"{[tuple(t.shape) for t in (mu_q, lv_q, mu_p, lv_p)]}")
+        R, T, E = shape
+        lens_d, D = None, R * T
+        if self.reduction == "valid":
+            if lens1 is None:
+                raise ValueError("KLObjective: reduction='valid' needs lens1 (cap_lens - 1)")
+            if torch.is_tensor(lens1) and lens1.is_cuda:
+                if tuple(lens1.shape) != (R,):
+                    raise ValueError(f"KLObjective: lens1 of shape {tuple(lens1.shape)} for {R} rows")
+                lens_d = lens1.to(torch.long).contiguous()
+                D = int(lens_d.clamp(0, T).sum()) if divisor is None else int(divisor)      # (the one read-back)
+            else:
+                host = np.asarray(lens1.cpu() if torch.is_tensor(lens1) else lens1)
+                if host.shape != (R,) or host.dtype.kind not in "iu":
+                    raise ValueError(f"KLObjective: lens1 must be {R} integers, got shape {host.shape}, dtype {host.dtype}")
+                if host.min() < 0 or host.max() > T:
+                    raise ValueError(f"KLObjective: lens1 outside [0, {T}]")
+                D = int(host.sum())
+                if divisor is not None and int(divisor) != D:
+                    raise ValueError(f"KLObjective: divisor {divisor} is not sum(lens1) = {D}")
+            if not 1 <= D <= R * T:
+                raise ValueError(f"KLObjective: {D} valid cells (D == 0: a batch of nothing but padding has no mean)")
+            if lens_d is None:
+                lens_d = _lib.h2d(torch.as_tensor(host.astype(np.int64)), mu_q.device)
+        kl, kl_raw, dims, steps, n_open = _KLObjectiveFn.apply(mu_q, lv_q, mu_p, lv_p, lens_d, D, self.free_bits,
+                                                               self.free_bits_over == "cell")
+        self.last = {"kl_raw": kl_raw, "kl_dims": dims, "kl_steps": steps, "gates_open": n_open}
+        return kl
+
+
 class _MSEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):

@@ -24,7 +24,7 @@ import torch.distributed as dist
 
 from . import _lib, streams
 from .optim import FlatOptimizer, check_group, resolve
-from .train_util import LabelSmoothingLoss, MSELoss, Normal_kl_loss, combine_losses
+from .train_util import KLObjective, LabelSmoothingLoss, MSELoss, Normal_kl_loss, combine_losses
 
 
 class FlatGradExchange:
@@ -107,6 +107,16 @@ def kl_weight_for(epoch, epochs, beta):
     return max(0.5, float(epoch) / epochs * beta)
 
 
+def kl_weight_cyclical(step, cycle_steps, ratio=0.5, beta=1.0, floor=0.0):
+    """Cyclical KL weight (Fu et al. 2019): within each cycle of ``cycle_steps`` steps the weight rises linearly from ``floor``
+    to ``beta`` over the first ``ratio`` of the cycle, then holds ``beta`` until the cycle ends and the next starts at ``floor``
+    again.  ``step`` counts from 0.  A host function, as ``kl_weight_for``: its value goes to ``TrainStep.step(kl_weight=)``."""
+    if cycle_steps < 1 or not 0.0 < ratio <= 1.0 or step < 0:
+        raise ValueError(f"kl_weight_cyclical: step {step} >= 0, cycle_steps {cycle_steps} >= 1 and 0 < ratio {ratio} <= 1 wanted")
+    pos = (step % cycle_steps) / float(cycle_steps)            # where in the cycle, [0, 1)
+    return float(floor + (beta - floor) * min(1.0, pos / ratio))
+
+
 def _group_property(key):
     def get(self):
         return self.optimizer.param_groups[0].get(key)
@@ -121,7 +131,15 @@ class TrainStep:
     conf["optimizer"] / conf["optimizer_args"]: "Adam", "AdamW" or "SGD" with torch's arguments and torch's defaults
     (``lr`` defaults to 5e-4 for all three; ``betas`` / ``eps`` / ``weight_decay`` given here are overridden by the same
     key in ``optimizer_args``).  ``self.optimizer`` is a ``torch.optim.Optimizer`` (acvae_amd.optim.FlatOptimizer) that LR
-    schedulers can drive; ``lr``, ``betas``, ``eps`` and ``weight_decay`` are views of its param group."""
+    schedulers can drive; ``lr``, ``betas``, ``eps`` and ``weight_decay`` are views of its param group.
+
+    ``kl_reduction`` / ``free_bits`` / ``free_bits_over``: the variational term (``acvae_amd.train_util.KLObjective``).  With the
+    defaults ("all", None) it is the reference's ``Normal_kl_loss``, the mean over all N x (Tc - 1) positions, padded ones
+    included, by the launches it always was.  ``kl_reduction="valid"`` averages over the positions the
+    cross-entropy runs over; ``free_bits=lam`` clamps the KL from below per latent dimension ("dim") or per position
+    ("cell").  ``parts`` then also carries the device diagnostics ``kl_raw``, ``kl_dims``, ``kl_steps`` and ``gates_open``.
+    Under data parallelism the divisor D is the rank's own count of positions, the rule the cross-entropy already follows
+    (each rank averages over its own tokens and the gradients are averaged over ranks).  ``scst_step`` has no KL term."""
 
     lr = _group_property("lr")
     betas = _group_property("betas")
@@ -130,7 +148,9 @@ class TrainStep:
 
     def __init__(self, model, vocab_size, lr=5e-4, betas=None, eps=None, weight_decay=None, max_grad_norm=1.0,
                  label_smoothing=True, smoothing=0.1, alpha=1.0, global_loss="MSE", process_group=None,
-                 broadcast_buffers=True, data_parallel=True, precision=None, optimizer="Adam", optimizer_args=None):
+                 broadcast_buffers=True, data_parallel=True, precision=None, optimizer="Adam", optimizer_args=None,
+                 kl_reduction="all", free_bits=None, free_bits_over="dim"):
+        kl_objective = KLObjective(kl_reduction, free_bits, free_bits_over)      # (refuses bad values before anything is built)
         group = resolve(optimizer, optimizer_args, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.optimizer_name = optimizer
         self.model = model
@@ -143,7 +163,8 @@ class TrainStep:
         if alpha is not None and global_loss != "MSE":
             raise NotImplementedError("global_loss other than 'MSE' (the shipped q_logs_utt/p_logs_utt are None)")
         self.criterion = LabelSmoothingLoss(vocab_size, self.smoothing)
-        self.kl_loss = Normal_kl_loss()
+        self.kl_objective = None if (kl_reduction == "all" and free_bits is None) else kl_objective
+        self.kl_loss = Normal_kl_loss() if self.kl_objective is None else self.kl_objective
         self.mse_loss = MSELoss()
         self.pg = process_group
         self.data_parallel = data_parallel          # False: a purely local step inside an initialised process group
@@ -310,12 +331,22 @@ class TrainStep:
         caps_src = staged.get("caps_d")
         targets = (caps if caps_src is None else caps_src)[:, 1:1 + out["logits"].shape[1]].to(torch.long)
         ce = self.criterion.masked(out["logits"], targets, lens1)     # == criterion(packed_logits, packed targets)
-        kl = self.kl_loss(out["q_means"], out["q_logs"], out["p_means"], out["p_logs"])
+        diag = {}
+        if self.kl_objective is None:
+            kl = self.kl_loss(out["q_means"], out["q_logs"], out["p_means"], out["p_logs"])
+        else:                                       # D from the host's lengths: nothing is read back
+            T = out["q_means"].shape[1]
+            host = np.clip(np.asarray(cap_lens).astype(np.int64) - 1, 0, T)
+            if torch.is_tensor(lens1) and lens1.is_cuda:
+                kl = self.kl_objective(out["q_means"], out["q_logs"], out["p_means"], out["p_logs"], lens1, divisor=int(host.sum()))
+            else:
+                kl = self.kl_objective(out["q_means"], out["q_logs"], out["p_means"], out["p_logs"], host)
+            diag = dict(self.kl_objective.last)
         mse = None
         if self.alpha is not None:
             mse = self.mse_loss(out["q_means_utt"], out["p_means_utt"])
         loss = combine_losses(ce, kl, mse, kl_weight, self.alpha if self.alpha is not None else 0.0)    # ce + w kl + alpha mse
-        return loss, {"ce": ce.detach(), "kl": kl.detach(), "mse": None if mse is None else mse.detach()}, out
+        return loss, {"ce": ce.detach(), "kl": kl.detach(), "mse": None if mse is None else mse.detach(), **diag}, out
 
     def prefetch(self, feats_host):
         """Queue the upload of a LATER step's feature batch now, on a copy stream of its own: the 8 MB host-to-device copy

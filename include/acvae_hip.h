@@ -1298,6 +1298,56 @@ int acvae_caption_terms(const float* logits, int64_t ld_n, int64_t ld_t, const i
 int acvae_caption_sums(const float* logprob, const int32_t* rank, const float* kl, const int64_t* lens1, double* nll,
                        double* kl_sum, int32_t* tokens, int32_t* hit1, int32_t* hit5, int R, int T, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The variational term of the training objective: KL over a chosen set of cells, free bits, per-dimension and per-step
+ * diagnostics (csrc/kl_objective.hip; acvae_amd/train_util.py: KLObjective is the front).  acvae_gauss_kl_fwd / bwd above
+ * stay the reference's Normal_kl_loss, which averages over padded positions too (F8); the reference has no masked form in
+ * use and no free bits.
+ *
+ * mu_q / lv_q / mu_p / lv_p f32 [R, T, E] contiguous (posterior mean and log-variance, prior mean and log-variance).
+ * lens1 int64 [R] (cap_lens - 1) or NULL.  Per element
+ *   k[r,t,e] = lv_p/2 - lv_q/2 + (exp(lv_q) + (mu_q - mu_p)^2) / (2 exp(lv_p)) - 1/2
+ * evaluated in FLOAT64 (as acvae_caption_terms' kl; exactly 0 where q == p bit for bit).  The cell set S and divisor D:
+ *   lens1 NULL:  every (r, t), and D must be R * T;
+ *   lens1 given: the cells with t < lens1[r] (0 allowed, a value > T counts as T), and D is the caller's sum of those
+ *                counts, 1 <= D <= R * T: the host knows the lengths, so nothing is read back.
+ * With m_e = (1/D) sum_{c in S} k[c,e] and s_c = sum_e k[c,e]:
+ *   free_bits == 0:                 kl = sum_e m_e                      (over_cell only chooses what gates_open counts)
+ *   free_bits != 0, over_cell == 0: kl = sum_e max(m_e, lam)            gates u8 [E]:     m_e > lam
+ *   free_bits != 0, over_cell != 0: kl = (1/D) sum_{c in S} max(s_c, lam)   gates u8 [R * T]: c in S and s_c > lam
+ * The gate is strict (a tie is closed); a NaN m_e or s_c makes kl NaN and its gate closed.  lam >= 0 and finite.
+ * Outputs, all written by the forward and none read back: kl f32 [1]; kl_raw f32 [1] = sum_e m_e whatever the free bits;
+ * kl_dims f32 [E] = m_e; kl_steps f32 [T] = the mean of s_c over the rows r with (r, t) in S, 0 for a step with none;
+ * gates_open i32 [1] = the number of open gates (free_bits == 0: E, or the number of cells of S if over_cell); gates as
+ * above (free_bits == 0: not written, may be NULL).
+ * Cells outside S are not read: a NaN or inf there changes nothing, forward or backward.
+ * Three launches in stream order (slab partials; per-dimension and per-step finish; scalar); all sums in float64 in a
+ * fixed order: the cells of a slab of ACVAE_KL_OBJECTIVE_SLAB consecutive cells, then the slabs ascending; a cell's
+ * columns in groups of four per lane, then the lanes' butterfly.  No atomics, no hand-off inside a launch, every output
+ * element stored once, bit-reproducible.  `scratch` holds acvae_kl_objective_scratch_bytes(R, T, E) bytes (8-byte aligned,
+ * ACVAE_EALIGN otherwise); every word that is read was written by the same call, so its contents on entry do not matter.
+ * 16-byte loads when E % 4 == 0 and the four bases are 16-byte aligned, scalar loads otherwise with the same order of
+ * additions (the same bits); any E >= 1.
+ * ACVAE_EINVAL before any launch: a NULL input or output (gates with free bits), R, T or E < 1, R * T >= 2^31, D outside
+ * [1, R * T] or != R * T without lens1, lam negative, NaN or inf with free bits.  Then ACVAE_EWORKSPACE for a scratch that
+ * is too small, also before any HIP call.
+ *
+ * acvae_kl_objective_bwd: one elementwise launch.  With g = grad_out[0] / D (fp32, as acvae_gauss_kl_bwd with D for rows)
+ *   dmu_q = g d / v_p   dlv_q = g (-1/2 + v_q / (2 v_p))   dmu_p = -g d / v_p   dlv_p = g (1/2 - (v_q + d^2) / (2 v_p))
+ * (d = mu_q - mu_p, v = exp(lv)) where the cell is in S and its gate is open (gates NULL: no free bits; over_cell says
+ * whether gates is per cell or per dimension); exact zeros elsewhere, without reading the inputs of a cell that is outside S
+ * or closed.  Any of the four outputs may be NULL (all four: nothing is launched).  lens1 and D as in the forward.
+ * ------------------------------------------------------------------------------------------- */
+#define ACVAE_KL_OBJECTIVE_SLAB 8
+int64_t acvae_kl_objective_scratch_bytes(int R, int T, int E);
+int acvae_kl_objective_fwd(const float* mu_q, const float* lv_q, const float* mu_p, const float* lv_p,
+                           const int64_t* lens1, int64_t D, int free_bits, int over_cell, double lam, float* kl,
+                           float* kl_raw, float* kl_dims, float* kl_steps, int32_t* gates_open, uint8_t* gates,
+                           void* scratch, int64_t scratch_bytes, int R, int T, int E, void* stream);
+int acvae_kl_objective_bwd(const float* mu_q, const float* lv_q, const float* mu_p, const float* lv_p,
+                           const int64_t* lens1, int64_t D, int over_cell, const uint8_t* gates, const float* grad_out,
+                           float* dmu_q, float* dlv_q, float* dmu_p, float* dlv_p, int R, int T, int E, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
