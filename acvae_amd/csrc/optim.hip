@@ -245,3 +245,79 @@ extern "C" int acvae_sgd_step(float* params, const float* grads, float* momentum
   A.grad_scale = grad_scale; A.max_norm = max_grad_norm; A.total_norm = total_norm;
   return launch_opt(OPT_SGD, mom, A, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Gradient accumulation and the weight EMA of TrainStep(accum_steps=, ema_decay=): two more streaming passes over the flat
+// buffers.  float4 main loop, scalar tail in block 0 (as sqsum_kernel), grid-stride under ACVAE_FLAT_BLOCKS_CAP blocks
+// (256 CUs x 8 blocks).  Every element is stored once; no atomics, no workspace.  Bytes per element: accumulate 12
+// (8 with first: acc is not read), EMA 12.
+// kernel-resource-usage (gfx950, -O3): accumulate_kernel<true> 12 VGPRs / 24 SGPRs, accumulate_kernel<false> 18 / 26,
+// ema_kernel 26 / 30; no scratch, no LDS, occupancy 8 waves per SIMD for all three.
+namespace {
+constexpr int FLAT_BLOCKS = ACVAE_FLAT_BLOCKS_CAP;
+
+template <bool FIRST>
+__global__ __launch_bounds__(TH) void accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, long n) {
+  const long n4 = n >> 2;
+  float4* a4 = reinterpret_cast<float4*>(acc);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  for (long i = blockIdx.x * (long)TH + threadIdx.x; i < n4; i += (long)gridDim.x * TH) {
+    float4 v = g4[i];
+    if (!FIRST) {
+      const float4 a = a4[i];
+      v.x = a.x + v.x; v.y = a.y + v.y; v.z = a.z + v.z; v.w = a.w + v.w;
+    }
+    a4[i] = v;
+  }
+  if (blockIdx.x == 0)
+    for (long i = (n4 << 2) + threadIdx.x; i < n; i += TH) acc[i] = FIRST ? g[i] : acc[i] + g[i];
+}
+
+__global__ __launch_bounds__(TH) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float w) {
+  const long n4 = n >> 2;
+  float4* e4 = reinterpret_cast<float4*>(ema);
+  const float4* p4 = reinterpret_cast<const float4*>(p);
+  for (long i = blockIdx.x * (long)TH + threadIdx.x; i < n4; i += (long)gridDim.x * TH) {
+    float4 e = e4[i];
+    const float4 v = p4[i];
+    e.x = lerp_t(e.x, v.x, w); e.y = lerp_t(e.y, v.y, w); e.z = lerp_t(e.z, v.z, w); e.w = lerp_t(e.w, v.w, w);
+    e4[i] = e;
+  }
+  if (blockIdx.x == 0)
+    for (long i = (n4 << 2) + threadIdx.x; i < n; i += TH) ema[i] = lerp_t(ema[i], p[i], w);
+}
+
+// [a, a + n) and [b, b + n) floats share a byte
+bool ranges_overlap(const float* a, const float* b, int64_t n) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  const uintptr_t bytes = (uintptr_t)n * sizeof(float);
+  return x < y ? y - x < bytes : x - y < bytes;
+}
+
+int flat_blocks(int64_t n) {
+  long nb = (n / 4 + TH - 1) / TH;
+  if (nb < 1) nb = 1;
+  if (nb > FLAT_BLOCKS) nb = FLAT_BLOCKS;
+  return (int)nb;
+}
+}  // namespace
+
+extern "C" int acvae_grad_accumulate(float* acc, const float* grads, int64_t n, int first, void* stream) {
+  if (!acc || !grads || n <= 0 || ranges_overlap(acc, grads, n)) return ACVAE_EINVAL;
+  if (!aligned16(acc) || !aligned16(grads)) return ACVAE_EALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  if (first) hipLaunchKernelGGL(accumulate_kernel<true>, dim3(flat_blocks(n)), dim3(TH), 0, st, acc, grads, (long)n);
+  else hipLaunchKernelGGL(accumulate_kernel<false>, dim3(flat_blocks(n)), dim3(TH), 0, st, acc, grads, (long)n);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_ema_step(float* ema, const float* params, int64_t n, double decay, void* stream) {
+  if (!ema || !params || n <= 0 || !(decay >= 0.0 && decay <= 1.0) || ranges_overlap(ema, params, n)) return ACVAE_EINVAL;
+  if (!aligned16(ema) || !aligned16(params)) return ACVAE_EALIGN;
+  // 1 - decay is formed in double and rounded once, as the optimisers' 1 - beta
+  hipLaunchKernelGGL(ema_kernel, dim3(flat_blocks(n)), dim3(TH), 0, (hipStream_t)stream, ema, params, (long)n,
+                     (float)(1.0 - decay));
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}

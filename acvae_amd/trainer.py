@@ -14,6 +14,7 @@ acvae_amd/optim.py) — with the MI355X-specific plumbing:
     reference uses plain BatchNorm2d) and rank 0's running buffers are broadcast before each forward
     (DDP's default broadcast_buffers=True).
 """
+import collections
 import contextlib
 import math
 import os
@@ -117,6 +118,22 @@ def kl_weight_cyclical(step, cycle_steps, ratio=0.5, beta=1.0, floor=0.0):
     return float(floor + (beta - floor) * min(1.0, pos / ratio))
 
 
+def ema_decay_at(decay, t, warmup=False):
+    """The EMA decay of the update that follows ``t`` applied updates: ``decay``, or with ``warmup`` min(decay, (1 + t) /
+    (10 + t)) (the first update averages with 1/10, the tenth with 10/19, ...).  A host float: nothing is synchronised."""
+    return min(float(decay), (1.0 + t) / (10.0 + t)) if warmup else float(decay)
+
+
+def check_accumulation(accum_steps, ema_decay, ema_warmup):
+    """ValueError for what TrainStep(accum_steps=, ema_decay=, ema_warmup=) refuses; host arithmetic only."""
+    if isinstance(accum_steps, bool) or not isinstance(accum_steps, (int, np.integer)) or accum_steps < 1:
+        raise ValueError(f"accum_steps must be an integer >= 1, not {accum_steps!r}")
+    if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+        raise ValueError(f"ema_decay must lie in [0, 1), not {ema_decay!r}")
+    if ema_warmup and ema_decay is None:
+        raise ValueError("ema_warmup=True needs ema_decay")
+
+
 def _group_property(key):
     def get(self):
         return self.optimizer.param_groups[0].get(key)
@@ -139,7 +156,24 @@ class TrainStep:
     cross-entropy runs over; ``free_bits=lam`` clamps the KL from below per latent dimension ("dim") or per position
     ("cell").  ``parts`` then also carries the device diagnostics ``kl_raw``, ``kl_dims``, ``kl_steps`` and ``gates_open``.
     Under data parallelism the divisor D is the rank's own count of positions, the rule the cross-entropy already follows
-    (each rank averages over its own tokens and the gradients are averaged over ranks).  ``scst_step`` has no KL term."""
+    (each rank averages over its own tokens and the gradients are averaged over ranks).  ``scst_step`` has no KL term.
+
+    ``accum_steps=k`` (k > 1): every call of ``step()`` / ``scst_step()`` is one micro-step.  Its backward writes the flat
+    gradient buffer as always and ``acvae_grad_accumulate`` adds that to a second flat buffer, ``flat_acc``; the first k - 1
+    micro-steps of a window stop there (``parts["applied"]`` is False, no ``grad_norm``), the k-th clips and applies the MEAN
+    of the window's gradients, each micro-step normalised over its own tokens: torch's ``(loss / k).backward()`` idiom, and the
+    rule the ranks of a data-parallel step follow.  ``step_count``, Adam's bias correction and LR schedulers count applied
+    updates; BatchNorm running statistics move at every micro-step.  A parameter is left alone by the update only if no
+    micro-step of the window gave it a gradient.  ``flush()`` applies a window that is not full (the end of an epoch).  Under
+    data parallelism only the k-th micro-step (or ``flush()``) exchanges gradients: one all-reduce of ``flat_acc`` behind the
+    last accumulate launch, in pieces of ``exchange.max_chunk`` elements, not overlapped with the backward.
+
+    ``ema_decay=d``: ``flat_ema``, an exponential moving average of the whole flat parameter buffer, moved by one
+    ``acvae_ema_step`` behind every applied update with decay d (``ema_warmup=True``: ``ema_decay_at``).  ``ema_weights()``
+    runs the model on it, ``ema_state_dict()`` / ``load_ema_state_dict()`` checkpoint it.  Every rank of a data-parallel job
+    computes the same average from the same parameters.
+
+    With ``accum_steps=1`` and ``ema_decay=None`` neither buffer exists and a step is the launches it always was."""
 
     lr = _group_property("lr")
     betas = _group_property("betas")
@@ -149,7 +183,15 @@ class TrainStep:
     def __init__(self, model, vocab_size, lr=5e-4, betas=None, eps=None, weight_decay=None, max_grad_norm=1.0,
                  label_smoothing=True, smoothing=0.1, alpha=1.0, global_loss="MSE", process_group=None,
                  broadcast_buffers=True, data_parallel=True, precision=None, optimizer="Adam", optimizer_args=None,
-                 kl_reduction="all", free_bits=None, free_bits_over="dim"):
+                 kl_reduction="all", free_bits=None, free_bits_over="dim", accum_steps=1, ema_decay=None, ema_warmup=False):
+        check_accumulation(accum_steps, ema_decay, ema_warmup)                   # (before anything is built)
+        self.accum_steps = int(accum_steps)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.micro_count = 0                        # position inside the accumulation window
+        self.ema_updates = 0                        # applied updates the average has seen (ema_warmup's t)
+        self._window_skipped = None                 # ranges without a gradient in EVERY micro-step of the window so far
+        self._in_ema = False
         kl_objective = KLObjective(kl_reduction, free_bits, free_bits_over)      # (refuses bad values before anything is built)
         group = resolve(optimizer, optimizer_args, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.optimizer_name = optimizer
@@ -185,7 +227,8 @@ class TrainStep:
         #   3 the last ConvBlock (72 % of Cnn10's encoder gradients, 14 MB): from acvae_encoder_bwd_hooked's callback
         #     right after that block's kernels are queued, while the shallower blocks still run.
         # Buckets over 32 MB go out in 32 MB pieces.
-        self.exchange = FlatGradExchange(self.flat_g, [self.n_text_dec, self.n_text - self.n_text_dec,
+        # With accum_steps > 1 the same buckets lie over flat_acc and go out behind the window's last accumulate launch.
+        self.exchange = FlatGradExchange(self._grad_src, [self.n_text_dec, self.n_text - self.n_text_dec,
                                                        self.n_enc - self.n_enc_deep, self.n_enc_deep], process_group)
         if self.world == 1:
             self.exchange.world = 1
@@ -208,6 +251,7 @@ class TrainStep:
             dist.broadcast(self.flat_p, src=0, group=self.pg)
             if self.flat_buf is not None:
                 dist.broadcast(self.flat_buf, src=0, group=self.pg)
+        self.flat_ema = None if self.ema_decay is None else self.flat_p.clone()      # (after rank 0's parameters arrived)
 
     def _dist(self):
         return self.data_parallel and dist.is_available() and dist.is_initialized() and \
@@ -270,6 +314,9 @@ class TrainStep:
                 v = self.flat_buf[off:off + b.numel()].view_as(b)
                 v.copy_(b.data); b.data = v
                 off += b.numel()
+        # accumulation: the buffer the window's gradients are summed in; the norm and the update then read it instead of flat_g
+        self.flat_acc = torch.zeros(total, device=dev) if self.accum_steps > 1 else None
+        self._grad_src = self.flat_g if self.flat_acc is None else self.flat_acc
         self.norm_partials = torch.empty(_lib.call("acvae_grad_norm_partials"), device=dev)
         self.total_norm = torch.zeros(1, device=dev)
 
@@ -279,7 +326,11 @@ class TrainStep:
         its kernels: ("decode", event) after acvae_decode_bwd unless it left gradients trailing on the side stream
         (`event` = recorded behind its last kernel), "text" after the posterior backward (every text-side gradient is
         queued now), ("encoder_block", b) from acvae_encoder_bwd_hooked after ConvBlock b, "encoder" when the encoder
-        is through.  The order of these calls is fixed by the autograd graph, hence identical on every rank."""
+        is through.  The order of these calls is fixed by the autograd graph, hence identical on every rank.
+        With accum_steps > 1 nothing is exchanged from inside a backward (DDP's no_sync): flat_acc goes out behind the
+        window's last accumulate launch (_apply_window)."""
+        if self.accum_steps > 1:
+            return
         if tag == "decode":
             self._decode_event = event
             if not self._proj_emb:               # with projected embeddings their gradients are still to come ("projemb")
@@ -393,6 +444,7 @@ class TrainStep:
         if frontend is not None:                    # first: a refused call touches nothing of the step's state
             from .frontend import refuse_augment
             refuse_augment(augment)
+        self._refuse_inside_ema("step")
         self.sync_buffers()
         ready = getattr(feats, "_acvae_ready", None)
         if ready is not None:                       # a batch uploaded by prefetch(): order this step behind its copy
@@ -423,6 +475,7 @@ class TrainStep:
             raise NotImplementedError("data-parallel SCST: the gradient exchange waits for the posterior's bucket, which a "
                                       "rollout never announces; run scst_step in a single process")
         from .seq_train_model import NScstWrapper, ScstWrapper
+        self._refuse_inside_ema("scst_step")
         self.sync_buffers()
         self._decode_event = self._decode_aux_event = self._text_event = None
         self._decode_deferred = self._projemb_seen = False
@@ -441,25 +494,24 @@ class TrainStep:
     def _backward_and_update(self, loss, parts):
         self.exchange.begin()
         loss.backward()
-        gscale = self.exchange.finish()
-        skipped = self._check_grad_aliasing()
-        st = _lib.current_stream()
-        n = self.n_active
-        tn = None
-        if self.max_grad_norm is not None and self.max_grad_norm > 0:
-            _lib.call("acvae_grad_norm", self.flat_g, n, gscale, self.norm_partials, self.total_norm, st)
-            tn = self.total_norm
-        self.step_count += 1
-        self._pending = (gscale, tn, skipped, st)
-        try:
-            self.optimizer.step()                  # the instance attribute: an LR scheduler's step tracking sees the call
-        finally:
-            self._pending = None
-            # the fused update writes the flat parameter buffer through raw pointers: no _version moves, so what the model
-            # caches per weight (attention projections of the step API, projected embedding table) is dropped by hand
-            self.model.drop_step_caches()
-        parts["loss"] = loss.detach()
-        parts["grad_norm"] = self.total_norm
+        if self.accum_steps == 1:
+            gscale = self.exchange.finish()
+            self._update(self._check_grad_aliasing(), gscale, _lib.current_stream())
+            parts["loss"] = loss.detach()
+            parts["grad_norm"] = self.total_norm
+        else:
+            # one micro-step: the backward has written flat_g (and its trailing work on the second stream is joined to the
+            # current stream, as for the norm); add it to the window's sum where the norm would be launched
+            skipped = set(self._check_grad_aliasing())
+            _lib.call("acvae_grad_accumulate", self.flat_acc, self.flat_g, self.n_active, int(self.micro_count == 0),
+                      _lib.current_stream())
+            self._window_skipped = skipped if self.micro_count == 0 else self._window_skipped & skipped
+            self.micro_count += 1
+            parts["loss"] = loss.detach()
+            parts["applied"] = self.micro_count == self.accum_steps
+            if parts["applied"]:
+                self._apply_window()
+                parts["grad_norm"] = self.total_norm
         # DDP's broadcast_buffers: rank 0's BatchNorm running statistics reach the other ranks before the next forward
         # touches them.  Issued here, behind this step's kernels and off the next step's critical path; joined by
         # sync_buffers() at the start of the next step (or by the caller before an evaluation pass).
@@ -479,6 +531,47 @@ class TrainStep:
                 _lib.check_persist_status(self.flat_p.device)
         return parts
 
+    def _update(self, skipped, gscale, st):
+        """Norm of gscale * (the gradient buffer), the fused update with the clip coefficient from it, and the EMA."""
+        tn = None
+        if self.max_grad_norm is not None and self.max_grad_norm > 0:
+            _lib.call("acvae_grad_norm", self._grad_src, self.n_active, gscale, self.norm_partials, self.total_norm, st)
+            tn = self.total_norm
+        self.step_count += 1
+        self._pending = (gscale, tn, skipped, st)
+        try:
+            self.optimizer.step()                  # the instance attribute: an LR scheduler's step tracking sees the call
+        finally:
+            self._pending = None
+            # the fused update writes the flat parameter buffer through raw pointers: no _version moves, so what the model
+            # caches per weight (attention projections of the step API, projected embedding table) is dropped by hand
+            self.model.drop_step_caches()
+        if self.flat_ema is not None:
+            d = ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup)
+            _lib.call("acvae_ema_step", self.flat_ema, self.flat_p, self.flat_p.numel(), d, st)
+            self.ema_updates += 1
+
+    def _apply_window(self):
+        """Close the accumulation window of ``micro_count`` micro-steps: all-reduce flat_acc (data parallel), then the norm
+        and the update with grad_scale 1 / (micro_count * world): the mean over micro-steps and ranks."""
+        m, self.micro_count = self.micro_count, 0
+        skipped, self._window_skipped = sorted(self._window_skipped), None
+        # every bucket of flat_acc behind an event recorded on this stream now, i.e. behind the accumulate launch
+        self.exchange.begin()
+        self.exchange.finish()
+        self._update(skipped, 1.0 / (m * self.exchange.world), _lib.current_stream())
+
+    def flush(self):
+        """Apply the micro-steps accumulated so far as one update (a window cut short, e.g. by the end of an epoch): the mean
+        over those ``micro_count`` micro-steps.  Returns {"applied": True, "grad_norm": device scalar}, or None when the
+        window is empty (or accum_steps == 1) and nothing was done.  Under data parallelism it issues the exchange, so every
+        rank must call it at the same point, with the same number of micro-steps behind it."""
+        self._refuse_inside_ema("flush")
+        if self.micro_count == 0:
+            return None
+        self._apply_window()
+        return {"applied": True, "grad_norm": self.total_norm}
+
     def _apply_update(self):
         """The fused update of the step that step() is running, with the hyperparameters of param_groups[0] as they are
         now (host floats: no synchronisation)."""
@@ -497,7 +590,7 @@ class TrainStep:
             # buffer exists, so that every launch has one `first` flag
             segs = self._sgd_segments(skipped, n) if mom != 0 else [(a, b, False) for a, b in self._segments(skipped, n)]
             for a, b, first in segs:
-                _lib.call("acvae_sgd_step", self.flat_p[a:b], self.flat_g[a:b],
+                _lib.call("acvae_sgd_step", self.flat_p[a:b], self._grad_src[a:b],
                           self.momentum_buffer[a:b] if mom != 0 else None, b - a, g["lr"], mom, g["dampening"],
                           g["weight_decay"], int(bool(g["nesterov"])), int(first), gscale, mg, tn, st)
             if mom != 0:
@@ -511,10 +604,10 @@ class TrainStep:
         # On this path every parameter gets a gradient every step and the loop runs once over the whole buffer.
         for a, b in self._segments(skipped, n):
             if not g["amsgrad"] and not g["decoupled_weight_decay"]:
-                _lib.call("acvae_adam_step", self.flat_p[a:b], self.flat_g[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b],
+                _lib.call("acvae_adam_step", self.flat_p[a:b], self._grad_src[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b],
                           b - a, g["lr"], b1, b2, g["eps"], g["weight_decay"], self.step_count, gscale, mg, tn, st)
             else:
-                _lib.call("acvae_adamw_step", self.flat_p[a:b], self.flat_g[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b],
+                _lib.call("acvae_adamw_step", self.flat_p[a:b], self._grad_src[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b],
                           self.max_exp_avg_sq[a:b] if g["amsgrad"] else None, b - a, g["lr"], b1, b2, g["eps"],
                           g["weight_decay"], int(bool(g["decoupled_weight_decay"])), int(bool(g["amsgrad"])),
                           self.step_count, gscale, mg, tn, st)
@@ -586,7 +679,76 @@ class TrainStep:
         return segs
 
     def state_dict(self):
-        return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+        sd = {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+        if self.flat_ema is not None:
+            sd["ema"], sd["ema_updates"] = self.flat_ema, self.ema_updates
+        if self.accum_steps > 1:
+            sd["micro_count"] = self.micro_count
+        return sd
+
+    # ------------------------------------------------------------------ the averaged weights
+    def _refuse_inside_ema(self, what):
+        if self._in_ema:
+            raise RuntimeError(f"TrainStep.{what}() inside ema_weights(): the model holds the averaged weights; leave the "
+                               "context before training on")
+
+    def _swap_ema(self):
+        tmp = self.flat_p.clone()
+        self.flat_p.copy_(self.flat_ema)
+        self.flat_ema.copy_(tmp)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with ts.ema_weights(): validate(model)``: the model on the averaged weights.  The contents of the flat parameter
+        buffer and of ``flat_ema`` change places (every ``p.data`` view stays what it is), what the model caches per weight is
+        dropped and a pending BatchNorm-buffer broadcast is joined; on exit, also when the body raised, the training weights
+        are back bit for bit.  ``step()``, ``scst_step()`` and ``flush()`` raise RuntimeError inside.  The BatchNorm running
+        statistics are the live ones: they are moving averages of the training run already, and are not averaged again."""
+        if self.flat_ema is None:
+            raise RuntimeError("TrainStep.ema_weights() needs TrainStep(..., ema_decay=)")
+        self._refuse_inside_ema("ema_weights")
+        self.sync_buffers()
+        self._swap_ema()
+        self._in_ema = True
+        self.model.drop_step_caches()
+        try:
+            yield self.model
+        finally:
+            self._swap_ema()
+            self._in_ema = False
+            self.model.drop_step_caches()
+
+    def ema_state_dict(self):
+        """The averaged parameters as clones in ``model.state_dict()``'s layout and names, with the live buffers (and any
+        parameter outside the flat buffer as it is): loads into the reference's model."""
+        if self.flat_ema is None:
+            raise RuntimeError("TrainStep.ema_state_dict() needs TrainStep(..., ema_decay=)")
+        self._refuse_inside_ema("ema_state_dict")
+        table, named = self._offsets(), dict(self.model.named_parameters())
+        out = collections.OrderedDict()
+        for k, v in self.model.state_dict().items():
+            p = named.get(k)
+            if p is not None and p in table:
+                out[k] = self.flat_ema[table[p]:table[p] + p.numel()].view_as(p).clone()
+            else:
+                out[k] = v.detach().clone()
+        return out
+
+    def load_ema_state_dict(self, sd):
+        """Inverse of ``ema_state_dict``: the parameters of ``sd`` become the average.  Its buffers are not read (they are the
+        model's own, which ``model.load_state_dict`` restores)."""
+        if self.flat_ema is None:
+            raise RuntimeError("TrainStep.load_ema_state_dict() needs TrainStep(..., ema_decay=)")
+        self._refuse_inside_ema("load_ema_state_dict")
+        table = self._offsets()
+        todo = [(k, p) for k, p in self.model.named_parameters() if p in table]
+        for k, p in todo:
+            if k not in sd:
+                raise KeyError(f"load_ema_state_dict: no {k!r}")
+            if tuple(sd[k].shape) != tuple(p.shape):
+                raise ValueError(f"load_ema_state_dict: {k!r} has shape {tuple(sd[k].shape)}, the parameter {tuple(p.shape)}")
+        for k, p in todo:
+            self.flat_ema[table[p]:table[p] + p.numel()].copy_(sd[k].reshape(-1))
 
     # ------------------------------------------------------------------ checkpoint in the reference's format
     def _offsets(self):

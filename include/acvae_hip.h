@@ -800,6 +800,21 @@ int acvae_adamw_step(float* params, const float* grads, float* exp_avg, float* e
 int acvae_sgd_step(float* params, const float* grads, float* momentum_buffer, int64_t n, double lr, double momentum,
                    double dampening, double weight_decay, int nesterov, int first, float grad_scale, float max_grad_norm,
                    const float* total_norm, void* stream);
+/* Gradient accumulation and the exponential moving average of the weights (TrainStep(accum_steps=, ema_decay=)): one
+ * streaming pass each over flat fp32 buffers, grid-stride under ACVAE_FLAT_BLOCKS_CAP blocks of 256 threads with four
+ * elements per thread and trip.  Every element is stored once; no atomics, no workspace, no host synchronisation.
+ * Both: a NULL pointer, n <= 0, or [dst, dst + n) and [src, src + n) sharing a byte -> ACVAE_EINVAL; a base that is not
+ * 16-B aligned -> ACVAE_EALIGN; both before any launch.
+ * acvae_grad_accumulate: first != 0: acc[i] = grads[i], and acc is not read (whatever it held, NaN included, reaches
+ *   nothing); first == 0: acc[i] = acc[i] + grads[i], one IEEE fp32 addition per element.  The norm of the accumulated
+ *   gradient is acvae_grad_norm on acc, the mean over k micro-steps a grad_scale of 1 / k there and in the update.
+ * acvae_ema_step: ema[i] = lerp(ema[i], params[i], w), w = (float)(1.0 - decay), by torch's rule (w < 0.5 ?
+ *   ema + w * (params - ema) : params - (params - ema) * (1 - w)), the one torch.optim.swa_utils.get_ema_multi_avg_fn
+ *   applies.  decay outside [0, 1] or NaN -> ACVAE_EINVAL.  ema == params gives ema back, decay == 1 leaves ema as it
+ *   is, decay == 0 copies params. */
+#define ACVAE_FLAT_BLOCKS_CAP 2048
+int acvae_grad_accumulate(float* acc, const float* grads, int64_t n, int first, void* stream);
+int acvae_ema_step(float* ema, const float* params, int64_t n, double decay, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training-time augmentation, datasets/augment.py:time_roll + spec_augment's time_mask / freq_mask (:30-65), on the
