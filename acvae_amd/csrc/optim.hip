@@ -321,3 +321,247 @@ extern "C" int acvae_ema_step(float* ema, const float* params, int64_t n, double
   ACVAE_LAUNCH_CHECK();
   return ACVAE_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Parameter groups (TrainStep(param_groups=)): the norm and the update with up to ACVAE_OPT_MAX_GROUPS sets of
+// hyperparameters.  The host cuts the flat range into chunks of at most OPT_CHUNK elements that never leave a group
+// (include/acvae_hip.h has the table's layout); a workgroup walks chunks b, b + grid, ..., so everything it reads from the
+// table and from the per-group hyperparameters is uniform and sits in scalar registers.  The table (12 B per chunk) is
+// on the device; the hyperparameters, which change every step, are a by-value kernel argument like OptArgs.  The element
+// arithmetic is opt_elem itself and the derived scalars are formed as acvae_adamw_step / acvae_sgd_step form them, so a
+// chunk comes out bit for bit as the one-group kernel over its range would leave it.  Every slice is a multiple of four
+// elements: no scalar tail.  A chunk that does not fit (negative start, no length, group >= n_groups, unknown bits) is
+// skipped, a length above OPT_CHUNK or an end behind n is cut: a bad table is never followed.
+// kernel-resource-usage (gfx950, -O3), VGPRs / SGPRs / LDS bytes: sqsum_chunks_kernel 20 / 44 / 64, norm_groups_final_kernel
+// 48 / 24 / 16448, opt_groups_kernel<Adam, amsgrad> 45 / 68 / 0, <Adam> 39 / 64 / 0, <SGD, momentum> 32 / 58 / 0, <SGD> 22 / 41 / 0;
+// no scratch, occupancy 8 waves per SIMD for all six.
+#include "job_table.h"
+// The chunk size, by measurement at 28.6 M elements (profiles/r22_param_groups.txt; -DACVAE_OPT_CHUNK=C builds a candidate):
+// 4096 and 8192 make the finishing launch of the norm walk 7000 / 3500 table rows (20 / 12 us against 6), 32768 leaves 890
+// workgroups for 256 CUs and both streaming kernels lose 14 - 20 %; 16384 holds all three to the one-group kernels' times.
+#ifndef ACVAE_OPT_CHUNK
+#define ACVAE_OPT_CHUNK 16384
+#endif
+namespace {
+constexpr int OPT_CHUNK = ACVAE_OPT_CHUNK;                 // elements; a multiple of 4 * TH keeps every trip of a full chunk full
+constexpr int OPT_CHUNK4 = OPT_CHUNK / 4;
+constexpr int GROUP_BLOCKS = 4096;                         // as launch_opt
+static_assert(OPT_CHUNK % 4 == 0 && OPT_CHUNK > 0, "chunks count float4s");
+
+struct GroupHyper {                                        // OptArgs' per-group part, same meaning of every field
+  float lr, a, b, c, d, wd, decay, step_size, bc2_sqrt;
+};
+struct GroupedArgs {
+  float* p; const float* g; float* s0; float* s1; float* s2;
+  long n;
+  const int* chunks;
+  int n_chunks, n_groups;
+  int flags;                                               // OPT_F_DECOUPLED | OPT_F_NESTEROV; OPT_F_FIRST comes from the chunk
+  float grad_scale, max_norm;
+  const float* total_norm;
+  acvae::JobTable<GroupHyper, ACVAE_OPT_MAX_GROUPS> hyper;
+};
+
+// chunk c of the table -> [a, e) in float4s and the group; false: skip it.  Uniform over the workgroup.
+__device__ __forceinline__ bool read_chunk(const int* __restrict__ chunks, int c, int n_groups, long n4, long& a, long& e,
+                                           int& group, bool& first) {
+  const int start = chunks[3 * c], len = chunks[3 * c + 1], tag = chunks[3 * c + 2];
+  group = tag & (ACVAE_OPT_CHUNK_FIRST - 1);
+  first = (tag & ACVAE_OPT_CHUNK_FIRST) != 0;
+  if (start < 0 || len <= 0 || tag < 0 || (tag & ~(2 * ACVAE_OPT_CHUNK_FIRST - 1)) || group >= n_groups) return false;
+  a = start;
+  e = a + (len < OPT_CHUNK4 ? len : OPT_CHUNK4);
+  if (e > n4) e = n4;
+  return a < e;
+}
+
+__global__ __launch_bounds__(TH) void sqsum_chunks_kernel(const float* __restrict__ g, const int* __restrict__ chunks,
+                                                          int n_chunks, int n_groups, float* __restrict__ partials) {
+  __shared__ float red[16];
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    long a = 0, e = 0;
+    int group;
+    bool first;
+    float acc = 0.f;
+    // (the norm has no n: the table's own bounds are all there is, the length still cut to a chunk)
+    if (read_chunk(chunks, c, n_groups, 0x7fffffffL + OPT_CHUNK4, a, e, group, first))
+      for (long i = a + threadIdx.x; i < e; i += TH) {
+        const float4 v = g4[i];
+        acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+      }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) partials[c] = acc;               // a skipped chunk stores its zero: nothing of partials is read unset
+  }
+}
+
+// One workgroup.  Thread t adds chunks [t * per, (t + 1) * per) in ascending order into one float64 sum per group (a
+// select, not a product: a NaN stays in its group), thread 0 adds the threads' sums in ascending order and then the groups.
+__global__ __launch_bounds__(TH) void norm_groups_final_kernel(const float* __restrict__ partials,
+                                                               const int* __restrict__ chunks, int n_chunks, int n_groups,
+                                                               float scale, float* __restrict__ group_norms,
+                                                               float* __restrict__ total_norm) {
+  __shared__ double sums[ACVAE_OPT_MAX_GROUPS][TH + 1];
+  double acc[ACVAE_OPT_MAX_GROUPS];
+#pragma unroll
+  for (int k = 0; k < ACVAE_OPT_MAX_GROUPS; ++k) acc[k] = 0.0;
+  const int per = (n_chunks + TH - 1) / TH;
+  const int c0 = threadIdx.x * per, c1 = c0 + per < n_chunks ? c0 + per : n_chunks;
+  for (int c = c0; c < c1; ++c) {
+    const int tag = chunks[3 * c + 2];
+    const int group = tag & (ACVAE_OPT_CHUNK_FIRST - 1);
+    const double v = (double)partials[c];
+    if (tag >= 0 && group < n_groups) {
+#pragma unroll
+      for (int k = 0; k < ACVAE_OPT_MAX_GROUPS; ++k) acc[k] += group == k ? v : 0.0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < ACVAE_OPT_MAX_GROUPS; ++k) sums[k][threadIdx.x] = acc[k];
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x < ACVAE_OPT_MAX_GROUPS)
+    for (int i = 0; i < TH; ++i) t += sums[threadIdx.x][i];
+  __syncthreads();
+  if (threadIdx.x < ACVAE_OPT_MAX_GROUPS) sums[threadIdx.x][0] = t;
+  __syncthreads();
+  if (threadIdx.x < n_groups) group_norms[threadIdx.x] = (float)(sqrt(t) * (double)scale);
+  if (threadIdx.x == 0) {
+    double all = 0.0;
+    for (int k = 0; k < n_groups; ++k) all += sums[k][0];
+    total_norm[0] = (float)(sqrt(all) * (double)scale);
+  }
+}
+
+template <int KIND, bool STATE>
+__global__ __launch_bounds__(TH) void opt_groups_kernel(GroupedArgs G) {
+  float coef = G.grad_scale;                               // as opt_kernel
+  if (G.total_norm && G.max_norm > 0.f) {
+    float c = G.max_norm / (G.total_norm[0] + 1e-6f);
+    coef *= c < 1.f ? c : 1.f;
+  }
+  constexpr bool ADAM = KIND == OPT_ADAM;
+  const bool w0 = ADAM || STATE;
+  const bool u1 = ADAM, u2 = ADAM && STATE;
+  const long n4 = G.n >> 2;
+  float4* p4 = reinterpret_cast<float4*>(G.p);
+  const float4* g4 = reinterpret_cast<const float4*>(G.g);
+  float4* s04 = reinterpret_cast<float4*>(G.s0);
+  float4* s14 = reinterpret_cast<float4*>(G.s1);
+  float4* s24 = reinterpret_cast<float4*>(G.s2);
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int c = blockIdx.x; c < G.n_chunks; c += gridDim.x) {
+    long a, e;
+    int group;
+    bool first;
+    if (!read_chunk(G.chunks, c, G.n_groups, n4, a, e, group, first)) continue;
+    const GroupHyper& h = G.hyper.job[group];
+    OptArgs A{};
+    A.lr = h.lr; A.a = h.a; A.b = h.b; A.c = h.c; A.d = h.d; A.wd = h.wd; A.decay = h.decay;
+    A.step_size = h.step_size; A.bc2_sqrt = h.bc2_sqrt;
+    A.flags = G.flags | (first ? OPT_F_FIRST : 0);
+    const bool r0 = ADAM || (STATE && !first);
+    for (long i = a + threadIdx.x; i < e; i += TH) {
+      float4 p = p4[i];
+      const float4 g = g4[i];
+      float4 s0 = r0 ? s04[i] : z, s1 = u1 ? s14[i] : z, s2 = u2 ? s24[i] : z;
+      opt_elem<KIND, STATE>(A, coef, p.x, g.x, s0.x, s1.x, s2.x);
+      opt_elem<KIND, STATE>(A, coef, p.y, g.y, s0.y, s1.y, s2.y);
+      opt_elem<KIND, STATE>(A, coef, p.z, g.z, s0.z, s1.z, s2.z);
+      opt_elem<KIND, STATE>(A, coef, p.w, g.w, s0.w, s1.w, s2.w);
+      p4[i] = p;
+      if (w0) s04[i] = s0;
+      if (u1) s14[i] = s1;
+      if (u2) s24[i] = s2;
+    }
+  }
+}
+
+int group_blocks(int n_chunks) { return n_chunks < GROUP_BLOCKS ? n_chunks : GROUP_BLOCKS; }
+
+int launch_opt_groups(int kind, bool state, const GroupedArgs& G, void* stream) {
+  const dim3 grid(group_blocks(G.n_chunks)), block(TH);
+  hipStream_t st = (hipStream_t)stream;
+  if (kind == OPT_ADAM) {
+    if (state) hipLaunchKernelGGL((opt_groups_kernel<OPT_ADAM, true>), grid, block, 0, st, G);
+    else hipLaunchKernelGGL((opt_groups_kernel<OPT_ADAM, false>), grid, block, 0, st, G);
+  } else {
+    if (state) hipLaunchKernelGGL((opt_groups_kernel<OPT_SGD, true>), grid, block, 0, st, G);
+    else hipLaunchKernelGGL((opt_groups_kernel<OPT_SGD, false>), grid, block, 0, st, G);
+  }
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+bool groups_ok(int n_groups, int n_chunks) { return n_groups >= 1 && n_groups <= ACVAE_OPT_MAX_GROUPS && n_chunks > 0; }
+}  // namespace
+
+extern "C" int64_t acvae_opt_chunk_elems(void) { return OPT_CHUNK; }
+
+extern "C" int acvae_grad_norm_groups(const float* grads, const int* chunks, int n_chunks, int n_groups, float grad_scale,
+                                      float* partials, float* group_norms, float* total_norm, void* stream) {
+  if (!grads || !chunks || !partials || !group_norms || !total_norm || !groups_ok(n_groups, n_chunks)) return ACVAE_EINVAL;
+  if (!aligned16(grads) || !aligned16(chunks)) return ACVAE_EALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(sqsum_chunks_kernel, dim3(group_blocks(n_chunks)), dim3(TH), 0, st, grads, chunks, n_chunks, n_groups,
+                     partials);
+  hipLaunchKernelGGL(norm_groups_final_kernel, dim3(1), dim3(TH), 0, st, partials, chunks, n_chunks, n_groups, grad_scale,
+                     group_norms, total_norm);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_adamw_groups_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                       float* max_exp_avg_sq, int64_t n, const int* chunks, int n_chunks, int n_groups,
+                                       const double* lr, const double* beta1, const double* beta2, const double* eps,
+                                       const double* weight_decay, int decoupled, int amsgrad, int64_t step,
+                                       float grad_scale, float max_grad_norm, const float* total_norm, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || (amsgrad && !max_exp_avg_sq) || !chunks || !lr || !beta1 || !beta2 ||
+      !eps || !weight_decay || n <= 0 || step <= 0 || !groups_ok(n_groups, n_chunks))
+    return ACVAE_EINVAL;
+  if (!aligned16(params) || !aligned16(grads) || !aligned16(exp_avg) || !aligned16(exp_avg_sq) ||
+      (amsgrad && !aligned16(max_exp_avg_sq)) || !aligned16(chunks))
+    return ACVAE_EALIGN;
+  GroupedArgs G{};
+  G.p = params; G.g = grads; G.s0 = exp_avg; G.s1 = exp_avg_sq; G.s2 = amsgrad ? max_exp_avg_sq : nullptr;
+  G.n = (long)n; G.chunks = chunks; G.n_chunks = n_chunks; G.n_groups = n_groups;
+  G.flags = decoupled ? OPT_F_DECOUPLED : 0;
+  G.grad_scale = grad_scale; G.max_norm = max_grad_norm; G.total_norm = total_norm;
+  for (int k = 0; k < n_groups; ++k) {                     // every derived scalar in double, rounded once (acvae_adamw_step)
+    const double bc1 = 1.0 - pow(beta1[k], (double)step);
+    const double bc2 = 1.0 - pow(beta2[k], (double)step);
+    GroupHyper h{};
+    h.lr = (float)lr[k];
+    h.a = (float)(1.0 - beta1[k]); h.b = (float)beta2[k]; h.c = (float)(1.0 - beta2[k]); h.d = (float)eps[k];
+    h.wd = (float)weight_decay[k]; h.decay = (float)(1.0 - lr[k] * weight_decay[k]);
+    h.step_size = (float)(lr[k] / bc1); h.bc2_sqrt = (float)sqrt(bc2);
+    G.hyper.add(h);
+  }
+  return launch_opt_groups(OPT_ADAM, amsgrad != 0, G, stream);
+}
+
+extern "C" int acvae_sgd_groups_step(float* params, const float* grads, float* momentum_buffer, int64_t n,
+                                     const int* chunks, int n_chunks, int n_groups, const double* lr,
+                                     const double* momentum, const double* weight_decay, double dampening, int nesterov,
+                                     float grad_scale, float max_grad_norm, const float* total_norm, void* stream) {
+  if (!params || !grads || !chunks || !lr || !momentum || !weight_decay || n <= 0 || !groups_ok(n_groups, n_chunks))
+    return ACVAE_EINVAL;
+  int with_mom = 0;
+  for (int k = 0; k < n_groups; ++k) with_mom += momentum[k] != 0.0;
+  if (with_mom != 0 && with_mom != n_groups) return ACVAE_EINVAL;     // the state exists for all groups or for none
+  const bool mom = with_mom != 0;
+  if ((mom && !momentum_buffer) || (nesterov && (!mom || dampening != 0.0))) return ACVAE_EINVAL;
+  if (!aligned16(params) || !aligned16(grads) || !aligned_or_null(mom ? momentum_buffer : nullptr) || !aligned16(chunks))
+    return ACVAE_EALIGN;
+  GroupedArgs G{};
+  G.p = params; G.g = grads; G.s0 = mom ? momentum_buffer : nullptr;
+  G.n = (long)n; G.chunks = chunks; G.n_chunks = n_chunks; G.n_groups = n_groups;
+  G.flags = nesterov ? OPT_F_NESTEROV : 0;
+  G.grad_scale = grad_scale; G.max_norm = max_grad_norm; G.total_norm = total_norm;
+  for (int k = 0; k < n_groups; ++k) {
+    GroupHyper h{};
+    h.lr = (float)lr[k]; h.a = (float)momentum[k]; h.b = (float)(1.0 - dampening); h.wd = (float)weight_decay[k];
+    G.hyper.add(h);
+  }
+  return launch_opt_groups(OPT_SGD, mom, G, stream);
+}

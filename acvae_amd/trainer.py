@@ -16,6 +16,7 @@ acvae_amd/optim.py) — with the MI355X-specific plumbing:
 """
 import collections
 import contextlib
+import ctypes
 import math
 import os
 
@@ -24,7 +25,8 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, streams
-from .optim import FlatOptimizer, check_group, resolve
+from .optim import (FlatOptimizer, check_coverage, check_group, check_groups, chunk_table, group_segments, resolve,
+                    resolve_groups)
 from .train_util import KLObjective, LabelSmoothingLoss, MSELoss, Normal_kl_loss, combine_losses
 
 
@@ -135,11 +137,19 @@ def check_accumulation(accum_steps, ema_decay, ema_warmup):
 
 
 def _group_property(key):
+    def only_group(self):
+        groups = self.optimizer.param_groups
+        if len(groups) != 1:
+            raise ValueError(f"TrainStep.{key} is the value of the only param group; this TrainStep has {len(groups)}: "
+                             f"read and set ts.optimizer.param_groups[i][{key!r}]")
+        return groups[0]
+
     def get(self):
-        return self.optimizer.param_groups[0].get(key)
+        return only_group(self).get(key)
 
     def set(self, value):
-        self.optimizer.param_groups[0][key] = tuple(value) if key == "betas" else value
+        group = only_group(self)                    # (raises before the value is looked at)
+        group[key] = tuple(value) if key == "betas" else value
     return property(get, set, doc=f"optimizer.param_groups[0][{key!r}]")
 
 
@@ -173,7 +183,18 @@ class TrainStep:
     runs the model on it, ``ema_state_dict()`` / ``load_ema_state_dict()`` checkpoint it.  Every rank of a data-parallel job
     computes the same average from the same parameters.
 
-    With ``accum_steps=1`` and ``ema_decay=None`` neither buffer exists and a step is the launches it always was."""
+    With ``accum_steps=1`` and ``ema_decay=None`` neither buffer exists and a step is the launches it always was.
+
+    ``param_groups``: None, or 1..8 dicts ``{"params": iterable of Parameters, **overrides}`` in torch's convention
+    (``acvae_amd.optim.split_params`` builds the common recipe).  A group may override ``lr``, ``betas``, ``eps``,
+    ``weight_decay`` (SGD: ``lr``, ``momentum``, ``weight_decay``); everything else comes from ``optimizer_args`` and is one
+    value for the whole flat buffer.  Every trainable parameter must be in exactly one group (frozen ones are ignored, the
+    encoder's pooled head may be listed or left out).  ``optimizer.param_groups`` then holds those groups and every one is
+    read on every step.  One group runs the launches it always ran; two or more run ``acvae_grad_norm_groups`` and one
+    grouped update over a chunk table that is uploaded once per distinct set of parameters without a gradient.  Clipping
+    stays global; ``parts["grad_norm_groups"]`` (device, [G]) is each group's share of ``parts["grad_norm"]``.  ``ts.lr`` and
+    its siblings raise with several groups.  Checkpoints index the parameters through the groups' lists in the order given,
+    as torch does."""
 
     lr = _group_property("lr")
     betas = _group_property("betas")
@@ -183,7 +204,8 @@ class TrainStep:
     def __init__(self, model, vocab_size, lr=5e-4, betas=None, eps=None, weight_decay=None, max_grad_norm=1.0,
                  label_smoothing=True, smoothing=0.1, alpha=1.0, global_loss="MSE", process_group=None,
                  broadcast_buffers=True, data_parallel=True, precision=None, optimizer="Adam", optimizer_args=None,
-                 kl_reduction="all", free_bits=None, free_bits_over="dim", accum_steps=1, ema_decay=None, ema_warmup=False):
+                 kl_reduction="all", free_bits=None, free_bits_over="dim", accum_steps=1, ema_decay=None, ema_warmup=False,
+                 param_groups=None):
         check_accumulation(accum_steps, ema_decay, ema_warmup)                   # (before anything is built)
         self.accum_steps = int(accum_steps)
         self.ema_decay = None if ema_decay is None else float(ema_decay)
@@ -194,6 +216,11 @@ class TrainStep:
         self._in_ema = False
         kl_objective = KLObjective(kl_reduction, free_bits, free_bits_over)      # (refuses bad values before anything is built)
         group = resolve(optimizer, optimizer_args, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        groups = None
+        if param_groups is not None:                # (refused before anything is built, too)
+            groups = resolve_groups(optimizer, group, param_groups)
+            head = model.encoder._head()
+            check_coverage(groups, [p for p in model.parameters() if p.requires_grad], (head.weight, head.bias))
         self.optimizer_name = optimizer
         self.model = model
         if precision is not None:                   # "f32" | "bf16" (bf16 forward / fp32 loss: BASELINE configs[2])
@@ -216,8 +243,16 @@ class TrainStep:
         self.max_steps_in_flight = int(os.environ.get("ACVAE_STEPS_IN_FLIGHT", "2"))
         self._in_flight = []
         self._copy_stream = None
-        self._flatten(group)
-        self.optimizer = FlatOptimizer(self, model.parameters(), optimizer, group)
+        self._flatten(group if groups is None else groups[0])      # (which state exists is the same in every group)
+        # checkpoints index parameters through these lists (torch's rule): model.parameters(), or the groups as given
+        self._group_lists = [list(model.parameters())] if groups is None else [g["params"] for g in groups]
+        self.optimizer = FlatOptimizer(self, model.parameters() if groups is None else groups, optimizer, group)
+        gi = {id(p): k for k, ps in enumerate(self._group_lists) for p in ps}
+        self._group_of = [gi.get(id(p), 0) for p in self.order]          # in flat order
+        self._tables = {}                           # (skipped, SGD-started) -> (device chunk table, partials, segments)
+        self.group_norms = None
+        if len(self._group_lists) > 1:
+            self.group_norms = torch.zeros(len(self._group_lists), device=self.flat_p.device)
         self._pending = None                        # (gscale, total_norm, skipped, stream) while step() applies the update
         # Buckets in flat order, each announced from inside the backward as soon as its gradients are queued:
         #   0 decoder + prior + heads (everything acvae_decode_bwd writes, 76 MB at V=5000): behind the decode backward,
@@ -499,6 +534,8 @@ class TrainStep:
             self._update(self._check_grad_aliasing(), gscale, _lib.current_stream())
             parts["loss"] = loss.detach()
             parts["grad_norm"] = self.total_norm
+            if self._norm_by_group():
+                parts["grad_norm_groups"] = self.group_norms
         else:
             # one micro-step: the backward has written flat_g (and its trailing work on the second stream is joined to the
             # current stream, as for the norm); add it to the window's sum where the norm would be launched
@@ -512,6 +549,8 @@ class TrainStep:
             if parts["applied"]:
                 self._apply_window()
                 parts["grad_norm"] = self.total_norm
+                if self._norm_by_group():
+                    parts["grad_norm_groups"] = self.group_norms
         # DDP's broadcast_buffers: rank 0's BatchNorm running statistics reach the other ranks before the next forward
         # touches them.  Issued here, behind this step's kernels and off the next step's critical path; joined by
         # sync_buffers() at the start of the next step (or by the caller before an evaluation pass).
@@ -534,7 +573,12 @@ class TrainStep:
     def _update(self, skipped, gscale, st):
         """Norm of gscale * (the gradient buffer), the fused update with the clip coefficient from it, and the EMA."""
         tn = None
-        if self.max_grad_norm is not None and self.max_grad_norm > 0:
+        if self._norm_by_group():
+            table, partials, _ = self._chunk_table(skipped)
+            _lib.call("acvae_grad_norm_groups", self._grad_src, table, table.shape[0], len(self._group_lists), gscale,
+                      partials, self.group_norms, self.total_norm, st)
+            tn = self.total_norm
+        elif self.max_grad_norm is not None and self.max_grad_norm > 0:
             _lib.call("acvae_grad_norm", self._grad_src, self.n_active, gscale, self.norm_partials, self.total_norm, st)
             tn = self.total_norm
         self.step_count += 1
@@ -570,15 +614,73 @@ class TrainStep:
         if self.micro_count == 0:
             return None
         self._apply_window()
-        return {"applied": True, "grad_norm": self.total_norm}
+        out = {"applied": True, "grad_norm": self.total_norm}
+        if self._norm_by_group():
+            out["grad_norm_groups"] = self.group_norms
+        return out
+
+    def _norm_by_group(self):
+        return self.group_norms is not None and self.max_grad_norm is not None and self.max_grad_norm > 0
+
+    def _chunk_table(self, skipped):
+        """(device table int32 [n_chunks, 3], partials [n_chunks], number of segments) of the grouped launches for this set of
+        parameters without a gradient (and, under SGD with momentum, this set of started buffers): built and uploaded once
+        per distinct set, so the usual step uploads nothing."""
+        skip = {a for a, _ in skipped}
+        offs = [off for _, off in self._active_params((), self.n_active)]
+        n_par = len(offs)                           # the active range is the first n_par parameters of the flat order
+        skipped_idx = frozenset(i for i, off in enumerate(offs) if off in skip)
+        first_idx = frozenset()
+        if self.momentum_buffer is not None:
+            first_idx = frozenset(i for i, p in enumerate(self.order[:n_par]) if p not in self._sgd_started)
+        key = (skipped_idx, first_idx)
+        hit = self._tables.get(key)
+        if hit is None:
+            sizes = [(p.numel() + 3) // 4 * 4 for p in self.order[:n_par]]
+            chunk = int(_lib.call("acvae_opt_chunk_elems"))
+            table = chunk_table(sizes, self._group_of[:n_par], skipped_idx, first_idx, chunk)
+            if table.shape[0] == 0:
+                raise RuntimeError("TrainStep: no parameter has a gradient")
+            dev = self.flat_p.device
+            hit = (torch.from_numpy(table).to(dev), torch.empty(table.shape[0], device=dev),
+                   len(group_segments(sizes, self._group_of[:n_par], skipped_idx, first_idx)))
+            self._tables[key] = hit
+        return hit
+
+    def _apply_groups(self, groups, gscale, tn, skipped, st):
+        """Two or more param groups: one grouped launch over the chunk table, every group's dict as it is now."""
+        name, G = self.optimizer_name, len(groups)
+        check_groups(name, groups)
+        table, _, _ = self._chunk_table(skipped)
+        arr = lambda vals: (ctypes.c_double * G)(*[float(v) for v in vals])
+        n, mg, g0 = self.n_active, float(self.max_grad_norm or 0.0), groups[0]
+        if name == "SGD":
+            mom = float(g0["momentum"]) != 0
+            if mom and self.momentum_buffer is None:
+                raise RuntimeError("SGD momentum became non-zero, but TrainStep was built with momentum == 0 (no buffer)")
+            _lib.call("acvae_sgd_groups_step", self.flat_p, self._grad_src, self.momentum_buffer if mom else None, n, table,
+                      table.shape[0], G, arr(g["lr"] for g in groups), arr(g["momentum"] for g in groups),
+                      arr(g["weight_decay"] for g in groups), float(g0["dampening"]), int(bool(g0["nesterov"])), gscale, mg,
+                      tn, st)
+            if mom:
+                self._sgd_started.update(p for p, _ in self._active_params(skipped, n))
+            return
+        if bool(g0["amsgrad"]) != (self.max_exp_avg_sq is not None):
+            raise RuntimeError("amsgrad cannot change after TrainStep was built (it decides which state exists)")
+        _lib.call("acvae_adamw_groups_step", self.flat_p, self._grad_src, self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq,
+                  n, table, table.shape[0], G, arr(g["lr"] for g in groups), arr(g["betas"][0] for g in groups),
+                  arr(g["betas"][1] for g in groups), arr(g["eps"] for g in groups), arr(g["weight_decay"] for g in groups),
+                  int(bool(g0["decoupled_weight_decay"])), int(bool(g0["amsgrad"])), self.step_count, gscale, mg, tn, st)
 
     def _apply_update(self):
-        """The fused update of the step that step() is running, with the hyperparameters of param_groups[0] as they are
-        now (host floats: no synchronisation)."""
+        """The fused update of the step that step() is running, with the hyperparameters of the param groups as they are
+        now (host floats: no synchronisation).  One group: the one-group entries and launches; more: _apply_groups."""
         if self._pending is None:
             raise RuntimeError("TrainStep.optimizer.step() applies the update of the step that TrainStep.step() is running "
                                "(it needs that step's gradients and norm): call TrainStep.step(...) instead")
         gscale, tn, skipped, st = self._pending
+        if len(self.optimizer.param_groups) > 1:
+            return self._apply_groups(self.optimizer.param_groups, gscale, tn, skipped, st)
         g = self.optimizer.param_groups[0]
         check_group(self.optimizer_name, g)
         n, mg = self.n_active, float(self.max_grad_norm or 0.0)
@@ -775,7 +877,9 @@ class TrainStep:
         "optimizer": ts.optimizer_state_dict()}`` is the checkpoint the reference writes (``:380-388``) and a
         ``torch.optim.<optimizer>`` over a reference model loads it.  ``ts.optimizer.state_dict()`` is this."""
         table = self._offsets()
-        params = list(self.model.parameters())     # the reference builds its optimiser over ALL model.parameters()
+        # the reference builds its optimiser over ALL model.parameters(); with param_groups= the ids enumerate the groups'
+        # lists in the order given (torch's rule), so torch.optim.<optimizer> over the same groups loads the result
+        params = [p for ps in self._group_lists for p in ps]
         bufs = self._state_buffers()
         sgd = self.optimizer_name == "SGD"
         state = {}
@@ -791,18 +895,31 @@ class TrainStep:
             for k, flat in bufs.items():
                 st[k] = flat[o:o + p.numel()].view_as(p).clone()
             state[i] = st
-        group = {k: v for k, v in self.optimizer.param_groups[0].items() if k != "params"}
-        group["params"] = list(range(len(params)))
-        return {"state": state, "param_groups": [group]}
+        out, first = [], 0
+        for pg, ps in zip(self.optimizer.param_groups, self._group_lists):
+            group = {k: v for k, v in pg.items() if k != "params"}
+            group["params"] = list(range(first, first + len(ps)))
+            first += len(ps)
+            out.append(group)
+        return {"state": state, "param_groups": out}
 
     def load_optimizer_state_dict(self, sd):
         """Inverse of ``optimizer_state_dict`` (also accepts the state dict of the matching ``torch.optim`` class built
         over the same model): resume training where the checkpoint left off.  ``ts.optimizer.load_state_dict()`` is this."""
         table = self._offsets()
-        params = list(self.model.parameters())
-        if len(sd["param_groups"]) != 1:
-            raise ValueError("TrainStep's optimizer has exactly one param group")
-        group = {k: v for k, v in sd["param_groups"][0].items() if k != "params"}
+        params = [p for ps in self._group_lists for p in ps]
+        if len(sd["param_groups"]) != len(self._group_lists):
+            raise ValueError("TrainStep's optimizer has exactly one param group" if len(self._group_lists) == 1 else
+                             f"the checkpoint has {len(sd['param_groups'])} param group(s), this TrainStep "
+                             f"{len(self._group_lists)}")
+        loaded = [{k: v for k, v in g.items() if k != "params"} for g in sd["param_groups"]]
+        if len(loaded) > 1:
+            for i, (g, ps) in enumerate(zip(sd["param_groups"], self._group_lists)):
+                if len(g["params"]) != len(ps):
+                    raise ValueError(f"param group {i} of the checkpoint holds {len(g['params'])} parameters, this "
+                                     f"TrainStep's {len(ps)}")
+            check_groups(self.optimizer_name, loaded)
+        group = loaded[0]
         check_group(self.optimizer_name, group)
         bufs = self._state_buffers()
         sgd = self.optimizer_name == "SGD"
@@ -810,9 +927,9 @@ class TrainStep:
             raise ValueError("checkpoint has SGD momentum, but this TrainStep was built with momentum == 0 (no buffer)")
         if not sgd and bool(group.get("amsgrad", False)) != ("max_exp_avg_sq" in bufs):
             raise ValueError(f"checkpoint has amsgrad={bool(group.get('amsgrad', False))}, this TrainStep the opposite")
-        pg = self.optimizer.param_groups[0]
-        for k, v in group.items():
-            pg[k] = tuple(v) if k == "betas" else v
+        for pg, g in zip(self.optimizer.param_groups, loaded):
+            for k, v in g.items():
+                pg[k] = tuple(v) if k == "betas" else v
         steps = set()
         for flat in bufs.values():
             flat.zero_()

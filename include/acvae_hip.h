@@ -815,6 +815,43 @@ int acvae_sgd_step(float* params, const float* grads, float* momentum_buffer, in
 #define ACVAE_FLAT_BLOCKS_CAP 2048
 int acvae_grad_accumulate(float* acc, const float* grads, int64_t n, int first, void* stream);
 int acvae_ema_step(float* ema, const float* params, int64_t n, double decay, void* stream);
+/* Parameter groups (TrainStep(param_groups=)): the norm and the update over the same flat buffers with up to
+ * ACVAE_OPT_MAX_GROUPS sets of hyperparameters.  The host cuts every segment (a run of adjacent parameters of one group that
+ * have a gradient and, for SGD, share the `first` flag) into chunks of at most acvae_opt_chunk_elems() elements; every
+ * parameter's slice is padded to 4 elements, so chunks count float4s.  `chunks` is a DEVICE table int32 [n_chunks, 3]:
+ *   [start / 4, length / 4, group | ACVAE_OPT_CHUNK_FIRST if this is the first SGD update of the chunk's parameters]
+ * built once and reused; the hyperparameters are HOST arrays of n_groups doubles and travel by value in the kernel argument
+ * (no host-to-device copy, no synchronisation).  A workgroup owns whole chunks (b, b + grid, ...), so its group is uniform.
+ * A chunk with start < 0, length <= 0, group >= n_groups or unknown bits in its third word is skipped (the norm counts it as
+ * zero); a length above the chunk size is cut to it and, in the steps, a range that leaves [0, n) is cut at n: a bad table
+ * is never followed out of the buffers it was made for.  Elements no chunk covers are neither read nor written.
+ * acvae_grad_norm_groups: partials[c] = the fp32 sum of squares of chunk c (one launch), then one finishing launch adds
+ *   them in float64 in a fixed order that depends on n_chunks alone: each of 256 threads adds a contiguous run of chunks in
+ *   ascending order into one sum per group, thread 0 adds the threads' sums in ascending order, then the groups in ascending
+ *   order.  group_norms[k] = grad_scale * sqrt(sum of group k), total_norm[0] = grad_scale * sqrt(sum of all).  No atomics,
+ *   every output stored once, nothing depends on what partials held: bit-reproducible.  A NaN / inf stays in its group
+ *   and in the total.
+ * acvae_adamw_groups_step / acvae_sgd_groups_step: acvae_adamw_step / acvae_sgd_step with per-group lr, betas, eps,
+ *   weight_decay (SGD: lr, momentum, weight_decay); decoupled, amsgrad, nesterov and dampening are common to all groups.
+ *   Every derived scalar is formed in double per group and rounded once, and the element arithmetic is the one-group
+ *   entries' own, so a chunk comes out bit for bit as the one-group entry over its range would leave it.  SGD's momentum
+ *   is zero in all groups (momentum_buffer may be NULL) or in none (ACVAE_EINVAL for a mix).
+ * All three: a NULL pointer, n_groups outside 1..ACVAE_OPT_MAX_GROUPS, n_chunks <= 0 (steps: n <= 0, step <= 0) ->
+ * ACVAE_EINVAL; a buffer or the table not 16-B aligned -> ACVAE_EALIGN; both before any launch. */
+#define ACVAE_OPT_MAX_GROUPS 8
+#define ACVAE_OPT_CHUNK_FIRST 256
+int64_t acvae_opt_chunk_elems(void);
+int acvae_grad_norm_groups(const float* grads, const int* chunks, int n_chunks, int n_groups, float grad_scale,
+                           float* partials, float* group_norms, float* total_norm, void* stream);
+int acvae_adamw_groups_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                            int64_t n, const int* chunks, int n_chunks, int n_groups, const double* lr,
+                            const double* beta1, const double* beta2, const double* eps, const double* weight_decay,
+                            int decoupled, int amsgrad, int64_t step, float grad_scale, float max_grad_norm,
+                            const float* total_norm, void* stream);
+int acvae_sgd_groups_step(float* params, const float* grads, float* momentum_buffer, int64_t n, const int* chunks,
+                          int n_chunks, int n_groups, const double* lr, const double* momentum,
+                          const double* weight_decay, double dampening, int nesterov, float grad_scale,
+                          float max_grad_norm, const float* total_norm, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training-time augmentation, datasets/augment.py:time_roll + spec_augment's time_mask / freq_mask (:30-65), on the
