@@ -273,7 +273,7 @@ __global__ __launch_bounds__(TH) void accumulate_kernel(float* __restrict__ acc,
     for (long i = (n4 << 2) + threadIdx.x; i < n; i += TH) acc[i] = FIRST ? g[i] : acc[i] + g[i];
 }
 
-__global__ __launch_bounds__(TH) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float w) {
+__device__ __forceinline__ void ema_body(float* __restrict__ ema, const float* __restrict__ p, long n, float w) {
   const long n4 = n >> 2;
   float4* e4 = reinterpret_cast<float4*>(ema);
   const float4* p4 = reinterpret_cast<const float4*>(p);
@@ -285,6 +285,10 @@ __global__ __launch_bounds__(TH) void ema_kernel(float* __restrict__ ema, const 
   }
   if (blockIdx.x == 0)
     for (long i = (n4 << 2) + threadIdx.x; i < n; i += TH) ema[i] = lerp_t(ema[i], p[i], w);
+}
+
+__global__ __launch_bounds__(TH) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float w) {
+  ema_body(ema, p, n, w);
 }
 
 // [a, a + n) and [b, b + n) floats share a byte
@@ -359,6 +363,7 @@ struct GroupedArgs {
   int flags;                                               // OPT_F_DECOUPLED | OPT_F_NESTEROV; OPT_F_FIRST comes from the chunk
   float grad_scale, max_norm;
   const float* total_norm;
+  const acvae_guard_record* guard;                         // the guarded entries' record (GUARD instantiations only)
   acvae::JobTable<GroupHyper, ACVAE_OPT_MAX_GROUPS> hyper;
 };
 
@@ -433,8 +438,12 @@ __global__ __launch_bounds__(TH) void norm_groups_final_kernel(const float* __re
   }
 }
 
-template <int KIND, bool STATE>
+// GUARD: the non-finite guard's form (further down).  The workgroup reads the record's decision once (uniform) and leaves
+// before it has touched anything when the update is skipped; otherwise Adam's step_size / bc2_sqrt are the record's, formed
+// on the device from its own count of applied updates.  Without GUARD the kernel is what it was.
+template <int KIND, bool STATE, bool GUARD = false>
 __global__ __launch_bounds__(TH) void opt_groups_kernel(GroupedArgs G) {
+  if (GUARD && G.guard->ok == 0) return;
   float coef = G.grad_scale;                               // as opt_kernel
   if (G.total_norm && G.max_norm > 0.f) {
     float c = G.max_norm / (G.total_norm[0] + 1e-6f);
@@ -459,6 +468,7 @@ __global__ __launch_bounds__(TH) void opt_groups_kernel(GroupedArgs G) {
     OptArgs A{};
     A.lr = h.lr; A.a = h.a; A.b = h.b; A.c = h.c; A.d = h.d; A.wd = h.wd; A.decay = h.decay;
     A.step_size = h.step_size; A.bc2_sqrt = h.bc2_sqrt;
+    if (GUARD && ADAM) { A.step_size = G.guard->step_size[group]; A.bc2_sqrt = G.guard->bc2_sqrt[group]; }
     A.flags = G.flags | (first ? OPT_F_FIRST : 0);
     const bool r0 = ADAM || (STATE && !first);
     for (long i = a + threadIdx.x; i < e; i += TH) {
@@ -482,7 +492,11 @@ int group_blocks(int n_chunks) { return n_chunks < GROUP_BLOCKS ? n_chunks : GRO
 int launch_opt_groups(int kind, bool state, const GroupedArgs& G, void* stream) {
   const dim3 grid(group_blocks(G.n_chunks)), block(TH);
   hipStream_t st = (hipStream_t)stream;
-  if (kind == OPT_ADAM) {
+  if (G.guard) {                                           // (SGD with a momentum buffer has no guarded form)
+    if (kind == OPT_ADAM && state) hipLaunchKernelGGL((opt_groups_kernel<OPT_ADAM, true, true>), grid, block, 0, st, G);
+    else if (kind == OPT_ADAM) hipLaunchKernelGGL((opt_groups_kernel<OPT_ADAM, false, true>), grid, block, 0, st, G);
+    else hipLaunchKernelGGL((opt_groups_kernel<OPT_SGD, false, true>), grid, block, 0, st, G);
+  } else if (kind == OPT_ADAM) {
     if (state) hipLaunchKernelGGL((opt_groups_kernel<OPT_ADAM, true>), grid, block, 0, st, G);
     else hipLaunchKernelGGL((opt_groups_kernel<OPT_ADAM, false>), grid, block, 0, st, G);
   } else {
@@ -564,4 +578,199 @@ extern "C" int acvae_sgd_groups_step(float* params, const float* grads, float* m
     G.hyper.add(h);
   }
   return launch_opt_groups(OPT_SGD, mom, G, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The non-finite guard (TrainStep(nonfinite="skip")): the decision whether an update is applied is formed on the device,
+// where the norm lives, and kept in a caller-owned record (include/acvae_hip.h has its layout).  Three single-workgroup
+// launches (witness, decide, and a restore that returns at once on an applied update) and guarded forms of the grouped
+// update and the EMA that return before touching anything when the record says skip.  Every word of the record is stored by
+// one thread with a vector store; no atomics.  Non-finite is a test of the exponent bits, so no floating-point mode bears
+// on it.
+// kernel-resource-usage (gfx950, -O3), VGPRs / SGPRs / LDS bytes: guard_witness_kernel 24 / 38 / 16, guard_decide_kernel
+// 36 / 85 / 0, ema_guarded_kernel 26 / 28 / 0 (ema_kernel: 26 / 28 / 0), guard_restore_kernel 12 / 24 / 0,
+// opt_groups_kernel<Adam, amsgrad, GUARD> 47 / 68 / 0, <Adam, GUARD> 40 / 62 / 0, <SGD, GUARD> 22 / 41 / 0; the four
+// instantiations without GUARD keep the figures above.  No scratch, occupancy 8 waves per SIMD for all seven.
+namespace {
+__device__ __forceinline__ int nonfinite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+__global__ __launch_bounds__(TH) void guard_witness_kernel(const float* __restrict__ loss, const float* __restrict__ buf,
+                                                           long n, acvae_guard_record* __restrict__ rec) {
+  __shared__ int bad_of_wave[TH / 64];
+  int bad = 0;
+  const long n4 = n >> 2;
+  const float4* b4 = reinterpret_cast<const float4*>(buf);
+  for (long i = threadIdx.x; i < n4; i += TH) {
+    const float4 v = b4[i];
+    bad |= nonfinite_bits(v.x) | nonfinite_bits(v.y) | nonfinite_bits(v.z) | nonfinite_bits(v.w);
+  }
+  for (long i = (n4 << 2) + threadIdx.x; i < n; i += TH) bad |= nonfinite_bits(buf[i]);
+  if (threadIdx.x == 0 && loss) bad |= nonfinite_bits(loss[0]);
+  bad = __any(bad) ? 1 : 0;
+  if ((threadIdx.x & 63) == 0) bad_of_wave[threadIdx.x >> 6] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int any = 0;
+    for (int w = 0; w < TH / 64; ++w) any |= bad_of_wave[w];
+    if (any) rec->window_bad = 1;                          // an OR: a clean call leaves the flag as it found it
+  }
+}
+
+struct DecideArgs {
+  double lr[ACVAE_OPT_MAX_GROUPS], beta1[ACVAE_OPT_MAX_GROUPS], beta2[ACVAE_OPT_MAX_GROUPS];
+  double ema_decay;
+  int kind, n_groups, ema_warmup;
+};
+
+// One wavefront.  Every lane reads the record, the barrier puts those loads in front of every store, lane k < n_groups
+// forms group k's scalars and lane 0 moves the counters.
+__global__ __launch_bounds__(64) void guard_decide_kernel(acvae_guard_record* rec, const float* __restrict__ total_norm,
+                                                          DecideArgs D) {
+  const long applied = rec->applied, skipped = rec->skipped, streak = rec->streak, ema_updates = rec->ema_updates;
+  const int window_bad = rec->window_bad;
+  const int ok = !nonfinite_bits(total_norm[0]) && window_bad == 0;
+  __syncthreads();
+  const int lane = threadIdx.x;
+  if (ok && D.kind == OPT_ADAM && lane < D.n_groups) {
+    const double t = (double)(applied + 1);
+    // (a select per group, not an index into the by-value arrays: they stay in scalar registers, no scratch)
+    double lr = 0.0, b1 = 0.0, b2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < ACVAE_OPT_MAX_GROUPS; ++k)
+      if (lane == k) { lr = D.lr[k]; b1 = D.beta1[k]; b2 = D.beta2[k]; }
+    const double bc1 = 1.0 - pow(b1, t);
+    const double bc2 = 1.0 - pow(b2, t);
+    rec->step_size[lane] = (float)(lr / bc1);
+    rec->bc2_sqrt[lane] = (float)sqrt(bc2);
+  }
+  if (lane == 0) {
+    if (ok) {
+      rec->applied = applied + 1;
+      rec->streak = 0;
+      if (D.ema_decay >= 0.0) {
+        const double u = (double)ema_updates;
+        const double warm = (1.0 + u) / (10.0 + u);
+        const double d = D.ema_warmup && warm < D.ema_decay ? warm : D.ema_decay;
+        rec->ema_w = (float)(1.0 - d);
+        rec->ema_updates = ema_updates + 1;
+      }
+    } else {
+      rec->skipped = skipped + 1;
+      rec->streak = streak + 1;
+    }
+    rec->ok = ok;
+    rec->window_bad = 0;
+  }
+}
+
+__global__ __launch_bounds__(TH) void ema_guarded_kernel(float* __restrict__ ema, const float* __restrict__ p, long n,
+                                                         const acvae_guard_record* __restrict__ rec) {
+  if (rec->ok == 0) return;
+  ema_body(ema, p, n, rec->ema_w);
+}
+
+__global__ __launch_bounds__(TH) void guard_restore_kernel(float* __restrict__ dst, const float* __restrict__ snap, long n,
+                                                           const acvae_guard_record* __restrict__ rec) {
+  if (rec->ok != 0) return;
+  const long n4 = n >> 2;
+  float4* d4 = reinterpret_cast<float4*>(dst);
+  const float4* s4 = reinterpret_cast<const float4*>(snap);
+  for (long i = blockIdx.x * (long)TH + threadIdx.x; i < n4; i += (long)gridDim.x * TH) d4[i] = s4[i];
+  if (blockIdx.x == 0)
+    for (long i = (n4 << 2) + threadIdx.x; i < n; i += TH) dst[i] = snap[i];
+}
+}  // namespace
+
+extern "C" int acvae_guard_witness(const float* loss, const float* buf, int64_t n_buf, acvae_guard_record* record,
+                                   void* stream) {
+  if (!record || n_buf < 0 || (!buf && n_buf > 0)) return ACVAE_EINVAL;
+  if (!aligned16(record) || !aligned_or_null(buf)) return ACVAE_EALIGN;
+  hipLaunchKernelGGL(guard_witness_kernel, dim3(1), dim3(TH), 0, (hipStream_t)stream, loss, buf, buf ? (long)n_buf : 0L,
+                     record);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_guard_decide(acvae_guard_record* record, const float* total_norm, int kind, int n_groups,
+                                  const double* lr, const double* beta1, const double* beta2, double ema_decay,
+                                  int ema_warmup, void* stream) {
+  if (!record || !total_norm || !lr || (kind != OPT_ADAM && kind != OPT_SGD) || (kind == OPT_ADAM && (!beta1 || !beta2)) ||
+      n_groups < 1 || n_groups > ACVAE_OPT_MAX_GROUPS || !(ema_decay <= 1.0))
+    return ACVAE_EINVAL;
+  if (!aligned16(record)) return ACVAE_EALIGN;
+  DecideArgs D{};
+  for (int k = 0; k < n_groups; ++k) {
+    D.lr[k] = lr[k];
+    if (kind == OPT_ADAM) { D.beta1[k] = beta1[k]; D.beta2[k] = beta2[k]; }
+  }
+  D.ema_decay = ema_decay; D.kind = kind; D.n_groups = n_groups; D.ema_warmup = ema_warmup != 0;
+  hipLaunchKernelGGL(guard_decide_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, record, total_norm, D);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_adamw_groups_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                               float* max_exp_avg_sq, int64_t n, const int* chunks, int n_chunks,
+                                               int n_groups, const double* lr, const double* beta1, const double* beta2,
+                                               const double* eps, const double* weight_decay, int decoupled, int amsgrad,
+                                               float grad_scale, float max_grad_norm, const float* total_norm,
+                                               const acvae_guard_record* record, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || (amsgrad && !max_exp_avg_sq) || !chunks || !lr || !beta1 || !beta2 ||
+      !eps || !weight_decay || !record || n <= 0 || !groups_ok(n_groups, n_chunks))
+    return ACVAE_EINVAL;
+  if (!aligned16(params) || !aligned16(grads) || !aligned16(exp_avg) || !aligned16(exp_avg_sq) ||
+      (amsgrad && !aligned16(max_exp_avg_sq)) || !aligned16(chunks) || !aligned16(record))
+    return ACVAE_EALIGN;
+  GroupedArgs G{};
+  G.p = params; G.g = grads; G.s0 = exp_avg; G.s1 = exp_avg_sq; G.s2 = amsgrad ? max_exp_avg_sq : nullptr;
+  G.n = (long)n; G.chunks = chunks; G.n_chunks = n_chunks; G.n_groups = n_groups;
+  G.flags = decoupled ? OPT_F_DECOUPLED : 0;
+  G.grad_scale = grad_scale; G.max_norm = max_grad_norm; G.total_norm = total_norm; G.guard = record;
+  for (int k = 0; k < n_groups; ++k) {                     // as acvae_adamw_groups_step; step_size / bc2_sqrt are the record's
+    GroupHyper h{};
+    h.lr = (float)lr[k];
+    h.a = (float)(1.0 - beta1[k]); h.b = (float)beta2[k]; h.c = (float)(1.0 - beta2[k]); h.d = (float)eps[k];
+    h.wd = (float)weight_decay[k]; h.decay = (float)(1.0 - lr[k] * weight_decay[k]);
+    G.hyper.add(h);
+  }
+  return launch_opt_groups(OPT_ADAM, amsgrad != 0, G, stream);
+}
+
+extern "C" int acvae_sgd_groups_step_guarded(float* params, const float* grads, int64_t n, const int* chunks, int n_chunks,
+                                             int n_groups, const double* lr, const double* weight_decay, float grad_scale,
+                                             float max_grad_norm, const float* total_norm,
+                                             const acvae_guard_record* record, void* stream) {
+  if (!params || !grads || !chunks || !lr || !weight_decay || !record || n <= 0 || !groups_ok(n_groups, n_chunks))
+    return ACVAE_EINVAL;
+  if (!aligned16(params) || !aligned16(grads) || !aligned16(chunks) || !aligned16(record)) return ACVAE_EALIGN;
+  GroupedArgs G{};
+  G.p = params; G.g = grads;
+  G.n = (long)n; G.chunks = chunks; G.n_chunks = n_chunks; G.n_groups = n_groups;
+  G.grad_scale = grad_scale; G.max_norm = max_grad_norm; G.total_norm = total_norm; G.guard = record;
+  for (int k = 0; k < n_groups; ++k) {                     // as acvae_sgd_groups_step with momentum 0 (b is not read)
+    GroupHyper h{};
+    h.lr = (float)lr[k]; h.b = 1.f; h.wd = (float)weight_decay[k];
+    G.hyper.add(h);
+  }
+  return launch_opt_groups(OPT_SGD, false, G, stream);
+}
+
+extern "C" int acvae_ema_step_guarded(float* ema, const float* params, int64_t n, const acvae_guard_record* record,
+                                      void* stream) {
+  if (!ema || !params || !record || n <= 0 || ranges_overlap(ema, params, n)) return ACVAE_EINVAL;
+  if (!aligned16(ema) || !aligned16(params) || !aligned16(record)) return ACVAE_EALIGN;
+  hipLaunchKernelGGL(ema_guarded_kernel, dim3(flat_blocks(n)), dim3(TH), 0, (hipStream_t)stream, ema, params, (long)n,
+                     record);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
+}
+
+extern "C" int acvae_guard_restore(float* dst, const float* snapshot, int64_t n, const acvae_guard_record* record,
+                                   void* stream) {
+  if (!dst || !snapshot || !record || n <= 0 || ranges_overlap(dst, snapshot, n)) return ACVAE_EINVAL;
+  if (!aligned16(dst) || !aligned16(snapshot) || !aligned16(record)) return ACVAE_EALIGN;
+  hipLaunchKernelGGL(guard_restore_kernel, dim3(flat_blocks(n)), dim3(TH), 0, (hipStream_t)stream, dst, snapshot, (long)n,
+                     record);
+  ACVAE_LAUNCH_CHECK();
+  return ACVAE_OK;
 }

@@ -136,6 +136,29 @@ def check_accumulation(accum_steps, ema_decay, ema_warmup):
         raise ValueError("ema_warmup=True needs ema_decay")
 
 
+DEFAULT_MAX_SKIPS = 50
+_UNSET = object()                                   # max_skips not given: DEFAULT_MAX_SKIPS with the guard, nothing without
+# the guard record of include/acvae_hip.h (acvae_guard_record) as int32 words
+GUARD_RECORD_BYTES = 112
+_GUARD_OK, _GUARD_WINDOW_BAD = 8, 9                 # int32 word offsets; the four int64 counters are words 0..7
+
+
+def check_guard(nonfinite, max_skips=_UNSET, optimizer=None, groups=()):
+    """ValueError for what TrainStep(nonfinite=, max_skips=) refuses; host arithmetic only.  ``groups``: the resolved
+    param-group dicts of ``optimizer`` (the momentum rule needs them)."""
+    if nonfinite not in (None, "skip"):
+        raise ValueError(f"nonfinite must be None or 'skip', not {nonfinite!r}")
+    if max_skips is not _UNSET and max_skips is not None:
+        if isinstance(max_skips, bool) or not isinstance(max_skips, (int, np.integer)) or max_skips < 1:
+            raise ValueError(f"max_skips must be a positive integer or None, not {max_skips!r}")
+    if max_skips is not _UNSET and nonfinite is None:
+        raise ValueError("max_skips= needs nonfinite='skip'")
+    if nonfinite is not None and optimizer == "SGD" and any(float(g.get("momentum", 0)) != 0 for g in groups):
+        raise ValueError("nonfinite='skip' does not support SGD with momentum != 0: whether a parameter's momentum buffer "
+                         "exists (the 'first update writes the buffer' flag) is tracked on the host per parameter and cannot "
+                         "follow a decision made on the device; plain SGD (momentum=0), Adam and AdamW are supported")
+
+
 def _group_property(key):
     def only_group(self):
         groups = self.optimizer.param_groups
@@ -194,7 +217,27 @@ class TrainStep:
     grouped update over a chunk table that is uploaded once per distinct set of parameters without a gradient.  Clipping
     stays global; ``parts["grad_norm_groups"]`` (device, [G]) is each group's share of ``parts["grad_norm"]``.  ``ts.lr`` and
     its siblings raise with several groups.  Checkpoints index the parameters through the groups' lists in the order given,
-    as torch does."""
+    as torch does.
+
+    ``nonfinite="skip"``: the non-finite guard.  A step (with ``accum_steps`` > 1: a window) is judged on the device: it is
+    bad when the gradient norm, the loss of any of its micro-steps or any floating-point module buffer (BatchNorm running
+    statistics) after any of its forwards is NaN or +-inf.  A bad step leaves the training state bit for bit as it was before
+    it: flat parameters, optimiser state, ``flat_ema``, the floating-point buffers, and the count that Adam's bias correction
+    and ``ema_warmup`` use, so the next good step is the one a run that never saw the bad batch would have made.  Nothing is
+    read back for it: ``acvae_guard_witness`` looks at the loss and the buffers, ``acvae_guard_decide`` forms the decision and
+    the bias-correction scalars from the device's own count of applied updates, the guarded update and EMA return at once on a
+    skip, and ``acvae_guard_restore`` puts the buffers' snapshot (taken at the start of the step or window) back.  The update
+    always runs as the grouped launches (a one-group chunk table for one group) and the norm is always computed, also with
+    ``max_grad_norm`` None / 0 (the clip itself then stays off).  ``parts["update_ok"]`` is a device int32 view of the last
+    decision (read it before the next update overwrites it); ``guard_counts()`` synchronises and returns ``applied`` /
+    ``skipped`` / ``streak``.  ``max_skips`` (default 50, None: no limit): once more than that many updates in a row were
+    skipped, ``step()`` raises RuntimeError naming the counts, where it waits for the step two behind it anyway
+    (``max_steps_in_flight``), or ``synchronize()`` does.  ``step_count`` and LR schedulers keep counting ATTEMPTED updates, as
+    ``torch.amp.GradScaler`` leaves the scheduler to its caller: update k runs at the learning rate of attempt k with the bias
+    correction of the applied updates before it.  Checkpoints store the applied count as torch's per-parameter ``step``.
+    Under data parallelism the witness's flag is all-reduced (MAX, 4 bytes) before the decision, so every rank decides
+    alike.  Not covered: SGD with momentum (refused), a finite but huge norm, loss scaling, integer buffers
+    (``num_batches_tracked`` moves on a skipped step), un-counting the LR scheduler, naming the offending clip."""
 
     lr = _group_property("lr")
     betas = _group_property("betas")
@@ -205,8 +248,9 @@ class TrainStep:
                  label_smoothing=True, smoothing=0.1, alpha=1.0, global_loss="MSE", process_group=None,
                  broadcast_buffers=True, data_parallel=True, precision=None, optimizer="Adam", optimizer_args=None,
                  kl_reduction="all", free_bits=None, free_bits_over="dim", accum_steps=1, ema_decay=None, ema_warmup=False,
-                 param_groups=None):
+                 param_groups=None, nonfinite=None, max_skips=_UNSET):
         check_accumulation(accum_steps, ema_decay, ema_warmup)                   # (before anything is built)
+        check_guard(nonfinite, max_skips)
         self.accum_steps = int(accum_steps)
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
@@ -221,6 +265,9 @@ class TrainStep:
             groups = resolve_groups(optimizer, group, param_groups)
             head = model.encoder._head()
             check_coverage(groups, [p for p in model.parameters() if p.requires_grad], (head.weight, head.bias))
+        check_guard(nonfinite, max_skips, optimizer, [group] if groups is None else groups)
+        self.nonfinite = nonfinite
+        self.max_skips = None if nonfinite is None else (DEFAULT_MAX_SKIPS if max_skips is _UNSET else max_skips)
         self.optimizer_name = optimizer
         self.model = model
         if precision is not None:                   # "f32" | "bf16" (bf16 forward / fp32 loss: BASELINE configs[2])
@@ -287,6 +334,26 @@ class TrainStep:
             if self.flat_buf is not None:
                 dist.broadcast(self.flat_buf, src=0, group=self.pg)
         self.flat_ema = None if self.ema_decay is None else self.flat_p.clone()      # (after rank 0's parameters arrived)
+        self._guard = None
+        if nonfinite is not None:
+            self._build_guard()
+
+    def _build_guard(self):
+        """The guard's device record (zeroed: nothing applied, nothing skipped), the buffers' snapshot, the norms' scratch
+        for one group and the page-locked ring the counters of the steps in flight are copied to."""
+        dev = self.flat_p.device
+        rec = torch.zeros(GUARD_RECORD_BYTES // 4, dtype=torch.int32, device=dev)
+        self._guard = rec
+        self._guard_counters = rec[:8].view(torch.int64)          # applied, skipped, streak, ema_updates
+        self._guard_ok = rec[_GUARD_OK:_GUARD_OK + 1]
+        self._guard_flag = rec[_GUARD_WINDOW_BAD:_GUARD_WINDOW_BAD + 1]
+        self._buf_snapshot = None if self.flat_buf is None else torch.empty_like(self.flat_buf)
+        self._guard_norms = self.group_norms if self.group_norms is not None else torch.zeros(1, device=dev)
+        slots = max(self.max_steps_in_flight, 0) + 2
+        self._guard_host = torch.zeros(slots, 4, dtype=torch.int64).pin_memory()
+        self._guard_slot = 0
+        self._guard_in_flight = []                  # the slot of every event in _in_flight (None: no decision in that call)
+        self._guard_last = None
 
     def _dist(self):
         return self.data_parallel and dist.is_available() and dist.is_initialized() and \
@@ -481,6 +548,7 @@ class TrainStep:
             refuse_augment(augment)
         self._refuse_inside_ema("step")
         self.sync_buffers()
+        self._guard_snapshot()
         ready = getattr(feats, "_acvae_ready", None)
         if ready is not None:                       # a batch uploaded by prefetch(): order this step behind its copy
             streams.hand_over(feats, ready)
@@ -512,6 +580,7 @@ class TrainStep:
         from .seq_train_model import NScstWrapper, ScstWrapper
         self._refuse_inside_ema("scst_step")
         self.sync_buffers()
+        self._guard_snapshot()
         self._decode_event = self._decode_aux_event = self._text_event = None
         self._decode_deferred = self._projemb_seen = False
         for p in self.order:
@@ -526,9 +595,26 @@ class TrainStep:
             parts["greedy_seqs"] = out["greedy_seqs"]
         return self._backward_and_update(out["loss"], parts)
 
+    def _guard_snapshot(self):
+        """At the start of a step or window: the floating-point buffers as a skipped update has to leave them (one
+        device-to-device copy; under data parallelism rank 0's broadcast of the previous step has been joined)."""
+        if self._guard is not None and self.micro_count == 0 and self.flat_buf is not None:
+            self._buf_snapshot.copy_(self.flat_buf)
+
+    def _guard_witness(self, loss):
+        """Behind the backward (the forward's buffer writes and everything trailing on the second stream are in front of
+        the current stream by now): OR into the record whether the loss or a buffer is non-finite."""
+        l = loss.detach()
+        if l.dtype != torch.float32 or l.numel() != 1 or not l.is_cuda:
+            raise RuntimeError("nonfinite='skip' needs the loss as one fp32 scalar on the device")
+        nb = 0 if self.flat_buf is None else self.flat_buf.numel()
+        _lib.call("acvae_guard_witness", l, self.flat_buf, nb, self._guard, _lib.current_stream())
+
     def _backward_and_update(self, loss, parts):
         self.exchange.begin()
         loss.backward()
+        if self._guard is not None:
+            self._guard_witness(loss)
         if self.accum_steps == 1:
             gscale = self.exchange.finish()
             self._update(self._check_grad_aliasing(), gscale, _lib.current_stream())
@@ -536,6 +622,8 @@ class TrainStep:
             parts["grad_norm"] = self.total_norm
             if self._norm_by_group():
                 parts["grad_norm_groups"] = self.group_norms
+            if self._guard is not None:
+                parts["update_ok"] = self._guard_ok
         else:
             # one micro-step: the backward has written flat_g (and its trailing work on the second stream is joined to the
             # current stream, as for the norm); add it to the window's sum where the norm would be launched
@@ -551,6 +639,8 @@ class TrainStep:
                 parts["grad_norm"] = self.total_norm
                 if self._norm_by_group():
                     parts["grad_norm_groups"] = self.group_norms
+                if self._guard is not None:
+                    parts["update_ok"] = self._guard_ok
         # DDP's broadcast_buffers: rank 0's BatchNorm running statistics reach the other ranks before the next forward
         # touches them.  Issued here, behind this step's kernels and off the next step's critical path; joined by
         # sync_buffers() at the start of the next step (or by the caller before an evaluation pass).
@@ -563,8 +653,13 @@ class TrainStep:
             ev = torch.cuda.Event()
             ev.record()
             self._in_flight.append(ev)
+            if self._guard is not None:
+                self._guard_in_flight.append(self._guard_last)
+                self._guard_last = None
             if len(self._in_flight) > self.max_steps_in_flight:
                 self._in_flight.pop(0).synchronize()
+                if self._guard is not None:         # that step's counters have arrived in page-locked memory
+                    self._check_streak(self._guard_in_flight.pop(0))
                 # a persistent launch of that step that could not complete has poisoned the step with NaN and raised the
                 # device's status word: turn it into an error at the first synchronisation point the loop has anyway
                 _lib.check_persist_status(self.flat_p.device)
@@ -572,6 +667,8 @@ class TrainStep:
 
     def _update(self, skipped, gscale, st):
         """Norm of gscale * (the gradient buffer), the fused update with the clip coefficient from it, and the EMA."""
+        if self._guard is not None:
+            return self._update_guarded(skipped, gscale, st)
         tn = None
         if self._norm_by_group():
             table, partials, _ = self._chunk_table(skipped)
@@ -594,6 +691,83 @@ class TrainStep:
             d = ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup)
             _lib.call("acvae_ema_step", self.flat_ema, self.flat_p, self.flat_p.numel(), d, st)
             self.ema_updates += 1
+
+    def _update_guarded(self, skipped, gscale, st):
+        """_update with the guard: norm -> decide -> guarded update -> guarded EMA -> restore, all on ``st``; then the
+        counters start their way to page-locked memory."""
+        table, partials, _ = self._chunk_table(skipped)
+        _lib.call("acvae_grad_norm_groups", self._grad_src, table, table.shape[0], len(self._group_lists), gscale,
+                  partials, self._guard_norms, self.total_norm, st)
+        if self.world > 1:
+            # the exchanged gradients, hence the norm, are the same on every rank; the witness is local
+            dist.all_reduce(self._guard_flag, op=dist.ReduceOp.MAX, group=self.pg)
+        clip = self.max_grad_norm is not None and self.max_grad_norm > 0
+        self.step_count += 1                        # attempted updates: what LR schedulers count, too
+        self._pending = (gscale, self.total_norm if clip else None, skipped, st)
+        try:
+            self.optimizer.step()                  # -> _apply_guarded: the decision and the guarded update
+        finally:
+            self._pending = None
+            self.model.drop_step_caches()
+        if self.flat_ema is not None:
+            _lib.call("acvae_ema_step_guarded", self.flat_ema, self.flat_p, self.flat_p.numel(), self._guard, st)
+        if self.flat_buf is not None:
+            _lib.call("acvae_guard_restore", self.flat_buf, self._buf_snapshot, self.flat_buf.numel(), self._guard, st)
+        if self.max_skips is not None:
+            slot, self._guard_slot = self._guard_slot, (self._guard_slot + 1) % self._guard_host.shape[0]
+            self._guard_host[slot].copy_(self._guard_counters, non_blocking=True)
+            self._guard_last = slot
+
+    def _apply_guarded(self, groups, gscale, tn, skipped, st):
+        """The decision (bias-correction scalars and EMA weight from the device's counts and the groups as they are now)
+        and the guarded grouped update; one group is a one-group chunk table."""
+        name, G = self.optimizer_name, len(groups)
+        check_groups(name, groups)
+        table, _, _ = self._chunk_table(skipped)
+        arr = lambda vals: (ctypes.c_double * G)(*[float(v) for v in vals])
+        n, mg, g0 = self.n_active, float(self.max_grad_norm or 0.0), groups[0]
+        lr = arr(g["lr"] for g in groups)
+        ema = -1.0 if self.flat_ema is None else self.ema_decay
+        if name == "SGD":
+            if any(float(g["momentum"]) != 0 for g in groups):
+                raise RuntimeError("SGD momentum became non-zero under nonfinite='skip' (the guard supports plain SGD only)")
+            _lib.call("acvae_guard_decide", self._guard, self.total_norm, 1, G, lr, None, None, ema, int(self.ema_warmup), st)
+            _lib.call("acvae_sgd_groups_step_guarded", self.flat_p, self._grad_src, n, table, table.shape[0], G, lr,
+                      arr(g["weight_decay"] for g in groups), gscale, mg, tn, self._guard, st)
+            return
+        if bool(g0["amsgrad"]) != (self.max_exp_avg_sq is not None):
+            raise RuntimeError("amsgrad cannot change after TrainStep was built (it decides which state exists)")
+        b1, b2 = arr(g["betas"][0] for g in groups), arr(g["betas"][1] for g in groups)
+        _lib.call("acvae_guard_decide", self._guard, self.total_norm, 0, G, lr, b1, b2, ema, int(self.ema_warmup), st)
+        _lib.call("acvae_adamw_groups_step_guarded", self.flat_p, self._grad_src, self.exp_avg, self.exp_avg_sq,
+                  self.max_exp_avg_sq, n, table, table.shape[0], G, lr, b1, b2, arr(g["eps"] for g in groups),
+                  arr(g["weight_decay"] for g in groups), int(bool(g0["decoupled_weight_decay"])), int(bool(g0["amsgrad"])),
+                  gscale, mg, tn, self._guard, st)
+
+    def _check_streak(self, slot):
+        """``slot`` of the page-locked ring holds the counters of a step whose work has completed: raise once more than
+        ``max_skips`` updates in a row were skipped."""
+        if slot is None or self.max_skips is None:
+            return
+        applied, skipped, streak, _ = (int(v) for v in self._guard_host[slot])
+        if streak > self.max_skips:
+            raise RuntimeError(f"TrainStep(nonfinite='skip'): {streak} updates in a row were non-finite and skipped "
+                               f"(max_skips={self.max_skips}; applied {applied}, skipped {skipped}, streak {streak}); the "
+                               "parameters, the optimiser state and the buffers are those of the last applied update")
+
+    def guard_counts(self):
+        """{"applied", "skipped", "streak"} of the guard's device record; synchronises the device."""
+        if self._guard is None:
+            raise RuntimeError("TrainStep.guard_counts() needs TrainStep(..., nonfinite='skip')")
+        torch.cuda.synchronize(self.flat_p.device)
+        applied, skipped, streak, _ = (int(v) for v in self._guard_counters.cpu())
+        return {"applied": applied, "skipped": skipped, "streak": streak}
+
+    def _applied_count(self):
+        """What Adam's bias correction counts: the host's step count, or with the guard the device's (a read-back)."""
+        if self._guard is None:
+            return self.step_count
+        return int(self._guard_counters[0].item())
 
     def _apply_window(self):
         """Close the accumulation window of ``micro_count`` micro-steps: all-reduce flat_acc (data parallel), then the norm
@@ -679,6 +853,8 @@ class TrainStep:
             raise RuntimeError("TrainStep.optimizer.step() applies the update of the step that TrainStep.step() is running "
                                "(it needs that step's gradients and norm): call TrainStep.step(...) instead")
         gscale, tn, skipped, st = self._pending
+        if self._guard is not None:
+            return self._apply_guarded(self.optimizer.param_groups, gscale, tn, skipped, st)
         if len(self.optimizer.param_groups) > 1:
             return self._apply_groups(self.optimizer.param_groups, gscale, tn, skipped, st)
         g = self.optimizer.param_groups[0]
@@ -743,6 +919,11 @@ class TrainStep:
         torch.cuda.synchronize(self.flat_p.device)
         self._in_flight.clear()
         _lib.check_persist_status(self.flat_p.device)
+        if self._guard is not None:
+            slots = [s for s in self._guard_in_flight + [self._guard_last] if s is not None]
+            self._guard_in_flight, self._guard_last = [], None
+            if slots:
+                self._check_streak(slots[-1])
 
     def sync_buffers(self):
         """Join the asynchronous BatchNorm-buffer broadcast of the previous step (a stream dependency under RCCL)."""
@@ -781,8 +962,10 @@ class TrainStep:
         return segs
 
     def state_dict(self):
-        sd = {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
+        sd = {"step": self._applied_count(), "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}
         if self.flat_ema is not None:
+            if self._guard is not None:             # the device's count is the one the warm-up uses
+                self.ema_updates = int(self._guard_counters[3].item())
             sd["ema"], sd["ema_updates"] = self.flat_ema, self.ema_updates
         if self.accum_steps > 1:
             sd["micro_count"] = self.micro_count
@@ -883,15 +1066,16 @@ class TrainStep:
         bufs = self._state_buffers()
         sgd = self.optimizer_name == "SGD"
         state = {}
+        applied = 0 if sgd else self._applied_count()      # with the guard: the device's count (a read-back)
         for i, p in enumerate(params):
             # torch's optimisers hold no state for a parameter that never had a gradient (frozen ones, and the pooled
             # head embed_pooled / fc1 whose output this path does not consume): no entry, like a reference checkpoint
             if not bufs or p not in table or p in self.never:
                 continue
-            if (sgd and p not in self._sgd_started) or (not sgd and self.step_count == 0):
+            if (sgd and p not in self._sgd_started) or (not sgd and applied == 0):
                 continue
             o = table[p]
-            st = {} if sgd else {"step": torch.tensor(float(self.step_count))}
+            st = {} if sgd else {"step": torch.tensor(float(applied))}
             for k, flat in bufs.items():
                 st[k] = flat[o:o + p.numel()].view_as(p).clone()
             state[i] = st
@@ -956,3 +1140,6 @@ class TrainStep:
         # find_unused_parameters) resume at the largest, which is exact for every parameter that was never skipped
         if not sgd:
             self.step_count = max(steps) if steps else 0
+            if self._guard is not None:             # the device's count of applied updates resumes there; no streak is open
+                self._guard_counters[0] = self.step_count
+                self._guard_counters[2] = 0

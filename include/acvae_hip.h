@@ -852,6 +852,64 @@ int acvae_sgd_groups_step(float* params, const float* grads, float* momentum_buf
                           int n_chunks, int n_groups, const double* lr, const double* momentum,
                           const double* weight_decay, double dampening, int nesterov, float grad_scale,
                           float max_grad_norm, const float* total_norm, void* stream);
+/* The non-finite guard (TrainStep(nonfinite="skip")): whether an update is applied is decided on the device, from the norm
+ * that lives there, and everything that moves the training state reads that decision.  A skipped update leaves every
+ * buffer bit for bit as it was.  The RECORD is caller-owned device memory of ACVAE_GUARD_RECORD_BYTES bytes, 16-B aligned,
+ * zeroed by the caller before the first use; only the entries below write it.  Layout (byte offset, type):
+ *     0  int64  applied        updates applied so far: the `step` of Adam's bias correction
+ *     8  int64  skipped        updates skipped so far
+ *    16  int64  streak         consecutive skips up to and including the last decision (0 after an applied update)
+ *    24  int64  ema_updates    updates the weight average has seen (ema_warmup's t)
+ *    32  int32  ok             the last decision: 1 apply, 0 skip
+ *    36  int32  window_bad     OR of the witnesses since the last decision
+ *    40  float  step_size[8]   per group, (float)(lr / (1 - beta1^applied)), formed in double at the last applied decision
+ *    72  float  bc2_sqrt[8]    per group, (float)sqrt(1 - beta2^applied)
+ *   104  float  ema_w          (float)(1 - decay) of the last applied decision
+ *   108  int32  reserved
+ * acvae_guard_witness: one workgroup; window_bad |= (*loss is NaN / +-inf) | (any of buf[0 .. n_buf) is NaN / +-inf).
+ *   loss (a device fp32 scalar) may be NULL (not looked at); buf == NULL with n_buf == 0 is legal (n_buf < 0, or a NULL
+ *   buf with n_buf > 0 -> ACVAE_EINVAL); buf 16-B aligned.  Finite values, +-0, denormals and +-FLT_MAX set nothing.
+ * acvae_guard_decide: one wavefront.  ok = isfinite(total_norm[0]) && !window_bad; ok: applied += 1, streak = 0; else
+ *   skipped += 1, streak += 1; window_bad = 0 either way.  When ok and kind == 0 (Adam / AdamW), for every group k
+ *   step_size[k] = (float)(lr[k] / (1 - pow(beta1[k], t))) and bc2_sqrt[k] = (float)sqrt(1 - pow(beta2[k], t)) with
+ *   t = applied after the increment, in double, rounded once: the scalars acvae_adamw_groups_step forms on the host for
+ *   step = t.  kind == 1 (SGD) forms none (beta1 / beta2 may be NULL).  When ok and 0 <= ema_decay <= 1:
+ *   ema_w = (float)(1 - d), d = ema_warmup ? min(ema_decay, (1 + u) / (10 + u)) : ema_decay with u = ema_updates, in
+ *   double, then ema_updates += 1; ema_decay < 0 means "no average" and leaves both alone.  lr / beta1 / beta2 are HOST
+ *   arrays of n_groups doubles and travel by value in the kernel argument.  kind outside {0, 1}, n_groups outside
+ *   1..ACVAE_OPT_MAX_GROUPS, ema_decay > 1 or NaN, a NULL record / total_norm / lr (kind 0: beta1 / beta2) -> ACVAE_EINVAL.
+ * acvae_adamw_groups_step_guarded / acvae_sgd_groups_step_guarded: the grouped steps without `step`: every workgroup
+ *   reads ok once and returns before touching anything when it is 0; otherwise a chunk takes step_size / bc2_sqrt of its
+ *   group from the record (Adam) and runs the unguarded kernel's arithmetic: with ok == 1 every buffer comes out bit for
+ *   bit as acvae_adamw_groups_step(step = applied) / acvae_sgd_groups_step leaves it.  SGD: momentum must be 0 in every
+ *   group (the first-update flag of the momentum buffer is the host's and cannot follow a device decision; ACVAE_EINVAL).
+ * acvae_ema_step_guarded: acvae_ema_step with w = ema_w of the record; nothing is touched when ok == 0.
+ * acvae_guard_restore: ok == 0: dst[0 .. n) = snapshot[0 .. n); ok == 1: neither is read or written.
+ * Both: NULL, n <= 0 or overlapping ranges -> ACVAE_EINVAL.  All six: a buffer or the record not 16-B aligned -> ACVAE_EALIGN;
+ * every refusal before any launch; no host synchronisation, no atomics, every word stored by one thread. */
+#define ACVAE_GUARD_RECORD_BYTES 112
+typedef struct acvae_guard_record {
+  int64_t applied, skipped, streak, ema_updates;
+  int32_t ok, window_bad;
+  float step_size[8], bc2_sqrt[8];
+  float ema_w;
+  int32_t reserved;
+} acvae_guard_record;
+int acvae_guard_witness(const float* loss, const float* buf, int64_t n_buf, acvae_guard_record* record, void* stream);
+int acvae_guard_decide(acvae_guard_record* record, const float* total_norm, int kind, int n_groups, const double* lr,
+                       const double* beta1, const double* beta2, double ema_decay, int ema_warmup, void* stream);
+int acvae_adamw_groups_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                    float* max_exp_avg_sq, int64_t n, const int* chunks, int n_chunks, int n_groups,
+                                    const double* lr, const double* beta1, const double* beta2, const double* eps,
+                                    const double* weight_decay, int decoupled, int amsgrad, float grad_scale,
+                                    float max_grad_norm, const float* total_norm, const acvae_guard_record* record,
+                                    void* stream);
+int acvae_sgd_groups_step_guarded(float* params, const float* grads, int64_t n, const int* chunks, int n_chunks,
+                                  int n_groups, const double* lr, const double* weight_decay, float grad_scale,
+                                  float max_grad_norm, const float* total_norm, const acvae_guard_record* record,
+                                  void* stream);
+int acvae_ema_step_guarded(float* ema, const float* params, int64_t n, const acvae_guard_record* record, void* stream);
+int acvae_guard_restore(float* dst, const float* snapshot, int64_t n, const acvae_guard_record* record, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training-time augmentation, datasets/augment.py:time_roll + spec_augment's time_mask / freq_mask (:30-65), on the
