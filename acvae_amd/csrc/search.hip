@@ -3,6 +3,8 @@
 //     acvae_decoder_step_fwd, acvae_attn_precompute);
 //   - the search over M members' averaged word probabilities, greedy or beam (acvae_ensemble_search), and the validation
 //     beam search of one model (acvae_beam_search), which is its M = 1 case plus beam 0's attention-weight history;
+//   - rollouts from the mixture, sample_n sampled or greedy rows per clip (acvae_ensemble_rollout): the same driver, a
+//     rollout's pick in the place of the flat top-k;
 //   - diverse beam search over M >= 1 members (acvae_ensemble_dbs_search; acvae_dbs_search is its M = 1 case), at the end.
 // The two drivers keep their own loops, search() over t and dbs_search() over (t, group), and share what belongs to a
 // member: its layout (MemberLayout), its prologue, its step and its gather by parent.
@@ -433,6 +435,20 @@ __global__ __launch_bounds__(FIN_THREADS) void beam_finish_kernel(
   }
 }
 
+// How a step of search() chooses its words.  Beam: the flat top-k.  The others are rollouts, `beam` independent rows per
+// clip that never change places (the states swap, no gather): greedy takes the mix kernel's argmax; gumbel / multinomial
+// draw on noise [T][R][V], by acvae_ensemble_mix_sample (one launch: mix, draw and bookkeeping) or, with top_k / top_p on,
+// by acvae_sample_next_word_truncated on the mixed row, which the `scores` block holds.
+struct Pick {
+  int mode;                                              // PICK_BEAM, or the ACVAE_SAMPLE_* code of a rollout
+  const float* noise = nullptr;
+  float temp = 1.f;
+  int top_k = 0;
+  float top_p = 1.f;
+  bool truncated() const { return top_k > 0 || top_p < 1.f; }
+};
+constexpr int PICK_BEAM = -1;
+
 // The driver behind both entry points; they have refused every bad argument, so nothing here fails before a launch.
 // greedy: seqs [R,T], logprobs [R,T].  Beam: seqs [N,T], logprobs [N] or null, attw_out [N,S,T] or null (not null only
 // with a layout made with keep_attw).
@@ -441,10 +457,12 @@ __global__ __launch_bounds__(FIN_THREADS) void beam_finish_kernel(
 // nothing on, no launch is added and no buffer is kept.
 // fin: finishing mode (beam only, L.keep_fin): one beam_retire_kernel launch behind every top-k, and beam_finish_kernel in
 // the place of beam_trace_kernel.  Off: neither, as with con.
-int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_idx, int64_t end_idx, int greedy,
+// pick: see Pick.  "greedy" below stands for every rollout: seqs [R,T] and logprobs [R,T], whatever picks the word.
+int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_idx, int64_t end_idx, const Pick& pick,
            int64_t* seqs, float* logprobs, float* attw_out, float* sc, int N, int beam, int T, int V,
            const acvae::Constraints& con, const Finishing& fin, hipStream_t s) {
   const int R = N * beam;
+  const bool greedy = pick.mode != PICK_BEAM;            // a rollout: rows keep their place, seqs is their history
   float* frec = fin.on ? sc + L.frec : nullptr;
   if (fin.on) ACVAE_TRY(norm_upload(fin.norm, sc + L.norm, T, s));
   int64_t* wh = L.keep_hist && con.on() ? (int64_t*)(sc + L.whist) : nullptr;   // the rows' histories at this step
@@ -477,9 +495,21 @@ int search(const SearchMember* mb, int M, const SearchLayout& L, int64_t start_i
       ACVAE_TRY(acvae::constrain_rows(sc + o.logits, V, greedy ? seqs : wh, T, t, R, V, (int)end_idx, con, s));
     }
     if (greedy) {
-      ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, nullptr, 0, arg, best, 1, R, V, s));
-      hipLaunchKernelGGL(greedy_pick_kernel, dim3((R + 255) / 256), dim3(256), 0, s, arg, best, seqs, logprobs, word,
-                         end_idx, t, T, R);
+      const float* noise_t = pick.noise ? pick.noise + (long)t * R * V : nullptr;
+      if (pick.mode != ACVAE_SAMPLE_GREEDY && !pick.truncated()) {
+        ACVAE_TRY(acvae_ensemble_mix_sample(logit_ptr, logit_ld, M, noise_t, V, pick.mode, pick.temp, nullptr, 0, seqs, T,
+                                            logprobs, T, word, end_idx, t, R, V, s));
+      } else {
+        if (pick.mode == ACVAE_SAMPLE_GREEDY) {
+          ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, nullptr, 0, arg, best, 1, R, V, s));
+        } else {
+          ACVAE_TRY(acvae_ensemble_mix(logit_ptr, logit_ld, M, nullptr, sc + L.scores, V, nullptr, nullptr, 0, R, V, s));
+          ACVAE_TRY(acvae_sample_next_word_truncated(sc + L.scores, V, 0, noise_t, V, 0, pick.mode, pick.temp, arg, best, 1,
+                                                     0, R, 1, V, pick.top_k, pick.top_p, nullptr, s));
+        }
+        hipLaunchKernelGGL(greedy_pick_kernel, dim3((R + 255) / 256), dim3(256), 0, s, arg, best, seqs, logprobs, word,
+                           end_idx, t, T, R);
+      }
       for (int m = 0; m < M; ++m) std::swap(cur[m], nxt[m]);   // the new states become the next step's previous ones
       continue;
     }
@@ -542,8 +572,8 @@ int beam_search_entry(const void* const* params, const float* mem, const int64_t
   // free: the prior LSTM is E wide whatever H is, and every state row is kept, zeroed and gathered by its own width.)
   if (start_idx < 0 || start_idx >= V || beam > 16) return ACVAE_EINVAL;
   if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
-  return search(&mb, 1, L, start_idx, end_idx, 0, seqs, nullptr, attw_out, (float*)scratch_v, N, beam, max_length, V, con,
-                fin, (hipStream_t)stream);
+  return search(&mb, 1, L, start_idx, end_idx, Pick{PICK_BEAM}, seqs, nullptr, attw_out, (float*)scratch_v, N, beam,
+                max_length, V, con, fin, (hipStream_t)stream);
 }
 
 int ensemble_search_entry(const void* const* const* params, const float* const* mem, const int64_t* const* mem_lens,
@@ -563,8 +593,32 @@ int ensemble_search_entry(const void* const* const* params, const float* const* 
   ACVAE_TRY(search_layout(mb, M, N, beam, max_length, V, 0, (con.on() || fin.on) && !greedy, fin.on, L));
   if (!greedy && beam > 16) return ACVAE_EUNSUPPORTED;   // acvae_topk_flat_batched selects k <= 16: refused here, not mid-call
   if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
-  return search(mb, M, L, start_idx, end_idx, greedy, seqs, logprobs, nullptr, (float*)scratch_v, N, beam, max_length, V, con,
-                fin, (hipStream_t)stream);
+  return search(mb, M, L, start_idx, end_idx, Pick{greedy ? ACVAE_SAMPLE_GREEDY : PICK_BEAM}, seqs, logprobs, nullptr,
+                (float*)scratch_v, N, beam, max_length, V, con, fin, (hipStream_t)stream);
+}
+
+// A rollout of sample_n rows per clip: the driver with a rollout's pick, and a rollout's refusals in front of it.
+int ensemble_rollout_entry(const void* const* const* params, const float* const* mem, const int64_t* const* mem_lens,
+                           const float* const* eps, const int* S, const int* E, const int* H, const int* A, int M,
+                           int64_t start_idx, int64_t end_idx, const Pick& pick, int64_t* seqs, float* logprobs,
+                           void* scratch_v, int64_t scratch_bytes, int N, int sample_n, int max_length, int V,
+                           const acvae::Constraints& con, void* stream) {
+  SearchMember mb[ACVAE_ENSEMBLE_MAX];
+  ACVAE_TRY(members_of(mb, M, S, E, H, A, params, mem, mem_lens, eps));
+  if (!members_complete(mb, M) || !seqs || !logprobs || !scratch_v) return ACVAE_EINVAL;
+  if (sample_n < 1) return ACVAE_EINVAL;
+  if (pick.mode != ACVAE_SAMPLE_GREEDY && pick.mode != ACVAE_SAMPLE_GUMBEL && pick.mode != ACVAE_SAMPLE_MULTINOMIAL)
+    return ACVAE_EINVAL;
+  if (!isfinite(pick.temp) || !(pick.temp > 0.f)) return ACVAE_EINVAL;
+  if (pick.top_k < 0 || !(pick.top_p > 0.f && pick.top_p <= 1.f)) return ACVAE_EINVAL;     // (a NaN top_p fails both)
+  if (pick.mode == ACVAE_SAMPLE_GREEDY ? pick.truncated() : !pick.noise) return ACVAE_EINVAL;
+  if (start_idx < 0 || start_idx >= V || end_idx < 0 || end_idx >= V) return ACVAE_EINVAL;
+  ACVAE_TRY(acvae::constraints_check_loop(con, V, (int)end_idx, max_length, 1));
+  SearchLayout L;
+  ACVAE_TRY(search_layout(mb, M, N, sample_n, max_length, V, 0, 0, 0, L));
+  if (scratch_bytes < L.total * 4) return ACVAE_EWORKSPACE;
+  return search(mb, M, L, start_idx, end_idx, pick, seqs, logprobs, nullptr, (float*)scratch_v, N, sample_n, max_length, V,
+                con, Finishing{}, (hipStream_t)stream);
 }
 
 acvae::Constraints constraints_of(float repetition_penalty, int no_repeat_ngram_size, int min_length,
@@ -686,6 +740,24 @@ extern "C" int acvae_ensemble_search_finishing(const void* const* const* params,
                                constraints_of(repetition_penalty, no_repeat_ngram_size, min_length, suppress_host, n_suppress),
                                finishing_of(length_norm_host, nbest, nbest_seqs, nbest_scores, nbest_logprobs, nbest_lengths),
                                stream);
+}
+
+extern "C" int64_t acvae_ensemble_rollout_scratch_bytes(int M, int N, int sample_n, int max_length, const int* S,
+                                                        const int* E, const int* H, const int* A, int V) {
+  return sample_n < 1 ? -1 : ensemble_scratch(M, N, sample_n, max_length, S, E, H, A, V, 0);
+}
+extern "C" int acvae_ensemble_rollout(const void* const* const* params, const float* const* mem,
+                                      const int64_t* const* mem_lens, const float* const* eps, const int* S, const int* E,
+                                      const int* H, const int* A, int M, int64_t start_idx, int64_t end_idx, int method,
+                                      float temp, int top_k, float top_p, const float* noise, int64_t* seqs, float* logprobs,
+                                      void* scratch_v, int64_t scratch_bytes, int N, int sample_n, int max_length, int V,
+                                      void* stream, float repetition_penalty, int no_repeat_ngram_size, int min_length,
+                                      const int* suppress_host, int n_suppress) {
+  Pick pick{method, noise, temp, top_k, top_p};
+  return ensemble_rollout_entry(params, mem, mem_lens, eps, S, E, H, A, M, start_idx, end_idx, pick, seqs, logprobs,
+                                scratch_v, scratch_bytes, N, sample_n, max_length, V,
+                                constraints_of(repetition_penalty, no_repeat_ngram_size, min_length, suppress_host, n_suppress),
+                                stream);
 }
 
 // ---- the two finishing kernels alone, on caller-built histories

@@ -6,7 +6,9 @@ inherited by the VAE runner): at every step the members' word probabilities are 
 (``acvae_ensemble_search``): per step every member runs its prior step and its decoder step on its own states, one
 ``acvae_ensemble_mix`` launch forms the mixture's log-probabilities, and the pick is the mix kernel's own argmax (greedy) or
 the flat top-k of ``acvae_beam_search`` (beam).  ``method="dbs"`` is ``acvae_ensemble_dbs_search``, likewise one call: the mixture's
-log-probabilities take the logits' place in ``Hybrid_VAEModel.diverse_beam_search``.
+log-probabilities take the logits' place in ``Hybrid_VAEModel.diverse_beam_search``.  ``Ensemble.rollout`` draws N captions
+per clip from the mixture (``acvae_ensemble_rollout``, one call: the same driver, one ``acvae_ensemble_mix_sample`` launch per
+step); it has no counterpart in the reference.
 
 The reference's ensemble code cannot run a ``Hybrid_VAEModel`` (it calls ``model.decoder`` without ``z`` and never runs
 the prior network), so its mixing rule is carried onto this model's step as ``Hybrid_VAEModel.beam_search`` runs it.  Two
@@ -129,9 +131,93 @@ class Ensemble(nn.Module):
         return search.beam_search(members, True, method == "greedy", beam, T, self.vocab_size, self.start_idx, self.end_idx,
                                   con, fin)
 
+    @torch.no_grad()
+    def rollout(self, feats, feat_lens, sample_n=1, method="sample", temp=1.0, top_k=None, top_p=None, rng="device",
+                max_length=20, repetition_penalty=None, no_repeat_ngram_size=None, min_length=None, suppress_tokens=None,
+                rerank=None):
+        """``sample_n`` captions per clip drawn from the mixture, ONE library call (``acvae_ensemble_rollout``) behind one
+        encoder pass per member and clip -> ``{"seqs": int64, "logprobs": f32}``, both [N * sample_n, max_length] on the
+        device, rows clip-major (row ``n * sample_n + j``) as ``Hybrid_VAEModel.rollout_shared_encoder`` returns them.
+        ``logprobs``: the mixture's log-probability (at temperature 1, under the full distribution) of each chosen word;
+        a row that has produced ``end_idx`` keeps it to the end, and the entries behind it carry no meaning.
+
+        ``method``: "sample" (multinomial), "gumbel", or "greedy" (the rows of a clip then differ by their prior noise
+        alone; ``sample_n=1`` is ``forward(method="greedy")`` bit for bit on the same ``eps``).  ``temp`` acts on the
+        MIXTURE: the members are mixed at temperature 1 and the mixture's log-probabilities are divided by ``temp``; the
+        members' logits are not tempered before the mixing.  ``top_k`` / ``top_p`` (``acvae_amd.search.truncation``)
+        truncate the mixture's row; the decoding constraints (``acvae_amd.search.constraints``) act on every member's
+        logits in front of the mixing.  ``rerank`` (an ``acvae_amd.consensus.Consensus``): ``seqs`` becomes the picked rows
+        [N, max_length] beside ``candidates``, ``consensus_scores`` and ``consensus_best``, as
+        ``Hybrid_VAEModel._rerank`` leaves them.
+
+        Noise.  Member m's prior noise is drawn on the CPU generator as its own search would (clip-major,
+        ``torch.randn(sample_n, E_m)`` per clip and step), members in order.  The word noise [max_length, N * sample_n, V]:
+        ``rng="device"`` (the default: there is no reference stream to reproduce) draws ONE seed on the CPU generator and
+        fills it on the device (``acvae_sample_noise``); ``rng="host"`` draws it on the CPU generator step by step, as a
+        single model's 2-input forward does.  ``self.noise = {"eps": [tensor [N, max_length, sample_n, E_m] per member],
+        "sample_noise": [max_length, N * sample_n, V]}`` (either key may be absent) replays them and is consumed by this
+        call.
+
+        ValueError in front of any work: a method other than the three, ``sample_n`` < 1, a ``temp`` that is not finite
+        and > 0, an unknown ``rng``, truncation with "greedy", and what ``search.constraints`` / ``search.rerank_check``
+        refuse (``rerank`` with fewer than 2 or more than 16 rows per clip, or with ``max_length`` > 64)."""
+        if method not in search.ROLLOUT_METHODS:
+            raise ValueError(f"Ensemble.rollout: method must be 'greedy', 'sample' or 'gumbel', not {method!r}")
+        if isinstance(sample_n, bool) or not isinstance(sample_n, (int, np.integer)) or sample_n < 1:
+            raise ValueError(f"Ensemble.rollout: sample_n must be an integer >= 1, got {sample_n!r}")
+        if rng not in ("host", "device"):
+            raise ValueError(f"rng must be 'host' or 'device', got {rng!r}")
+        try:
+            temp32 = float(np.float32(temp))                               # the value the kernel divides by
+        except (TypeError, ValueError):
+            raise ValueError(f"Ensemble.rollout: temp must be a finite number > 0, got {temp!r}") from None
+        if isinstance(temp, bool) or not (np.isfinite(temp32) and temp32 > 0.0):
+            raise ValueError(f"Ensemble.rollout: temp must be a finite number > 0, got {temp!r}")
+        n, T, V = int(sample_n), int(max_length), self.vocab_size
+        keywords = dict(method=method, max_length=T, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                        no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length, suppress_tokens=suppress_tokens)
+        top_k, top_p = search.truncation(keywords, True, False)            # (no_grad: nothing is recorded)
+        con = search.constraints(keywords, V, self.end_idx, T, True, False)
+        search.rerank_check(rerank, n, keywords, T, False)
+        replay = self.noise if self.noise is not None else {}
+        self.noise = None
+        eps_replay, word_replay = replay.get("eps"), replay.get("sample_noise")
+        if eps_replay is not None and len(eps_replay) != len(self.models):
+            raise ValueError(f"Ensemble: noise['eps'] holds {len(eps_replay)} tensors for {len(self.models)} members")
+        _lib.require_cuda(feats)
+        members = []
+        for k, model in enumerate(self.models):
+            model.eval()
+            model._forward_token = getattr(model, "_forward_token", 0) + 1
+            encoded = model.encoder(feats, copy.copy(np.asarray(feat_lens)))    # its own copy: the encoder divides it in place
+            members.append(model._search_member(encoded, lambda N, E, dev: search._search_noise(
+                N, T, n, E, dev, None if eps_replay is None else eps_replay[k])))
+        dev, R = members[0][0].device, members[0][0].shape[0] * n
+        noise, code = None, search.ROLLOUT_METHODS[method]
+        if method != "greedy":
+            if word_replay is not None:
+                noise = _lib.h2d(torch.as_tensor(word_replay)[:T].reshape(T, R, V), dev, torch.float32).contiguous()
+            elif rng == "device":
+                seed = int(torch.randint(0, 2 ** 62, (1,)))                # after the members' draws: torch.manual_seed fixes it
+                noise = torch.empty(T, R, V, device=dev)
+                _lib.call("acvae_sample_noise", noise, noise.numel(), code, seed, _lib.current_stream())
+            else:
+                host = torch.empty(T, R, V)
+                for t in range(T):                                         # Hybrid_VAEModel._host_prepare's draws, per step
+                    if method == "gumbel":
+                        torch.neg(torch.log(-torch.log(torch.rand(R, V) + 1e-20) + 1e-20), out=host[t])
+                    else:
+                        host[t].exponential_(1)
+                noise = _lib.h2d(host, dev, torch.float32)
+        out = search.ensemble_rollout(members, method, temp32, top_k, top_p, noise, n, T, V, self.start_idx, self.end_idx, con)
+        if rerank is not None:                                             # as Hybrid_VAEModel._rerank
+            got = rerank.select(out["seqs"], n, self.start_idx, self.end_idx)
+            out.update(candidates=out["seqs"], seqs=got["seqs"], consensus_scores=got["scores"], consensus_best=got["best"])
+        return out
+
 
 def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None, dcase_format=False, zh=False,
-                      batch_size=32, frontend=None, **kwargs):
+                      batch_size=32, frontend=None, sample_n=None, rerank=None, diversity=None, **kwargs):
     """The decoding half of ``BaseRunner.ensemble`` (base_runner.py:433-478): ``items`` are ``(audio_id, feature [T, F])`` as
     for ``evaluate()``, batched with ``collate_fn([1])`` (no replication); ``kwargs`` (``method``, ``beam_size``,
     ``max_length``, the constrained-decoding keywords and ``finish_on_end`` / ``length_penalty`` / ``nbest``, with
@@ -144,11 +230,36 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
     dict.  ``accuracy`` (an ``acvae_amd.accuracy.Accuracy``, default None = nothing changes): the rows the file shows (one
     caption per clip; the filled rows of ``method="dbs"``; the n-best list of a finishing search) are handed to it with the
     batch's keys before they are downloaded, as ``evaluate(accuracy=)`` does, with the same refusals in front of any work;
-    read ``accuracy.result()`` afterwards.  METEOR and SPICE stay outside."""
+    read ``accuracy.result()`` afterwards.  METEOR and SPICE stay outside.
+
+    ``sample_n`` (default None = every call and launch of today): the batches go through ``Ensemble.rollout`` instead,
+    ``sample_n`` captions per clip from the mixture, and ``kwargs`` are ``rollout``'s (``method``, ``temp``, ``top_k``,
+    ``top_p``, ``rng``, ``max_length``, the constrained-decoding keywords).  The file shows the clip's ``sample_n`` captions
+    or, with ``rerank`` (an ``acvae_amd.consensus.Consensus``), the one it picks.  ``diversity`` (an
+    ``acvae_amd.diversity.Diversity``) is handed the clip's ``sample_n`` rollouts (with ``rerank`` its candidates) and
+    ``accuracy`` the rows the file shows, both on the device before the download, with the refusals ``evaluate()`` makes
+    for the same arguments.  ``rerank`` and ``diversity`` need ``sample_n``: a search returns its own best hypotheses."""
     refuse_augmented(frontend, "ensemble_evaluate")
     accuracy = kwargs.pop("accuracy", None)
-    shown = None
-    if accuracy is not None:                       # one search per clip: the captions it returns, by forward's defaults
+    shown = per_clip = None
+    if sample_n is None:
+        for name, v in (("rerank", rerank), ("diversity", diversity)):
+            if v is not None:
+                raise ValueError(f"ensemble_evaluate({name}=) needs sample_n: it acts on a clip's sampled captions")
+    else:                                          # (refusals come in front of any work, rollout's own in its first batch)
+        max_length = kwargs.get("max_length", 20)
+        search.rerank_check(rerank, sample_n, dict(kwargs, method=kwargs.get("method", "sample")), max_length, False)
+        if diversity is not None:
+            from .diversity import MAX_LENGTH, Diversity
+            if not isinstance(diversity, Diversity):
+                raise ValueError(f"diversity must be an acvae_amd.diversity.Diversity, got {type(diversity).__name__}")
+            per_clip = diversity.check(sample_n, "ensemble_evaluate(diversity=)")
+            if max_length > MAX_LENGTH:
+                raise ValueError(f"ensemble_evaluate(diversity=): max_length={max_length}; the kernel takes rows of at most "
+                                 f"{MAX_LENGTH} tokens")
+        if accuracy is not None:                   # the captions the file shows per clip: with rerank the picked one
+            shown = accuracy_check(accuracy, 1 if rerank is not None else sample_n, max_length, zh, "ensemble_evaluate")
+    if accuracy is not None and sample_n is None:  # one search per clip: the captions it returns, by forward's defaults
         counts = dict(method=kwargs.get("method", "greedy"), beam_size=kwargs.get("beam_size", 5),
                       group_size=kwargs.get("group_size", 5), group_nbest=kwargs.get("group_nbest", True))
         if kwargs.get("finish_on_end"):
@@ -169,8 +280,16 @@ def ensemble_evaluate(models_or_ensemble, items, vocabulary, caption_output=None
         pending.clear()
         if frontend is not None:
             batch[1], batch[-1] = frontend(batch[1], batch[-1], device=device)
-        output = ens(batch[1].to(device), batch[-1], **kwargs)
-        rows = output["nbest_seqs"] if "nbest_seqs" in output and output["nbest_seqs"].shape[1] > 1 else output["seqs"]
+        if sample_n is not None:
+            output = ens.rollout(batch[1].to(device), batch[-1], sample_n=sample_n, rerank=rerank, **kwargs)
+            rows = output["seqs"]
+            if diversity is not None:              # the clip's rollouts as they stand on the device: nothing comes back
+                diversity.update(output.get("candidates", rows), per_clip)
+            if rerank is None:                     # every rollout is one of the clip's captions
+                rows = rows.reshape(len(batch[0]), sample_n, rows.shape[-1])
+        else:
+            output = ens(batch[1].to(device), batch[-1], **kwargs)
+            rows = output["nbest_seqs"] if "nbest_seqs" in output and output["nbest_seqs"].shape[1] > 1 else output["seqs"]
         if accuracy is not None:                   # the rows the file shows, as they stand on the device
             accuracy.update(batch[0], accuracy_rows(rows, shown), shown)
         collect_predictions(batch[0], rows.cpu().numpy(), vocabulary, zh, key2pred)

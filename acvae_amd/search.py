@@ -329,6 +329,28 @@ def beam_search(members, ensemble, greedy, beam, T, V, start_idx, end_idx, con, 
     return out
 
 
+ROLLOUT_METHODS = {"greedy": int(_lib._defs["ACVAE_SAMPLE_GREEDY"]), "gumbel": int(_lib._defs["ACVAE_SAMPLE_GUMBEL"]),
+                   "sample": int(_lib._defs["ACVAE_SAMPLE_MULTINOMIAL"])}
+
+
+def ensemble_rollout(members, method, temp, top_k, top_p, noise, sample_n, T, V, start_idx, end_idx, con):
+    """``sample_n`` rollouts per clip over ``T`` steps from the members' mixture, ONE call (``acvae_ensemble_rollout``): the
+    rows of a clip share its memory, nothing is replicated.  ``noise`` f32 [T, N * sample_n, V] on the device (None with
+    ``method="greedy"``).  -> {"seqs" i64, "logprobs" f32}, both [N * sample_n, T], rows clip-major."""
+    who, widths, lead, keep = _member_args(members, True)
+    dev, N = members[0][0].device, members[0][0].shape[0]
+    sb = _lib.call("acvae_ensemble_rollout_scratch_bytes", *lead, N, sample_n, T, *widths, V)
+    if sb < 0:
+        raise RuntimeError(f"acvae_ensemble_rollout: unsupported dimensions (N={N}, sample_n={sample_n}, max_length={T})")
+    scratch = scratch_buffer(sb, dev)
+    seqs = torch.empty(N * sample_n, T, dtype=torch.long, device=dev)
+    logprobs = torch.empty(N * sample_n, T, device=dev)
+    _lib.call("acvae_ensemble_rollout", *who, *widths, *lead, start_idx, end_idx, ROLLOUT_METHODS[method], float(temp), top_k,
+              float(top_p), noise, seqs, logprobs, scratch, sb, N, sample_n, T, V, _lib.current_stream(),
+              *_constraint_args(con))
+    return {"seqs": seqs, "logprobs": logprobs}
+
+
 def diverse_beam_search(members, ensemble, G, bdash, T, V, start_idx, end_idx, temperature, diversity_lambda, group_nbest,
                         beam_size):
     """Diverse beam search, ``G`` groups of ``bdash`` beams over ``T`` steps, ONE call (``acvae_[ensemble_]dbs_search``).

@@ -1157,6 +1157,53 @@ int acvae_ensemble_search(const void* const* const* params, const float* const* 
                           int64_t scratch_bytes, int N, int beam, int max_length, int V, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ensemble rollouts: sample_n sampled (or greedy) captions per clip from the mixture.  No counterpart in the reference.
+ *
+ * acvae_ensemble_mix_sample, one launch per sampled step: the mixture's log-probabilities v[r,c] exactly as
+ * acvae_ensemble_mix forms them with prev = NULL, scored by acvae_sample_next_word's rule on the caller's noise row
+ * (noise + r * ld_noise, ld_noise >= V):
+ *   ACVAE_SAMPLE_GUMBEL       w = argmax_c (v_c + g_c) / temp
+ *   ACVAE_SAMPLE_MULTINOMIAL  w = argmax_c expf(v_c / temp) / q_c
+ * first maximum wins; a row whose scores are all NaN gets a word in [0, V).  `temp` acts on the MIXTURE: the members are
+ * mixed at temperature 1 and v is divided by temp, not the members' logits before the mixing.  Then the greedy search's
+ * bookkeeping of step t: a row with t > 0 and seqs[r * ld_seqs + t - 1] == end_idx gets end_idx; seqs[r * ld_seqs + t]
+ * and word[r] (the word fed to the next step) receive the word, logprobs[r * ld_logprobs + t] = v[r, w] of the CHOSEN
+ * word w (untempered; also for a row that is held at end_idx).  out (row stride ld_out >= V) may be NULL: the mixed row
+ * then never reaches memory.  ACVAE_EINVAL before any launch: what acvae_ensemble_mix refuses of logits / ld / M / R / V,
+ * a method other than the two, temp not finite or <= 0, noise / seqs / logprobs / word NULL, t < 0, ld_seqs or
+ * ld_logprobs <= t, ld_noise < V, out with ld_out < V.  No workspace, no atomics.
+ *
+ * acvae_ensemble_rollout, the whole rollout as one call: acvae_ensemble_search's driver with the pick chosen by `method`.
+ * Rows R = N * sample_n, row n * sample_n + j is rollout j of clip n; the rows of a clip share its memory.  Members as for
+ * acvae_ensemble_search, with eps[m] [max_length][R][E[m]].  Every step: the members' steps on the shared word, the
+ * constraints (off: 1.0f, 0, 0, NULL, 0) on every member's logits with the seqs row as the history, then
+ *   ACVAE_SAMPLE_GREEDY       acvae_ensemble_mix's argmax and the bookkeeping launch (sample_n = 1: acvae_ensemble_search's
+ *                             greedy call bit for bit); noise may be NULL, top_k must be 0 and top_p 1;
+ *   GUMBEL / MULTINOMIAL      top_k == 0 and top_p == 1: one acvae_ensemble_mix_sample launch on noise[t] (noise
+ *                             [max_length][R][V], as acvae_sample_noise draws it); otherwise acvae_ensemble_mix writes
+ *                             the mixed row, acvae_sample_next_word_truncated(top_k, top_p) draws from it (the row is a
+ *                             normalised log-probability row already) and the bookkeeping launch follows.
+ * A row that has produced end_idx keeps emitting and feeding it; all max_length steps run, nothing is read back.
+ * seqs int64 [R,max_length], logprobs f32 [R,max_length]: the mixture's log-probability of each chosen word.
+ * Refused before any launch: M outside [1, ACVAE_ENSEMBLE_MAX], a NULL entry, sample_n < 1, a method outside the three,
+ * temp not finite or <= 0, a sampling method with noise NULL, top_k < 0, top_p outside (0, 1], truncation with
+ * ACVAE_SAMPLE_GREEDY, start_idx / end_idx outside [0, V), what the constrained entries refuse (ACVAE_EINVAL);
+ * N * sample_n > 2^20 (ACVAE_EUNSUPPORTED); scratch below acvae_ensemble_rollout_scratch_bytes() (ACVAE_EWORKSPACE).
+ * ------------------------------------------------------------------------------------------- */
+int acvae_ensemble_mix_sample(const float* const* logits, const int64_t* ld, int M, const float* noise, int64_t ld_noise,
+                              int method, float temp, float* out, int64_t ld_out, int64_t* seqs, int64_t ld_seqs,
+                              float* logprobs, int64_t ld_logprobs, int64_t* word, int64_t end_idx, int t, int R, int V,
+                              void* stream);
+int64_t acvae_ensemble_rollout_scratch_bytes(int M, int N, int sample_n, int max_length, const int* S, const int* E,
+                                             const int* H, const int* A, int V);
+int acvae_ensemble_rollout(const void* const* const* params, const float* const* mem, const int64_t* const* mem_lens,
+                           const float* const* eps, const int* S, const int* E, const int* H, const int* A, int M,
+                           int64_t start_idx, int64_t end_idx, int method, float temp, int top_k, float top_p,
+                           const float* noise, int64_t* seqs, float* logprobs, void* scratch, int64_t scratch_bytes, int N,
+                           int sample_n, int max_length, int V, void* stream, float repetition_penalty,
+                           int no_repeat_ngram_size, int min_length, const int* suppress_host, int n_suppress);
+
+/* ---------------------------------------------------------------------------------------------
  * Constrained decoding on the device: four controls on a row's logits x at step t, applied inside every decoding loop in
  * front of the selection.  No counterpart in the reference.  h[0..t) is the row's history: the words it has emitted so
  * far, <start> not among them.  All are off by default, and with all four off every entry below runs exactly the launches
