@@ -787,9 +787,21 @@ using namespace mfma;
 //     frequency and the 2 x 4 gradient pixels of both output-channel halves (ds_read_b32, channel-contiguous over lanes) and
 //     spends 12-16 adds (6-8 v_pk_add_f32) for 8 MFMAs; all signs of A and Bt are folded into the order of subtractions;
 //   * LDS holds the raw window [pixel][64 ci] and the gradients [tile][2x2][64 co]; the channel index is XOR-ed with 32
-//     for odd tile columns / odd tiles so that the two lane halves of a read never meet in a bank.
-constexpr int WG_XW_PIX = 136;                 // window pixels per stage: 4 x 34 (W >= 32) .. 10 x 10 (W = 8)
-constexpr int WG_XW_WORDS = WG_XW_PIX * 64;
+//     for odd tile columns / odd tiles so that the two lane halves of a read never meet in a bank;
+//   * staging (round 25): nothing on the way into LDS is decided per item inside the loop.  The window is loaded through a
+//     buffer descriptor of the current clip (rows above / below it read as zero in hardware), its padding columns are slots
+//     zeroed once per buffer, padding and dead items store into a dummy pixel, the last stage of a workgroup stages itself
+//     again instead of branching around the staging, the loop exists once with and once without the BatchNorm + ReLU
+//     operand, and the gradient DMA takes its masked arm only in a stage that reaches below the clip (details at the
+//     code).  Static count of the _s4 main loop, per 128 MFMAs (two stages): 434 other vector instructions (46 compares, 22
+//     selects, 48 64-bit moves, 44 + 40 integer adds / ands, 22 64-bit address operations; 36 saveexec, 49 branches) -> 226
+//     with the activation (the 96 packed adds of the transforms; 20 + 20 packed multiplies / adds and 40 v_med3_f32 of the
+//     activation, 11 selects, 12 compares, 10 adds, 8 address operations; 14 saveexec, all on the masked DMA arm) and 121
+//     without: 3.4 -> 1.8 / 0.95 per MFMA.
+//     Measured: 3.62 -> 3.31 ms for the seven layers in isolation, 0.513 -> 0.473 ms per launch inside the step
+//     (profiles/r25_wgrad_staging.txt), results bit-identical.
+constexpr int WG_XW_PIX = 136;                // window pixels per stage: 4 x 34 (W >= 32) .. 10 x 10 (W = 8)
+constexpr int WG_XW_WORDS = WG_XW_PIX * 64 + 64;   // + the dummy pixel that padding and dead staging items write
 constexpr int WG_DY_WORDS = 16 * 4 * 64;
 
 struct WinoWgradParams {
@@ -819,21 +831,46 @@ __device__ __forceinline__ void wino_wgrad_body(const WinoWgradParams& p, float*
   const int z = blockIdx.x, cib = blockIdx.y, cob = blockIdx.z;
   const int H = p.H, W = p.W;
   constexpr int STW = 1 << SS, WC = 2 * STW + 2;
-  const int WR = 2 * p.RS + 2;
+  constexpr int RS = 16 >> SS, WR = 2 * RS + 2;          // tile rows per stage (= p.RS), window rows
   const int g_begin = z * p.per, g_end = min(p.total, g_begin + p.per);
 
-  // ---------------------------------------------------------------- staging items (window coordinates are per thread)
+  // ---------------------------------------------------------------- staging items (fixed over the stages of a workgroup)
+  // item e = tid + 512 j -> window pixel e / 16 (row wy of WR, column wx of WC), channel quad e % 16.  Per item the loop keeps
+  // ONE byte offset inside the window and ONE LDS word per buffer - no coordinates, no liveness or validity masks:
+  //   * loads are buffer loads against a descriptor of the CURRENT clip (base X + n H W Cin, H W Cin 4 bytes): a window row
+  //     above the clip (y = -1: the 32-bit offset wraps past the size) or below it (y >= H) reads as zero in hardware, never as
+  //     the neighbouring clip.  The hardware checks voffset only, so the stage's base goes into voffset too: one v_add_u32 with
+  //     a scalar operand per item;
+  //   * the window's padding COLUMNS have in-range (row-wrapped) addresses, so the descriptor cannot zero them; but they are
+  //     static per BUFFER: with one segment per tile row (W <= 32) the first and last window column are padding in every
+  //     stage, and at W = 64 (two segments: the left column is padding in segment 0, the right one in segment 1) a clip has an
+  //     even number of stages, so the segment is the parity of the global stage index and xw0 holds segment g_begin & 1 in
+  //     every stage, xw1 the other.  Those slots are zeroed once per buffer, here, and never written again;
+  //   * padding items and items past the window store into a dummy pixel behind the window that nobody reads (xlo0 / xlo1:
+  //     the item's LDS word in xw0 / xw1), items past the window also load from an offset that is out of range in every stage:
+  //     every load and every ds_write_b128 of the loop is unconditional.
   const int quad = tid & 15;
-  int xyx[5], xlo[5];        // window (row << 8 | column) and LDS word of the thread's items
-  unsigned xlive = 0;
+  const bool two = SS == 4 && p.segs == 2;
+  const int seg_b0 = two ? (g_begin & 1) : 0;            // the segment xw0 holds
+  unsigned xoff[5];
+  int xlo0[5], xlo1[5];
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
     const int e = tid + 512 * j, wp = e >> 4;
     const bool lv = wp < WR * WC;
-    xlive |= (lv ? 1u : 0u) << j;
     const int wy = wp / WC, wx = wp - wy * WC;
-    xyx[j] = (wy << 8) | wx;
-    xlo[j] = wp * 64 + ((quad * 4) ^ (32 * ((wx >> 1) & 1)));
+    const bool padl = wx == 0, padr = wx == WC - 1;
+    const bool pad0 = two ? (seg_b0 ? padr : padl) : (padl || padr), pad1 = two ? (seg_b0 ? padl : padr) : (padl || padr);
+    const int slot = wp * 64 + ((quad * 4) ^ (32 * ((wx >> 1) & 1))), dummy = WG_XW_PIX * 64 + quad * 4;
+    xoff[j] = lv ? (unsigned)(((wy * W + wx) * p.Cin + quad * 4) * 4) : 0x80000000u;
+    xlo0[j] = lv && !pad0 ? slot : dummy;
+    xlo1[j] = lv && !pad1 ? slot : dummy;
+  }
+  for (int i = tid; i < WR * 32; i += 512) {
+    const int wy = i >> 5, side = (i >> 4) & 1, wx = side ? WC - 1 : 0;
+    const int slot = (wy * WC + wx) * 64 + (i & 15) * 4;       // all 16 quads of the pixel: the swizzle does not matter
+    if (!two || side == seg_b0) *reinterpret_cast<float4*>(xw0 + slot) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!two || side != seg_b0) *reinterpret_cast<float4*>(xw1 + slot) = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
   const bool act = p.scale != nullptr;
@@ -843,58 +880,81 @@ __device__ __forceinline__ void wino_wgrad_body(const WinoWgradParams& p, float*
   }
   // The gradient tiles go global -> LDS by LDS-DMA (no transform to apply, no registers, no ds_write): a DMA instruction of a
   // wavefront moves one tile = 4 pixels x 64 channels, lane l = (pixel l / 16, 16-byte slot l % 16), and the XOR swizzle of the
-  // channel with the tile parity sits on the SOURCE address.  A DMA cannot zero-fill: lanes whose pixel lies below the image
-  // (odd H / the clip's last stage) are masked out of the DMA and store zeros themselves - nobody reads that buffer before
-  // the next barrier.
-  const int WCin = W * p.Cin;
+  // channel with the tile parity sits on the SOURCE address: a per-lane element offset inside the stage, computed once, on a
+  // scalar base per stage.  A DMA cannot zero-fill: lanes whose pixel lies below the image are masked out of the DMA and store
+  // zeros themselves (nobody reads that buffer before the next barrier) - but only a stage that reaches below the clip (odd
+  // H / a partial last stage: a scalar condition) takes that arm at all, every other stage issues its two DMAs unmasked.
+  unsigned dyoff[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int t = wave * 2 + i, pp = lane >> 4, pq = lane & 15;
+    dyoff[i] = (unsigned)(((2 * (t >> SS) + (pp >> 1)) * W + 2 * (t & (STW - 1)) + (pp & 1)) * p.Cout + ((pq ^ (8 * i)) << 2));
+  }
+  const unsigned clip_bytes = (unsigned)(H * W * p.Cin) * 4u;      // the launcher keeps a clip below 2^30 bytes
   float4 px[5];
-  unsigned xok = 0;
+  bool xin[5];               // act only: the item's load was inside the clip (else BatchNorm + ReLU of the zero must stay zero)
   // stage g = (clip n, stage s of the clip): advanced incrementally (wave-uniform scalars; the two integer divisions per stage
   // were a visible part of the stage's issue time)
   const int seg_shift = p.segs == 2 ? 1 : 0;
   auto issue_dy = [&](int n, int s, float* dys) {
     const int trow = s >> seg_shift, seg = s & (p.segs - 1);
-    const int ty0 = trow * p.RS, tx0 = seg * 16;          // first tile of the stage
+    const int ty0 = trow * RS, tx0 = seg * 16;            // first tile of the stage
+    const float* sbase = p.dY + (unsigned)(((n * H + 2 * ty0) * W + 2 * tx0) * p.Cout + cob * 64);
+    if (2 * (ty0 + RS) <= H) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int t = wave * 2 + i, pp = lane >> 4, pq = lane & 15;
-      const int y = 2 * (ty0 + (t >> p.st_shift)) + (pp >> 1), x = 2 * (tx0 + (t & (STW - 1))) + (pp & 1);
-      float* dst = dys + t * 256;
-      if (y < H) {
-        const float* src = p.dY + (unsigned)(((n * H + y) * W + x) * p.Cout + cob * 64 + ((pq ^ (8 * (t & 1))) << 2));
-        __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
-      } else {
-        *reinterpret_cast<float4*>(dst + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int i = 0; i < 2; ++i) __builtin_amdgcn_global_load_lds(sbase + dyoff[i], dys + (wave_s * 2 + i) * 256, 16, 0, 0);
+    } else {
+      // the lane id afresh (mbcnt), not `lane` from the top of the kernel: that one would be live across the main loop for
+      // the sake of this rare arm, and the loop has no register to spare (as for lane_e behind the loop)
+      const int lane_d = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int t = wave_s * 2 + i;
+        float* dst = dys + t * 256;
+        if (2 * (ty0 + (t >> SS)) + (lane_d >> 5) < H) __builtin_amdgcn_global_load_lds(sbase + dyoff[i], dst, 16, 0, 0);
+        else *reinterpret_cast<float4*>(dst + lane_d * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
   };
-  auto issue_x = [&](int n, int s) {
+  auto issue_x = [&](auto actt, int n, int s) {
+    constexpr bool ACT = decltype(actt)::value;
     const int trow = s >> seg_shift, seg = s & (p.segs - 1);
-    const int ty0 = trow * p.RS, tx0 = seg * 16;
-    // 32-bit element offsets (the launcher refuses tensors of 2^31 elements or more): a wave-uniform base per stage plus a
-    // per-item part - no 64-bit multiplies per item
-    const int xbase = ((n * H + 2 * ty0 - 1) * W + (2 * tx0 - 1)) * p.Cin + cib * 64 + quad * 4;
-    xok = 0;
+    const int ty0 = trow * RS, tx0 = seg * 16;
+    // 32-bit offsets (the launcher refuses tensors of 2^31 elements or more); negative for the row above the clip
+    const unsigned xbase = (unsigned)((((2 * ty0 - 1) * W + (2 * tx0 - 1)) * p.Cin + cib * 64) * 4);
+    const __amdgpu_buffer_rsrc_t xrs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X) + (unsigned)(n * H * W * p.Cin), 0, (int)clip_bytes, 0x00020000);
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
-      const int wy = xyx[j] >> 8, wx = xyx[j] & 255;
-      const int y = 2 * ty0 - 1 + wy, x = 2 * tx0 - 1 + wx;
-      const bool ok = ((xlive >> j) & 1u) && y >= 0 && y < H && x >= 0 && x < W;
-      xok |= (ok ? 1u : 0u) << j;
-      const unsigned off = ok ? (unsigned)(xbase + wy * WCin + wx * p.Cin) : 0u;     // always a legal address
-      px[j] = *reinterpret_cast<const float4*>(p.X + off);
+      typedef unsigned wg_v4u __attribute__((ext_vector_type(4)));
+      const unsigned off = xoff[j] + xbase;
+      const wg_v4u v = __builtin_amdgcn_raw_buffer_load_b128(xrs, (int)off, 0, 0);
+      px[j] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+      if (ACT) xin[j] = off < clip_bytes;
     }
   };
-  auto put_part = [&](float* xw, int j0, int j1) {
+  // Padding under the activation: relu(0 * sc + sh) is not zero, so an item whose load was out of range must still store an
+  // exact zero.  One select per item on the precomputed condition picks the upper limit of the ReLU's clamp (+inf / 0), and
+  // v_med3_f32 takes the place of v_max_f32: med3(a, 0, +inf) = max(a, 0) bit for bit for every finite or infinite a, med3(a, 0, 0)
+  // = 0.  (a = NaN: v_max_f32 returns the other operand, 0; v_med3_f32 with a NaN operand returns min3, which skips the NaN: 0
+  // as well, with either limit.)
+  auto put_part = [&](auto actt, float* xw, const int (&xlo)[5], int j0, int j1) {
+    constexpr bool ACT = decltype(actt)::value;
 #pragma unroll
     for (int j = j0; j < j1; ++j) {
       float4 v = px[j];
-      if (act) {
-        v.x = fmaxf(v.x * sc.x + sh.x, 0.f); v.y = fmaxf(v.y * sc.y + sh.y, 0.f);
-        v.z = fmaxf(v.z * sc.z + sh.z, 0.f); v.w = fmaxf(v.w * sc.w + sh.w, 0.f);
+      if (ACT) {
+        const float lim = xin[j] ? __builtin_inff() : 0.f;
+        // x * sc + sh, two values per issue slot (as asm: left alone the backend scalarises three of the five items)
+        f32x2 lo, hi;
+        asm("v_pk_mul_f32 %0, %2, %4\n\tv_pk_mul_f32 %1, %3, %5\n\tv_pk_add_f32 %0, %0, %6\n\tv_pk_add_f32 %1, %1, %7"
+            : "=&v"(lo), "=&v"(hi)
+            : "v"(f32x2{v.x, v.y}), "v"(f32x2{v.z, v.w}), "v"(f32x2{sc.x, sc.y}), "v"(f32x2{sc.z, sc.w}), "v"(f32x2{sh.x, sh.y}),
+              "v"(f32x2{sh.z, sh.w}));
+        v.x = __builtin_amdgcn_fmed3f(lo[0], 0.f, lim); v.y = __builtin_amdgcn_fmed3f(lo[1], 0.f, lim);
+        v.z = __builtin_amdgcn_fmed3f(hi[0], 0.f, lim); v.w = __builtin_amdgcn_fmed3f(hi[1], 0.f, lim);
       }
-      if (!((xok >> j) & 1u)) v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if ((xlive >> j) & 1u) *reinterpret_cast<float4*>(xw + xlo[j]) = v;
+      *reinterpret_cast<float4*>(xw + xlo[j]) = v;
     }
   };
 
@@ -999,25 +1059,25 @@ __device__ __forceinline__ void wino_wgrad_body(const WinoWgradParams& p, float*
   // their loads together in front of the stage's first MFMA and staged together behind its last: 2560 + 1420 cycles of a
   // 15 900-cycle stage with the pipe idle - in-kernel counters of round 2.)
 #define WG_SB() __builtin_amdgcn_sched_barrier(0)
-  auto compute = [&](const float* xw, const float* dys, bool more, int nn, int ns, float* xw_n, float* dy_n) {
+  auto compute = [&](auto actt, const float* xw, const float* dys, int nn, int ns, float* xw_n, const int (&xlo_n)[5], float* dy_n) {
     Frag fa, fb;
     load(std::integral_constant<int, 0>(), xw, dys, fa);
     load(std::integral_constant<int, 1>(), xw, dys, fb); WG_SB(); mm(fa); WG_SB();
-    if (more) issue_dy(nn, ns, dy_n);
+    issue_dy(nn, ns, dy_n);
     WG_SB();
     load(std::integral_constant<int, 2>(), xw, dys, fa); WG_SB(); mm(fb); WG_SB();
-    if (more) issue_x(nn, ns);
+    issue_x(actt, nn, ns);
     WG_SB();
     load(std::integral_constant<int, 3>(), xw, dys, fb); WG_SB(); mm(fa); WG_SB();
     load(std::integral_constant<int, 4>(), xw, dys, fa); WG_SB(); mm(fb); WG_SB();
     load(std::integral_constant<int, 5>(), xw, dys, fb); WG_SB(); mm(fa); WG_SB();
-    if (more) put_part(xw_n, 0, 2);
+    put_part(actt, xw_n, xlo_n, 0, 2);
     WG_SB();
     load(std::integral_constant<int, 6>(), xw, dys, fa); WG_SB(); mm(fb); WG_SB();
-    if (more) put_part(xw_n, 2, 4);
+    put_part(actt, xw_n, xlo_n, 2, 4);
     WG_SB();
     load(std::integral_constant<int, 7>(), xw, dys, fb); WG_SB(); mm(fa); WG_SB();
-    if (more) put_part(xw_n, 4, 5);
+    put_part(actt, xw_n, xlo_n, 4, 5);
     WG_SB();
     mm(fb);
     WG_SB();
@@ -1027,21 +1087,30 @@ __device__ __forceinline__ void wino_wgrad_body(const WinoWgradParams& p, float*
 #undef WG_SB
 
   // ---------------------------------------------------------------- main loop: one barrier per 16-tile stage
-  if (g_begin < g_end) {
+  // No run-time condition in a stage but the clip's ragged last tile row: the last stage of the workgroup stages ITSELF once
+  // more (loads that hit L2, stores into buffers nobody reads any more) instead of skipping the staging under a branch, and
+  // the loop exists twice, with and without the activation on the operand.  The price is one stage's loads (five buffer loads
+  // per thread, two DMAs per wavefront) on top of the `per` stages of a workgroup: 1 / per more load instructions - 0.8-1.6 % at
+  // the training shapes (per = 63 .. 128), but 100 % where the plan gives per = 1 (N * spc <= Z: tiny inputs only).  A plan
+  // that moved the real layers toward per = 1 would have to bring the branch back.
+  auto run = [&](auto actt) {
     int n = g_begin / p.spc, sidx = g_begin - n * p.spc;
     issue_dy(n, sidx, dy0);
-    issue_x(n, sidx);
-    put_part(xw0, 0, 5);
+    issue_x(actt, n, sidx);
+    put_part(actt, xw0, xlo0, 0, 5);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int g = g_begin; g < g_end; g += 2) {
-      if (++sidx == p.spc) { sidx = 0; ++n; }
-      compute(xw0, dy0, g + 1 < g_end, n, sidx, xw1, dy1);          // dy1 / xw1: last read at stage g - 1, behind the barrier
+      if (g + 1 < g_end && ++sidx == p.spc) { sidx = 0; ++n; }
+      compute(actt, xw0, dy0, n, sidx, xw1, xlo1, dy1);          // dy1 / xw1: last read at stage g - 1, behind the barrier
       if (g + 1 < g_end) {
-        if (++sidx == p.spc) { sidx = 0; ++n; }
-        compute(xw1, dy1, g + 2 < g_end, n, sidx, xw0, dy0);
+        if (g + 2 < g_end && ++sidx == p.spc) { sidx = 0; ++n; }
+        compute(actt, xw1, dy1, n, sidx, xw0, xlo0, dy0);
       }
     }
+  };
+  if (g_begin < g_end) {
+    if (act) run(std::true_type()); else run(std::false_type());
   }
 
   // ---------------------------------------------------------------- slab: [z][position][ci][co]
@@ -1163,8 +1232,9 @@ bool conv3x3_wino_wgrad_ok(int H, int W, int Cin, int Cout) {
   return Cin % 64 == 0 && Cout % 64 == 0;
 }
 // the kernel addresses X and dY with 32-bit element offsets
+// and one clip of X through a buffer descriptor whose out-of-range side also has to hold every wrapped (negative) offset
 static bool wino_wgrad_fits(int N, int H, int W, int Cin, int Cout) {
-  return (long)N * H * W * (Cin > Cout ? Cin : Cout) < (1L << 31);
+  return (long)N * H * W * (Cin > Cout ? Cin : Cout) < (1L << 31) && (long)H * W * Cin * 4 <= (1L << 30);
 }
 long conv3x3_wino_wgrad_slab_floats(int N, int H, int W, int Cin, int Cout) {
   if (!conv3x3_wino_wgrad_ok(H, W, Cin, Cout)) return 0;
